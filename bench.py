@@ -3,6 +3,7 @@
 at N=8192, d=8, fp64.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank/GPU)
+  python bench.py ... --dump-outputs DIR                 (also write the last timed step's results as DIR/<name>.npy)
 
 A step = one pass of the hot path over one batch of synthetic input: a lock-step batch of B independent
 evalFnMulti-equivalent likelihood evaluations (covariance fill + Cholesky + solves + logL, sigma^2, beta), each at
@@ -527,7 +528,13 @@ def main():
     ap.add_argument("--no-interactive", action="store_true", help="skip the interactive_mode-through-the-CLI region")
     ap.add_argument("--interactive-queries", type=int, default=None, help="points piped through the CLI (default: --queries / 1e6)")
     ap.add_argument("--pca8-steps", type=int, default=8, help="lock-step batches of evaluations per PCA component")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0's lock-step "
+                         "batch of likelihood evaluations: value, sigma2, beta, logdet, quad, info, status) as DIR/<name>.npy, "
+                         "float64; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher: start the N ranks ourselves, as fresh children, BEFORE anything in this process touches the GPU
@@ -678,6 +685,13 @@ def main():
     RING = abi.RESULT_RING
     pending = [[] for _ in ctxs]            # per context: step indices enqueued and not yet collected
     values = np.full((K, B), np.nan)
+    last_step = None                        # everything step K-1 handed back (--dump-outputs)
+
+    def took(j, r):
+        nonlocal last_step
+        values[j] = r["value"]
+        if j == K - 1:
+            last_step = r
     t0 = time.perf_counter()
     for j, ch in enumerate(chunks):
         s_ = j % nstreams
@@ -685,17 +699,22 @@ def main():
         if len(pending[s_]) == RING - 1:
             r = c.loglik_batch_collect_back(RING - 2, B)
             assert np.all(r["status"] == 0), r
-            values[pending[s_].pop(0)] = r["value"]
+            took(pending[s_].pop(0), r)
         c.loglik_batch_enqueue(np.array([theta(i) for i in ch]))
         pending[s_].append(j)
     for s_, c in enumerate(ctxs):
         while pending[s_]:
             r = c.loglik_batch_collect_back(len(pending[s_]) - 1, B)
             assert np.all(r["status"] == 0), r
-            values[pending[s_].pop(0)] = r["value"]
+            took(pending[s_].pop(0), r)
     barrier()
     tA = time.perf_counter() - t0
     assert np.all(np.isfinite(values)), "a likelihood value of the timed region is not finite"
+    if args.dump_outputs and rank == 0:
+        # one lock-step batch of B evaluations: a few KB in all, written whole
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("value", "sigma2", "beta", "logdet", "quad", "info", "status"):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(last_step[name], dtype=np.float64))
     last = {"value": float(values[-1, -1])}
     if distributed:
         tt = torch.tensor([tA], dtype=torch.float64, device=tdev)

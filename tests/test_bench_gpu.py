@@ -1,12 +1,14 @@
 """bench.py itself in the GPU suite: the N > 1 path (the parent starts the ranks, one process group, the barrier / all_reduce
 / padded all_gather of every region, the component -> rank deal of the configs[3] region) on two gloo ranks that share the
 one GPU of the box, with the plumbing workload -- what the driver's scaling run executes with RCCL on a real node
-(there the CLI ranks of regions D and F gather through gpemu_rccl_allgather; here, sharing a device, through files)."""
+(there the CLI ranks of regions D and F gather through gpemu_rccl_allgather; here, sharing a device, through files);
+and --dump-outputs, the results of the last timed step written for comparing two builds."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,3 +38,30 @@ def test_bench_two_gloo_ranks_sharing_the_gpu():
     f = j["pca8_trained_by_cli_ranks"]
     assert "error" not in f and f["processes"] == 2 and not f["ranks_failed"] and f["components_trained_here"] == 4
     assert len(f["snapshot_sha256"]) == 64
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs: what the last of the --steps timed steps handed back (one lock-step batch of likelihood evaluations),
+    as float64 .npy files; two runs with the same arguments write the same bits"""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "5",
+                              "--warmup", "1", "--no-cpu-baseline", "--no-grad", "--no-predict", "--no-train", "--no-pca8",
+                              "--no-interactive", "--no-single", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 5 and j["ms_per_step"] > 0
+        B = j["evaluations_per_step"]
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert sorted(got) == ["beta", "info", "logdet", "quad", "sigma2", "status", "value"]
+        assert all(a.dtype == np.float64 and a.shape[0] == B for a in got.values())
+        assert np.all(np.isfinite(got["value"])) and np.all(got["status"] == 0) and got["beta"].ndim == 2
+        assert len(np.unique(got["value"])) == B                        # B distinct thetas, not one result repeated
+        dumps.append(got)
+    for name, a in dumps[0].items():
+        assert a.tobytes() == dumps[1][name].tobytes(), name
