@@ -4,6 +4,7 @@ at N=8192, d=8, fp64.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank/GPU)
   python bench.py ... --dump-outputs DIR                 (also write the last timed step's results as DIR/<name>.npy)
+  python bench.py ... --full                             (also everything else below: gate, rooflines, regions B-F)
 
 A step = one pass of the hot path over one batch of synthetic input: a lock-step batch of B independent
 evalFnMulti-equivalent likelihood evaluations (covariance fill + Cholesky + solves + logL, sigma^2, beta), each at
@@ -18,13 +19,19 @@ A third timed region measures what estimate_thetas really calls per BFGS step (l
 675-680): evalFnGradMulti, value + gradient from one factorisation, as lock-step batches (gpemu_loglik_grad_batch) on
 a pow-exp model of the same size (the reference has no Matern gradient).
 
+A plain run does only what the headline figure needs: set-up, the W warm-up and K timed steps of the likelihood
+evaluations (region A), --dump-outputs, the line.  The rest runs with --full alone: the parity gate against the oracle in
+front of the clock, the rooflines, the one-at-a-time figure, the prediction and value+gradient regions above, the CLI and
+PCA regions (D to F) and the CPU baseline, each of them still skipped by its own --no-* option.
+
 Multi-GPU: the evaluations / query blocks are independent units sharded one share per rank with no data-path
 collective; a single all-gather of the per-rank results ends each region ("weak" scaling: per-rank work fixed).
 `python bench.py --gpus N` with no RANK in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, before this process touches the GPU) and forwards
 rank 0's line; under the driver's own torchrun launch the ranks are already there.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with "roofline" and "cpu_baseline" objects.
+Prints ONE JSON line on rank 0: the headline fields ("metric", "value", "unit", "ms_per_step", ...); with --full also
+the other regions' objects, "roofline" and "cpu_baseline" among them.
 """
 import argparse
 import ctypes as C
@@ -503,7 +510,6 @@ def main():
     ap.add_argument("--steps", type=int, default=24, help="timed steps; one step = one lock-step batch of --batch evaluations")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--queries", type=int, default=None, help="total prediction points per rank (default 1e6)")
     ap.add_argument("--streams", type=int, default=2,
                     help="concurrent evaluation contexts (HIP streams) per GPU: the panel chain of one context's batch "
                          "overlaps the trailing updates of the other's")
@@ -511,27 +517,32 @@ def main():
                     help="independent evaluations factored in lock-step per context (gpemu_loglik_batch: the device "
                          "form of the reference's restart threads / callEvalLhoodList); 1 = one matrix per launch; "
                          "default 16 at N >= 8192, up to 64 for smaller models (the panel chain weighs more there)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sizes", default="1024,1536,2048",
-                    help="sample sizes of the CPU baseline (one oracle evaluation per core at each); the default takes about a "
-                         "minute, adding 4096 about a quarter of an hour")
-    ap.add_argument("--no-predict", action="store_true")
-    ap.add_argument("--no-grad", action="store_true", help="skip the value+gradient region")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-evaluation-at-a-time latency figure")
-    ap.add_argument("--grad-steps", type=int, default=None, help="timed value+gradient batches (default min(steps, 8))")
-    ap.add_argument("--no-train", action="store_true", help="skip the estimate_thetas-through-the-C-layer region")
-    ap.add_argument("--grad-batch", type=int, default=None, help="evaluations per value+gradient batch (default min(batch, 16))")
-    ap.add_argument("--train-runs", type=int, default=64, help="BFGS runs (restarts) of that region (GPEMU_RESTARTS)")
-    ap.add_argument("--train-literal", action="store_true",
-                    help="that region with the reference's literal gradient formulas instead of the exact gradient")
-    ap.add_argument("--no-pca8", action="store_true", help="skip the 8-PCA-component region (BASELINE configs[3])")
-    ap.add_argument("--no-interactive", action="store_true", help="skip the interactive_mode-through-the-CLI region")
-    ap.add_argument("--interactive-queries", type=int, default=None, help="points piped through the CLI (default: --queries / 1e6)")
-    ap.add_argument("--pca8-steps", type=int, default=8, help="lock-step batches of evaluations per PCA component")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller (rank 0's lock-step "
                          "batch of likelihood evaluations: value, sigma2, beta, logdet, quad, info, status) as DIR/<name>.npy, "
                          "float64; the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity gate against the oracle, the "
+                         "rooflines, the other regions of the line (options below) and the CPU baseline")
+    fa = ap.add_argument_group("with --full", "what a --full run adds to the headline region (a plain run ignores these)")
+    fa.add_argument("--queries", type=int, default=None, help="total prediction points per rank (default 1e6)")
+    fa.add_argument("--no-cpu-baseline", action="store_true")
+    fa.add_argument("--cpu-sizes", default="1024,1536,2048",
+                    help="sample sizes of the CPU baseline (one oracle evaluation per core at each); the default takes about a "
+                         "minute, adding 4096 about a quarter of an hour")
+    fa.add_argument("--no-predict", action="store_true")
+    fa.add_argument("--no-grad", action="store_true", help="skip the value+gradient region")
+    fa.add_argument("--no-single", action="store_true", help="skip the one-evaluation-at-a-time latency figure")
+    fa.add_argument("--grad-steps", type=int, default=None, help="timed value+gradient batches (default min(steps, 8))")
+    fa.add_argument("--no-train", action="store_true", help="skip the estimate_thetas-through-the-C-layer region")
+    fa.add_argument("--grad-batch", type=int, default=None, help="evaluations per value+gradient batch (default min(batch, 16))")
+    fa.add_argument("--train-runs", type=int, default=64, help="BFGS runs (restarts) of that region (GPEMU_RESTARTS)")
+    fa.add_argument("--train-literal", action="store_true",
+                    help="that region with the reference's literal gradient formulas instead of the exact gradient")
+    fa.add_argument("--no-pca8", action="store_true", help="skip the 8-PCA-component region (BASELINE configs[3])")
+    fa.add_argument("--no-interactive", action="store_true", help="skip the interactive_mode-through-the-CLI region")
+    fa.add_argument("--interactive-queries", type=int, default=None, help="points piped through the CLI (default: --queries / 1e6)")
+    fa.add_argument("--pca8-steps", type=int, default=8, help="lock-step batches of evaluations per PCA component")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -611,9 +622,9 @@ def main():
     def theta(i):
         return synth.perturbed_thetas(kind, d, seed, rank + world_size * i)
 
-    # ---- correctness gate before timing (small N, same seeds): HIP vs oracle, 1e-8 relative
+    # ---- correctness gate before timing (small N, same seeds): HIP vs oracle, 1e-8 relative (--full)
     gate = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import oracle as O
         gate = {}
         # N=512 and N=2048 on the same seeds (the N=2048 oracle run is ~15 s of CPU: skipped together
@@ -725,6 +736,31 @@ def main():
         assert len(rows) == world_size
     evals_per_s = ngpus * K * B / tA
     note(f"region A: {evals_per_s:.1f} evaluations/s")
+    headline = {
+        "metric": "estimate_thetas likelihood-evals/sec + predictions/sec at N=8192 d=8 fp64",
+        "value": evals_per_s, "unit": "likelihood-evals/s",
+        "n_gpus": ngpus, "steps": K, "warmup": W, "ms_per_step": tA / K * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: N={N}, d={d}, cov_fn={kind} "
+                               f"({'pow-exp' if kind == 1 else 'Matern32' if kind == 2 else 'Matern52'}), "
+                               f"regression_order={order}, {nq} prediction points per rank",
+                   "parallelism": f"independent evaluations / query blocks x{ngpus} GPUs, one all-gather; per GPU "
+                                  f"{nstreams} contexts x lock-step batches of {B} evaluations",
+                   "streams_per_gpu": nstreams, "batch": B,
+                   "step": f"one lock-step batch of {B} independent likelihood evaluations"},
+        "evaluations_per_step": B, "ms_per_evaluation": tA / (K * B) * 1e3,
+    }
+    if not args.full:
+        # a plain run ends here: the line holds the headline fields alone
+        if rank == 0:
+            print(json.dumps(headline))
+        for c in ctxs:
+            c.close()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel (fp64 MFMA GEMM of the Cholesky trailing updates), HIP events on the
     #      ctx stream around every launch; rank 0 only.  Taken right behind region A: the same kernels in the state of the
@@ -1084,20 +1120,7 @@ def main():
         cpu = cpu_baseline(kind, order, N, d, seed, [int(v) for v in args.cpu_sizes.split(",")])
 
     if rank == 0:
-        out = {
-            "metric": "estimate_thetas likelihood-evals/sec + predictions/sec at N=8192 d=8 fp64",
-            "value": evals_per_s, "unit": "likelihood-evals/s",
-            "n_gpus": ngpus, "steps": K, "warmup": W, "ms_per_step": tA / K * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: N={N}, d={d}, cov_fn={kind} "
-                                   f"({'pow-exp' if kind == 1 else 'Matern32' if kind == 2 else 'Matern52'}), "
-                                   f"regression_order={order}, {nq} prediction points per rank",
-                       "parallelism": f"independent evaluations / query blocks x{ngpus} GPUs, one all-gather; per GPU "
-                                      f"{nstreams} contexts x lock-step batches of {B} evaluations",
-                       "streams_per_gpu": nstreams, "batch": B,
-                       "step": f"one lock-step batch of {B} independent likelihood evaluations"},
-            "evaluations_per_step": B, "ms_per_evaluation": tA / (K * B) * 1e3,
+        out = dict(headline, **{
             "predictions": pred,
             "interactive_mode_cli": inter,
             "value_grad": vg,
@@ -1111,7 +1134,7 @@ def main():
             "cpu_baseline": cpu,
             "speedup_vs_cpu_all_cores": (evals_per_s / cpu["value"]) if cpu else None,
             "parity_gate": gate,
-        }
+        })
         print(json.dumps(out))
     for c in ctxs:
         c.close()

@@ -2,7 +2,8 @@
 / padded all_gather of every region, the component -> rank deal of the configs[3] region) on two gloo ranks that share the
 one GPU of the box, with the plumbing workload -- what the driver's scaling run executes with RCCL on a real node
 (there the CLI ranks of regions D and F gather through gpemu_rccl_allgather; here, sharing a device, through files);
-and --dump-outputs, the results of the last timed step written for comparing two builds."""
+and --dump-outputs, the results of the last timed step written for comparing two builds; a plain run (no --full) with its
+headline fields alone."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_gloo_ranks_sharing_the_gpu():
     env = dict(os.environ, BENCH_BACKEND="gloo", GPEMU_GATHER="file")     # (two RCCL ranks cannot share a device)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "3",
-                          "--warmup", "1", "--no-cpu-baseline", "--train-runs", "6", "--pca8-steps", "1"],
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--train-runs", "6", "--pca8-steps", "1"],
                          env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -65,3 +66,26 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_bit_for_bit(tmp_p
         dumps.append(got)
     for name, a in dumps[0].items():
         assert a.tobytes() == dumps[1][name].tobytes(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_bench_runs_the_headline_region_alone(gpus):
+    """without --full: set-up, warm-up, the timed steps and the line -- its headline fields, consistent with each other, and
+    nothing of the parity gate, the rooflines, the other regions or the CPU baseline; one rank, and two gloo ranks sharing
+    the GPU"""
+    env = dict(os.environ, BENCH_BACKEND="gloo") if gpus > 1 else None
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "tiny", "--steps", "4",
+                          "--warmup", "2"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["metric"] == "estimate_thetas likelihood-evals/sec + predictions/sec at N=8192 d=8 fp64"
+    assert j["unit"] == "likelihood-evals/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["n_gpus"] == gpus and j["steps"] == 4 and j["warmup"] == 2 and j["ms_per_step"] > 0
+    # value = evaluations per second over the timed steps, all ranks = n_gpus * evaluations_per_step / ms_per_step
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 - gpus * j["evaluations_per_step"]) < 1e-9 * gpus * j["evaluations_per_step"]
+    for k in ("parity_gate", "roofline", "roofline_other", "single_evaluation", "predictions", "interactive_mode_cli", "value_grad",
+              "estimate_thetas_c_layer", "pca8", "pca8_trained_by_cli_ranks", "cpu_baseline", "speedup_vs_cpu_all_cores"):
+        assert k not in j, k
