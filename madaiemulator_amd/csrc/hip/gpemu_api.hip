@@ -188,16 +188,15 @@ extern "C" int gpemu_ctx_create(gpemu_ctx **out, int device)
 	// the per-matrix result slots (three device and three pinned allocations: milliseconds) are made by the first
 	// factorisation (ensure_batch_slots): a context that only ever answers queries -- a component of a multi-output emulator
 	// set up by gpemu_predict_setup_batch -- never needs them
-	ctx->batch_cap = 0;
 	int least = 0, greatest = 0;
 	if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = 0; greatest = 0; }
 	bool ok = hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, greatest) == hipSuccess;
 	for (int i = 0; ok && i < gpemu_ctx::RES_RING; i++)
-		ok = hipEventCreateWithFlags(&ctx->res_ev[i], hipEventDisableTiming) == hipSuccess;
+		ok = hipEventCreateWithFlags(&ctx->ring[i].ev, hipEventDisableTiming) == hipSuccess;
 	const char *tr = getenv("GPEMU_TRACE");
 	if (ok && tr && atoi(tr) > 0) {                 // in-kernel timestamps: 4096 launch slots of 8 x u64
 		ctx->trace_cap = 4096;
-		if (hipMalloc(&ctx->dTrace, (size_t)ctx->trace_cap * 64) != hipSuccess) { ctx->dTrace = nullptr; ctx->trace_cap = 0; }
+		if (ctx->dTrace.grow((size_t)ctx->trace_cap * 8) != hipSuccess) ctx->trace_cap = 0;
 	}
 	const char *ng = getenv("GPEMU_NO_GRAPH");
 	if (ng && ng[0] == '1') ctx->use_graph = false;
@@ -222,44 +221,50 @@ static void free_graphs(gpemu_ctx *ctx)
 	ctx->warm.clear();
 }
 
+// The one way a buffer of a context grows.  Nothing but a compare when it is large enough; otherwise enqueued work that may
+// still use the old allocation is waited for, then release and allocate (contents are not kept).  graphed: the cached launch
+// graphs hold the buffer's address -- dT and dInfo, which is all potrf_rec touches that can move -- and go when it moves.
+// oom: the message of a failed allocation (the error is then cleared); none: the runtime's own, like any failed call.
+template <class B>
+static int grow(gpemu_ctx *ctx, B &buf, size_t n, bool graphed = false, const char *oom = nullptr)
+{
+	if (buf.size() >= n) return GPEMU_OK;
+	if (graphed) free_graphs(ctx);
+	if (buf) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	const hipError_t e = buf.grow(n);
+	if (e != hipSuccess && oom) {
+		(void)hipGetLastError();
+		return fail(ctx, GPEMU_ERR_HIP, oom);
+	}
+	HIPCHK(ctx, e);
+	return GPEMU_OK;
+}
+
+// everything sized by the model (the per-matrix result slots, the symmetric-matrix cache and the upload ring stay)
 static void free_model(gpemu_ctx *ctx)
 {
 	free_graphs(ctx);
-	double **ptrs[] = {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
-	                   &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha};
-	for (auto p : ptrs) { if (*p) hipFree(*p); *p = nullptr; }
-	ctx->dVar = nullptr;                      // (the second half of dMean's allocation)
-	ctx->T_rows = 0; ctx->pred_ready = false; ctx->cinv_ready = false; ctx->pred_batch = 0; ctx->stage_cap = 0;
+	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
+	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha})
+		b->reset();
+	ctx->hStage.reset();
+	ctx->pred_ready = false; ctx->cinv_ready = false;
 	ctx->pred_pending = 0;
-	ctx->S_dim = 0; ctx->S_cap = 0; ctx->gradpart_len = 0; ctx->alpha_cap = 0;
+	ctx->S_dim = 0;
 }
 
-extern "C" void gpemu_ctx_destroy(gpemu_ctx *ctx)
+gpemu_ctx::~gpemu_ctx()
 {
-	if (!ctx) return;
-	hipSetDevice(ctx->device);
-	if (ctx->stream) hipStreamSynchronize(ctx->stream);
-	free_model(ctx);
-	for (auto e : ctx->prof.ev) hipEventDestroy(e);
-	if (ctx->dInfo) hipFree(ctx->dInfo);
-	if (ctx->dTrace) hipFree(ctx->dTrace);
-	if (ctx->dParams) hipFree(ctx->dParams);
-	if (ctx->hParams) hipHostFree(ctx->hParams);
-	for (auto e : ctx->param_ev) if (e) hipEventDestroy(e);
-	if (ctx->dSym) hipFree(ctx->dSym);
-	if (ctx->dSymV) hipFree(ctx->dSymV);
-	if (ctx->dSymOut) hipFree(ctx->dSymOut);
-	if (ctx->dRes) hipFree(ctx->dRes);
-	if (ctx->hResRing) hipHostFree(ctx->hResRing);
-	if (ctx->hInfoRing) hipHostFree(ctx->hInfoRing);
-	if (ctx->dGradSum) hipFree(ctx->dGradSum);
-	if (ctx->hGradRing) hipHostFree(ctx->hGradRing);
-	if (ctx->hGph) hipHostFree(ctx->hGph);
-	for (auto e : ctx->res_ev) if (e) hipEventDestroy(e);
-	if (ctx->hStage) hipHostFree(ctx->hStage);
-	if (ctx->stream) hipStreamDestroy(ctx->stream);
-	delete ctx;
+	hipSetDevice(device);
+	if (stream) hipStreamSynchronize(stream);
+	free_model(this);
+	for (auto e : prof.ev) hipEventDestroy(e);
+	for (auto e : pring.ev) if (e) hipEventDestroy(e);
+	for (auto &s : ring) if (s.ev) hipEventDestroy(s.ev);
+	if (stream && own_stream) hipStreamDestroy(stream);
 }
+
+extern "C" void gpemu_ctx_destroy(gpemu_ctx *ctx) { delete ctx; }
 
 extern "C" int gpemu_set_mode(gpemu_ctx *ctx, int flags)
 {
@@ -283,13 +288,13 @@ extern "C" int gpemu_dev_alloc(gpemu_ctx *ctx, size_t bytes, void **dptr)
 {
 	if (!ctx || !dptr) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	HIPCHK(ctx, hipMalloc(dptr, bytes));
+	HIPCHK(ctx, DeviceMem::alloc(dptr, bytes));
 	return GPEMU_OK;
 }
 extern "C" int gpemu_dev_free(gpemu_ctx *ctx, void *dptr)
 {
 	if (!ctx) return GPEMU_ERR_ARG;
-	HIPCHK(ctx, hipFree(dptr));
+	HIPCHK(ctx, DeviceMem::release(dptr));
 	return GPEMU_OK;
 }
 extern "C" int gpemu_dev_upload(gpemu_ctx *ctx, void *dst, const void *src, size_t bytes)
@@ -313,48 +318,35 @@ extern "C" int gpemu_dev_download(gpemu_ctx *ctx, void *dst, const void *src, si
 // workspace for nb tall matrices of rows_each rows, packed one after the other (stride rows_each * Np)
 static int ensure_T(gpemu_ctx *ctx, size_t rows_each, int nb = 1)
 {
-	const size_t rows = rows_each * (size_t)nb;
 	ctx->nb = nb;
 	ctx->T_stride = rows_each * (size_t)ctx->Np;
-	if (ctx->T_rows >= rows) return GPEMU_OK;
-	free_graphs(ctx);
-	if (ctx->dT) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->dT); ctx->dT = nullptr; ctx->T_rows = 0; }
-	if (hipMalloc(&ctx->dT, rows * (size_t)ctx->Np * sizeof(double)) != hipSuccess) {
-		(void)hipGetLastError();
-		ctx->dT = nullptr;
-		return fail(ctx, GPEMU_ERR_HIP, "out of device memory for the factorisation workspace (smaller batch?)");
-	}
-	ctx->T_rows = rows;
-	return GPEMU_OK;
+	return grow(ctx, ctx->dT, ctx->T_stride * (size_t)nb, true, "out of device memory for the factorisation workspace (smaller batch?)");
 }
 
 // per-matrix result slots (info word, Gram partials, Gram + log det, pinned mirrors) for a batch of nb
 static int ensure_batch_slots(gpemu_ctx *ctx, int nb)
 {
-	if (nb <= ctx->batch_cap && ctx->dGramPart && ctx->dInfo) return GPEMU_OK;
-	if (nb < ctx->batch_cap) nb = ctx->batch_cap;
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	free_graphs(ctx);                      // captured launches hold the old pointers
-	if (ctx->dInfo) hipFree(ctx->dInfo);
-	if (ctx->dRes) hipFree(ctx->dRes);
-	if (ctx->hResRing) hipHostFree(ctx->hResRing);
-	if (ctx->hInfoRing) hipHostFree(ctx->hInfoRing);
-	if (ctx->dGramPart) hipFree(ctx->dGramPart);
-	if (ctx->dGradSum) hipFree(ctx->dGradSum);
-	if (ctx->hGradRing) hipHostFree(ctx->hGradRing);
-	ctx->dGradSum = nullptr; ctx->hGradRing = nullptr;
-	ctx->dInfo = nullptr; ctx->dRes = nullptr; ctx->hRes = ctx->hResRing = nullptr; ctx->hInfo = ctx->hInfoRing = nullptr; ctx->dGramPart = nullptr;
-	ctx->res_seq = 0;                      // results still in the old ring are gone with it
-	HIPCHK(ctx, hipMalloc(&ctx->dInfo, (size_t)nb * sizeof(int)));
-	HIPCHK(ctx, hipMalloc(&ctx->dRes, (size_t)nb * ctx->res_len * sizeof(double)));
-	HIPCHK(ctx, hipHostMalloc((void **)&ctx->hResRing, (size_t)gpemu_ctx::RES_RING * nb * ctx->res_len * sizeof(double)));
-	HIPCHK(ctx, hipHostMalloc((void **)&ctx->hInfoRing, (size_t)gpemu_ctx::RES_RING * nb * sizeof(int)));
-	ctx->hRes = ctx->hResRing; ctx->hInfo = ctx->hInfoRing;
-	HIPCHK(ctx, hipMalloc(&ctx->dGramPart, (size_t)nb * (ctx->Np / 64) * ctx->Rp * ctx->Rp * sizeof(double)));
-	HIPCHK(ctx, hipMalloc(&ctx->dGradSum, (size_t)nb * gpemu_ctx::GRAD_NP_MAX * sizeof(double)));
-	HIPCHK(ctx, hipHostMalloc((void **)&ctx->hGradRing, (size_t)gpemu_ctx::RES_RING * nb * gpemu_ctx::GRAD_NP_MAX * sizeof(double)));
-	ctx->batch_cap = nb;
-	return GPEMU_OK;
+	if (nb > ctx->batch_cap()) {
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		ctx->res_seq = 0;                      // results still in the old ring are gone with it
+		ctx->dInfo.reset();                    // (the capacity is zero until all of them are there again)
+		const size_t n = (size_t)nb, rn = (size_t)gpemu_ctx::RES_RING * n;
+		int rc = grow(ctx, ctx->dRes, n * ctx->res_len);
+		if (!rc) rc = grow(ctx, ctx->hResRing, rn * ctx->res_len);
+		if (!rc) rc = grow(ctx, ctx->hInfoRing, rn);
+		if (!rc) rc = grow(ctx, ctx->dGradSum, n * gpemu_ctx::GRAD_NP_MAX);
+		if (!rc) rc = grow(ctx, ctx->hGradRing, rn * gpemu_ctx::GRAD_NP_MAX);
+		if (!rc) rc = grow(ctx, ctx->dInfo, n, true);
+		if (rc) return rc;
+		for (size_t i = 0; i < (size_t)gpemu_ctx::RES_RING; i++) {
+			ResSlot &s = ctx->ring[i];
+			s.nb = 0;
+			s.res = ctx->hResRing + i * n * ctx->res_len;
+			s.info = ctx->hInfoRing + i * n;
+			s.grad = ctx->hGradRing + i * n * gpemu_ctx::GRAD_NP_MAX;
+		}
+	}
+	return grow(ctx, ctx->dGramPart, (size_t)ctx->batch_cap() * (ctx->Np / 64) * ctx->Rp * ctx->Rp);
 }
 
 extern "C" int gpemu_set_model(gpemu_ctx *ctx, int kind, int order, int N, int d, const double *X, const double *y)
@@ -374,11 +366,9 @@ extern "C" int gpemu_set_model(gpemu_ctx *ctx, int kind, int order, int N, int d
 	ctx->Rp = 64;
 	ctx->hX.assign(X, X + (size_t)N * d);
 	ctx->hY.assign(y, y + N);
-	HIPCHK(ctx, hipMalloc(&ctx->dX, (size_t)N * d * sizeof(double)));
-	HIPCHK(ctx, hipMalloc(&ctx->dY, (size_t)N * sizeof(double)));
-	HIPCHK(ctx, hipMalloc(&ctx->dRrows, (size_t)ctx->Rp * ctx->Np * sizeof(double)));
-	if (ctx->batch_cap > 0)
-		HIPCHK(ctx, hipMalloc(&ctx->dGramPart, (size_t)ctx->batch_cap * (ctx->Np / 64) * ctx->Rp * ctx->Rp * sizeof(double)));
+	HIPCHK(ctx, ctx->dX.grow((size_t)N * d));
+	HIPCHK(ctx, ctx->dY.grow((size_t)N));
+	HIPCHK(ctx, ctx->dRrows.grow((size_t)ctx->Rp * ctx->Np));
 	HIPCHK(ctx, hipMemcpyAsync(ctx->dX, ctx->hX.data(), (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(ctx->dY, ctx->hY.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	{
@@ -397,13 +387,13 @@ extern "C" int gpemu_set_model(gpemu_ctx *ctx, int kind, int order, int N, int d
 			for (int k = 0; k < d; k++) ctx->xhalf[k] = 0.5 * (hi[k] - lo[k]);
 			for (int i = 0; i < N; i++)
 				for (int k = 0; k < d; k++) xg[(size_t)i * d + k] = X[(size_t)i * d + k] - 0.5 * (hi[k] + lo[k]);
-			HIPCHK(ctx, hipMalloc(&ctx->dXg, (size_t)N * d * sizeof(double)));
+			HIPCHK(ctx, ctx->dXg.grow((size_t)N * d));
 			// (on the context's own stream, never the legacy stream: a plain hipMemcpy fails with "operation would make the
 			// legacy stream depend on a capturing blocking stream" while ANOTHER host thread records its launch graph)
 			HIPCHK(ctx, hipMemcpyAsync(ctx->dXg, xg.data(), (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 			std::vector<double> mid(d);
 			for (int k = 0; k < d; k++) mid[k] = 0.5 * (hi[k] + lo[k]);
-			HIPCHK(ctx, hipMalloc(&ctx->dMid, (size_t)d * sizeof(double)));
+			HIPCHK(ctx, ctx->dMid.grow((size_t)d));
 			HIPCHK(ctx, hipMemcpyAsync(ctx->dMid, mid.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 			HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 		}
@@ -652,8 +642,6 @@ static int run_potrf(gpemu_ctx *ctx, int inv)
 }
 
 // fill C(theta_b) into matrix b of T (lower tiles only), load the RHS rows, reset the info words
-constexpr unsigned PARAM_RING = 4;
-
 // rrows / rstride: right-hand-side rows of the batch when they are not the context's own (rstride != 0: matrix b takes
 // rrows + b * rstride -- the components of a multi-output model, gpemu_predict_setup_batch)
 static int stage_matrices(gpemu_ctx *ctx, const CovParams *ps, int nb, int inv, const double *rrows = nullptr, long rstride = 0)
@@ -666,20 +654,20 @@ static int stage_matrices(gpemu_ctx *ctx, const CovParams *ps, int nb, int inv, 
 	// one upload of the nb hyper-parameter sets, one launch for the nb fills and R-row copies.  The upload goes through a
 	// pinned ring of four entries (a pageable source makes hipMemcpyAsync wait for the stream: enqueued batches of small
 	// models then take 6 us per evaluation instead of 2); an entry is reused once its own copy has executed.
-	if (!ctx->dParams) {
-		HIPCHK(ctx, hipMalloc(&ctx->dParams, (size_t)GPEMU_MAX_BATCH * sizeof(CovParams)));
-		HIPCHK(ctx, hipHostMalloc((void **)&ctx->hParams, (size_t)PARAM_RING * GPEMU_MAX_BATCH * sizeof(CovParams)));
-		HIPCHK(ctx, hipHostMalloc((void **)&ctx->hGph, (size_t)PARAM_RING * GPEMU_MAX_BATCH * GPEMU_MAX_PARAMS * sizeof(double)));
-		for (unsigned i = 0; i < PARAM_RING; i++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->param_ev[i], hipEventDisableTiming));
+	ParamRing &pr = ctx->pring;
+	if (!ctx->dParams) {                   // (allocated last: there means that the ring is complete)
+		HIPCHK(ctx, pr.params.grow((size_t)ParamRing::RING * GPEMU_MAX_BATCH));
+		HIPCHK(ctx, pr.gph.grow((size_t)ParamRing::RING * GPEMU_MAX_BATCH * GPEMU_MAX_PARAMS));
+		for (auto &e : pr.ev) if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		HIPCHK(ctx, ctx->dParams.grow((size_t)GPEMU_MAX_BATCH));
 	}
 	{
-		const unsigned slot = ctx->param_next++ % PARAM_RING;
-		ctx->param_slot = slot;
-		HIPCHK(ctx, hipEventSynchronize(ctx->param_ev[slot]));        // (a never-recorded event is complete)
-		CovParams *hp = ctx->hParams + (size_t)slot * GPEMU_MAX_BATCH;
+		pr.slot = pr.next++ % ParamRing::RING;
+		HIPCHK(ctx, hipEventSynchronize(pr.ev[pr.slot]));             // (a never-recorded event is complete)
+		CovParams *hp = pr.params + (size_t)pr.slot * GPEMU_MAX_BATCH;
 		memcpy(hp, ps, (size_t)nb * sizeof(CovParams));
 		HIPCHK(ctx, hipMemcpyAsync(ctx->dParams, hp, (size_t)nb * sizeof(CovParams), hipMemcpyHostToDevice, ctx->stream));
-		HIPCHK(ctx, hipEventRecord(ctx->param_ev[slot], ctx->stream));
+		HIPCHK(ctx, hipEventRecord(pr.ev[pr.slot], ctx->stream));
 	}
 	{
 		const double nlow = 0.5 * (double)Np * Np * nb;
@@ -706,17 +694,15 @@ static int enqueue_results(gpemu_ctx *ctx)
 	HIPCHK(ctx, launch_finish(ctx->stream, ctx->dGramPart, Np / 64, Rp, ctx->nrhs, ctx->dT, Np, ctx->N, ctx->dRes, nb,
 	                          (long)ctx->T_stride, (long)ctx->res_len));
 	// the results land in the next slot of a pinned ring (RES_RING batches stay readable: a throughput caller collects
-	// batch j while batches j+1 .. j+RES_RING-1 are in flight); hRes / hInfo point at the newest slot
-	const int slot = (int)(ctx->res_seq % gpemu_ctx::RES_RING);
+	// batch j while batches j+1 .. j+RES_RING-1 are in flight)
 	ctx->res_seq++;
-	ctx->hRes = ctx->hResRing + (size_t)slot * ctx->batch_cap * ctx->res_len;
-	ctx->hInfo = ctx->hInfoRing + (size_t)slot * ctx->batch_cap;
-	ctx->res_nb[slot] = nb;
-	ctx->res_kind[slot] = 0;
-	HIPCHK(ctx, hipMemcpyAsync(ctx->hRes, ctx->dRes, ((size_t)(nb - 1) * ctx->res_len + (size_t)Rp * Rp + 1) * sizeof(double),
+	ResSlot &s = ctx->newest();
+	s.nb = nb;
+	s.kind = 0;
+	HIPCHK(ctx, hipMemcpyAsync(s.res, ctx->dRes, ((size_t)(nb - 1) * ctx->res_len + (size_t)Rp * Rp + 1) * sizeof(double),
 	                           hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->hInfo, ctx->dInfo, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipEventRecord(ctx->res_ev[slot], ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(s.info, ctx->dInfo, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipEventRecord(s.ev, ctx->stream));
 	return GPEMU_OK;
 }
 
@@ -755,11 +741,12 @@ static bool small_chol_inverse(std::vector<double> &A, int n)
 
 struct HostLik { double yy, quad, sigma2, logdet; std::vector<double> beta, Q, Hy; int status; };
 
-static HostLik host_likelihood(gpemu_ctx *ctx, int b = 0)
+// from the results of one matrix (Gram matrix of [y|H] under C^-1, then log det C): element b of a ring slot
+static HostLik host_likelihood(const gpemu_ctx *ctx, const ResSlot &s, int b = 0)
 {
 	HostLik r;
 	const int Rp = ctx->Rp, nreg = ctx->nreg;
-	const double *G = ctx->hRes + (size_t)b * ctx->res_len;
+	const double *G = s.res + (size_t)b * ctx->res_len;
 	r.logdet = G[Rp * Rp];
 	r.yy = G[0];
 	r.Hy.resize(nreg);
@@ -814,11 +801,11 @@ extern "C" int gpemu_loglik_batch_enqueue(gpemu_ctx *ctx, int nb, const double *
 	return enqueue_results(ctx);
 }
 
-// results of element b of the last enqueued batch (after the stream has been synchronised)
-static int collect_one(gpemu_ctx *ctx, int b, double *neg_loglik, double *sigma2, double *beta, double *logdet,
+// results of element b of the batch in ring slot s (after its event or the stream has been waited for)
+static int collect_one(gpemu_ctx *ctx, const ResSlot &s, int b, double *neg_loglik, double *sigma2, double *beta, double *logdet,
                        double *quad, int *info)
 {
-	const int inf = (ctx->hInfo[b] >= INFO_NONE) ? 0 : ctx->hInfo[b];
+	const int inf = (s.info[b] >= INFO_NONE) ? 0 : s.info[b];
 	if (info) *info = inf;
 	if (inf != 0) {
 		if (neg_loglik) *neg_loglik = NAN;
@@ -828,7 +815,7 @@ static int collect_one(gpemu_ctx *ctx, int b, double *neg_loglik, double *sigma2
 		if (beta) for (int a = 0; a < ctx->nreg; a++) beta[a] = NAN;
 		return fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
 	}
-	HostLik r = host_likelihood(ctx, b);
+	HostLik r = host_likelihood(ctx, s, b);
 	if (beta) for (int a = 0; a < ctx->nreg; a++) beta[a] = r.beta[a];
 	if (sigma2) *sigma2 = r.sigma2;
 	if (logdet) *logdet = r.logdet;
@@ -842,18 +829,25 @@ static int collect_one(gpemu_ctx *ctx, int b, double *neg_loglik, double *sigma2
 	return GPEMU_OK;
 }
 
+static void collect_batch(gpemu_ctx *ctx, const ResSlot &s, int nb, double *neg_loglik, double *sigma2, double *beta, double *logdet,
+                          double *quad, int *info, int *status)
+{
+	for (int b = 0; b < nb; b++) {
+		const int rc = collect_one(ctx, s, b, neg_loglik ? neg_loglik + b : nullptr, sigma2 ? sigma2 + b : nullptr,
+		                           beta ? beta + (size_t)b * ctx->nreg : nullptr, logdet ? logdet + b : nullptr,
+		                           quad ? quad + b : nullptr, info ? info + b : nullptr);
+		if (status) status[b] = rc;
+	}
+}
+
 extern "C" int gpemu_loglik_batch_collect(gpemu_ctx *ctx, int nb, double *neg_loglik, double *sigma2, double *beta,
                                           double *logdet, double *quad, int *info, int *status)
 {
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (nb < 1 || nb != ctx->nb) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
+	if (!ctx->res_seq) return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	for (int b = 0; b < nb; b++) {
-		const int rc = collect_one(ctx, b, neg_loglik ? neg_loglik + b : nullptr, sigma2 ? sigma2 + b : nullptr,
-		                           beta ? beta + (size_t)b * ctx->nreg : nullptr, logdet ? logdet + b : nullptr,
-		                           quad ? quad + b : nullptr, info ? info + b : nullptr);
-		if (status) status[b] = rc;
-	}
+	collect_batch(ctx, ctx->newest(), nb, neg_loglik, sigma2, beta, logdet, quad, info, status);
 	return GPEMU_OK;
 }
 
@@ -864,21 +858,11 @@ extern "C" int gpemu_loglik_batch_collect_back(gpemu_ctx *ctx, int back, int nb,
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (back < 0 || back >= gpemu_ctx::RES_RING || (unsigned long long)back >= ctx->res_seq)
 		return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
-	const int slot = (int)((ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING);
-	if (nb < 1 || nb != ctx->res_nb[slot]) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
-	if (ctx->res_kind[slot] != 0) return fail(ctx, GPEMU_ERR_STATE, "that batch is a value+gradient batch: use gpemu_loglik_grad_batch_collect_back");
-	HIPCHK(ctx, hipEventSynchronize(ctx->res_ev[slot]));
-	double *saveR = ctx->hRes;
-	int *saveI = ctx->hInfo;
-	ctx->hRes = ctx->hResRing + (size_t)slot * ctx->batch_cap * ctx->res_len;
-	ctx->hInfo = ctx->hInfoRing + (size_t)slot * ctx->batch_cap;
-	for (int b = 0; b < nb; b++) {
-		const int rc = collect_one(ctx, b, neg_loglik ? neg_loglik + b : nullptr, sigma2 ? sigma2 + b : nullptr,
-		                           beta ? beta + (size_t)b * ctx->nreg : nullptr, logdet ? logdet + b : nullptr,
-		                           quad ? quad + b : nullptr, info ? info + b : nullptr);
-		if (status) status[b] = rc;
-	}
-	ctx->hRes = saveR; ctx->hInfo = saveI;
+	const ResSlot &s = ctx->ring[(ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING];
+	if (nb < 1 || nb != s.nb) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
+	if (s.kind != 0) return fail(ctx, GPEMU_ERR_STATE, "that batch is a value+gradient batch: use gpemu_loglik_grad_batch_collect_back");
+	HIPCHK(ctx, hipEventSynchronize(s.ev));
+	collect_batch(ctx, s, nb, neg_loglik, sigma2, beta, logdet, quad, info, status);
 	return GPEMU_OK;
 }
 
@@ -901,8 +885,9 @@ extern "C" int gpemu_loglik_collect(gpemu_ctx *ctx, double *neg_loglik, double *
 {
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (ctx->nb != 1) return fail(ctx, GPEMU_ERR_STATE, "the enqueued work is a batch: use gpemu_loglik_batch_collect");
+	if (!ctx->res_seq) return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	return collect_one(ctx, 0, neg_loglik, sigma2, beta, logdet, quad, info);
+	return collect_one(ctx, ctx->newest(), 0, neg_loglik, sigma2, beta, logdet, quad, info);
 }
 
 extern "C" int gpemu_loglik(gpemu_ctx *ctx, const double *thetas, int nthetas, double *neg_loglik, double *sigma2,
@@ -925,15 +910,12 @@ extern "C" int gpemu_cov_matrix(gpemu_ctx *ctx, const double *thetas, int ntheta
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int Np = ctx->Np, N = ctx->N;
-	double *buf = nullptr;
-	HIPCHK(ctx, hipMalloc(&buf, (size_t)Np * Np * sizeof(double)));
-	hipError_t e = launch_cov_fill(ctx->stream, buf, Np, ctx->dX, N, Np, ctx->dX, N, Np, ctx->d, p, 0);
-	if (e == hipSuccess)
-		e = hipMemcpy2DAsync(c_out, (size_t)N * sizeof(double), buf, (size_t)Np * sizeof(double),
-		                     (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	hipFree(buf);
-	HIPCHK(ctx, e);
+	DevBuf<double> buf;
+	HIPCHK(ctx, buf.grow((size_t)Np * Np));
+	HIPCHK(ctx, launch_cov_fill(ctx->stream, buf, Np, ctx->dX, N, Np, ctx->dX, N, Np, ctx->d, p, 0));
+	HIPCHK(ctx, hipMemcpy2DAsync(c_out, (size_t)N * sizeof(double), buf, (size_t)Np * sizeof(double),
+	                             (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 
@@ -955,18 +937,14 @@ extern "C" int gpemu_kvectors(gpemu_ctx *ctx, const double *thetas, int nthetas,
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int Np = ctx->Np, N = ctx->N, Mp = round_up(M, 64);
-	double *buf = nullptr, *dq = nullptr;
-	HIPCHK(ctx, hipMalloc(&buf, (size_t)Mp * Np * sizeof(double)));
-	hipError_t e = hipMalloc(&dq, (size_t)M * ctx->d * sizeof(double));
-	if (e == hipSuccess) e = hipMemcpyAsync(dq, xq, (size_t)M * ctx->d * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = fill_kvectors(ctx, buf, dq, M, Mp, p);
-	if (e == hipSuccess)
-		e = hipMemcpy2DAsync(k_out, (size_t)N * sizeof(double), buf, (size_t)Np * sizeof(double),
-		                     (size_t)N * sizeof(double), M, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	hipFree(buf);
-	if (dq) hipFree(dq);
-	HIPCHK(ctx, e);
+	DevBuf<double> buf, dq;
+	HIPCHK(ctx, buf.grow((size_t)Mp * Np));
+	HIPCHK(ctx, dq.grow((size_t)M * ctx->d));
+	HIPCHK(ctx, hipMemcpyAsync(dq, xq, (size_t)M * ctx->d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, fill_kvectors(ctx, buf, dq, M, Mp, p));
+	HIPCHK(ctx, hipMemcpy2DAsync(k_out, (size_t)N * sizeof(double), buf, (size_t)Np * sizeof(double),
+	                             (size_t)N * sizeof(double), M, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 
@@ -985,7 +963,8 @@ static int factor_with_inverse(gpemu_ctx *ctx, const double *thetas, int nthetas
 	rc = enqueue_results(ctx);
 	if (rc) return rc;
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	const int inf = (*ctx->hInfo >= INFO_NONE) ? 0 : *ctx->hInfo;
+	const int word = ctx->newest().info[0];
+	const int inf = (word >= INFO_NONE) ? 0 : word;
 	if (info) *info = inf;
 	if (inf) return fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
 	return GPEMU_OK;
@@ -999,8 +978,8 @@ static int build_prediction_state(gpemu_ctx *src, int b, gpemu_ctx *dst, const C
 {
 	const int Np = src->Np, Rp = src->Rp, nreg = src->nreg, N = src->N;
 	const size_t la_rows = (size_t)Np + Rp;
-	if (!dst->dLinvAug) HIPCHK(src, hipMalloc(&dst->dLinvAug, la_rows * Np * sizeof(double)));
-	if (!dst->dBetaQ) HIPCHK(src, hipMalloc(&dst->dBetaQ, (size_t)(nreg + nreg * nreg) * sizeof(double)));
+	HIPCHK(src, dst->dLinvAug.grow(la_rows * Np));          // (made once per model: never moved under enqueued work)
+	HIPCHK(src, dst->dBetaQ.grow((size_t)(nreg + nreg * nreg)));
 	const double *Tb = src->dT + (size_t)b * src->T_stride;
 	const double *Zt = Tb + (size_t)Np * Np;
 	const double *U = Tb + (size_t)(Np + Rp) * Np;
@@ -1050,7 +1029,7 @@ extern "C" int gpemu_predict_setup(gpemu_ctx *ctx, const double *thetas, int nth
 	CovParams p;
 	int rc = factor_with_inverse(ctx, thetas, nthetas, &p, info);
 	if (rc) return rc;
-	HostLik r = host_likelihood(ctx);
+	HostLik r = host_likelihood(ctx, ctx->newest());
 	if (r.status) return fail(ctx, r.status, "H^T C^-1 H is not positive definite");
 	rc = build_prediction_state(ctx, 0, ctx, p, r, thetas, nthetas);
 	if (rc) return rc;
@@ -1091,28 +1070,27 @@ extern "C" int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const do
 	const int Np = lead->Np, Rp = lead->Rp, nreg = lead->nreg;
 	// the components' right-hand-side rows [y_c | H]^T side by side (each context built its own at gpemu_set_model /
 	// gpemu_set_training, synchronously)
-	double *rr = nullptr;
-	const size_t rlen = (size_t)Rp * Np;
-	HIPCHK(lead, hipMalloc(&rr, (size_t)n * rlen * sizeof(double)));
-	hipError_t e = hipSuccess;
-	for (int c = 0; c < n && e == hipSuccess; c++)
-		e = hipMemcpyAsync(rr + (size_t)c * rlen, ctxs[c]->dRrows, rlen * sizeof(double), hipMemcpyDeviceToDevice, lead->stream);
-	int rc = GPEMU_OK;
-	if (e != hipSuccess) { lead->err = std::string("right-hand-side rows: ") + hipGetErrorString(e); rc = GPEMU_ERR_HIP; }
-	if (!rc) rc = stage_matrices(lead, ps.data(), n, 1, rr, (long)rlen);
-	if (!rc) rc = run_potrf(lead, 1);
-	if (!rc) rc = enqueue_results(lead);
-	if (!rc && hipStreamSynchronize(lead->stream) != hipSuccess) { lead->err = "stream synchronisation failed"; rc = GPEMU_ERR_HIP; }
-	hipFree(rr);
-	if (rc) return rc;
+	{
+		DevBuf<double> rr;                             // (released when the batch has been factored)
+		const size_t rlen = (size_t)Rp * Np;
+		HIPCHK(lead, rr.grow((size_t)n * rlen));
+		for (int c = 0; c < n; c++)
+			HIPCHK(lead, hipMemcpyAsync(rr + (size_t)c * rlen, ctxs[c]->dRrows, rlen * sizeof(double), hipMemcpyDeviceToDevice, lead->stream));
+		int rc = stage_matrices(lead, ps.data(), n, 1, rr, (long)rlen);
+		if (!rc) rc = run_potrf(lead, 1);
+		if (!rc) rc = enqueue_results(lead);
+		if (rc) return rc;
+		HIPCHK(lead, hipStreamSynchronize(lead->stream));
+	}
+	const ResSlot &res = lead->newest();               // the batch just factored
 	int worst = GPEMU_OK;
 	for (int c = 0; c < n; c++) {
-		const int inf = (lead->hInfo[c] >= INFO_NONE) ? 0 : lead->hInfo[c];
+		const int inf = (res.info[c] >= INFO_NONE) ? 0 : res.info[c];
 		if (info) info[c] = inf;
 		int st = GPEMU_OK;
 		if (inf) st = GPEMU_ERR_NOT_PD;
 		else {
-			HostLik r = host_likelihood(lead, c);
+			HostLik r = host_likelihood(lead, res, c);
 			if (r.status) st = r.status;
 			else {
 				st = build_prediction_state(lead, c, ctxs[c], ps[c], r, thetas + (size_t)c * nthetas, nthetas);
@@ -1162,16 +1140,10 @@ constexpr int PRED_SPLIT_MAX = 16;
 
 static int ensure_pred_batch(gpemu_ctx *ctx, int mb)
 {
-	if (ctx->pred_batch >= mb) return GPEMU_OK;
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	if (ctx->dKq) hipFree(ctx->dKq);
-	if (ctx->dV) hipFree(ctx->dV);
-	ctx->dKq = ctx->dV = nullptr; ctx->pred_batch = 0;
-	HIPCHK(ctx, hipMalloc(&ctx->dKq, (size_t)mb * ctx->Np * sizeof(double)));
+	const int rc = grow(ctx, ctx->dKq, (size_t)mb * ctx->Np);
+	if (rc) return rc;
 	// V also holds the split-K partial products of small batches: PRED_SPLIT_MAX slices of up to 128 query rows
-	HIPCHK(ctx, hipMalloc(&ctx->dV, (size_t)std::max(mb, 128 * PRED_SPLIT_MAX) * (ctx->Np + ctx->Rp) * sizeof(double)));
-	ctx->pred_batch = mb;
-	return GPEMU_OK;
+	return grow(ctx, ctx->dV, (size_t)std::max(mb, 128 * PRED_SPLIT_MAX) * (ctx->Np + ctx->Rp));
 }
 
 constexpr int PRED_BATCH_MAX = 16384;
@@ -1260,30 +1232,27 @@ extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *
 	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int d = ctx->d;
-	if (ctx->stage_cap < M) {
+	if (ctx->stage_cap() < (size_t)M) {
+		const size_t cap = (size_t)std::max(M, 64);
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->dXq) hipFree(ctx->dXq);
-		if (ctx->dMean) hipFree(ctx->dMean);
-		if (ctx->hStage) hipHostFree(ctx->hStage);
-		ctx->dXq = ctx->dMean = ctx->dVar = nullptr; ctx->hStage = nullptr; ctx->stage_cap = 0;
-		const int cap = std::max(M, 64);
-		HIPCHK(ctx, hipMalloc(&ctx->dXq, (size_t)cap * d * sizeof(double)));
-		HIPCHK(ctx, hipMalloc(&ctx->dMean, (size_t)2 * cap * sizeof(double)));    // means, then variances (one allocation: a small
-		ctx->dVar = ctx->dMean + cap;                                             // batch comes back in ONE copy)
-		HIPCHK(ctx, hipHostMalloc((void **)&ctx->hStage, (size_t)cap * (d + 2) * sizeof(double)));
-		ctx->stage_cap = cap;
+		ctx->hStage.reset();                           // (the capacity is zero until all three are there again)
+		int rc = grow(ctx, ctx->dXq, cap * d);
+		if (!rc) rc = grow(ctx, ctx->dMean, 2 * cap);
+		if (rc) return rc;
+		HIPCHK(ctx, ctx->hStage.grow(cap * (d + 2)));
 	}
-	double *hx = ctx->hStage, *hm = ctx->hStage + (size_t)ctx->stage_cap * d, *hv = hm + ctx->stage_cap;
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d, *hv = hm + cap;
 	memcpy(hx, xq, (size_t)M * d * sizeof(double));
 	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	int rc = gpemu_predict_batch_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar);
+	int rc = gpemu_predict_batch_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar());
 	if (rc) return rc;
-	if (ctx->stage_cap <= 1024) {
-		// (hm | hv on the host and dMean | dVar on the device have the same layout, stage_cap entries apart)
-		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, ((size_t)ctx->stage_cap + M) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (cap <= 1024) {
+		// (hm | hv on the host and dMean | dVar on the device have the same layout, cap entries apart)
+		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (cap + M) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	} else {
 		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	}
 	ctx->pred_pending = M;
 	return GPEMU_OK;
@@ -1294,7 +1263,7 @@ extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, 
 	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	const double *hm = ctx->hStage + (size_t)ctx->stage_cap * ctx->d, *hv = hm + ctx->stage_cap;
+	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
 	memcpy(mean, hm, (size_t)M * sizeof(double));
 	memcpy(var, hv, (size_t)M * sizeof(double));
 	ctx->pred_pending = 0;
@@ -1318,12 +1287,9 @@ static int build_corner(gpemu_ctx *ctx, int b0 = 0, int nbc = 1)
 {
 	const int Np = ctx->Np, Rp = ctx->Rp;
 	const size_t dim = (size_t)Np + Rp;
-	if (ctx->S_dim < dim || ctx->S_cap < nbc) {
-		if (ctx->dS) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->dS); ctx->dS = nullptr; }
-		ctx->S_dim = 0; ctx->S_cap = 0;
-		HIPCHK(ctx, hipMalloc(&ctx->dS, (size_t)nbc * dim * dim * sizeof(double)));
-		ctx->S_dim = dim; ctx->S_cap = nbc;
-	}
+	const int rc = grow(ctx, ctx->dS, (size_t)nbc * dim * dim);
+	if (rc) return rc;
+	ctx->S_dim = dim;
 	GemmArgs g;
 	memset(&g, 0, sizeof g);
 	g.C = ctx->dS; g.ldc = (long)ctx->S_dim;
@@ -1413,30 +1379,22 @@ static int grad_enqueue_chunk(gpemu_ctx *ctx, int b0, int nbc, const double *th_
 	const bool exact = (ctx->mode & GPEMU_MODE_EXACT_GRAD) != 0;
 	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;           // length-scale directions
 	const size_t gslot = (size_t)ctx->Np + 2 * GPEMU_MAX_PARAMS;    // per corner: alpha scratch | length thetas | beta
-	if (ctx->alpha_cap < nbc) {
-		if (ctx->dAlpha) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->dAlpha); ctx->dAlpha = nullptr; }
-		ctx->alpha_cap = 0;
-		HIPCHK(ctx, hipMalloc(&ctx->dAlpha, (size_t)nbc * gslot * sizeof(double)));
-		ctx->alpha_cap = nbc;
-	}
+	rc = grow(ctx, ctx->dAlpha, (size_t)nbc * gslot);
+	if (rc) return rc;
 	const int nt = (N + 63) / 64, ntiles = nt * (nt + 1) / 2;
 	const int np = 2 * d + 2;
 	const size_t need = (size_t)ntiles * np;
-	if (ctx->gradpart_len < need * nbc) {
-		if (ctx->dGradPart) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); hipFree(ctx->dGradPart); }
-		ctx->dGradPart = nullptr; ctx->gradpart_len = 0;
-		HIPCHK(ctx, hipMalloc(&ctx->dGradPart, need * nbc * sizeof(double)));
-		ctx->gradpart_len = need * nbc;
-	}
+	rc = grow(ctx, ctx->dGradPart, need * nbc);
+	if (rc) return rc;
 	// the length thetas of the chunk: from the pinned entry that belongs to this batch's hyper-parameter upload (reused
-	// only after param_ev of the entry, re-recorded below behind this copy)
-	double *gph = ctx->hGph + ((size_t)ctx->param_slot * GPEMU_MAX_BATCH + b0) * GPEMU_MAX_PARAMS;
+	// only after the entry's event, re-recorded below behind this copy)
+	double *gph = ctx->pring.gph + ((size_t)ctx->pring.slot * GPEMU_MAX_BATCH + b0) * GPEMU_MAX_PARAMS;
 	for (int i = 0; i < nbc; i++)
 		for (int k = 0; k < GPEMU_MAX_PARAMS; k++)
 			gph[(size_t)i * GPEMU_MAX_PARAMS + k] = k < nlen ? th_all[(size_t)(b0 + i) * nthetas + 2 + k] : 0.0;
 	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dAlpha + ctx->Np, gslot * sizeof(double), gph, GPEMU_MAX_PARAMS * sizeof(double),
 	                             GPEMU_MAX_PARAMS * sizeof(double), nbc, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(ctx, hipEventRecord(ctx->param_ev[ctx->param_slot], ctx->stream));
+	HIPCHK(ctx, hipEventRecord(ctx->pring.ev[ctx->pring.slot], ctx->stream));
 	if (exact)
 		HIPCHK(ctx, launch_beta_solve(ctx->stream, ctx->dRes + (size_t)b0 * ctx->res_len, (long)ctx->res_len, Rp, ctx->nreg, nbc,
 		                              ctx->dAlpha, (long)gslot, ctx->Np));
@@ -1479,41 +1437,37 @@ extern "C" int gpemu_loglik_grad_batch_enqueue(gpemu_ctx *ctx, int nb, const dou
 	if (rc) return rc;
 	rc = enqueue_results(ctx);                       // Gram, log det, info words -> the next slot of the pinned ring
 	if (rc) return rc;
-	const int slot = (int)((ctx->res_seq - 1) % gpemu_ctx::RES_RING);
+	ResSlot &s = ctx->newest();
 	// the ring entry becomes a collectable value+gradient batch only once EVERYTHING of it is on the stream: until then it
-	// is marked empty (res_nb = 0), so that after a failure below a later collect of this slot is refused
+	// is marked empty (nb = 0), so that after a failure below a later collect of this slot is refused
 	// (GPEMU_ERR_STATE) instead of returning a gradient built from whatever the pinned ring held
-	ctx->res_nb[slot] = 0;
-	ctx->res_kind[slot] = 1;
-	ctx->res_th[slot] = th;
-	ctx->res_nthetas[slot] = nthetas;
-	ctx->res_mode[slot] = ctx->mode;
+	s.nb = 0;
+	s.kind = 1;
+	s.th = th;
+	s.nthetas = nthetas;
+	s.mode = ctx->mode;
 	const int chunk = grad_chunk_size(ctx, nb);
 	for (int b0 = 0; b0 < nb; b0 += chunk) {
 		rc = grad_enqueue_chunk(ctx, b0, std::min(chunk, nb - b0), th.data(), nthetas);
 		if (rc) return rc;
 	}
-	HIPCHK(ctx, hipMemcpyAsync(ctx->hGradRing + (size_t)slot * ctx->batch_cap * gpemu_ctx::GRAD_NP_MAX, ctx->dGradSum,
-	                           (size_t)nb * gpemu_ctx::GRAD_NP_MAX * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipEventRecord(ctx->res_ev[slot], ctx->stream));     // (re-recorded: now behind the gradient sums as well)
-	ctx->res_nb[slot] = nb;
+	HIPCHK(ctx, hipMemcpyAsync(s.grad, ctx->dGradSum, (size_t)nb * gpemu_ctx::GRAD_NP_MAX * sizeof(double), hipMemcpyDeviceToHost,
+	                           ctx->stream));
+	HIPCHK(ctx, hipEventRecord(s.ev, ctx->stream));                  // (re-recorded: now behind the gradient sums as well)
+	s.nb = nb;
 	return GPEMU_OK;
 }
 
-// host half of a value+gradient batch whose results sit in ring slot `slot` (its event has been waited for)
-static int grad_collect_slot(gpemu_ctx *ctx, int slot, int nb, double *neg_loglik, double *sigma2, double *beta, double *grad,
+// host half of a value+gradient batch whose results sit in ring slot s (its event has been waited for)
+static int grad_collect_slot(gpemu_ctx *ctx, const ResSlot &s, int nb, double *neg_loglik, double *sigma2, double *beta, double *grad,
                              int *info, int *status)
 {
-	const int nthetas = ctx->res_nthetas[slot], ng = nthetas - 1, d = ctx->d;
-	const bool exact = (ctx->res_mode[slot] & GPEMU_MODE_EXACT_GRAD) != 0;       // as it was when the batch was enqueued
+	const int nthetas = s.nthetas, ng = nthetas - 1, d = ctx->d;
+	const bool exact = (s.mode & GPEMU_MODE_EXACT_GRAD) != 0;                     // as it was when the batch was enqueued
 	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;
-	const double *th_all = ctx->res_th[slot].data();
-	double *saveR = ctx->hRes;
-	int *saveI = ctx->hInfo;
-	ctx->hRes = ctx->hResRing + (size_t)slot * ctx->batch_cap * ctx->res_len;
-	ctx->hInfo = ctx->hInfoRing + (size_t)slot * ctx->batch_cap;
+	const double *th_all = s.th.data();
 	for (int b = 0; b < nb; b++) {
-		const int inf = (ctx->hInfo[b] >= INFO_NONE) ? 0 : ctx->hInfo[b];
+		const int inf = (s.info[b] >= INFO_NONE) ? 0 : s.info[b];
 		int st = GPEMU_OK;
 		if (info) info[b] = inf;
 		if (grad) for (int i = 0; i < ng; i++) grad[(size_t)b * ng + i] = NAN;
@@ -1523,7 +1477,7 @@ static int grad_collect_slot(gpemu_ctx *ctx, int slot, int nb, double *neg_logli
 		if (inf) {
 			st = fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
 		} else {
-			const HostLik r = host_likelihood(ctx, b);
+			const HostLik r = host_likelihood(ctx, s, b);
 			if (r.status) {
 				st = fail(ctx, r.status, "H^T C^-1 H is not positive definite");
 			} else {
@@ -1532,7 +1486,7 @@ static int grad_collect_slot(gpemu_ctx *ctx, int slot, int nb, double *neg_logli
 				if (sigma2) sigma2[b] = r.sigma2;
 				if (beta) for (int a = 0; a < ctx->nreg; a++) beta[(size_t)b * ctx->nreg + a] = r.beta[a];
 				if (grad) {
-					const double *sums = ctx->hGradRing + ((size_t)slot * ctx->batch_cap + b) * gpemu_ctx::GRAD_NP_MAX;
+					const double *sums = s.grad + (size_t)b * gpemu_ctx::GRAD_NP_MAX;
 					double *g = grad + (size_t)b * ng;
 					if (exact) {
 						// d(-logL)/dtheta = 1/2 sum_ab (A_ab - alpha_a alpha_b) dC_ab: slot nlen = nugget direction, slots < nlen the lengths
@@ -1551,7 +1505,6 @@ static int grad_collect_slot(gpemu_ctx *ctx, int slot, int nb, double *neg_logli
 		}
 		if (status) status[b] = st;
 	}
-	ctx->hRes = saveR; ctx->hInfo = saveI;
 	return GPEMU_OK;
 }
 
@@ -1562,11 +1515,11 @@ extern "C" int gpemu_loglik_grad_batch_collect_back(gpemu_ctx *ctx, int back, in
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (back < 0 || back >= gpemu_ctx::RES_RING || (unsigned long long)back >= ctx->res_seq)
 		return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
-	const int slot = (int)((ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING);
-	if (nb < 1 || nb != ctx->res_nb[slot]) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
-	if (ctx->res_kind[slot] != 1) return fail(ctx, GPEMU_ERR_STATE, "that batch is a likelihood batch: use gpemu_loglik_batch_collect_back");
-	HIPCHK(ctx, hipEventSynchronize(ctx->res_ev[slot]));
-	return grad_collect_slot(ctx, slot, nb, neg_loglik, sigma2, beta, grad, info, status);
+	const ResSlot &s = ctx->ring[(ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING];
+	if (nb < 1 || nb != s.nb) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
+	if (s.kind != 1) return fail(ctx, GPEMU_ERR_STATE, "that batch is a likelihood batch: use gpemu_loglik_batch_collect_back");
+	HIPCHK(ctx, hipEventSynchronize(s.ev));
+	return grad_collect_slot(ctx, s, nb, neg_loglik, sigma2, beta, grad, info, status);
 }
 
 extern "C" int gpemu_loglik_grad_batch_collect(gpemu_ctx *ctx, int nb, double *neg_loglik, double *sigma2, double *beta,
@@ -1665,14 +1618,20 @@ extern "C" int gpemu_trace_dump(gpemu_ctx *ctx, const char *path)
 // low-level compatibility entries: the reference's libRbind-era interface passes N x N matrices through host
 // memory (emulate-fns.c:275-299, regression.c:120-176, emulator.c:672-785).  The O(N^2)/O(N^3) work still runs here.
 // ---------------------------------------------------------------------------
+// scratch state for ONE n x n matrix of the caller's on ctx's stream, which it borrows: the sizes of that matrix, no model
+static void scratch_for_matrix(gpemu_ctx *tmp, const gpemu_ctx *ctx, int n)
+{
+	tmp->device = ctx->device; tmp->stream = ctx->stream; tmp->own_stream = false; tmp->use_graph = false; tmp->sched = ctx->sched;
+	tmp->Np = round_up(n, LEAF); tmp->Rp = 64; tmp->N = n; tmp->nrhs = 0; tmp->nb = 1;
+}
+
 // C -> C^-1 in place (both triangles), log det C = 2 sum log L_ii; *info = 1-based index of the first pivot <= 0
 extern "C" int gpemu_chol_inverse(gpemu_ctx *ctx, int n, double *a, int lda, double *logdet, int *info)
 {
 	if (!ctx || n < 1 || !a || lda < n) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	gpemu_ctx tmp;                       // scratch state on the caller's stream: sizes of this matrix, no model
-	tmp.device = ctx->device; tmp.stream = ctx->stream; tmp.use_graph = false; tmp.sched = ctx->sched;
-	tmp.Np = round_up(n, LEAF); tmp.Rp = 64; tmp.N = n; tmp.nrhs = 0; tmp.nb = 1;
+	gpemu_ctx tmp;
+	scratch_for_matrix(&tmp, ctx, n);
 	const int Np = tmp.Np, Rp = tmp.Rp;
 	const size_t rows = (size_t)2 * Np + Rp, dim = (size_t)Np + Rp;
 	std::vector<double> h((size_t)Np * Np, 0.0), diag((size_t)n);
@@ -1680,34 +1639,25 @@ extern "C" int gpemu_chol_inverse(gpemu_ctx *ctx, int n, double *a, int lda, dou
 		for (int j = 0; j <= i; j++)
 			h[(size_t)i * Np + j] = (i < n) ? a[(size_t)i * lda + j] : (i == j ? 1.0 : 0.0);
 	int big = INFO_NONE, inf = 0;
-	hipError_t e = hipMalloc(&tmp.dT, rows * Np * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc(&tmp.dInfo, sizeof(int));
-	if (e == hipSuccess) e = hipMalloc(&tmp.dS, dim * dim * sizeof(double));
-	if (e == hipSuccess) { tmp.S_dim = dim; tmp.S_cap = 1; }
-	if (e == hipSuccess) e = hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream);
-	if (e == hipSuccess) e = hipMemsetAsync(tmp.dT + (size_t)Np * Np, 0, (size_t)Rp * Np * 8, tmp.stream);
-	if (e == hipSuccess) e = launch_set_identity_rows(tmp.stream, tmp.dT + (size_t)(Np + Rp) * Np, Np, Np);
-	if (e == hipSuccess) e = hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream);
-	if (e == hipSuccess) e = potrf_rec(&tmp, 0, Np, 1);
-	if (e == hipSuccess) e = hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream);
-	if (e == hipSuccess)
-		e = hipMemcpy2DAsync(diag.data(), sizeof(double), tmp.dT, ((size_t)Np + 1) * sizeof(double), sizeof(double), n,
-		                     hipMemcpyDeviceToHost, tmp.stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(tmp.stream);
+	HIPCHK(ctx, tmp.dT.grow(rows * Np));
+	HIPCHK(ctx, tmp.dInfo.grow(1));
+	HIPCHK(ctx, tmp.dS.grow(dim * dim));
+	HIPCHK(ctx, hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream));
+	HIPCHK(ctx, hipMemsetAsync(tmp.dT + (size_t)Np * Np, 0, (size_t)Rp * Np * 8, tmp.stream));
+	HIPCHK(ctx, launch_set_identity_rows(tmp.stream, tmp.dT + (size_t)(Np + Rp) * Np, Np, Np));
+	HIPCHK(ctx, hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream));
+	HIPCHK(ctx, potrf_rec(&tmp, 0, Np, 1));
+	HIPCHK(ctx, hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(diag.data(), sizeof(double), tmp.dT, ((size_t)Np + 1) * sizeof(double), sizeof(double), n,
+	                             hipMemcpyDeviceToHost, tmp.stream));
+	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
 	const int bad = (inf >= INFO_NONE) ? 0 : inf;
-	if (e == hipSuccess && !bad) {
-		int rc = build_corner(&tmp);         // C^-1 = U U^T, lower triangle at (Rp, Rp) of the corner matrix
-		if (rc) e = hipErrorUnknown;
-		if (e == hipSuccess)
-			e = hipMemcpy2DAsync(a, (size_t)lda * sizeof(double), tmp.dS + (size_t)Rp * dim + Rp, dim * sizeof(double),
-			                     (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, tmp.stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(tmp.stream);
+	if (!bad) {
+		if (build_corner(&tmp)) return fail(ctx, GPEMU_ERR_HIP, tmp.err.c_str());   // C^-1 = U U^T, lower triangle at (Rp, Rp) of the corner
+		HIPCHK(ctx, hipMemcpy2DAsync(a, (size_t)lda * sizeof(double), tmp.dS + (size_t)Rp * dim + Rp, dim * sizeof(double),
+		                             (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, tmp.stream));
+		HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
 	}
-	if (tmp.dT) hipFree(tmp.dT);
-	if (tmp.dInfo) hipFree(tmp.dInfo);
-	if (tmp.dS) hipFree(tmp.dS);
-	tmp.dT = nullptr; tmp.dInfo = nullptr; tmp.dS = nullptr; tmp.stream = nullptr;
-	HIPCHK(ctx, e);
 	if (info) *info = bad;
 	if (bad) return fail(ctx, GPEMU_ERR_NOT_PD, "matrix is not positive definite");
 	double ld = 0.0;
@@ -1784,29 +1734,19 @@ extern "C" int gpemu_symm_apply(gpemu_ctx *ctx, int n, const double *a, int lda,
 	}
 	if (!current) {
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->sym_pad != Npad || !ctx->dSym) {
-			if (ctx->dSym) hipFree(ctx->dSym);
-			ctx->dSym = nullptr;
-			HIPCHK(ctx, hipMalloc(&ctx->dSym, (size_t)Npad * Npad * sizeof(double)));
-			ctx->sym_pad = Npad;
-			ctx->sym_vcap = 0;
-		}
+		const int rc = grow(ctx, ctx->dSym, (size_t)Npad * Npad);
+		if (rc) return rc;
+		ctx->sym_pad = Npad;
 		HIPCHK(ctx, hipMemsetAsync(ctx->dSym, 0, (size_t)Npad * Npad * sizeof(double), ctx->stream));
 		HIPCHK(ctx, hipMemcpy2DAsync(ctx->dSym, (size_t)Npad * sizeof(double), a, (size_t)lda * sizeof(double),
 		                             (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, ctx->stream));
 		if (!same_key) fp = matrix_checksum(a, n, lda);      // (a new matrix: its checksum for the calls that follow)
 		ctx->sym_key = a; ctx->sym_N = n; ctx->sym_lda = lda; ctx->sym_fp = fp;
 	}
-	if (ctx->sym_vcap < nvec) {
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->dSymV) hipFree(ctx->dSymV);
-		if (ctx->dSymOut) hipFree(ctx->dSymOut);
-		ctx->dSymV = ctx->dSymOut = nullptr; ctx->sym_vcap = 0;
-		const int cap = round_up(nvec, 64);
-		HIPCHK(ctx, hipMalloc(&ctx->dSymV, (size_t)cap * Npad * sizeof(double)));
-		HIPCHK(ctx, hipMalloc(&ctx->dSymOut, (size_t)cap * Npad * sizeof(double)));
-		ctx->sym_vcap = cap;
-	}
+	const size_t vlen = (size_t)round_up(nvec, 64) * Npad;
+	int rc = grow(ctx, ctx->dSymV, vlen);
+	if (!rc) rc = grow(ctx, ctx->dSymOut, vlen);
+	if (rc) return rc;
 	HIPCHK(ctx, hipMemsetAsync(ctx->dSymV, 0, (size_t)nvec * Npad * sizeof(double), ctx->stream));
 	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dSymV, (size_t)Npad * sizeof(double), v, (size_t)n * sizeof(double),
 	                             (size_t)n * sizeof(double), nvec, hipMemcpyHostToDevice, ctx->stream));
@@ -1829,18 +1769,14 @@ extern "C" int gpemu_derivative_gauss(gpemu_ctx *ctx, int n, const double *xcol,
 {
 	if (!ctx || n < 1 || !xcol || !out || ldo < n) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	double *dx = nullptr, *dout = nullptr;
-	HIPCHK(ctx, hipMalloc(&dx, (size_t)n * sizeof(double)));
-	hipError_t e = hipMalloc(&dout, (size_t)n * n * sizeof(double));
-	if (e == hipSuccess) e = hipMemcpyAsync(dx, xcol, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = launch_deriv_gauss(ctx->stream, dout, n, dx, n, theta_len);
-	if (e == hipSuccess)
-		e = hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double), dout, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n,
-		                     hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	hipFree(dx);
-	if (dout) hipFree(dout);
-	HIPCHK(ctx, e);
+	DevBuf<double> dx, dout;
+	HIPCHK(ctx, dx.grow((size_t)n));
+	HIPCHK(ctx, dout.grow((size_t)n * n));
+	HIPCHK(ctx, hipMemcpyAsync(dx, xcol, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, launch_deriv_gauss(ctx->stream, dout, n, dx, n, theta_len));
+	HIPCHK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double), dout, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n,
+	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 
@@ -1855,18 +1791,14 @@ extern "C" int gpemu_trace_product(gpemu_ctx *ctx, int n, const double *a, int l
 	int rc = gpemu_symm_apply(ctx, n, a, lda, 1, one.data(), tmp.data());      // makes sure a is resident in dSym
 	if (rc) return rc;
 	const int Npad = ctx->sym_pad;
-	double *dB = nullptr, *dPart = nullptr;
-	HIPCHK(ctx, hipMalloc(&dB, (size_t)Npad * Npad * sizeof(double)));
-	hipError_t e = hipMalloc(&dPart, (size_t)n * sizeof(double));
-	if (e == hipSuccess)
-		e = hipMemcpy2DAsync(dB, (size_t)Npad * sizeof(double), b, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double), n,
-		                     hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = launch_trace_product(ctx->stream, ctx->dSym, dB, Npad, n, dPart);
-	if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), dPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	hipFree(dB);
-	if (dPart) hipFree(dPart);
-	HIPCHK(ctx, e);
+	DevBuf<double> dB, dPart;
+	HIPCHK(ctx, dB.grow((size_t)Npad * Npad));
+	HIPCHK(ctx, dPart.grow((size_t)n));
+	HIPCHK(ctx, hipMemcpy2DAsync(dB, (size_t)Npad * sizeof(double), b, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double), n,
+	                             hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, launch_trace_product(ctx->stream, ctx->dSym, dB, Npad, n, dPart));
+	HIPCHK(ctx, hipMemcpyAsync(tmp.data(), dPart, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	double t = 0.0;
 	for (int i = 0; i < n; i++) t += tmp[i];
 	*trace = t;
@@ -1881,10 +1813,10 @@ extern "C" int gpemu_test_gemm_nt(gpemu_ctx *ctx, int m, int n, int k, double al
 {
 	if (!ctx || m < 1 || n < 1 || k < 1 || (k % GEMM_BK) != 0) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	double *da = nullptr, *db = nullptr, *dc = nullptr;
-	HIPCHK(ctx, hipMalloc(&da, (size_t)m * k * 8));
-	HIPCHK(ctx, hipMalloc(&db, (size_t)n * k * 8));
-	HIPCHK(ctx, hipMalloc(&dc, (size_t)m * n * 8));
+	DevBuf<double> da, db, dc;
+	HIPCHK(ctx, da.grow((size_t)m * k));
+	HIPCHK(ctx, db.grow((size_t)n * k));
+	HIPCHK(ctx, dc.grow((size_t)m * n));
 	HIPCHK(ctx, hipMemcpyAsync(da, a, (size_t)m * k * 8, hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(db, b, (size_t)n * k * 8, hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(dc, c, (size_t)m * n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1896,7 +1828,6 @@ extern "C" int gpemu_test_gemm_nt(gpemu_ctx *ctx, int m, int n, int k, double al
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(c, dc, (size_t)m * n * 8, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	hipFree(da); hipFree(db); hipFree(dc);
 	return GPEMU_OK;
 }
 
@@ -1954,10 +1885,10 @@ extern "C" int gpemu_test_gemm_bench(gpemu_ctx *ctx, int m, int n, int k, int ld
 	if (!ctx || m < 1 || n < 1 || k < 16 || (k % GEMM_BK) != 0 || reps < 1 || (cfg != 0 && cfg != 2 && cfg != 8)) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const long ld = std::max(std::max(k, n), ld_in);
-	double *da = nullptr, *dc = nullptr;
+	DevBuf<double> da, dc;
 	const size_t rows = (size_t)std::max(m, n);
-	HIPCHK(ctx, hipMalloc(&da, rows * ld * 8));
-	HIPCHK(ctx, hipMalloc(&dc, (size_t)m * ld * 8));
+	HIPCHK(ctx, da.grow(rows * ld));
+	HIPCHK(ctx, dc.grow((size_t)m * ld));
 	HIPCHK(ctx, launch_fill_random(ctx->stream, da, rows * ld, 1u));
 	HIPCHK(ctx, launch_fill_random(ctx->stream, dc, (size_t)m * ld, 2u));
 	if (getenv("GPEMU_BENCH_ZERO")) {      // zero operands: the clock-limited ceiling (no data-dependent switching power)
@@ -1990,7 +1921,6 @@ extern "C" int gpemu_test_gemm_bench(gpemu_ctx *ctx, int m, int n, int k, int ld
 	float ms = 0.f;
 	hipEventElapsedTime(&ms, e0, e1);
 	hipEventDestroy(e0); hipEventDestroy(e1);
-	hipFree(da); hipFree(dc);
 	HIPCHK(ctx, e);
 	if (ms_avg) *ms_avg = ms / reps;
 	if (flops) *flops = gemm_flops(g);
@@ -2001,30 +1931,23 @@ extern "C" int gpemu_test_potrf(gpemu_ctx *ctx, int n, double *a, int *info)
 {
 	if (!ctx || n < 1 || !a) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	// run through a scratch ctx-like state: temporarily adopt sizes
 	gpemu_ctx tmp;
-	tmp.device = ctx->device; tmp.stream = ctx->stream; tmp.use_graph = false; tmp.sched = ctx->sched;
-	tmp.Np = round_up(n, LEAF); tmp.Rp = 64; tmp.N = n; tmp.nrhs = 0;
+	scratch_for_matrix(&tmp, ctx, n);
 	const int Np = tmp.Np;
 	std::vector<double> h((size_t)(Np + 64) * Np, 0.0);
 	for (int i = 0; i < Np; i++)
 		for (int j = 0; j <= i; j++)
 			h[(size_t)i * Np + j] = (i < n) ? a[(size_t)i * n + j] : (i == j ? 1.0 : 0.0);
-	hipError_t e = hipMalloc(&tmp.dT, h.size() * 8);
-	if (e == hipSuccess) e = hipMalloc(&tmp.dInfo, sizeof(int));
-	int big = INFO_NONE;
-	if (e == hipSuccess) e = hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream);
-	if (e == hipSuccess) e = potrf_rec(&tmp, 0, Np, 0);
-	if (e == hipSuccess) e = hipStreamSynchronize(tmp.stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(h.data(), tmp.dT, h.size() * 8, hipMemcpyDeviceToHost, tmp.stream);
-	int inf = 0;
-	if (e == hipSuccess) e = hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(tmp.stream);
-	if (tmp.dT) hipFree(tmp.dT);
-	if (tmp.dInfo) hipFree(tmp.dInfo);
-	tmp.dT = nullptr; tmp.dInfo = nullptr; tmp.stream = nullptr;
-	HIPCHK(ctx, e);
+	HIPCHK(ctx, tmp.dT.grow(h.size()));
+	HIPCHK(ctx, tmp.dInfo.grow(1));
+	int big = INFO_NONE, inf = 0;
+	HIPCHK(ctx, hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream));
+	HIPCHK(ctx, hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream));
+	HIPCHK(ctx, potrf_rec(&tmp, 0, Np, 0));
+	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
+	HIPCHK(ctx, hipMemcpyAsync(h.data(), tmp.dT, h.size() * 8, hipMemcpyDeviceToHost, tmp.stream));
+	HIPCHK(ctx, hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream));
+	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
 	if (info) *info = (inf >= INFO_NONE) ? 0 : inf;
 	for (int i = 0; i < n; i++)
 		for (int j = 0; j < n; j++) a[(size_t)i * n + j] = (j <= i) ? h[(size_t)i * Np + j] : 0.0;

@@ -98,6 +98,52 @@ struct Sched {
 	int stagger_us = 20;         // GPEMU_STAGGER_US: first-round offset between the two workgroups of a CU in the 128x128 GEMM (0 = none)
 };
 
+// The one owner of device or pinned host memory in this library: move-only, released by the destructor, knows its element
+// count.  grow() is a compare when the capacity suffices; otherwise it releases and allocates afresh (contents are NOT
+// kept), and after a failed allocation the buffer is empty.  Reads as the plain pointer it holds.  Work that may still use
+// a context's buffer is waited for by the context's grow() (gpemu_api.hip), not here.
+struct DeviceMem {
+	static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+	static hipError_t release(void *p) { return hipFree(p); }
+};
+struct PinnedMem {
+	static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes); }
+	static hipError_t release(void *p) { return hipHostFree(p); }
+};
+
+template <class T, class Mem>
+class Buf {
+	T *p_ = nullptr;
+	size_t n_ = 0;
+public:
+	Buf() = default;
+	Buf(Buf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+	Buf &operator=(Buf &&o) noexcept
+	{
+		if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+		return *this;
+	}
+	~Buf() { reset(); }
+	operator T *() const { return p_; }
+	size_t size() const { return n_; }
+	void reset()
+	{
+		if (p_) (void)Mem::release(p_);
+		p_ = nullptr; n_ = 0;
+	}
+	hipError_t grow(size_t n)
+	{
+		if (n <= n_) return hipSuccess;
+		reset();
+		const hipError_t e = Mem::alloc((void **)&p_, n * sizeof(T));
+		if (e != hipSuccess) { p_ = nullptr; return e; }
+		n_ = n;
+		return hipSuccess;
+	}
+};
+template <class T> using DevBuf = Buf<T, DeviceMem>;
+template <class T> using PinnedBuf = Buf<T, PinnedMem>;
+
 struct ProfState {
 	int cls = GPEMU_PROF_NONE;
 	std::vector<hipEvent_t> ev;   // pairs
@@ -106,51 +152,71 @@ struct ProfState {
 	std::vector<std::string> tag;  // one label per launch (GPEMU_PROF_DUMP=1 prints them with their times)
 };
 
+// One entry of the result ring: the results of an enqueued batch stay readable while the next RES_RING - 1 are enqueued.
+struct ResSlot {
+	hipEvent_t ev = nullptr;     // recorded behind the copies into the slot
+	int nb = 0;                  // batch size; 0: nothing collectable here
+	int kind = 0;                // 0: likelihood batch, 1: value+gradient batch
+	std::vector<double> th;      // value+gradient batches: the thetas they were enqueued with (theta[0] = 0)
+	int nthetas = 0;
+	int mode = 0;                // the context's mode flags when the batch was enqueued
+	double *res = nullptr;       // the slot's part of the three pinned rings (set by ensure_batch_slots):
+	int *info = nullptr;         //   nb x res_len results, nb info words,
+	double *grad = nullptr;      //   nb x GRAD_NP_MAX gradient sums
+};
+
+// Pinned upload ring of the hyper-parameters: an entry is reused once the copies out of it have executed.
+struct ParamRing {
+	static constexpr unsigned RING = 4;
+	PinnedBuf<CovParams> params;     // RING x GPEMU_MAX_BATCH
+	PinnedBuf<double> gph;           // the length thetas of value+gradient batches: RING x GPEMU_MAX_BATCH x GPEMU_MAX_PARAMS
+	hipEvent_t ev[RING] = {};        // recorded behind the copies out of an entry
+	unsigned next = 0;
+	unsigned slot = 0;               // entry of the batch being enqueued
+};
+
 } // namespace gpemu
 
 struct gpemu_ctx {
+	gpemu_ctx() = default;
+	~gpemu_ctx();                      // waits for the stream, then releases everything (gpemu_api.hip)
 	int device = 0;
 	hipStream_t stream = nullptr;      // the context's one stream: every launch and copy of the context is ordered on it
+	bool own_stream = true;            // false: borrowed from another context (the matrix-only entries), not destroyed with this one
 	gpemu::Sched sched;                // schedule switches, fixed at creation
 	std::string err;
 
 	// model
 	int kind = 0, order = 0, N = 0, d = 0, nreg = 0, nrhs = 0;
 	int Np = 0, Rp = 0;
-	double *dX = nullptr;        // N x d
-	double *dXg = nullptr;       // N x d, centred per dimension (x - mid_k): operands of the Gram-form fill
-	double *dMid = nullptr;      // d: the centres mid_k (the Gram-form k-vectors centre their query rows with them)
+	gpemu::DevBuf<double> dX;    // N x d
+	gpemu::DevBuf<double> dXg;   // N x d, centred per dimension (x - mid_k): operands of the Gram-form fill
+	gpemu::DevBuf<double> dMid;  // d: the centres mid_k (the Gram-form k-vectors centre their query rows with them)
 	std::vector<double> xhalf;   // d: half range of each design coordinate
-	double *dY = nullptr;        // N
-	double *dRrows = nullptr;    // Rp x Np : row 0 = y, rows 1..nreg = H columns, zero padded
+	gpemu::DevBuf<double> dY;    // N
+	gpemu::DevBuf<double> dRrows; // Rp x Np : row 0 = y, rows 1..nreg = H columns, zero padded
 	std::vector<double> hX, hY;
 
-	// factorisation workspace: tall matrix T (rows x Np)
-	double *dT = nullptr;
-	size_t T_rows = 0;           // allocated rows (all matrices of a batch together)
+	// factorisation workspace: tall matrix T (all matrices of a batch together)
+	gpemu::DevBuf<double> dT;
 	int nb = 1;                  // matrices factored in lock-step by the current / last factorisation
 	size_t T_stride = 0;         // elements between consecutive matrices of the batch
-	int batch_cap = 0;           // allocated per-matrix result slots (dInfo, dGramPart, dRes, hRes, hInfo)
-	int *dInfo = nullptr;
-	double *dGramPart = nullptr; // [Np/128][Rp*Rp]
-	double *dRes = nullptr;      // Rp*Rp gram + logdet + spare
-	double *hRes = nullptr;      // pinned mirror: the newest slot of the ring below
-	int *hInfo = nullptr;        // pinned, likewise
-	static constexpr int RES_RING = 4;   // result slots: batch j stays readable while j+1 .. j+3 are enqueued
-	double *hResRing = nullptr;  // RES_RING x batch_cap x res_len
-	int *hInfoRing = nullptr;    // RES_RING x batch_cap
-	hipEvent_t res_ev[RES_RING] = {nullptr, nullptr, nullptr, nullptr};   // recorded behind the copies into a slot
-	int res_nb[RES_RING] = {0, 0, 0, 0};
-	int res_kind[RES_RING] = {0, 0, 0, 0};          // 0: likelihood batch, 1: value+gradient batch
-	std::vector<double> res_th[RES_RING];           // value+gradient batches: the thetas they were enqueued with (theta[0] = 0)
-	int res_nthetas[RES_RING] = {0, 0, 0, 0};
-	int res_mode[RES_RING] = {0, 0, 0, 0};          // the context's mode flags when the batch was enqueued
+	gpemu::DevBuf<double> dGramPart; // batch_cap() x [Np/64][Rp*Rp]: sized by model and batch, gone with the model
+
+	// per-matrix result slots, sized by the largest batch so far and kept across models (ensure_batch_slots)
+	gpemu::DevBuf<double> dRes;  // per matrix: Rp*Rp gram + logdet + spare
+	static constexpr int RES_RING = 4;
 	static constexpr int GRAD_NP_MAX = 2 * GPEMU_MAX_PARAMS + 2;   // reduced gradient sums per batch element
-	double *dGradSum = nullptr;  // batch_cap x GRAD_NP_MAX
-	double *hGradRing = nullptr; // pinned, RES_RING x batch_cap x GRAD_NP_MAX
-	double *hGph = nullptr;      // pinned upload ring of the length thetas: PARAM_RING x GPEMU_MAX_BATCH x GPEMU_MAX_PARAMS
-	unsigned param_slot = 0;     // ring entry of the hyper-parameter upload of the batch being enqueued
-	unsigned long long res_seq = 0;      // batches enqueued since the ring was (re)allocated
+	gpemu::PinnedBuf<double> hResRing;  // RES_RING x batch_cap() x res_len
+	gpemu::PinnedBuf<int> hInfoRing;    // RES_RING x batch_cap()
+	gpemu::DevBuf<double> dGradSum;     // batch_cap() x GRAD_NP_MAX
+	gpemu::PinnedBuf<double> hGradRing; // RES_RING x batch_cap() x GRAD_NP_MAX
+	gpemu::DevBuf<int> dInfo;           // batch_cap() info words
+	int batch_cap() const { return (int)dInfo.size(); }   // (dInfo is allocated last: its size says that all of them are there)
+	gpemu::ResSlot ring[RES_RING];
+	unsigned long long res_seq = 0;     // batches enqueued since the ring was (re)allocated
+	gpemu::ResSlot &newest() { return ring[(res_seq + RES_RING - 1) % RES_RING]; }
+	gpemu::ParamRing pring;
 	size_t res_len = 0;
 
 	// cached launch graphs for potrf, keyed by (Np, rows_total, with_inverse)
@@ -163,45 +229,41 @@ struct gpemu_ctx {
 
 	// prediction state
 	bool pred_ready = false;
-	double *dLinvAug = nullptr;  // (Np + Rp) x Np : rows [0,Np) = L^-1, row Np = gamma, rows Np+1.. = W^T
-	double *dBetaQ = nullptr;    // beta (nreg) then Q (nreg*nreg)
+	gpemu::DevBuf<double> dLinvAug;  // (Np + Rp) x Np : rows [0,Np) = L^-1, row Np = gamma, rows Np+1.. = W^T
+	gpemu::DevBuf<double> dBetaQ;    // beta (nreg) then Q (nreg*nreg)
 	double kappa = 0;
 	gpemu::CovParams pred_cov;
 	std::vector<double> h_beta, h_Q;
-	double *dKq = nullptr, *dV = nullptr; // batch buffers
-	int pred_batch = 0;
-	double *dXq = nullptr, *dMean = nullptr, *dVar = nullptr; // staging for host-buffer entry
-	int stage_cap = 0;
-	double *hStage = nullptr;    // pinned: stage_cap*d query coordinates, then stage_cap means, then stage_cap variances
+	gpemu::DevBuf<double> dKq, dV;   // batch buffers
+	// staging for the host-buffer entry, stage_cap() queries: dXq coordinates; dMean means, then variances (one allocation: a
+	// small batch comes back in ONE copy); hStage pinned, coordinates, then means, then variances
+	gpemu::DevBuf<double> dXq, dMean;
+	gpemu::PinnedBuf<double> hStage;
+	size_t stage_cap() const { return hStage.size() / (size_t)(d + 2); }   // (hStage is allocated last, and gone with the model)
+	double *dVar() const { return dMean + stage_cap(); }
 	int pred_pending = 0;        // queries of an enqueued, not yet collected prediction batch
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
-	double *dS = nullptr;        // S_cap corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
-	size_t S_dim = 0;
-	int S_cap = 0;
+	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
+	size_t S_dim = 0;            // their side and leading dimension
 
 	// gradient scratch
-	double *dGradPart = nullptr;
+	gpemu::DevBuf<double> dGradPart;   // tile partial sums of all corners in flight
 	// gpemu_symm_apply: a host-resident symmetric matrix kept on the device between calls
-	double *dSym = nullptr, *dSymV = nullptr, *dSymOut = nullptr;
+	gpemu::DevBuf<double> dSym, dSymV, dSymOut;
 	const double *sym_key = nullptr;
-	int sym_N = 0, sym_lda = 0, sym_pad = 0, sym_vcap = 0;
+	int sym_N = 0, sym_lda = 0, sym_pad = 0;   // sym_pad: padded side and leading dimension of dSym, dSymV, dSymOut
 	uint64_t sym_fp = 0;          // checksum of every element of the cached host matrix
 	bool sym_pinned = false;      // gpemu_symm_pin: the caller vouches for the buffer, no per-call checksum
-	gpemu::CovParams *dParams = nullptr;   // hyper-parameters of the batch elements (GPEMU_MAX_BATCH slots)
-	gpemu::CovParams *hParams = nullptr;   // pinned upload ring: PARAM_RING x GPEMU_MAX_BATCH slots, one event per ring entry
-	hipEvent_t param_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	unsigned param_next = 0;
-	double *dAlpha = nullptr;    // gradient, per corner in flight: Np doubles of alpha = C^-1 y, then GPEMU_MAX_PARAMS length thetas
-	int alpha_cap = 0;
-	size_t gradpart_len = 0;     // doubles of dGradPart (all corners)
+	gpemu::DevBuf<gpemu::CovParams> dParams;   // hyper-parameters of the batch elements (GPEMU_MAX_BATCH slots)
+	gpemu::DevBuf<double> dAlpha;    // gradient, per corner in flight: Np doubles of alpha = C^-1 y, then GPEMU_MAX_PARAMS length thetas
 
 	int mode = 0;                 // GPEMU_MODE_* flags (gpemu_set_mode; defaults from the environment)
 	gpemu::ProfState prof;
 	// GPEMU_TRACE=1: per-launch device timestamps (wall_clock64) written by the kernels themselves, so that the
 	// concurrent timeline of several contexts can be read (rocprofv3 serialises kernels)
-	unsigned long long *dTrace = nullptr;
+	gpemu::DevBuf<unsigned long long> dTrace;
 	int trace_cap = 0, trace_next = 0;
 	std::vector<std::string> trace_tag;
 	std::vector<double> last_thetas;

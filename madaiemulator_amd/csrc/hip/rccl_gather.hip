@@ -186,9 +186,9 @@ extern "C" int gpemu_rccl_comm_allgather(void *comm, const double *send, int cou
 	(void)hipGetDevice(&cur);
 	if (hipSetDevice(S->device) != hipSuccess) { (void)hipGetLastError(); return fail(errbuf, errlen, GPEMU_ERR_HIP, "hipSetDevice failed"); }
 	(void)hipGetLastError();
-	double *dsend = nullptr, *drecv = nullptr;
-	hipError_t h = hipMalloc(&dsend, (size_t)count * sizeof(double));
-	if (h == hipSuccess) h = hipMalloc(&drecv, (size_t)count * S->world * sizeof(double));
+	gpemu::DevBuf<double> dsend, drecv;
+	hipError_t h = dsend.grow((size_t)count);
+	if (h == hipSuccess) h = drecv.grow((size_t)count * S->world);
 	if (h == hipSuccess) h = hipMemcpyAsync(dsend, send, (size_t)count * sizeof(double), hipMemcpyHostToDevice, S->stream);
 	int rc = GPEMU_OK;
 	std::string msg;
@@ -202,8 +202,8 @@ extern "C" int gpemu_rccl_comm_allgather(void *comm, const double *send, int cou
 		if (h == hipSuccess) h = hipStreamSynchronize(S->stream);
 		if (h != hipSuccess) { rc = GPEMU_ERR_HIP; msg = std::string("gather results: ") + hipGetErrorString(h); }
 	}
-	if (dsend) hipFree(dsend);
-	if (drecv) hipFree(drecv);
+	dsend.reset();
+	drecv.reset();
 	(void)hipGetLastError();
 	(void)hipSetDevice(cur);
 	return rc == GPEMU_OK ? GPEMU_OK : fail(errbuf, errlen, rc, msg);

@@ -1478,6 +1478,56 @@ def test_model_switching_soak_is_deterministic():
         c.close()
 
 
+def _free_device_bytes():
+    import ctypes
+    fr, tot = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert abi.load().gpemu_device_memory(0, ctypes.byref(fr), ctypes.byref(tot)) == 0
+    return fr.value
+
+
+def _context_life_cycle():
+    """one context from creation to destruction with every kind of storage it can own in use; returns free bytes before - after"""
+    before = _free_device_bytes()
+    c = abi.Context(0)
+    N, d = 1000, 3
+    X, y = synth.design(N, d, 11)
+    c.set_model(1, 1, X, y)
+    th = thetas_for(1, d)
+    ths = np.array([synth.perturbed_thetas(1, d, 5, i) for i in range(3)])
+    assert np.all(c.loglik_batch(ths)["status"] == 0)                       # workspace, result slots, upload ring
+    th0 = np.concatenate([[0.0], th[1:]])
+    assert np.all(np.isfinite(c.loglik_grad_batch(np.array([th0, th0]))["grad"]))   # inverse rows, corners, gradient scratch
+    c.predict_setup(th)
+    m, v = c.predict(synth.queries(300, d, 7))                              # prediction state, sweep and staging buffers
+    assert np.all(np.isfinite(m)) and np.all(np.isfinite(v))
+    rng = np.random.default_rng(3)
+    B = rng.standard_normal((200, 200))
+    A = B @ B.T / 200 + np.eye(200) * 0.5
+    inv, _, info, rc = c.chol_inverse(A)                                    # the scratch state of the matrix-only entries
+    assert rc == 0 and info == 0
+    assert np.all(np.isfinite(c.symm_apply(inv, rng.standard_normal((3, 200)))))   # the symmetric-matrix cache
+    c.close()
+    return before - _free_device_bytes()
+
+
+# Free device memory that a context's life cycle may cost.  The yardstick is the library before its buffers had owners (every
+# allocation released by hand): the same cycles there, in a process of their own, lost 195035136 bytes over the first and 0
+# over each of the next three, twice over.  The first cycle of a process pays for the runtime's pools and this library's code
+# objects, which stay; a later one starts from them, and so does the first when other tests have run before it.
+# (Free bytes are the device's, not the process's: another process on the device moves them.)
+LIFE_CYCLE_FIRST_MAX = 195035136
+LIFE_CYCLE_LATER_MAX = 0
+
+
+def test_context_life_cycle_returns_device_memory():
+    """free device memory (gpemu_device_memory) before a context is created and after it is destroyed, with a likelihood
+    batch, a value+gradient batch, a prediction set-up and sweep, gpemu_chol_inverse and gpemu_symm_apply in between"""
+    first = _context_life_cycle()
+    later = _context_life_cycle()
+    print(f"free bytes lost over a context's life cycle: first {first}, later {later}")
+    assert first <= LIFE_CYCLE_FIRST_MAX and later <= LIFE_CYCLE_LATER_MAX, (first, later)
+
+
 # ------------------------------------------------------------------ error behaviour at the boundary
 def test_error_codes(gpu_ctx):
     X, y = synth.design(50, 2, 1)
