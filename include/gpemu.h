@@ -216,6 +216,22 @@ int gpemu_predict_batch_collect(gpemu_ctx *ctx, int npoints, double *mean, doubl
 int gpemu_predict_batch_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev,
                             double *mean_dev, double *var_dev);
 
+/* ---- leave-one-out validation of a trained emulator -----------------
+ * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
+ * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
+ * including the nugget: emulator.c:672-785, emulator_struct.c:124-143), from the state gpemu_predict_setup[_batch] left
+ * in HBM, in closed form (Dubrule 1983, universal kriging).  With P = C^-1 - W Q W^T, W = C^-1 H, Q = (H^T C^-1 H)^-1:
+ *   P_ii = sum_{k >= i} (L^-1)_ki^2 - w_i^T Q w_i,   var_i = 1 / P_ii,   mean_i = y_i - gamma_i / P_ii
+ * One pass over the lower triangle of L^-1 (8 N (N+1) / 2 bytes) instead of N factorisations.
+ * One difference from the refit: the closed form works on the matrix C, whose elements are not clamped, while the refit's
+ * k-vector (makeKVector_fnptr, emulator.c:588-590) zeroes entries below 1e-10.  Where no off-diagonal element of C is
+ * below 1e-10 the two agree to rounding; where some are, they differ by at most the effect of those entries.
+ * GPEMU_ERR_STATE without a valid prediction set-up; GPEMU_ERR_ARG when N <= nreg + 1 (no degrees of freedom are left with
+ * one point removed) or an output is NULL.  Two calls on the same state return the same bits. */
+int gpemu_loo(gpemu_ctx *ctx, double *mean /* N host */, double *var /* N host */);
+/* the same with result buffers in HBM (device pointers): only enqueues on the context's stream, no host sync */
+int gpemu_loo_dev(gpemu_ctx *ctx, double *mean_dev, double *var_dev);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */
@@ -257,6 +273,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_POTRF   4   /* whole factorisation (graph launch) */
 #define GPEMU_PROF_GEMM_BIG 5  /* only the GEMM launches on the 128x128 8-wave kernel (the dominant kernel of a batch) */
 #define GPEMU_PROF_GEMM_K512 6 /* only the GEMM launches with a contraction length >= 512 */
+#define GPEMU_PROF_LOO     7   /* the two launches of gpemu_loo[_dev]: column sums over L^-1 (bytes = 8 N (N+1) / 2), finish */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

@@ -15,6 +15,7 @@ POWEREXP, MATERN32, MATERN52 = 1, 2, 3
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_PD, ERR_REGRESSION, ERR_STATE = range(7)
 PROF_NONE, PROF_GEMM, PROF_FILL, PROF_LEAF, PROF_POTRF, PROF_GEMM_BIG, PROF_GEMM_K512 = range(7)
+PROF_LOO = 7
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -59,6 +60,8 @@ SYMBOLS = {
     "gpemu_predict_batch_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_batch_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "gpemu_predict_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -322,6 +325,15 @@ class Context:
         m, v = np.empty(self._npred), np.empty(self._npred)
         self._chk(self.L.gpemu_predict_batch_collect(self.h, self._npred, _p(m), _p(v)))
         return m, v
+
+    def loo(self):
+        """leave-one-out mean and variance at every training point, from the resident prediction state -> (mean, var)"""
+        m, v = np.empty(self.N), np.empty(self.N)
+        self._chk(self.L.gpemu_loo(self.h, _p(m), _p(v)))
+        return m, v
+
+    def loo_dev(self, mean_dev, var_dev):
+        self._chk(self.L.gpemu_loo_dev(self.h, mean_dev, var_dev))
 
     def chol_inverse(self, A):
         A = _a(A).copy()

@@ -245,9 +245,11 @@ static void free_model(gpemu_ctx *ctx)
 {
 	free_graphs(ctx);
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
-	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha})
+	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
+	                &ctx->dLooPart, &ctx->dLoo})
 		b->reset();
 	ctx->hStage.reset();
+	ctx->hLoo.reset();
 	ctx->pred_ready = false; ctx->cinv_ready = false;
 	ctx->pred_pending = 0;
 	ctx->S_dim = 0;
@@ -1276,6 +1278,52 @@ extern "C" int gpemu_predict_batch(gpemu_ctx *ctx, int M, const double *xq, doub
 	int rc = gpemu_predict_batch_enqueue(ctx, M, xq);
 	if (rc) return rc;
 	return gpemu_predict_batch_collect(ctx, M, mean, var);
+}
+
+// ---------------------------------------------------------------------------
+// leave-one-out prediction at every training point (gpemu.h): one pass over the lower triangle of the resident L^-1 and a
+// finishing launch, on the context's stream.  Touches only what the context owns (dLinvAug, dBetaQ, dY and its own
+// scratch), so a context whose state came from gpemu_predict_setup_batch is served like any other.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_loo_dev(gpemu_ctx *ctx, double *mean_dev, double *var_dev)
+{
+	if (!ctx || !mean_dev || !var_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	const int N = ctx->N, Np = ctx->Np, nreg = ctx->nreg;
+	if (N <= nreg + 1) return fail(ctx, GPEMU_ERR_ARG, "leave-one-out needs N > nregression_fns + 1");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = grow(ctx, ctx->dLooPart, loo_scratch_elems(N, Np));
+	if (rc) return rc;
+	if (prof_on(ctx, GPEMU_PROF_LOO)) { ctx->prof.tag.push_back("loo_colsq"); ctx->prof.tag.push_back("loo_finish"); }
+	{
+		ProfScope ps(ctx, GPEMU_PROF_LOO, (double)N * (N + 1), 8.0 * ((double)N * (N + 1) / 2));
+		HIPCHK(ctx, launch_loo_colsq(ctx->stream, ctx->dLinvAug, Np, N, Np, ctx->dLooPart));
+	}
+	{
+		// the partials (lower half of the chunk x column table), gamma and the W^T rows, y in; mean and variance out
+		ProfScope ps(ctx, GPEMU_PROF_LOO, 2.0 * N * nreg * nreg,
+		             8.0 * ((double)loo_scratch_elems(N, Np) / 2 + (double)N * (nreg + 4)));
+		HIPCHK(ctx, launch_loo_finish(ctx->stream, ctx->dLooPart, ctx->dLinvAug, Np, N, Np, nreg, ctx->dBetaQ, ctx->dY, mean_dev,
+		                              var_dev));
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_loo(gpemu_ctx *ctx, double *mean, double *var)
+{
+	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	const size_t N = (size_t)ctx->N;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	int rc = grow(ctx, ctx->dLoo, 2 * N);
+	if (!rc) rc = grow(ctx, ctx->hLoo, 2 * N);
+	if (!rc) rc = gpemu_loo_dev(ctx, ctx->dLoo, ctx->dLoo + N);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(ctx->hLoo, ctx->dLoo, 2 * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	memcpy(mean, ctx->hLoo, N * sizeof(double));
+	memcpy(var, ctx->hLoo + N, N * sizeof(double));
+	return GPEMU_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -245,6 +245,9 @@ struct gpemu_ctx {
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
+	// leave-one-out (gpemu_loo): partial column sums; means then variances (N each) on the device and in pinned memory
+	gpemu::DevBuf<double> dLooPart, dLoo;
+	gpemu::PinnedBuf<double> hLoo;
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
 
@@ -325,5 +328,11 @@ hipError_t launch_gram_partials(hipStream_t s, const double *Z, long ld, int Np,
                                 int nbatch = 1, long zstride = 0);
 hipError_t launch_finish(hipStream_t s, const double *part, int nparts, int Rp, int nrhs, const double *T, long ld,
                          int N, double *res, int nbatch = 1, long tstride = 0, long rstride = 0);
+// leave-one-out (gpemu_loo): column sums of squares of the lower triangle of L^-1 as partials per (row chunk, column), then
+// their fixed-order sum with the regression term, mean and variance per training point.  part: loo_scratch_elems doubles.
+size_t loo_scratch_elems(int N, int Np);
+hipError_t launch_loo_colsq(hipStream_t s, const double *LinvAug, long ld, int N, int Np, double *part);
+hipError_t launch_loo_finish(hipStream_t s, const double *part, const double *LinvAug, long ld, int N, int Np, int nreg,
+                             const double *betaQ, const double *y, double *mean, double *var);
 
 } // namespace gpemu

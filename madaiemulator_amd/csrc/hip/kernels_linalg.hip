@@ -1493,4 +1493,118 @@ hipError_t launch_finish(hipStream_t s, const double *part, int nparts, int Rp, 
 	return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Leave-one-out prediction at every training point from the resident prediction state (Dubrule 1983; gpemu_loo).
+//   P = C^-1 - W Q W^T,  P_ii = sum_{k >= i} (L^-1)_ki^2 - w_i^T Q w_i,  var_i = 1 / P_ii,  mean_i = y_i - gamma_i / P_ii
+// Stage 1, loo_colsq_kernel: sums of squares down the columns of the lower triangle of L^-1 (rows [0, N) of LinvAug, row
+// stride ld).  The matrix is row-major, so a wave reads 128 consecutive doubles of one row with 16-byte loads and every
+// lane keeps the sums of its own two columns while the wave walks down LOO_RC rows; a workgroup is four waves side by
+// side (LOO_SW = 512 columns, 4 KB of a row), a grid entry one (column strip, row chunk) pair at or below the strip's
+// diagonal -- the others are not launched.  What lies above the diagonal of L^-1 (transpose of the factorisation's U:
+// exact zeros inside the diagonal tiles, which the prediction product relies on, unspecified further out) is never
+// added: a load is issued only for a pair of columns (c, c + 1) with c <= row, and of the pair that holds the diagonal
+// the element (row, row + 1) is masked.  Rows and columns N .. Np (the identity pad) are left out.
+// part[chunk][column], written for every launched (strip, chunk) and all its columns < Np, zeros included.
+// No atomics and no waiting between workgroups: stage 2 adds the partials of a column in a fixed order.
+// ---------------------------------------------------------------------------
+constexpr int LOO_RC = 64;        // rows per chunk
+constexpr int LOO_SW = 512;       // columns per strip: 4 waves x 64 lanes x 2
+constexpr int LOO_UNROLL = 8;     // independent 16-byte loads per lane in flight
+
+__global__ __launch_bounds__(256) void loo_colsq_kernel(const double *Linv, long ld, int N, int Np, int nchunks, double *part)
+{
+	// grid entry -> (strip s, chunk c >= s * LOO_SW / LOO_RC); strip s owns nchunks - s * (LOO_SW / LOO_RC) entries
+	int s = 0, c = blockIdx.x;
+	for (;;) {
+		const int own = nchunks - s * (LOO_SW / LOO_RC);
+		if (c < own) break;
+		c -= own;
+		s++;
+	}
+	c += s * (LOO_SW / LOO_RC);
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int col = s * LOO_SW + wave * 128 + lane * 2;
+	if (col >= Np) return;                                 // (Np is even: the pair is inside the row or wholly outside)
+	const int r0 = c * LOO_RC;
+	const int r1 = min(r0 + LOO_RC, N);
+	double a0 = 0.0, a1 = 0.0;
+	for (int r = r0; r < r1; r += LOO_UNROLL) {
+		double2 v[LOO_UNROLL];
+#pragma unroll
+		for (int u = 0; u < LOO_UNROLL; u++) {
+			const int row = r + u;
+			v[u] = make_double2(0.0, 0.0);
+			if (row < r1 && col <= row) v[u] = *reinterpret_cast<const double2 *>(Linv + (long)row * ld + col);
+		}
+#pragma unroll
+		for (int u = 0; u < LOO_UNROLL; u++) {
+			a0 = fma(v[u].x, v[u].x, a0);
+			if (col + 1 <= r + u) a1 = fma(v[u].y, v[u].y, a1);
+		}
+	}
+	*reinterpret_cast<double2 *>(part + (long)c * Np + col) = make_double2(a0, a1);
+}
+
+// Stage 2, loo_finish_kernel: 64 training points per workgroup, four threads per point.  Thread (point i, quarter g) adds
+// the partials of column i over its quarter of the chunks in chunk order and the rows a = g, g + 4, ... of w_i^T Q w_i
+// (w_i from the W^T rows of LinvAug, staged in LDS; Q from betaQ); the four shares are then added in the order 0, 1, 2, 3.
+// Every sum has one fixed order, so two calls give the same bits.
+__global__ __launch_bounds__(256) void loo_finish_kernel(const double *part, int nchunks, const double *LinvAug, long ld, int N,
+                                                         int Np, int nreg, const double *betaQ, const double *y, double *mean,
+                                                         double *var)
+{
+	__shared__ double ws[63 * 64];
+	__shared__ double ssq[4 * 64], sreg[4 * 64];
+	const int tid = threadIdx.x, li = tid & 63, g = tid >> 6;
+	const int i0 = blockIdx.x * 64, i = i0 + li;           // (i < Np always: the grid covers ceil(N / 64) <= Np / 64 blocks)
+	const double *Wt = LinvAug + (long)(Np + 1) * ld;
+	for (int a = g; a < nreg; a += 4) ws[a * 64 + li] = Wt[(long)a * ld + i];
+	// the first chunk launched for this column's strip .. the last chunk, in four contiguous quarters
+	const int cfirst = (i / LOO_SW) * (LOO_SW / LOO_RC);
+	const int len = nchunks - cfirst, q = (len + 3) / 4;
+	const int cb = cfirst + g * q, ce = min(cb + q, nchunks);
+	double sum = 0.0;
+	for (int c = cb; c < ce; c++) sum += part[(long)c * Np + i];
+	__syncthreads();
+	const double *Q = betaQ + nreg;
+	double reg = 0.0;
+	for (int a = g; a < nreg; a += 4) {
+		double t = 0.0;
+		for (int b = 0; b < nreg; b++) t = fma(Q[a * nreg + b], ws[b * 64 + li], t);
+		reg = fma(ws[a * 64 + li], t, reg);
+	}
+	ssq[g * 64 + li] = sum;
+	sreg[g * 64 + li] = reg;
+	__syncthreads();
+	if (g == 0 && i < N) {
+		const double d = ((ssq[li] + ssq[64 + li]) + ssq[128 + li]) + ssq[192 + li];
+		const double r = ((sreg[li] + sreg[64 + li]) + sreg[128 + li]) + sreg[192 + li];
+		const double pii = d - r;
+		const double gamma = LinvAug[(long)Np * ld + i];
+		mean[i] = y[i] - gamma / pii;
+		var[i] = 1.0 / pii;
+	}
+}
+
+size_t loo_scratch_elems(int N, int Np) { return (size_t)((N + LOO_RC - 1) / LOO_RC) * (size_t)Np; }
+
+hipError_t launch_loo_colsq(hipStream_t s, const double *LinvAug, long ld, int N, int Np, double *part)
+{
+	const int nchunks = (N + LOO_RC - 1) / LOO_RC, per = LOO_SW / LOO_RC;
+	long entries = 0;
+	for (int st = 0; st * LOO_SW < Np && nchunks - st * per > 0; st++) entries += nchunks - st * per;
+	hipLaunchKernelGGL(loo_colsq_kernel, dim3((unsigned)entries), dim3(256), 0, s, LinvAug, ld, N, Np, nchunks, part);
+	return hipGetLastError();
+}
+
+hipError_t launch_loo_finish(hipStream_t s, const double *part, const double *LinvAug, long ld, int N, int Np, int nreg,
+                             const double *betaQ, const double *y, double *mean, double *var)
+{
+	if (nreg > 63) return hipErrorInvalidValue;
+	const int nchunks = (N + LOO_RC - 1) / LOO_RC;
+	hipLaunchKernelGGL(loo_finish_kernel, dim3((N + 63) / 64), dim3(256), 0, s, part, nchunks, LinvAug, ld, N, Np, nreg, betaQ, y,
+	                   mean, var);
+	return hipGetLastError();
+}
+
 } // namespace gpemu

@@ -924,6 +924,40 @@ void emulate_points_collect(emulator_struct *e, int npoints, double *mean, doubl
 	if (rc) die(en->ctx, rc, "emulate_point");
 }
 
+/* leave-one-out at every training point (gpemu_loo) */
+void emulate_loo(emulator_struct *e, double *mean, double *variance)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	int rc = gpemu_loo(en->ctx, mean, variance);
+	if (rc) die(en->ctx, rc, "emulate_loo");
+}
+
+/* its two halves: the launches go onto the component's own stream and the results wait in a device buffer (means, then
+ * variances); collect downloads them, which waits for that stream only, and releases the buffer */
+void emulate_loo_enqueue(emulator_struct *e, void **dev_out)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	const size_t n = (size_t)e->nmodel_points;
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(en->ctx, 2 * n * sizeof(double), &dev);
+	if (!rc) rc = gpemu_loo_dev(en->ctx, (double *)dev, (double *)dev + n);
+	if (rc) die(en->ctx, rc, "emulate_loo");
+	*dev_out = dev;
+}
+
+void emulate_loo_collect(emulator_struct *e, void *dev, double *mean, double *variance)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	const size_t n = (size_t)e->nmodel_points;
+	int rc = gpemu_dev_download(en->ctx, mean, dev, n * sizeof(double));
+	if (!rc) rc = gpemu_dev_download(en->ctx, variance, (const double *)dev + n, n * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	if (rc) die(en->ctx, rc, "emulate_loo");
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

@@ -1,10 +1,11 @@
 /*
  * interactive_emulator -- command-line front end, drop-in for the reference's
- * src/interactive_emulator.c (same three modes, options, file formats and stdout protocol):
+ * src/interactive_emulator.c (same three modes, options, file formats and stdout protocol), and one mode more:
  *
  *   interactive_emulator estimate_thetas INPUT_MODEL_FILE MODEL_SNAPSHOT_FILE [OPTIONS]
  *   interactive_emulator interactive_mode MODEL_SNAPSHOT_FILE [OPTIONS]
  *   interactive_emulator print_thetas MODEL_SNAPSHOT_FILE
+ *   interactive_emulator validate MODEL_SNAPSHOT_FILE [--pca_output] [--quiet]     (not in the reference)
  *
  * Kept quirks: --covariance_fn is atoi'd and compared with POWEREXPCOVFN=1 /
  * MATERN32=2 / MATERN52=3 (0 and 1 both mean power-exponential); --pca_variance falls through
@@ -39,6 +40,8 @@ static const char useage[] =
 	"  interactive_emulator interactive_mode MODEL_SNAPSHOT_FILE [OPTIONS]\n"
 	"or\n"
 	"  interactive_emulator print_thetas MODEL_SNAPSHOT_FILE\n"
+	"or\n"
+	"  interactive_emulator validate MODEL_SNAPSHOT_FILE [--pca_output] [--quiet]  (leave-one-out mean and variance per training point)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -171,6 +174,54 @@ static int interactive_mode(struct cmdLineOpts *o)
 	return rc == 0 ? 0 : EXIT_FAILURE;
 }
 
+/* Leave-one-out validation of a trained snapshot (not in the reference, which leaves validation to a held-out campaign):
+ * one line per training point in design order, "mean_0 variance_0 mean_1 variance_1 ..." -- what the emulator trained on
+ * the other N - 1 points at the same thetas answers at that point (emulate_loo_multi) -- and one summary line per output
+ * on stderr: the root mean square of (training value as given in the input - leave-one-out mean), so that in observable
+ * space the PCA truncation shows, and the mean of residual^2 / variance, near 1 for a calibrated emulator. */
+static int validate(struct cmdLineOpts *o)
+{
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	multi_emulator *emu = alloc_multi_emulator(model);
+	const int d = model->nparams, nt = model->nt, N = model->nmodel_points;
+	const int nout = o->pcaOutputFlag ? model->nr : nt;
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "%d\n", d);
+		for (int i = 0; i < d; i++) fprintf(out, "%s%d\n", "param_", i);
+		fprintf(out, "%d\n", 2 * nt);
+		for (int i = 0; i < nt; i++) fprintf(out, "%s_%d\n%s_%d\n", "mean", i, "variance", i);
+	}
+	double *mean = (double *)malloc(sizeof(double) * (size_t)N * nout), *var = (double *)malloc(sizeof(double) * (size_t)N * nout);
+	emulate_loo_multi(emu, o->pcaOutputFlag, mean, var);
+	for (int i = 0; i < N; i++) {
+		for (int j = 0; j < nout; j++)
+			fprintf(out, "%s%.17g %.17g", j ? " " : "", mean[(size_t)i * nout + j], var[(size_t)i * nout + j]);
+		fprintf(out, "\n");
+	}
+	fflush(out);
+	if (!o->quietFlag)
+		for (int j = 0; j < nout; j++) {
+			double ss = 0.0, sz = 0.0;
+			for (int i = 0; i < N; i++) {
+				const double given = o->pcaOutputFlag ? gsl_vector_get(model->pca_model_array[j]->training_vector, i)
+				                                      : gsl_matrix_get(model->training_matrix, i, j);
+				const double r = given - mean[(size_t)i * nout + j];
+				ss += r * r;
+				sz += r * r / var[(size_t)i * nout + j];
+			}
+			fprintf(stderr, "# loo output %d: rmse %.17g mean_standardised_sq %.17g\n", j, sqrt(ss / N), sz / N);
+		}
+	free(mean); free(var);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static int print_thetas(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -266,6 +317,7 @@ int main(int argc, char **argv)
 	if (!strcmp(o->run_mode, "estimate_thetas")) rc = estimate_thetas(o);
 	else if (!strcmp(o->run_mode, "interactive_mode")) rc = interactive_mode(o);
 	else if (!strcmp(o->run_mode, "print_thetas")) rc = print_thetas(o);
+	else if (!strcmp(o->run_mode, "validate")) rc = validate(o);
 	else { free(o); return perr(useage); }
 	free(o);
 	return rc;

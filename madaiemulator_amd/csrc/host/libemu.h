@@ -242,6 +242,12 @@ void emulate_points(emulator_struct *e, gsl_matrix *points, double *mean, double
 /* emulate_points in two halves (device work runs in between): used to query all PCA components at the same time */
 void emulate_points_enqueue(emulator_struct *e, gsl_matrix *points);
 void emulate_points_collect(emulator_struct *e, int npoints, double *mean, double *variance);
+/* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
+ * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
+void emulate_loo(emulator_struct *e, double *mean, double *variance);
+/* emulate_loo in two halves, like emulate_points_enqueue / _collect: *dev_out is the device buffer the results wait in */
+void emulate_loo_enqueue(emulator_struct *e, void **dev_out);
+void emulate_loo_collect(emulator_struct *e, void *dev, double *mean, double *variance);
 
 /* ---- multi_modelstruct.h / multivar_support.h ---------------------------------- */
 multi_modelstruct *alloc_multimodelstruct(gsl_matrix *xmodel_in, gsl_matrix *training_matrix_in, int cov_fn_index,
@@ -259,6 +265,9 @@ void emulate_point_multi(multi_emulator *emu, gsl_vector *the_point, gsl_vector 
 void emulate_point_multi_pca(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance);
 /* extension: batched form of the two calls above; outputs are npoints x nt (or x nr) row-major */
 void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out);
+/* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
+ * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
+void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);
 
 /* ---- libRbind/rbind.h: the batched likelihood entry point, R-free (rbind.c:626-724) ---------------- */
 void callEvalLhoodList(double *xmodel_in, int *nparams_in, double *pointList_in, int *nevalPoints_in,

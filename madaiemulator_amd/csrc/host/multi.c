@@ -494,6 +494,28 @@ void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space
 	free(mp); free(vp); free(mc); free(vc);
 }
 
+/* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
+ * waited for, as above; component results are N x nr in design order, then the same back-projection */
+void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
+{
+	const int np = emu->nmodel_points, nr = emu->nr;
+	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *vp = (double *)malloc(sizeof(double) * (size_t)np * nr);
+	double *mc = (double *)malloc(sizeof(double) * (size_t)np), *vc = (double *)malloc(sizeof(double) * (size_t)np);
+	void **dev = (void **)malloc(sizeof(void *) * (size_t)nr);
+	for (int c = 0; c < nr; c++) emulate_loo_enqueue(emu->emu_struct_array[c], &dev[c]);
+	for (int c = 0; c < nr; c++) {
+		emulate_loo_collect(emu->emu_struct_array[c], dev[c], mc, vc);
+		for (int q = 0; q < np; q++) { mp[(size_t)q * nr + c] = mc[q]; vp[(size_t)q * nr + c] = vc[q]; }
+	}
+	if (pca_space) {
+		memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
+		memcpy(var_out, vp, sizeof(double) * (size_t)np * nr);
+	} else {
+		backproject(emu, np, mp, vp, mean_out, var_out);
+	}
+	free(mp); free(vp); free(mc); free(vc); free(dev);
+}
+
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
 	gsl_matrix view;
