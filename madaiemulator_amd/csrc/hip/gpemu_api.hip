@@ -25,12 +25,16 @@ using namespace gpemu;
 	} while (0)
 
 constexpr int INFO_NONE = 0x7f7f7f7f;   // "no failed pivot": what hipMemsetAsync(.., 0x7f, ..) leaves in *info
+static int pivot_info(int word) { return (word >= INFO_NONE) ? 0 : word; }   // 1-based index of the first failed pivot, 0: none
 
 static int fail(gpemu_ctx *ctx, int code, const char *msg)
 {
 	if (ctx) ctx->err = msg;
 	return code;
 }
+
+// the prediction state and the explicit inverse no longer belong to what the workspace, the model or the mode now say
+static void invalidate_prediction(gpemu_ctx *ctx) { ctx->pred_ready = false; ctx->cinv_ready = false; }
 
 // ---------------------------------------------------------------------------
 // profiling helpers
@@ -70,6 +74,9 @@ static unsigned long long *trace_slot(gpemu_ctx *ctx, const char *fmt, int a = 0
 	return ctx->dTrace + 8 * (size_t)ctx->trace_next++;
 }
 
+// GPEMU_TRACE: zeroed device slots for the launches that follow (nothing when tracing is off)
+static hipError_t trace_clear(gpemu_ctx *ctx) { return ctx->dTrace ? hipMemsetAsync(ctx->dTrace, 0, (size_t)ctx->trace_cap * 64, ctx->stream) : hipSuccess; }
+
 // algorithmic flops of one GEMM call: 2 * (k-range) summed over the output elements the call owns
 // (lower trapezoid for tri; rows of an upper-triangular A start at k = row - kstart_off; rows of a
 // lower-triangular B end at k = col - kend_off)
@@ -92,15 +99,21 @@ static double gemm_flops(const GemmArgs &a)
 	return fl;
 }
 
+// every schedule switch a GEMM call carries, in one list: gemm() applies it, and so does whoever asks about a call first or launches directly
+static void apply_sched(const Sched &sc, GemmArgs &a)
+{
+	a.big_tiles = sc.gemm_big_tiles;
+	a.table_sb = sc.gemm_table;
+	a.keep_idle_waves = sc.idle_waves ? 0 : 1;
+	a.stagger_ticks = sc.stagger_us * 100;
+	a.row_table = sc.corner_row_table;
+	a.no_neg_modifier = sc.neg_modifier ? 0 : 1;
+}
+
 static hipError_t gemm(gpemu_ctx *ctx, const GemmArgs &a_in)
 {
 	GemmArgs a = a_in;
-	a.big_tiles = ctx->sched.gemm_big_tiles;
-	a.table_sb = ctx->sched.gemm_table;
-	a.keep_idle_waves = ctx->sched.idle_waves ? 0 : 1;
-	a.stagger_ticks = ctx->sched.stagger_us * 100;
-	a.row_table = ctx->sched.corner_row_table;
-	a.no_neg_modifier = ctx->sched.neg_modifier ? 0 : 1;
+	apply_sched(ctx->sched, a);
 	a.trace = trace_slot(ctx, "gemm m=%d n=%d k=%d", a.m, a.n, a.k1 - a.k0);
 	// GPEMU_PROF_GEMM: every GEMM launch; GPEMU_PROF_GEMM_BIG: only the launches that run the 128x128 8-wave kernel
 	// (gemm_nt_kernel<128,128,4,4,2,0>, the dominant kernel of a batched factorisation); GPEMU_PROF_GEMM_K512: only
@@ -250,7 +263,7 @@ static void free_model(gpemu_ctx *ctx)
 		b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
-	ctx->pred_ready = false; ctx->cinv_ready = false;
+	invalidate_prediction(ctx);
 	ctx->pred_pending = 0;
 	ctx->S_dim = 0;
 }
@@ -263,7 +276,7 @@ gpemu_ctx::~gpemu_ctx()
 	for (auto e : prof.ev) hipEventDestroy(e);
 	for (auto e : pring.ev) if (e) hipEventDestroy(e);
 	for (auto &s : ring) if (s.ev) hipEventDestroy(s.ev);
-	if (stream && own_stream) hipStreamDestroy(stream);
+	if (stream) hipStreamDestroy(stream);
 }
 
 extern "C" void gpemu_ctx_destroy(gpemu_ctx *ctx) { delete ctx; }
@@ -271,7 +284,7 @@ extern "C" void gpemu_ctx_destroy(gpemu_ctx *ctx) { delete ctx; }
 extern "C" int gpemu_set_mode(gpemu_ctx *ctx, int flags)
 {
 	if (!ctx || (flags & ~(GPEMU_MODE_EXACT_GRAD | GPEMU_MODE_MATERN_LOG))) return GPEMU_ERR_ARG;
-	if (flags != ctx->mode) { ctx->pred_ready = false; ctx->cinv_ready = false; }   // the kernel's meaning may have changed
+	if (flags != ctx->mode) invalidate_prediction(ctx);   // the kernel's meaning may have changed
 	ctx->mode = flags;
 	return GPEMU_OK;
 }
@@ -415,7 +428,7 @@ extern "C" int gpemu_set_training(gpemu_ctx *ctx, const double *y)
 	HIPCHK(ctx, hipMemcpyAsync(ctx->dY, ctx->hY.data(), (size_t)ctx->N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, launch_build_rrows(ctx->stream, ctx->dRrows, ctx->Np, ctx->Rp, ctx->dX, ctx->dY, ctx->N, ctx->d, ctx->order));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->pred_ready = false; ctx->cinv_ready = false;
+	invalidate_prediction(ctx);
 	return GPEMU_OK;
 }
 
@@ -472,25 +485,37 @@ static int make_cov_params(gpemu_ctx *ctx, const double *thetas, int nthetas, Co
 	return GPEMU_OK;
 }
 
+// nb theta vectors, nthetas apart -> their CovParams
+static int make_cov_params_batch(gpemu_ctx *ctx, int nb, const double *thetas, int nthetas, std::vector<CovParams> *ps)
+{
+	ps->resize((size_t)nb);
+	int rc = GPEMU_OK;
+	for (int b = 0; !rc && b < nb; b++) rc = make_cov_params(ctx, thetas ? thetas + (size_t)b * nthetas : nullptr, nthetas, &(*ps)[b]);
+	return rc;
+}
+
 // ---------------------------------------------------------------------------
 // recursive tall Cholesky
 //   T rows [0,Np)            : C (lower), identity padded
 //   T rows [Np,Np+Rp)        : right-hand sides as rows (y, H columns) -> Z^T = (L^-1 [y|H])^T
 //   T rows [Np+Rp,Np+Rp+Np)  : identity -> U = L^-T (only with inv)
 // potrf_rec(c0,n) factors the column panel [c0,c0+n) for every row below it.
+// The matrices come as a view (Tall); stream, schedule switches, profiling and trace are the context's.
 // ---------------------------------------------------------------------------
+// (the context's own workspace as it stands: after staging, which sets nb and the stride, and never kept across calls)
+static Tall tall_of(gpemu_ctx *ctx) { return Tall{ctx->dT, ctx->dInfo, ctx->Np, ctx->Rp, ctx->nb, (long)ctx->T_stride}; }
+
 // *fa_done: set when the update ran with the factor-ahead tile, i.e. the 64x64 diagonal block at c0+k is already
 // factored when the update has finished and the next leaf must not factor it again
-static hipError_t trailing_update(gpemu_ctx *ctx, int c0, int k, int ncols, int inv, bool *fa_done)
+static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, int ncols, int inv, bool *fa_done)
 {
 	// C[rows >= r0, cols r0 .. r0+ncols) -= P P^T with P = the factored panel columns [c0, c0+k) and r0 = c0 + k
-	const long ld = ctx->Np;
+	const long ld = t.Np;
 	const int r0 = c0 + k;
-	const int row_end = ctx->Np + ctx->Rp + (inv ? c0 + k : 0);   // identity rows < c0+k have fill-in in the panel
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
-	g.C = ctx->dT + (long)r0 * ld + r0;
-	g.A = ctx->dT + (long)r0 * ld + c0;
+	const int row_end = t.Np + t.Rp + (inv ? c0 + k : 0);         // identity rows < c0+k have fill-in in the panel
+	GemmArgs g{};
+	g.C = t.T + (long)r0 * ld + r0;
+	g.A = t.T + (long)r0 * ld + c0;
 	g.B = g.A;
 	g.ldc = g.lda = g.ldb = ld;
 	g.m = row_end - r0;
@@ -498,14 +523,14 @@ static hipError_t trailing_update(gpemu_ctx *ctx, int c0, int k, int ncols, int 
 	g.k0 = 0; g.k1 = k;
 	g.alpha = -1.0; g.beta = 1;
 	g.tri = 1; g.diag_off = 0;
-	g.nbatch = ctx->nb; g.bsC = g.bsA = g.bsB = (long)ctx->T_stride;
-	g.big_tiles = ctx->sched.gemm_big_tiles;                      // (gemm() sets these too: needed here for the tile-shape question)
+	g.nbatch = t.nb; g.bsC = g.bsA = g.bsB = t.stride;
+	apply_sched(ctx->sched, g);                                   // (gemm() does too: here for the tile-shape questions below)
 	g.fa = ctx->sched.factor_ahead ? 1 : 0;
 	g.fa_c0 = r0;
-	g.fa_info = ctx->dInfo;
+	g.fa_info = t.info;
 	*fa_done = g.fa && gemm_factor_ahead_ok(g);
 	if (!*fa_done) g.fa = 0;
-	const int c_rows = ctx->Np - r0;                              // rows of the matrix proper under r0
+	const int c_rows = t.Np - r0;                                 // rows of the matrix proper under r0
 	if (ctx->sched.split_rhs_rows && gemm_uses_big_tiles(g) && c_rows % GEMM_BM == 0 && c_rows >= ncols && g.m > c_rows) {
 		// 128x128 tiles: the 64 right-hand-side rows between the matrix rows and the identity rows would shift every tile row
 		// behind them by half a tile and leave the last one half empty (2-5 % of the tile slots of a big update: 48 of 1224
@@ -518,13 +543,13 @@ static hipError_t trailing_update(gpemu_ctx *ctx, int c0, int k, int ncols, int 
 		if (e != hipSuccess) return e;
 		GemmArgs b = g;
 		b.C = g.C + (long)c_rows * ld; b.A = g.A + (long)c_rows * ld;
-		b.m = ctx->Rp; b.tri = 0; b.force_cfg = 2;
+		b.m = t.Rp; b.tri = 0; b.force_cfg = 2;
 		e = gemm(ctx, b);
 		if (e != hipSuccess) return e;
-		const int i_rows = g.m - c_rows - ctx->Rp;
+		const int i_rows = g.m - c_rows - t.Rp;
 		if (i_rows > 0) {
 			GemmArgs c = g;
-			c.C = g.C + (long)(c_rows + ctx->Rp) * ld; c.A = g.A + (long)(c_rows + ctx->Rp) * ld;
+			c.C = g.C + (long)(c_rows + t.Rp) * ld; c.A = g.A + (long)(c_rows + t.Rp) * ld;
 			c.m = i_rows; c.tri = 0;
 			e = gemm(ctx, c);
 		}
@@ -536,17 +561,17 @@ static hipError_t trailing_update(gpemu_ctx *ctx, int c0, int k, int ncols, int 
 // diag_done: the 64x64 diagonal block at (c0,c0) is already factored (by the factor-ahead tile of the update before)
 // defer_c0 >= 0: the leaf solve of this block also solves, in place, the 64 rows under the diagonal block at defer_c0 (the
 // pair's first block, which leaf_pair_kernel leaves untouched there)
-static hipError_t potrf_rec(gpemu_ctx *ctx, int c0, int n, int inv, bool diag_done = false, int defer_c0 = -1)
+static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int inv, bool diag_done = false, int defer_c0 = -1)
 {
-	const long ld = ctx->Np;
-	const int base_end = ctx->Np + ctx->Rp;
+	const long ld = t.Np;
+	const int base_end = t.Np + t.Rp;
 	if (n <= LEAF) {
 		const int row_end = base_end + (inv ? c0 + LEAF : 0);
 		ProfScope ps(ctx, GPEMU_PROF_LEAF, 0.0, 0.0);
 		unsigned long long *trf = trace_slot(ctx, "leaf_factor c0=%d", c0);
 		unsigned long long *trs = trace_slot(ctx, "leaf_solve c0=%d m=%d", c0, row_end - (c0 + LEAF));
-		return launch_leaf(ctx->stream, ctx->dT, ld, c0, row_end - (c0 + LEAF), ctx->dInfo, trf, trs, ctx->nb,
-		                   (long)ctx->T_stride, diag_done, ctx->sched.leaf_staged, ctx->sched.diag_inv_ahead != 0, defer_c0);
+		return launch_leaf(ctx->stream, t.T, ld, c0, row_end - (c0 + LEAF), t.info, trf, trs, t.nb, t.stride, diag_done,
+		                   ctx->sched.leaf_staged, ctx->sched.diag_inv_ahead != 0, defer_c0);
 	}
 	if (n == 2 * LEAF && ctx->sched.leaf_pair && ctx->sched.diag_inv_ahead) {
 		// a 128-column pair: [factor the first diagonal block,] leaf_pair_kernel (solve of the first block + K=64 update with
@@ -556,14 +581,14 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, int c0, int n, int inv, bool diag_do
 		ProfScope ps(ctx, GPEMU_PROF_LEAF, 0.0, 0.0);
 		if (!diag_done) {
 			unsigned long long *trf = trace_slot(ctx, "leaf_factor c0=%d", c0);
-			hipError_t e = launch_leaf(ctx->stream, ctx->dT, ld, c0, 0, ctx->dInfo, trf, nullptr, ctx->nb, (long)ctx->T_stride, false);
+			hipError_t e = launch_leaf(ctx->stream, t.T, ld, c0, 0, t.info, trf, nullptr, t.nb, t.stride, false);
 			if (e != hipSuccess) return e;
 		}
 		unsigned long long *trp = trace_slot(ctx, "leaf_pair c0=%d m=%d", c0, m_below);
 		const bool fa = ctx->sched.factor_ahead != 0;
-		hipError_t e = launch_leaf_pair(ctx->stream, ctx->dT, ld, c0, m_below, ctx->dInfo, trp, ctx->nb, (long)ctx->T_stride, fa);
+		hipError_t e = launch_leaf_pair(ctx->stream, t.T, ld, c0, m_below, t.info, trp, t.nb, t.stride, fa);
 		if (e != hipSuccess) return e;
-		return potrf_rec(ctx, c0 + LEAF, LEAF, inv, fa, c0);
+		return potrf_rec(ctx, t, c0 + LEAF, LEAF, inv, fa, c0);
 	}
 	// automatic outer panel width: a batch has enough tiles per launch to afford the longer panel chain of a wider
 	// panel and gains from the larger K of its trailing updates and the fewer read-modify-write passes over the
@@ -573,7 +598,7 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, int c0, int n, int inv, bool diag_do
 	// per value+gradient evaluation in batches of 16.
 	// Round 5, measured at N = 4096 (profiles/r05_n4096_schedule_switches.txt): with the inverse rows 512 beats 1024 there
 	// (value+gradient batches of 16 / 64: +2 %), without them 1024 .. 4096 are within 0.5 % of each other.
-	const int nb_top = ctx->sched.nb_top > 0 ? ctx->sched.nb_top : (ctx->nb >= 2 ? (inv ? (ctx->Np <= 4096 ? 512 : 1024) : 2048) : 512);
+	const int nb_top = ctx->sched.nb_top > 0 ? ctx->sched.nb_top : (t.nb >= 2 ? (inv ? (t.Np <= 4096 ? 512 : 1024) : 2048) : 512);
 	if (n > nb_top) {
 		// right-looking over panels of nb_top columns: the trailing update touches the whole remaining
 		// matrix (thousands of tiles, K = panel width), which fills the chip far better than the few huge-K
@@ -581,53 +606,52 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, int c0, int n, int inv, bool diag_do
 		bool next_done = diag_done;
 		for (int c = c0; c < c0 + n; c += nb_top) {
 			const int nb = std::min(nb_top, c0 + n - c);
-			hipError_t e = potrf_rec(ctx, c, nb, inv, next_done);
+			hipError_t e = potrf_rec(ctx, t, c, nb, inv, next_done);
 			next_done = false;
 			if (e != hipSuccess) return e;
 			const int rest = c0 + n - (c + nb);
 			if (rest <= 0) continue;
-			e = trailing_update(ctx, c, nb, rest, inv, &next_done);
+			e = trailing_update(ctx, t, c, nb, rest, inv, &next_done);
 			if (e != hipSuccess) return e;
 		}
 		return hipSuccess;
 	}
 	const int n1 = ((n / LEAF + 1) / 2) * LEAF;
-	hipError_t e = potrf_rec(ctx, c0, n1, inv, diag_done);
+	hipError_t e = potrf_rec(ctx, t, c0, n1, inv, diag_done);
 	if (e != hipSuccess) return e;
 	bool right_done = false;
-	e = trailing_update(ctx, c0, n1, n - n1, inv, &right_done);
+	e = trailing_update(ctx, t, c0, n1, n - n1, inv, &right_done);
 	if (e != hipSuccess) return e;
-	return potrf_rec(ctx, c0 + n1, n - n1, inv, right_done);
+	return potrf_rec(ctx, t, c0 + n1, n - n1, inv, right_done);
+}
+
+// the whole factorisation with plain launches (or under capture), its trace tags from slot 0
+static hipError_t potrf_all(gpemu_ctx *ctx, const Tall &t, int inv)
+{
+	ctx->trace_next = 0; ctx->trace_tag.clear();
+	return potrf_rec(ctx, t, 0, t.Np, inv);
 }
 
 static int run_potrf(gpemu_ctx *ctx, int inv)
 {
+	const Tall t = tall_of(ctx);
 	const bool profiling = ctx->prof.cls == GPEMU_PROF_GEMM || ctx->prof.cls == GPEMU_PROF_LEAF || ctx->prof.cls == GPEMU_PROF_GEMM_BIG ||
 	                       ctx->prof.cls == GPEMU_PROF_GEMM_K512;
-	if (ctx->dTrace) {
-		HIPCHK(ctx, hipMemsetAsync(ctx->dTrace, 0, (size_t)ctx->trace_cap * 64, ctx->stream));   // fresh slots
-	}
+	HIPCHK(ctx, trace_clear(ctx));
 	double fl = (double)ctx->nb * ctx->Np * ctx->Np * ctx->Np / 3.0;
 	ProfScope ps(ctx, GPEMU_PROF_POTRF, fl, 0.0);
-	if (!ctx->use_graph || profiling) {
-		ctx->trace_next = 0; ctx->trace_tag.clear();
-		HIPCHK(ctx, potrf_rec(ctx, 0, ctx->Np, inv));
-		return GPEMU_OK;
-	}
-	gpemu_ctx::GraphKey key{ctx->Np, ctx->Rp, inv, ctx->nb};
+	const gpemu_ctx::GraphKey key{ctx->Np, ctx->Rp, inv, ctx->nb};
 	auto it = ctx->graphs.find(key);
-	if (it == ctx->graphs.end() && ctx->warm.insert(key).second) {
-		// first factorisation of this shape: plain launches (host-side tables of the GEMM tile order are built
-		// on first use and cannot be allocated under stream capture); the next call records the graph
-		ctx->trace_next = 0; ctx->trace_tag.clear();
-		HIPCHK(ctx, potrf_rec(ctx, 0, ctx->Np, inv));
+	// plain launches: without graphs, under profiling, and for the first factorisation of a shape (host-side tables of the
+	// GEMM tile order are built on first use and cannot be allocated under stream capture); the next call records the graph
+	if (!ctx->use_graph || profiling || (it == ctx->graphs.end() && ctx->warm.insert(key).second)) {
+		HIPCHK(ctx, potrf_all(ctx, t, inv));
 		return GPEMU_OK;
 	}
 	if (it == ctx->graphs.end()) {
 		hipGraph_t graph = nullptr;
-		ctx->trace_next = 0; ctx->trace_tag.clear();
 		HIPCHK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-		hipError_t e = potrf_rec(ctx, 0, ctx->Np, inv);
+		hipError_t e = potrf_all(ctx, t, inv);
 		hipError_t e2 = hipStreamEndCapture(ctx->stream, &graph);
 		if (e != hipSuccess || e2 != hipSuccess) {
 			if (graph) hipGraphDestroy(graph);
@@ -685,8 +709,6 @@ static int stage_matrices(gpemu_ctx *ctx, const CovParams *ps, int nb, int inv, 
 	HIPCHK(ctx, hipMemsetAsync(ctx->dInfo, 0x7f, (size_t)nb * sizeof(int), ctx->stream));
 	return GPEMU_OK;
 }
-
-static int stage_matrix(gpemu_ctx *ctx, const CovParams &p, int inv) { return stage_matrices(ctx, &p, 1, inv); }
 
 static int enqueue_results(gpemu_ctx *ctx)
 {
@@ -789,46 +811,49 @@ extern "C" int gpemu_loglik_batch_enqueue(gpemu_ctx *ctx, int nb, const double *
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
 	if (nb < 1 || nb > GPEMU_MAX_BATCH) return fail(ctx, GPEMU_ERR_ARG, "batch size must be 1..GPEMU_MAX_BATCH");
-	std::vector<CovParams> ps((size_t)nb);
-	for (int b = 0; b < nb; b++) {
-		int rc = make_cov_params(ctx, thetas ? thetas + (size_t)b * nthetas : nullptr, nthetas, &ps[b]);
-		if (rc) return rc;
-	}
+	std::vector<CovParams> ps;
+	int rc = make_cov_params_batch(ctx, nb, thetas, nthetas, &ps);
+	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	int rc = stage_matrices(ctx, ps.data(), nb, 0);
+	rc = stage_matrices(ctx, ps.data(), nb, 0);
 	if (rc) return rc;
 	rc = run_potrf(ctx, 0);
 	if (rc) return rc;
-	ctx->pred_ready = false; ctx->cinv_ready = false;
+	invalidate_prediction(ctx);
 	return enqueue_results(ctx);
 }
 
-// results of element b of the batch in ring slot s (after its event or the stream has been waited for)
+// -log L as the reference writes it: its literal for log 2 pi (estimator-fns.c:48) and its order of operations
+static double neg_loglik_of(const HostLik &r, int N)
+{
+	const double log_2_pi = 1.83788;
+	return -1 * (-(1.0 / 2.0) * r.logdet - (N / 2.0) * log_2_pi + r.quad * (-1.0 / 2.0));
+}
+
+// element b of the batch in ring slot s (after its event or the stream has been waited for): the info word, then the host
+// half of the likelihood.  Returns the element's status, the message set; GPEMU_ERR_NOT_PD leaves *r untouched
+static int element_likelihood(gpemu_ctx *ctx, const ResSlot &s, int b, int *info, HostLik *r)
+{
+	const int inf = pivot_info(s.info[b]);
+	if (info) *info = inf;
+	if (inf) return fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
+	*r = host_likelihood(ctx, s, b);
+	return r->status ? fail(ctx, r->status, "H^T C^-1 H is not positive definite") : GPEMU_OK;
+}
+
+// results of element b of the batch in ring slot s.  After a regression failure logdet is still the matrix's, the rest NaN.
 static int collect_one(gpemu_ctx *ctx, const ResSlot &s, int b, double *neg_loglik, double *sigma2, double *beta, double *logdet,
                        double *quad, int *info)
 {
-	const int inf = (s.info[b] >= INFO_NONE) ? 0 : s.info[b];
-	if (info) *info = inf;
-	if (inf != 0) {
-		if (neg_loglik) *neg_loglik = NAN;
-		if (sigma2) *sigma2 = NAN;
-		if (logdet) *logdet = NAN;
-		if (quad) *quad = NAN;
-		if (beta) for (int a = 0; a < ctx->nreg; a++) beta[a] = NAN;
-		return fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
-	}
-	HostLik r = host_likelihood(ctx, s, b);
-	if (beta) for (int a = 0; a < ctx->nreg; a++) beta[a] = r.beta[a];
-	if (sigma2) *sigma2 = r.sigma2;
-	if (logdet) *logdet = r.logdet;
-	if (quad) *quad = r.quad;
-	if (neg_loglik) {
-		const double log_2_pi = 1.83788;                                     // estimator-fns.c:48 (literal)
-		const double ll = -(1.0 / 2.0) * r.logdet - (ctx->N / 2.0) * log_2_pi + r.quad * (-1.0 / 2.0);
-		*neg_loglik = -1 * ll;
-	}
-	if (r.status) return fail(ctx, r.status, "H^T C^-1 H is not positive definite");
-	return GPEMU_OK;
+	HostLik r;
+	const int st = element_likelihood(ctx, s, b, info, &r);
+	const bool pd = st != GPEMU_ERR_NOT_PD;
+	if (beta) for (int a = 0; a < ctx->nreg; a++) beta[a] = pd ? r.beta[a] : NAN;
+	if (sigma2) *sigma2 = pd ? r.sigma2 : NAN;
+	if (logdet) *logdet = pd ? r.logdet : NAN;
+	if (quad) *quad = pd ? r.quad : NAN;
+	if (neg_loglik) *neg_loglik = pd ? neg_loglik_of(r, ctx->N) : NAN;
+	return st;
 }
 
 static void collect_batch(gpemu_ctx *ctx, const ResSlot &s, int nb, double *neg_loglik, double *sigma2, double *beta, double *logdet,
@@ -853,18 +878,29 @@ extern "C" int gpemu_loglik_batch_collect(gpemu_ctx *ctx, int nb, double *neg_lo
 	return GPEMU_OK;
 }
 
+// the batch enqueued `back` batches (of either kind) before the newest one (0 = newest), when it has nb elements and is of
+// this kind (ResSlot::kind); otherwise nullptr, the message set (every such failure is a GPEMU_ERR_STATE)
+static const ResSlot *ring_slot_back(gpemu_ctx *ctx, int back, int nb, int kind)
+{
+	auto no = [ctx](const char *msg) { fail(ctx, GPEMU_ERR_STATE, msg); return (const ResSlot *)nullptr; };
+	if (back < 0 || back >= gpemu_ctx::RES_RING || (unsigned long long)back >= ctx->res_seq) return no("no such batch in the result ring");
+	const ResSlot &s = ctx->ring[(ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING];
+	if (nb < 1 || nb != s.nb) return no("batch size differs from the enqueued batch");
+	if (s.kind != kind)
+		return no(kind ? "that batch is a likelihood batch: use gpemu_loglik_batch_collect_back"
+		               : "that batch is a value+gradient batch: use gpemu_loglik_grad_batch_collect_back");
+	return &s;
+}
+
 // results of the batch enqueued `back` batches before the newest one (0 = newest); waits for THAT batch only
 extern "C" int gpemu_loglik_batch_collect_back(gpemu_ctx *ctx, int back, int nb, double *neg_loglik, double *sigma2,
                                                double *beta, double *logdet, double *quad, int *info, int *status)
 {
 	if (!ctx) return GPEMU_ERR_ARG;
-	if (back < 0 || back >= gpemu_ctx::RES_RING || (unsigned long long)back >= ctx->res_seq)
-		return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
-	const ResSlot &s = ctx->ring[(ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING];
-	if (nb < 1 || nb != s.nb) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
-	if (s.kind != 0) return fail(ctx, GPEMU_ERR_STATE, "that batch is a value+gradient batch: use gpemu_loglik_grad_batch_collect_back");
-	HIPCHK(ctx, hipEventSynchronize(s.ev));
-	collect_batch(ctx, s, nb, neg_loglik, sigma2, beta, logdet, quad, info, status);
+	const ResSlot *s = ring_slot_back(ctx, back, nb, 0);
+	if (!s) return GPEMU_ERR_STATE;
+	HIPCHK(ctx, hipEventSynchronize(s->ev));
+	collect_batch(ctx, *s, nb, neg_loglik, sigma2, beta, logdet, quad, info, status);
 	return GPEMU_OK;
 }
 
@@ -958,15 +994,14 @@ static int factor_with_inverse(gpemu_ctx *ctx, const double *thetas, int nthetas
 	int rc = make_cov_params(ctx, thetas, nthetas, p);
 	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	rc = stage_matrix(ctx, *p, 1);
+	rc = stage_matrices(ctx, p, 1, 1);
 	if (rc) return rc;
 	rc = run_potrf(ctx, 1);
 	if (rc) return rc;
 	rc = enqueue_results(ctx);
 	if (rc) return rc;
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	const int word = ctx->newest().info[0];
-	const int inf = (word >= INFO_NONE) ? 0 : word;
+	const int inf = pivot_info(ctx->newest().info[0]);
 	if (info) *info = inf;
 	if (inf) return fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
 	return GPEMU_OK;
@@ -988,8 +1023,7 @@ static int build_prediction_state(gpemu_ctx *src, int b, gpemu_ctx *dst, const C
 	// rows [0,Np): L^-1 = U^T
 	HIPCHK(src, launch_transpose(src->stream, dst->dLinvAug, Np, U, Np, Np));
 	// (C^-1 [y|H])^T = Z^T U^T : rows Np.. of LinvAug used as scratch first
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
+	GemmArgs g{};
 	g.C = dst->dLinvAug + (size_t)Np * Np; g.ldc = Np;
 	g.A = Zt; g.lda = Np;
 	g.B = U; g.ldb = Np;
@@ -1027,7 +1061,7 @@ extern "C" int gpemu_predict_setup(gpemu_ctx *ctx, const double *thetas, int nth
 {
 	if (!ctx) return GPEMU_ERR_ARG;
 	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
-	ctx->pred_ready = false; ctx->cinv_ready = false;
+	invalidate_prediction(ctx);
 	CovParams p;
 	int rc = factor_with_inverse(ctx, thetas, nthetas, &p, info);
 	if (rc) return rc;
@@ -1061,13 +1095,10 @@ extern "C" int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const do
 		    x->mode != lead->mode || x->hX != lead->hX)
 			return fail(lead, GPEMU_ERR_ARG, "the contexts of a batched set-up share device, design, covariance function, regression order and modes");
 		if (x->pred_pending) return fail(lead, GPEMU_ERR_STATE, "a prediction batch is enqueued in one of the contexts: collect it first");
-		x->pred_ready = false; x->cinv_ready = false;
+		invalidate_prediction(x);
 	}
-	std::vector<CovParams> ps((size_t)n);
-	for (int c = 0; c < n; c++) {
-		int rc = make_cov_params(lead, thetas ? thetas + (size_t)c * nthetas : nullptr, nthetas, &ps[c]);
-		if (rc) return rc;
-	}
+	std::vector<CovParams> ps;
+	if (const int rc = make_cov_params_batch(lead, n, thetas, nthetas, &ps)) return rc;
 	HIPCHK(lead, hipSetDevice(lead->device));
 	const int Np = lead->Np, Rp = lead->Rp, nreg = lead->nreg;
 	// the components' right-hand-side rows [y_c | H]^T side by side (each context built its own at gpemu_set_model /
@@ -1087,7 +1118,7 @@ extern "C" int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const do
 	const ResSlot &res = lead->newest();               // the batch just factored
 	int worst = GPEMU_OK;
 	for (int c = 0; c < n; c++) {
-		const int inf = (res.info[c] >= INFO_NONE) ? 0 : res.info[c];
+		const int inf = pivot_info(res.info[c]);
 		if (info) info[c] = inf;
 		int st = GPEMU_OK;
 		if (inf) st = GPEMU_ERR_NOT_PD;
@@ -1162,14 +1193,13 @@ extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_d
 	for (int q0 = 0; q0 < M; q0 += cap) {
 		const int mb = std::min(cap, M - q0);
 		const int mbp = round_up(mb, 64);
-		GemmArgs g;
-		memset(&g, 0, sizeof g);
+		GemmArgs g{};
 		g.C = ctx->dV; g.ldc = Np + Rp;
 		g.A = ctx->dKq; g.lda = Np;
 		g.B = ctx->dLinvAug; g.ldb = Np;
 		g.m = mb; g.n = Np + Rp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
 		g.kend_mode = 1; g.kend_off = 0;
-		g.big_tiles = ctx->sched.gemm_big_tiles;
+		apply_sched(ctx->sched, g);                     // (gemm() does too: here for the tile-shape question below)
 		// a few queries (emulate_point: ONE) give one or two tile rows with K = N each: split K over the chip
 		// (0.46 -> 0.1 ms per call at N=8192); the slices are summed in order by the finishing kernel
 		int nslice = 1;
@@ -1330,25 +1360,19 @@ extern "C" int gpemu_loo(gpemu_ctx *ctx, double *mean, double *var)
 // explicit inverse: S = Aug Aug^T with Aug = [Z^T ; U]  ->  S[Rp+i][Rp+j] = (C^-1)_ij,
 // S[Rp+i][a] = (C^-1 [y|H])_ia   (lower triangle only)
 // ---------------------------------------------------------------------------
-// corners of the nbc batch elements b0 .. b0+nbc-1 (one batched product)
-static int build_corner(gpemu_ctx *ctx, int b0 = 0, int nbc = 1)
+// corners of the nbc elements b0 .. b0+nbc-1 of the factored batch t (one batched product) into S: squares of side and
+// leading dimension lds = Np + Rp, one after the other
+static hipError_t build_corner(gpemu_ctx *ctx, const Tall &t, double *S, long lds, int b0 = 0, int nbc = 1)
 {
-	const int Np = ctx->Np, Rp = ctx->Rp;
-	const size_t dim = (size_t)Np + Rp;
-	const int rc = grow(ctx, ctx->dS, (size_t)nbc * dim * dim);
-	if (rc) return rc;
-	ctx->S_dim = dim;
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
-	g.C = ctx->dS; g.ldc = (long)ctx->S_dim;
-	g.A = ctx->dT + (size_t)b0 * ctx->T_stride + (size_t)Np * Np; g.lda = Np;
-	g.B = g.A; g.ldb = Np;
-	g.m = (int)dim; g.n = (int)dim; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+	GemmArgs g{};
+	g.C = S; g.ldc = lds;
+	g.A = t.T + (size_t)b0 * t.stride + (size_t)t.Np * t.Np; g.lda = t.Np;
+	g.B = g.A; g.ldb = t.Np;
+	g.m = (int)lds; g.n = (int)lds; g.k0 = 0; g.k1 = t.Np; g.alpha = 1.0; g.beta = 0;
 	g.tri = 1; g.diag_off = 0;
-	g.kstart_mode = 1; g.kstart_off = Rp;
-	g.nbatch = nbc; g.bsC = (long)(ctx->S_dim * ctx->S_dim); g.bsA = g.bsB = (long)ctx->T_stride;
-	HIPCHK(ctx, gemm(ctx, g));
-	return GPEMU_OK;
+	g.kstart_mode = 1; g.kstart_off = t.Rp;
+	g.nbatch = nbc; g.bsC = lds * lds; g.bsA = g.bsB = t.stride;
+	return gemm(ctx, g);
 }
 
 extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
@@ -1366,8 +1390,11 @@ extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
 		if (rc) return rc;
 	}
 	if (!ctx->cinv_ready) {
-		int rc = build_corner(ctx);
+		const size_t dim = (size_t)ctx->Np + ctx->Rp;
+		int rc = grow(ctx, ctx->dS, dim * dim);
 		if (rc) return rc;
+		ctx->S_dim = dim;
+		HIPCHK(ctx, build_corner(ctx, tall_of(ctx), ctx->dS, (long)dim));
 		ctx->cinv_ready = true;
 	}
 	const int N = ctx->N, Rp = ctx->Rp;
@@ -1420,10 +1447,12 @@ static int grad_check_args(gpemu_ctx *ctx, int nthetas)
 // gradient reductions of the batch elements b0 .. b0+nbc-1 of the factorisation in the workspace, into dGradSum
 static int grad_enqueue_chunk(gpemu_ctx *ctx, int b0, int nbc, const double *th_all, int nthetas)
 {
-	int rc = build_corner(ctx, b0, nbc);
-	if (rc) return rc;
 	const int N = ctx->N, d = ctx->d, Rp = ctx->Rp;
-	const size_t dim = ctx->S_dim, sstride = dim * dim;
+	const size_t dim = (size_t)ctx->Np + Rp, sstride = dim * dim;
+	int rc = grow(ctx, ctx->dS, (size_t)nbc * sstride);
+	if (rc) return rc;
+	ctx->S_dim = dim;
+	HIPCHK(ctx, build_corner(ctx, tall_of(ctx), ctx->dS, (long)dim, b0, nbc));
 	const bool exact = (ctx->mode & GPEMU_MODE_EXACT_GRAD) != 0;
 	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;           // length-scale directions
 	const size_t gslot = (size_t)ctx->Np + 2 * GPEMU_MAX_PARAMS;    // per corner: alpha scratch | length thetas | beta
@@ -1469,16 +1498,13 @@ extern "C" int gpemu_loglik_grad_batch_enqueue(gpemu_ctx *ctx, int nb, const dou
 	int rc = grad_check_args(ctx, nthetas);
 	if (rc) return rc;
 	if (nb < 1 || nb > GPEMU_MAX_BATCH) return fail(ctx, GPEMU_ERR_ARG, "batch size must be 1..GPEMU_MAX_BATCH");
-	std::vector<double> th((size_t)nb * nthetas);
-	std::vector<CovParams> ps((size_t)nb);
-	for (int b = 0; b < nb; b++) {
-		for (int i = 0; i < nthetas; i++) th[(size_t)b * nthetas + i] = thetas[(size_t)b * nthetas + i];
-		th[(size_t)b * nthetas] = 0.0;                // maxmultimin.c:441
-		rc = make_cov_params(ctx, &th[(size_t)b * nthetas], nthetas, &ps[b]);
-		if (rc) return rc;
-	}
+	std::vector<double> th(thetas, thetas + (size_t)nb * nthetas);
+	for (int b = 0; b < nb; b++) th[(size_t)b * nthetas] = 0.0;     // maxmultimin.c:441
+	std::vector<CovParams> ps;
+	rc = make_cov_params_batch(ctx, nb, th.data(), nthetas, &ps);
+	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	ctx->pred_ready = false; ctx->cinv_ready = false;
+	invalidate_prediction(ctx);
 	rc = stage_matrices(ctx, ps.data(), nb, 1);
 	if (rc) return rc;
 	rc = run_potrf(ctx, 1);
@@ -1513,45 +1539,30 @@ static int grad_collect_slot(gpemu_ctx *ctx, const ResSlot &s, int nb, double *n
 	const int nthetas = s.nthetas, ng = nthetas - 1, d = ctx->d;
 	const bool exact = (s.mode & GPEMU_MODE_EXACT_GRAD) != 0;                     // as it was when the batch was enqueued
 	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;
-	const double *th_all = s.th.data();
 	for (int b = 0; b < nb; b++) {
-		const int inf = (s.info[b] >= INFO_NONE) ? 0 : s.info[b];
-		int st = GPEMU_OK;
-		if (info) info[b] = inf;
-		if (grad) for (int i = 0; i < ng; i++) grad[(size_t)b * ng + i] = NAN;
-		if (beta) for (int a = 0; a < ctx->nreg; a++) beta[(size_t)b * ctx->nreg + a] = NAN;
-		if (neg_loglik) neg_loglik[b] = NAN;
-		if (sigma2) sigma2[b] = NAN;
-		if (inf) {
-			st = fail(ctx, GPEMU_ERR_NOT_PD, "covariance matrix is not positive definite");
-		} else {
-			const HostLik r = host_likelihood(ctx, s, b);
-			if (r.status) {
-				st = fail(ctx, r.status, "H^T C^-1 H is not positive definite");
-			} else {
-				const double log_2_pi = 1.83788;
-				if (neg_loglik) neg_loglik[b] = -1 * (-(1.0 / 2.0) * r.logdet - (ctx->N / 2.0) * log_2_pi + r.quad * (-1.0 / 2.0));
-				if (sigma2) sigma2[b] = r.sigma2;
-				if (beta) for (int a = 0; a < ctx->nreg; a++) beta[(size_t)b * ctx->nreg + a] = r.beta[a];
-				if (grad) {
-					const double *sums = s.grad + (size_t)b * gpemu_ctx::GRAD_NP_MAX;
-					double *g = grad + (size_t)b * ng;
-					if (exact) {
-						// d(-logL)/dtheta = 1/2 sum_ab (A_ab - alpha_a alpha_b) dC_ab: slot nlen = nugget direction, slots < nlen the lengths
-						g[0] = 0.5 * sums[nlen];
-						for (int k = 0; k < nlen; k++) g[k + 1] = 0.5 * sums[k];
-					} else {
-						const double aa = sums[2 * d + 1];
-						const double amp = exp(log(r.sigma2));                          // maxmultimin.c:503,514
-						const double nug = exp(th_all[(size_t)b * nthetas + 1]);         // :515
-						// G(dC) = -1/2 tr(A dC) + 1/2 alpha^T dC alpha ;  grad = -G   (:527,535; getGradientCn :571-608)
-						g[0] = -1.0 * (-0.5 * nug * sums[2 * d] + 0.5 * nug * aa);
-						for (int k = 0; k < d; k++) g[k + 1] = -1.0 * (amp * (-0.5 * sums[2 * k] + 0.5 * sums[2 * k + 1]));
-					}
-				}
-			}
-		}
+		HostLik r;
+		const int st = element_likelihood(ctx, s, b, info ? info + b : nullptr, &r);
+		const bool ok = st == GPEMU_OK;                   // (any failure, the regression's too, leaves NaN everywhere)
 		if (status) status[b] = st;
+		if (neg_loglik) neg_loglik[b] = ok ? neg_loglik_of(r, ctx->N) : NAN;
+		if (sigma2) sigma2[b] = ok ? r.sigma2 : NAN;
+		if (beta) for (int a = 0; a < ctx->nreg; a++) beta[(size_t)b * ctx->nreg + a] = ok ? r.beta[a] : NAN;
+		if (grad) for (int i = 0; i < ng; i++) grad[(size_t)b * ng + i] = NAN;
+		if (!grad || !ok) continue;
+		const double *sums = s.grad + (size_t)b * gpemu_ctx::GRAD_NP_MAX;
+		double *g = grad + (size_t)b * ng;
+		if (exact) {
+			// d(-logL)/dtheta = 1/2 sum_ab (A_ab - alpha_a alpha_b) dC_ab: slot nlen = nugget direction, slots < nlen the lengths
+			g[0] = 0.5 * sums[nlen];
+			for (int k = 0; k < nlen; k++) g[k + 1] = 0.5 * sums[k];
+		} else {
+			const double aa = sums[2 * d + 1];
+			const double amp = exp(log(r.sigma2));                          // maxmultimin.c:503,514
+			const double nug = exp(s.th[(size_t)b * nthetas + 1]);           // :515
+			// G(dC) = -1/2 tr(A dC) + 1/2 alpha^T dC alpha ;  grad = -G   (:527,535; getGradientCn :571-608)
+			g[0] = -1.0 * (-0.5 * nug * sums[2 * d] + 0.5 * nug * aa);
+			for (int k = 0; k < d; k++) g[k + 1] = -1.0 * (amp * (-0.5 * sums[2 * k] + 0.5 * sums[2 * k + 1]));
+		}
 	}
 	return GPEMU_OK;
 }
@@ -1561,13 +1572,10 @@ extern "C" int gpemu_loglik_grad_batch_collect_back(gpemu_ctx *ctx, int back, in
                                                     double *beta, double *grad, int *info, int *status)
 {
 	if (!ctx) return GPEMU_ERR_ARG;
-	if (back < 0 || back >= gpemu_ctx::RES_RING || (unsigned long long)back >= ctx->res_seq)
-		return fail(ctx, GPEMU_ERR_STATE, "no such batch in the result ring");
-	const ResSlot &s = ctx->ring[(ctx->res_seq - 1 - (unsigned long long)back) % gpemu_ctx::RES_RING];
-	if (nb < 1 || nb != s.nb) return fail(ctx, GPEMU_ERR_STATE, "batch size differs from the enqueued batch");
-	if (s.kind != 1) return fail(ctx, GPEMU_ERR_STATE, "that batch is a likelihood batch: use gpemu_loglik_batch_collect_back");
-	HIPCHK(ctx, hipEventSynchronize(s.ev));
-	return grad_collect_slot(ctx, s, nb, neg_loglik, sigma2, beta, grad, info, status);
+	const ResSlot *s = ring_slot_back(ctx, back, nb, 1);
+	if (!s) return GPEMU_ERR_STATE;
+	HIPCHK(ctx, hipEventSynchronize(s->ev));
+	return grad_collect_slot(ctx, *s, nb, neg_loglik, sigma2, beta, grad, info, status);
 }
 
 extern "C" int gpemu_loglik_grad_batch_collect(gpemu_ctx *ctx, int nb, double *neg_loglik, double *sigma2, double *beta,
@@ -1666,45 +1674,42 @@ extern "C" int gpemu_trace_dump(gpemu_ctx *ctx, const char *path)
 // low-level compatibility entries: the reference's libRbind-era interface passes N x N matrices through host
 // memory (emulate-fns.c:275-299, regression.c:120-176, emulator.c:672-785).  The O(N^2)/O(N^3) work still runs here.
 // ---------------------------------------------------------------------------
-// scratch state for ONE n x n matrix of the caller's on ctx's stream, which it borrows: the sizes of that matrix, no model
-static void scratch_for_matrix(gpemu_ctx *tmp, const gpemu_ctx *ctx, int n)
-{
-	tmp->device = ctx->device; tmp->stream = ctx->stream; tmp->own_stream = false; tmp->use_graph = false; tmp->sched = ctx->sched;
-	tmp->Np = round_up(n, LEAF); tmp->Rp = 64; tmp->N = n; tmp->nrhs = 0; tmp->nb = 1;
-}
-
+// The two matrix-only entries (gpemu_chol_inverse, gpemu_test_potrf) factor ONE n x n matrix of the caller's in buffers of their
+// own, through a view over them, on the calling context's stream and with its switches; its model and workspace stay untouched.
 // C -> C^-1 in place (both triangles), log det C = 2 sum log L_ii; *info = 1-based index of the first pivot <= 0
 extern "C" int gpemu_chol_inverse(gpemu_ctx *ctx, int n, double *a, int lda, double *logdet, int *info)
 {
 	if (!ctx || n < 1 || !a || lda < n) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	gpemu_ctx tmp;
-	scratch_for_matrix(&tmp, ctx, n);
-	const int Np = tmp.Np, Rp = tmp.Rp;
+	const int Np = round_up(n, LEAF), Rp = 64;
 	const size_t rows = (size_t)2 * Np + Rp, dim = (size_t)Np + Rp;
 	std::vector<double> h((size_t)Np * Np, 0.0), diag((size_t)n);
 	for (int i = 0; i < Np; i++)
 		for (int j = 0; j <= i; j++)
 			h[(size_t)i * Np + j] = (i < n) ? a[(size_t)i * lda + j] : (i == j ? 1.0 : 0.0);
 	int big = INFO_NONE, inf = 0;
-	HIPCHK(ctx, tmp.dT.grow(rows * Np));
-	HIPCHK(ctx, tmp.dInfo.grow(1));
-	HIPCHK(ctx, tmp.dS.grow(dim * dim));
-	HIPCHK(ctx, hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream));
-	HIPCHK(ctx, hipMemsetAsync(tmp.dT + (size_t)Np * Np, 0, (size_t)Rp * Np * 8, tmp.stream));
-	HIPCHK(ctx, launch_set_identity_rows(tmp.stream, tmp.dT + (size_t)(Np + Rp) * Np, Np, Np));
-	HIPCHK(ctx, hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream));
-	HIPCHK(ctx, potrf_rec(&tmp, 0, Np, 1));
-	HIPCHK(ctx, hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream));
-	HIPCHK(ctx, hipMemcpy2DAsync(diag.data(), sizeof(double), tmp.dT, ((size_t)Np + 1) * sizeof(double), sizeof(double), n,
-	                             hipMemcpyDeviceToHost, tmp.stream));
-	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
-	const int bad = (inf >= INFO_NONE) ? 0 : inf;
+	DevBuf<double> dT, dS;
+	DevBuf<int> dInfo;
+	HIPCHK(ctx, dT.grow(rows * Np));
+	HIPCHK(ctx, dInfo.grow(1));
+	HIPCHK(ctx, dS.grow(dim * dim));
+	const Tall t{dT, dInfo, Np, Rp, 1, (long)(rows * Np)};
+	HIPCHK(ctx, trace_clear(ctx));
+	HIPCHK(ctx, hipMemcpyAsync(dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemsetAsync(dT + (size_t)Np * Np, 0, (size_t)Rp * Np * 8, ctx->stream));
+	HIPCHK(ctx, launch_set_identity_rows(ctx->stream, dT + (size_t)(Np + Rp) * Np, Np, Np));
+	HIPCHK(ctx, hipMemcpyAsync(dInfo, &big, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, potrf_all(ctx, t, 1));
+	HIPCHK(ctx, hipMemcpyAsync(&inf, dInfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(diag.data(), sizeof(double), dT, ((size_t)Np + 1) * sizeof(double), sizeof(double), n,
+	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	const int bad = pivot_info(inf);
 	if (!bad) {
-		if (build_corner(&tmp)) return fail(ctx, GPEMU_ERR_HIP, tmp.err.c_str());   // C^-1 = U U^T, lower triangle at (Rp, Rp) of the corner
-		HIPCHK(ctx, hipMemcpy2DAsync(a, (size_t)lda * sizeof(double), tmp.dS + (size_t)Rp * dim + Rp, dim * sizeof(double),
-		                             (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, tmp.stream));
-		HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
+		HIPCHK(ctx, build_corner(ctx, t, dS, (long)dim));   // C^-1 = U U^T, lower triangle at (Rp, Rp) of the corner
+		HIPCHK(ctx, hipMemcpy2DAsync(a, (size_t)lda * sizeof(double), dS + (size_t)Rp * dim + Rp, dim * sizeof(double),
+		                             (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	if (info) *info = bad;
 	if (bad) return fail(ctx, GPEMU_ERR_NOT_PD, "matrix is not positive definite");
@@ -1798,8 +1803,7 @@ extern "C" int gpemu_symm_apply(gpemu_ctx *ctx, int n, const double *a, int lda,
 	HIPCHK(ctx, hipMemsetAsync(ctx->dSymV, 0, (size_t)nvec * Npad * sizeof(double), ctx->stream));
 	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dSymV, (size_t)Npad * sizeof(double), v, (size_t)n * sizeof(double),
 	                             (size_t)n * sizeof(double), nvec, hipMemcpyHostToDevice, ctx->stream));
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
+	GemmArgs g{};
 	g.C = ctx->dSymOut; g.ldc = Npad;
 	g.A = ctx->dSymV; g.lda = Npad;
 	g.B = ctx->dSym; g.ldb = Npad;
@@ -1868,8 +1872,7 @@ extern "C" int gpemu_test_gemm_nt(gpemu_ctx *ctx, int m, int n, int k, double al
 	HIPCHK(ctx, hipMemcpyAsync(da, a, (size_t)m * k * 8, hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(db, b, (size_t)n * k * 8, hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(dc, c, (size_t)m * n * 8, hipMemcpyHostToDevice, ctx->stream));
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
+	GemmArgs g{};
 	g.C = dc; g.A = da; g.B = db; g.ldc = n; g.lda = k; g.ldb = k; g.m = m; g.n = n; g.k0 = 0; g.k1 = k;
 	g.alpha = alpha; g.beta = beta;
 	HIPCHK(ctx, gemm(ctx, g));
@@ -1887,14 +1890,12 @@ extern "C" int gpemu_test_staged_matrix(gpemu_ctx *ctx, int nb, const double *th
 {
 	if (!ctx || !thetas || !out || nb < 1 || nb > GPEMU_MAX_BATCH || b < 0 || b >= nb) return GPEMU_ERR_ARG;
 	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
-	std::vector<CovParams> ps((size_t)nb);
-	for (int i = 0; i < nb; i++) {
-		int rc = make_cov_params(ctx, thetas + (size_t)i * nthetas, nthetas, &ps[i]);
-		if (rc) return rc;
-	}
+	std::vector<CovParams> ps;
+	int rc = make_cov_params_batch(ctx, nb, thetas, nthetas, &ps);
+	if (rc) return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	ctx->pred_ready = false; ctx->cinv_ready = false;
-	int rc = stage_matrices(ctx, ps.data(), nb, 0);
+	invalidate_prediction(ctx);
+	rc = stage_matrices(ctx, ps.data(), nb, 0);
 	if (rc) return rc;
 	const int N = ctx->N, Np = ctx->Np;
 	HIPCHK(ctx, hipMemcpy2DAsync(out, (size_t)N * sizeof(double), ctx->dT + (size_t)b * ctx->T_stride, (size_t)Np * sizeof(double),
@@ -1943,21 +1944,15 @@ extern "C" int gpemu_test_gemm_bench(gpemu_ctx *ctx, int m, int n, int k, int ld
 		HIPCHK(ctx, hipMemsetAsync(da, 0, rows * ld * 8, ctx->stream));
 		HIPCHK(ctx, hipMemsetAsync(dc, 0, (size_t)m * ld * 8, ctx->stream));
 	}
-	GemmArgs g;
-	memset(&g, 0, sizeof g);
+	GemmArgs g{};
 	g.C = dc; g.A = da; g.B = da; g.ldc = ld; g.lda = ld; g.ldb = ld; g.m = m; g.n = n; g.k0 = 0; g.k1 = k;
 	g.alpha = -1.0; g.beta = beta; g.tri = tri;
 	if (getenv("GPEMU_BENCH_LD0")) { g.lda = 0; g.ldb = 0; }   // every operand row aliases row 0: staging loads always hit L1/L2
-	if (ctx->dTrace) {
-		ctx->trace_next = 0; ctx->trace_tag.clear();
-		HIPCHK(ctx, hipMemsetAsync(ctx->dTrace, 0, (size_t)ctx->trace_cap * 64, ctx->stream));
-		g.trace = trace_slot(ctx, "gemm_bench m=%d n=%d k=%d", m, n, k);
-	}
+	ctx->trace_next = 0; ctx->trace_tag.clear();
+	HIPCHK(ctx, trace_clear(ctx));
+	g.trace = trace_slot(ctx, "gemm_bench m=%d n=%d k=%d", m, n, k);   // (nullptr when tracing is off)
 	g.force_cfg = cfg;                                      // 2: 64x64 tiles, 8: 128x128 tiles, 0: the automatic choice
-	g.big_tiles = ctx->sched.gemm_big_tiles; g.table_sb = ctx->sched.gemm_table;
-	g.keep_idle_waves = ctx->sched.idle_waves ? 0 : 1;
-	g.stagger_ticks = ctx->sched.stagger_us * 100;
-	g.no_neg_modifier = ctx->sched.neg_modifier ? 0 : 1;
+	apply_sched(ctx->sched, g);
 	hipEvent_t e0, e1;
 	hipEventCreate(&e0); hipEventCreate(&e1);
 	hipError_t e = launch_gemm(ctx->stream, g);
@@ -1979,24 +1974,26 @@ extern "C" int gpemu_test_potrf(gpemu_ctx *ctx, int n, double *a, int *info)
 {
 	if (!ctx || n < 1 || !a) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	gpemu_ctx tmp;
-	scratch_for_matrix(&tmp, ctx, n);
-	const int Np = tmp.Np;
-	std::vector<double> h((size_t)(Np + 64) * Np, 0.0);
+	const int Np = round_up(n, LEAF), Rp = 64;
+	std::vector<double> h((size_t)(Np + Rp) * Np, 0.0);
 	for (int i = 0; i < Np; i++)
 		for (int j = 0; j <= i; j++)
 			h[(size_t)i * Np + j] = (i < n) ? a[(size_t)i * n + j] : (i == j ? 1.0 : 0.0);
-	HIPCHK(ctx, tmp.dT.grow(h.size()));
-	HIPCHK(ctx, tmp.dInfo.grow(1));
+	DevBuf<double> dT;
+	DevBuf<int> dInfo;
+	HIPCHK(ctx, dT.grow(h.size()));
+	HIPCHK(ctx, dInfo.grow(1));
+	const Tall t{dT, dInfo, Np, Rp, 1, (long)h.size()};
 	int big = INFO_NONE, inf = 0;
-	HIPCHK(ctx, hipMemcpyAsync(tmp.dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, tmp.stream));
-	HIPCHK(ctx, hipMemcpyAsync(tmp.dInfo, &big, sizeof(int), hipMemcpyHostToDevice, tmp.stream));
-	HIPCHK(ctx, potrf_rec(&tmp, 0, Np, 0));
-	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
-	HIPCHK(ctx, hipMemcpyAsync(h.data(), tmp.dT, h.size() * 8, hipMemcpyDeviceToHost, tmp.stream));
-	HIPCHK(ctx, hipMemcpyAsync(&inf, tmp.dInfo, sizeof(int), hipMemcpyDeviceToHost, tmp.stream));
-	HIPCHK(ctx, hipStreamSynchronize(tmp.stream));
-	if (info) *info = (inf >= INFO_NONE) ? 0 : inf;
+	HIPCHK(ctx, trace_clear(ctx));
+	HIPCHK(ctx, hipMemcpyAsync(dT, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dInfo, &big, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, potrf_all(ctx, t, 0));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(h.data(), dT, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(&inf, dInfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (info) *info = pivot_info(inf);
 	for (int i = 0; i < n; i++)
 		for (int j = 0; j < n; j++) a[(size_t)i * n + j] = (j <= i) ? h[(size_t)i * Np + j] : 0.0;
 	return GPEMU_OK;

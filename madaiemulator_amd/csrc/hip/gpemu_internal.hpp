@@ -7,6 +7,7 @@
 #include <vector>
 #include <map>
 #include <set>
+#include <tuple>
 
 #include "gpemu.h"
 
@@ -74,6 +75,9 @@ struct GemmArgs {
 	int row_table;       // 1: the square product with row-start skipping (C^-1 = U U^T) gives whole tile rows to an XCD (build_row_table)
 	int stagger_ticks;   // > 0: of the launch's first round, the workgroup in the odd slot of its CU starts this many 10 ns ticks late (kernel comment)
 };
+
+// what a lock-step factorisation works on: nb tall matrices, stride elements apart, and their info words (a view, no owner)
+struct Tall { double *T; int *info; int Np, Rp, nb; long stride; };
 
 // Schedule switches of ONE context: read from the environment once, when the context is created (INTEGRATION.md lists
 // the variables), and constant for its lifetime.  Two contexts of a process may differ; nothing process-wide is written
@@ -178,11 +182,9 @@ struct ParamRing {
 } // namespace gpemu
 
 struct gpemu_ctx {
-	gpemu_ctx() = default;
 	~gpemu_ctx();                      // waits for the stream, then releases everything (gpemu_api.hip)
 	int device = 0;
 	hipStream_t stream = nullptr;      // the context's one stream: every launch and copy of the context is ordered on it
-	bool own_stream = true;            // false: borrowed from another context (the matrix-only entries), not destroyed with this one
 	gpemu::Sched sched;                // schedule switches, fixed at creation
 	std::string err;
 
@@ -219,10 +221,8 @@ struct gpemu_ctx {
 	gpemu::ParamRing pring;
 	size_t res_len = 0;
 
-	// cached launch graphs for potrf, keyed by (Np, rows_total, with_inverse)
-	struct GraphKey { int Np; int aug_fixed; int inv; int nb; bool operator<(const GraphKey &o) const {
-		if (Np != o.Np) return Np < o.Np; if (aug_fixed != o.aug_fixed) return aug_fixed < o.aug_fixed;
-		if (inv != o.inv) return inv < o.inv; return nb < o.nb; } };
+	// cached launch graphs for potrf, keyed by (Np, Rp, with_inverse, nb)
+	using GraphKey = std::tuple<int, int, int, int>;
 	std::map<GraphKey, hipGraphExec_t> graphs;
 	std::set<GraphKey> warm;     // shapes factored once with plain launches (the graph is recorded on the second call)
 	bool use_graph = true;
@@ -270,6 +270,9 @@ struct gpemu_ctx {
 	int trace_cap = 0, trace_next = 0;
 	std::vector<std::string> trace_tag;
 	std::vector<double> last_thetas;
+private:
+	explicit gpemu_ctx() = default;    // made by gpemu_ctx_create and nowhere else (explicit: no aggregate initialisation either)
+	friend int gpemu_ctx_create(gpemu_ctx **out, int device);
 };
 
 namespace gpemu {
