@@ -292,6 +292,32 @@ int gpemu_trace_dump(gpemu_ctx *ctx, const char *path);
  * alpha must be +1 or -1 (the accumulators start from C/alpha) */
 int gpemu_test_gemm_nt(gpemu_ctx *ctx, int m, int n, int k, double alpha, int beta,
                        const double *a, const double *b, double *c);
+/* ONE launch of the GEMM kernel in any of its modes, on operands inside one host buffer (the arena):
+ *   C = beta*C + alpha * A[m x K] * B[n x K]^T over k in [k0, k1), C, A and B at element offsets offC/offA/offB.
+ * tri: only tiles that meet the lower triangle are computed (elements above the diagonal inside them may or may not be
+ * written).  kstart_mode: tiles skip k < floor16(first row - kstart_off), the caller promises A[i][k] = 0 for
+ * k < i - kstart_off.  kend_mode: tiles skip k >= ceil16(last column + 1 - kend_off), the caller promises B[j][k] = 0 for
+ * k > j - kend_off.  nbatch > 1: that many problems, bsC/bsA/bsB elements apart.  ksplit > 1: slice s of the k-range,
+ * klen = ceil16(ceil((k1 - k0) / ksplit)) long, goes to C + s*bsC (beta = 0, one problem).  force_cfg: 2 = 64x64 tiles,
+ * 8 = 128x128 tiles, 0 = the context's automatic choice.  fa: the workgroup of tile (0,0) leaves the updated 64x64 block
+ * as its Cholesky factor (lower triangle; the part above the diagonal of that block is scratch), a failed pivot at
+ * row r (1-based) of matrix b gives info_out[b] = fa_c0 + r, otherwise 0; needs tri, alpha = -1, beta = 1, 64x64 tiles.
+ * The whole arena is uploaded, and downloaded after the launch.  GPEMU_ERR_ARG, before anything runs, if the launch
+ * could address an element outside [0, arena_len), if k0 or k1 is no multiple of 16 or k1 <= k0, beta is not 0/1,
+ * beta = 1 with alpha not +-1, ksplit > 1 with beta or nbatch > 1, force_cfg is not 0/2/8, or fa is set and the launch
+ * would not take the factor-ahead tile.  info_out: max(nbatch, 1) words, may be NULL. */
+typedef struct gpemu_gemm_launch_args {
+	long offC, offA, offB;
+	long ldc, lda, ldb;
+	long bsC, bsA, bsB;
+	double alpha;
+	int m, n, k0, k1;
+	int beta, tri;
+	int kstart_mode, kstart_off, kend_mode, kend_off;
+	int nbatch, ksplit, force_cfg;
+	int fa, fa_c0;
+} gpemu_gemm_launch_args;
+int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_gemm_launch_args *args, int *info_out);
 /* micro-benchmark of one GEMM shape on device-resident random operands: cfg 0 = the automatic tile choice, 2 = 64x64
  * tiles (4 waves), 8 = 128x128 tiles (8 waves); tri = lower-trapezoid update as in the factorisation; HIP-event timed. */
 int gpemu_test_gemm_bench(gpemu_ctx *ctx, int m, int n, int k, int ld, int cfg, int tri, int beta, int reps,

@@ -22,6 +22,15 @@ RESULT_RING = 4
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 
+
+class GemmLaunchArgs(C.Structure):
+    """gpemu_gemm_launch_args of include/gpemu.h (every field defaults to 0)"""
+    _fields_ = ([(f, C.c_long) for f in ("offC", "offA", "offB", "ldc", "lda", "ldb", "bsC", "bsA", "bsB")] +
+                [("alpha", C.c_double)] +
+                [(f, C.c_int) for f in ("m", "n", "k0", "k1", "beta", "tri", "kstart_mode", "kstart_off", "kend_mode",
+                                        "kend_off", "nbatch", "ksplit", "force_cfg", "fa", "fa_c0")])
+
+
 # every symbol include/gpemu.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gpemu_ctx_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -79,6 +88,7 @@ SYMBOLS = {
     "gpemu_prof_end": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _dp]),
     "gpemu_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gpemu_test_gemm_nt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp]),
+    "gpemu_test_gemm_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(GemmLaunchArgs), _ip]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
     "gpemu_test_potrf": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
@@ -424,6 +434,15 @@ class Context:
         n = B.shape[0]
         self._chk(self.L.gpemu_test_gemm_nt(self.h, m, n, k, alpha, beta, _p(A), _p(B), _p(Cm)))
         return Cm
+
+    def test_gemm_launch(self, arena, **args):
+        """one GEMM launch in any of its modes on operands inside `arena` (gpemu_test_gemm_launch; args: the fields of
+        GemmLaunchArgs) -> (the arena after the launch, info word per matrix).  GpemuError(ERR_ARG) for a refused launch."""
+        out = _a(arena).ravel().copy()
+        a = GemmLaunchArgs(**{k: float(v) if k == "alpha" else int(v) for k, v in args.items()})
+        info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
+        self._chk(self.L.gpemu_test_gemm_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
+        return out, info
 
     def trace_dump(self, path):
         self._chk(self.L.gpemu_trace_dump(self.h, str(path).encode()))

@@ -1882,6 +1882,84 @@ extern "C" int gpemu_test_gemm_nt(gpemu_ctx *ctx, int m, int n, int k, double al
 	return GPEMU_OK;
 }
 
+// One gemm() call with caller-chosen GemmArgs on operands that live in ONE host buffer, the arena (C, A and B at element
+// offsets, as in production, where C sits in the same tall workspace as A and B): uploads the whole arena, applies the
+// context's Sched exactly as gemm() does (force_cfg on top), launches, and downloads the whole arena, so that a test sees
+// every element the launch must and must not have touched.
+// What the kernel may address is computed here first, and anything outside [0, arena_len) is refused: operand rows are
+// clamped to m-1 / n-1, only the columns [k0, k1) of A and B are read, and rows < m, columns < n of each of the
+// max(nbatch, ksplit, 1) C blocks are read (beta) and written.  Everything launch_gemm refuses, and what it takes on
+// trust (k0, k1 multiples of 16, k1 > k0), comes back as GPEMU_ERR_ARG as well.
+// The skipping modes drop k-blocks on the ASSUMPTION that the operand is zero there; the caller owes the kernel
+//   kstart_mode: A[i][k] = 0 for k < i - kstart_off   (the rows of [Z^T; U], build_corner: kstart_off dense rows first)
+//   kend_mode:   B[j][k] = 0 for k > j - kend_off     (the rows of L^-1; rows j >= k1 behind them are dense)
+// and the result equals the full product over [k0, k1) only under them.
+// fa: one info word per matrix, INFO_NONE before the launch, decoded by pivot_info afterwards (as gpemu_test_potrf); a
+// launch that would not take the factor-ahead tile is refused, never run without it.
+extern "C" int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_gemm_launch_args *p, int *info_out)
+{
+	if (!ctx || !arena || !p) return GPEMU_ERR_ARG;
+	constexpr long DIM_MAX = 1L << 20, LD_MAX = 1L << 24, LEN_MAX = 1L << 32, STRIDE_MAX = 1L << 32;   // no product below leaves 63 bits
+	if (arena_len < 1 || arena_len > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: arena length");
+	if (p->m < 1 || p->n < 1 || p->m > DIM_MAX || p->n > DIM_MAX) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: m, n");
+	if (p->k0 < 0 || p->k1 <= p->k0 || p->k1 > DIM_MAX || (p->k0 % GEMM_BK) != 0 || (p->k1 % GEMM_BK) != 0)
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: k0, k1 must be multiples of 16 with k0 < k1");
+	if (p->beta != 0 && p->beta != 1) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: beta is 0 or 1");
+	if (p->beta && p->alpha != 1.0 && p->alpha != -1.0) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: beta = 1 needs alpha = +-1");
+	if (p->force_cfg != 0 && p->force_cfg != 2 && p->force_cfg != 8) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: force_cfg is 0, 2 or 8");
+	if (p->nbatch < 0 || p->nbatch > GPEMU_MAX_BATCH || p->ksplit < 0 || p->ksplit > GPEMU_MAX_BATCH)
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: nbatch, ksplit");
+	if (p->ksplit > 1 && (p->beta || p->nbatch > 1)) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: split-K takes beta = 0 and one problem");
+	if ((p->tri != 0 && p->tri != 1) || (p->kstart_mode != 0 && p->kstart_mode != 1) || (p->kend_mode != 0 && p->kend_mode != 1) ||
+	    (p->fa != 0 && p->fa != 1) || p->kstart_off < 0 || p->kstart_off > DIM_MAX || p->kend_off < 0 || p->kend_off > DIM_MAX ||
+	    p->fa_c0 < 0 || p->fa_c0 > DIM_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: mode flags");
+	if (p->ldc < 1 || p->lda < 1 || p->ldb < 1 || p->ldc > LD_MAX || p->lda > LD_MAX || p->ldb > LD_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: leading dimensions");
+	if (std::labs(p->bsC) > STRIDE_MAX || std::labs(p->bsA) > STRIDE_MAX || std::labs(p->bsB) > STRIDE_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: batch strides");
+	const bool split = p->ksplit > 1;
+	const int nblk = std::max(std::max(p->nbatch, p->ksplit), 1);
+	// smallest and largest element index of one operand over all blocks (the stride may have either sign)
+	auto inside = [&](long off, long stride, long first, long last) {
+		const long s0 = 0, s1 = (long)(nblk - 1) * stride;
+		return off >= 0 && off <= arena_len && off + first + std::min(s0, s1) >= 0 && off + last + std::max(s0, s1) < arena_len;
+	};
+	if (!inside(p->offC, p->bsC, 0, (long)(p->m - 1) * p->ldc + p->n - 1) ||
+	    !inside(p->offA, split ? 0 : p->bsA, p->k0, (long)(p->m - 1) * p->lda + p->k1 - 1) ||
+	    !inside(p->offB, split ? 0 : p->bsB, p->k0, (long)(p->n - 1) * p->ldb + p->k1 - 1))
+		return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: the launch would address memory outside the arena");
+
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dArena;
+	DevBuf<int> dInfo;
+	HIPCHK(ctx, dArena.grow((size_t)arena_len));
+	HIPCHK(ctx, dInfo.grow((size_t)nblk));
+	GemmArgs g{};
+	g.C = dArena + p->offC; g.A = dArena + p->offA; g.B = dArena + p->offB;
+	g.ldc = p->ldc; g.lda = p->lda; g.ldb = p->ldb; g.m = p->m; g.n = p->n; g.k0 = p->k0; g.k1 = p->k1;
+	g.alpha = p->alpha; g.beta = p->beta; g.tri = p->tri;
+	g.kstart_mode = p->kstart_mode; g.kstart_off = p->kstart_off; g.kend_mode = p->kend_mode; g.kend_off = p->kend_off;
+	g.bsC = p->bsC; g.bsA = p->bsA; g.bsB = p->bsB; g.nbatch = p->nbatch; g.ksplit = p->ksplit;
+	g.force_cfg = p->force_cfg; g.fa = p->fa; g.fa_c0 = p->fa_c0; g.fa_info = dInfo;
+	if (g.fa) {
+		GemmArgs probe = g;
+		apply_sched(ctx->sched, probe);
+		if (!gemm_factor_ahead_ok(probe)) return fail(ctx, GPEMU_ERR_ARG, "gemm_launch: this launch would not take the factor-ahead tile");
+	}
+	std::vector<int> inf((size_t)nblk, INFO_NONE);
+	HIPCHK(ctx, hipMemcpyAsync(dArena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dInfo, inf.data(), (size_t)nblk * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, gemm(ctx, g));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(arena, dArena, (size_t)arena_len * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(inf.data(), dInfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (info_out)
+		for (int b = 0; b < std::max(p->nbatch, 1); b++) info_out[b] = pivot_info(inf[(size_t)b]);
+	return GPEMU_OK;
+}
+
 // The matrix a lock-step batch is factored from: stages nb matrices exactly as gpemu_loglik_batch does (ONE launch of
 // cov_stage_batch_kernel: lower tiles only, every matrix its own hyper-parameters) and copies the N x N block of matrix b
 // to the host without factorising.  Tiles strictly above the diagonal are not written by that path (out keeps what the
