@@ -216,6 +216,23 @@ int gpemu_predict_batch_collect(gpemu_ctx *ctx, int npoints, double *mean, doubl
 int gpemu_predict_batch_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev,
                             double *mean_dev, double *var_dev);
 
+/* ---- the mean alone: makeEmulatedMean (emulator.c:672-704) over makeKVector_fnptr's clamped k-vector (:578-593) ----
+ * mean[q] = h(x*_q)^T beta + sum_i k(x_i, x*_q) gamma_i,  gamma = C^-1 (y - H beta), for M query rows xq[M*d]: N kernel
+ * evaluations and N multiply-adds per query, no product with L^-1 (that is the variance's).  The k values are the ones the
+ * k-vectors of gpemu_predict_batch hold (same covariance code, nugget rule and < 1e-10 -> 0 clamp), used on chip: no k-vector
+ * is written, the batch buffers of gpemu_predict_batch are neither touched nor allocated.  The value agrees with
+ * gpemu_predict_batch's mean to rounding, NOT bit for bit: the sum over the design runs in another order.  That order is the
+ * same for a query whatever else the call holds: two calls, a query alone or among others, any entry below -- same bits.
+ * Any M (blocks of 16 384 internally).  GPEMU_ERR_STATE without a prediction set-up (gpemu_predict_setup or
+ * gpemu_predict_setup_batch); GPEMU_ERR_ARG on a NULL pointer or npoints < 1.  The enqueue / collect pair shares the
+ * staging and the one-batch-per-context rule with gpemu_predict_batch_enqueue / _collect; a batch is collected by the
+ * collect of its own kind (the other one: GPEMU_ERR_STATE, the batch stays enqueued). */
+int gpemu_predict_mean(gpemu_ctx *ctx, int npoints, const double *xq, double *mean);
+int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
+int gpemu_predict_mean_collect(gpemu_ctx *ctx, int npoints, double *mean);
+/* device pointers: only enqueues on the context's stream, no host synchronisation (the first call sizes the scratch) */
+int gpemu_predict_mean_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev);
+
 /* ---- leave-one-out validation of a trained emulator -----------------
  * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
  * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
@@ -274,6 +291,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_GEMM_BIG 5  /* only the GEMM launches on the 128x128 8-wave kernel (the dominant kernel of a batch) */
 #define GPEMU_PROF_GEMM_K512 6 /* only the GEMM launches with a contraction length >= 512 */
 #define GPEMU_PROF_LOO     7   /* the two launches of gpemu_loo[_dev]: column sums over L^-1 (bytes = 8 N (N+1) / 2), finish */
+#define GPEMU_PROF_MEAN    8   /* the two launches of the mean-only sweep: flops = M*N*(kernel + 2) with kernel = 3 d (the squared distance), bytes = 8*M*(d+1) */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

@@ -16,6 +16,7 @@ POWEREXP, MATERN32, MATERN52 = 1, 2, 3
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_PD, ERR_REGRESSION, ERR_STATE = range(7)
 PROF_NONE, PROF_GEMM, PROF_FILL, PROF_LEAF, PROF_POTRF, PROF_GEMM_BIG, PROF_GEMM_K512 = range(7)
 PROF_LOO = 7
+PROF_MEAN = 8
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -69,6 +70,10 @@ SYMBOLS = {
     "gpemu_predict_batch_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_batch_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "gpemu_predict_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_mean": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "gpemu_predict_mean_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "gpemu_predict_mean_collect": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "gpemu_predict_mean_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -396,6 +401,26 @@ class Context:
 
     def predict_dev(self, M, xq_dev, mean_dev, var_dev):
         self._chk(self.L.gpemu_predict_batch_dev(self.h, M, xq_dev, mean_dev, var_dev))
+
+    # the posterior mean alone: fused k-vector . gamma sweep, no product with L^-1 and no batch buffers
+    def predict_mean(self, Xq):
+        Xq = _a(Xq).reshape(-1, self.d)
+        mean = np.empty(Xq.shape[0])
+        self._chk(self.L.gpemu_predict_mean(self.h, Xq.shape[0], _p(Xq), _p(mean)))
+        return mean
+
+    def predict_mean_dev(self, M, xq_dev, mean_dev):
+        self._chk(self.L.gpemu_predict_mean_dev(self.h, M, xq_dev, mean_dev))
+
+    def predict_mean_enqueue(self, Xq):
+        Xq = _a(Xq).reshape(-1, self.d)
+        self._npred = Xq.shape[0]
+        self._chk(self.L.gpemu_predict_mean_enqueue(self.h, Xq.shape[0], _p(Xq)))
+
+    def predict_mean_collect(self):
+        m = np.empty(self._npred)
+        self._chk(self.L.gpemu_predict_mean_collect(self.h, self._npred, _p(m)))
+        return m
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

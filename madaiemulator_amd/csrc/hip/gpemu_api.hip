@@ -259,12 +259,13 @@ static void free_model(gpemu_ctx *ctx)
 	free_graphs(ctx);
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
 	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
-	                &ctx->dLooPart, &ctx->dLoo})
+	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart})
 		b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	invalidate_prediction(ctx);
 	ctx->pred_pending = 0;
+	ctx->pred_pending_mean = false;
 	ctx->S_dim = 0;
 }
 
@@ -1254,6 +1255,21 @@ extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_d
 	return GPEMU_OK;
 }
 
+// the staging of the host-buffer entries (mean+variance and mean-only share it), for at least M queries
+static int ensure_pred_stage(gpemu_ctx *ctx, int M)
+{
+	if (ctx->stage_cap() >= (size_t)M) return GPEMU_OK;
+	const int d = ctx->d;
+	const size_t cap = (size_t)std::max(M, 64);
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->hStage.reset();                           // (the capacity is zero until all three are there again)
+	int rc = grow(ctx, ctx->dXq, cap * d);
+	if (!rc) rc = grow(ctx, ctx->dMean, 2 * cap);
+	if (rc) return rc;
+	HIPCHK(ctx, ctx->hStage.grow(cap * (d + 2)));
+	return GPEMU_OK;
+}
+
 // host-buffer entry, asynchronous form: the queries are staged through pinned memory, the batch runs on the context's
 // stream and the results come back into pinned memory; nothing blocks until gpemu_predict_batch_collect.  Several
 // contexts (the PCA components of a multi-output emulator) can so work on one query at the same time.
@@ -1264,15 +1280,7 @@ extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *
 	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int d = ctx->d;
-	if (ctx->stage_cap() < (size_t)M) {
-		const size_t cap = (size_t)std::max(M, 64);
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		ctx->hStage.reset();                           // (the capacity is zero until all three are there again)
-		int rc = grow(ctx, ctx->dXq, cap * d);
-		if (!rc) rc = grow(ctx, ctx->dMean, 2 * cap);
-		if (rc) return rc;
-		HIPCHK(ctx, ctx->hStage.grow(cap * (d + 2)));
-	}
+	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
 	const size_t cap = ctx->stage_cap();
 	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d, *hv = hm + cap;
 	memcpy(hx, xq, (size_t)M * d * sizeof(double));
@@ -1287,6 +1295,7 @@ extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *
 		HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	}
 	ctx->pred_pending = M;
+	ctx->pred_pending_mean = false;
 	return GPEMU_OK;
 }
 
@@ -1294,6 +1303,7 @@ extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, 
 {
 	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is mean-only: collect it with gpemu_predict_mean_collect");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
 	memcpy(mean, hm, (size_t)M * sizeof(double));
@@ -1308,6 +1318,85 @@ extern "C" int gpemu_predict_batch(gpemu_ctx *ctx, int M, const double *xq, doub
 	int rc = gpemu_predict_batch_enqueue(ctx, M, xq);
 	if (rc) return rc;
 	return gpemu_predict_batch_collect(ctx, M, mean, var);
+}
+
+// ---------------------------------------------------------------------------
+// mean-only sweep (gpemu.h): two launches per block of up to PRED_BATCH_MAX queries on the context's stream -- the fused
+// k-vector . gamma kernel and the slice sum with h^T beta.  Reads dX, dXg, dMid, the gamma row of dLinvAug and dBetaQ; its
+// only scratch is dMeanPart.  dKq and dV are neither read nor allocated.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_predict_mean_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev)
+{
+	if (!ctx || M < 1 || !xq_dev || !mean_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int Np = ctx->Np, N = ctx->N, d = ctx->d;
+	const int nslice = predict_mean_slices(Np);
+	const int cap = std::min(PRED_BATCH_MAX, round_up(M, 64));
+	// (laid out with the row length it was sized for: a later, shorter call uses the same stride)
+	int rc = grow(ctx, ctx->dMeanPart, (size_t)nslice * cap);
+	if (rc) return rc;
+	const long pstride = (long)(ctx->dMeanPart.size() / (size_t)nslice);
+	const CovParams &p = ctx->pred_cov;
+	const bool gram = p.gram && ctx->sched.kvec_gram && ctx->dXg && ctx->dMid;
+	const double *gamma = ctx->dLinvAug + (size_t)Np * Np;
+	for (int q0 = 0; q0 < M; q0 += cap) {
+		const int mb = std::min(cap, M - q0);
+		const double *xq = xq_dev + (size_t)q0 * d;
+		if (prof_on(ctx, GPEMU_PROF_MEAN)) { ctx->prof.tag.push_back("predict_mean"); ctx->prof.tag.push_back("predict_mean_finish"); }
+		{
+			// flops: per element the squared distance (3 d) and the product with gamma (2); bytes: coordinates in, mean out
+			ProfScope ps(ctx, GPEMU_PROF_MEAN, (double)mb * N * (3.0 * d + 2.0), 8.0 * (double)mb * (d + 1));
+			HIPCHK(ctx, launch_predict_mean(ctx->stream, ctx->dMeanPart, pstride, xq, mb, ctx->dX, ctx->dXg, ctx->dMid, gamma, N, Np, d, p, gram));
+		}
+		{
+			ProfScope ps(ctx, GPEMU_PROF_MEAN, 2.0 * mb * ctx->nreg, 0.0);
+			HIPCHK(ctx, launch_predict_mean_finish(ctx->stream, ctx->dMeanPart, pstride, nslice, mb, ctx->nreg, d, xq, ctx->dBetaQ,
+			                                       mean_dev + q0));
+		}
+	}
+	return GPEMU_OK;
+}
+
+// host buffers, in two halves: the staging (and the one-batch-per-context rule) is the mean+variance pair's
+extern "C" int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int M, const double *xq)
+{
+	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d;
+	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	const int rc = gpemu_predict_mean_dev(ctx, M, ctx->dXq, ctx->dMean);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	ctx->pred_pending = M;
+	ctx->pred_pending_mean = true;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_mean_collect(gpemu_ctx *ctx, int M, double *mean)
+{
+	if (!ctx || !mean) return GPEMU_ERR_ARG;
+	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (!ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch has variances: collect it with gpemu_predict_batch_collect");
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
+	ctx->pred_pending = 0;
+	ctx->pred_pending_mean = false;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_mean(gpemu_ctx *ctx, int M, const double *xq, double *mean)
+{
+	if (!ctx || M < 1 || !xq || !mean) return GPEMU_ERR_ARG;
+	const int rc = gpemu_predict_mean_enqueue(ctx, M, xq);
+	if (rc) return rc;
+	return gpemu_predict_mean_collect(ctx, M, mean);
 }
 
 // ---------------------------------------------------------------------------

@@ -242,6 +242,8 @@ struct gpemu_ctx {
 	size_t stage_cap() const { return hStage.size() / (size_t)(d + 2); }   // (hStage is allocated last, and gone with the model)
 	double *dVar() const { return dMean + stage_cap(); }
 	int pred_pending = 0;        // queries of an enqueued, not yet collected prediction batch
+	bool pred_pending_mean = false;   // that batch came from gpemu_predict_mean_enqueue (no variances in the staging)
+	gpemu::DevBuf<double> dMeanPart;  // mean-only sweep: slice partial sums, predict_mean_slices(Np) x queries of a block
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
@@ -300,6 +302,13 @@ hipError_t launch_kvec_small(hipStream_t s, double *Kq, long ld, const double *X
                              const CovParams &p);
 hipError_t launch_predict_finish_small(hipStream_t s, const double *Vp, long ldv, long sstride, int nslice, int M, int Np, int nreg,
                                        int d, const double *Xq, const double *betaQ, double kappa, double *mean, double *var);
+// the mean-only sweep (gpemu_predict_mean): partial sums k*.gamma per (design slice, query) without storing a k-vector, then
+// their sum in slice order plus h^T beta.  part: predict_mean_slices(Np) rows of pstride >= M doubles.
+int predict_mean_slices(int Np);
+hipError_t launch_predict_mean(hipStream_t s, double *part, long pstride, const double *Xq, int M, const double *X, const double *Xg,
+                               const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p, bool gram);
+hipError_t launch_predict_mean_finish(hipStream_t s, const double *part, long pstride, int nslice, int M, int nreg, int d,
+                                      const double *Xq, const double *beta, double *mean);
 hipError_t launch_grad_partials(hipStream_t s, const double *S, long lds, int soff, long sstride, int nb, const double *X, int N,
                                 int d, double *ag, int np_pad, long gstride, double *part, long pstride, int *nparts,
                                 int exact_kind = 0, int nbeta = 0, const CovParams *pp_dev = nullptr, bool lit_noclamp = false,

@@ -99,6 +99,20 @@ __device__ __forceinline__ double fast_sqrt(double a)
 	return (a > 0.0) ? s : 0.0;
 }
 
+// value of an element from a = sum ((x_k - y_k) w_k)^2, difference form, before the nugget rule and the clamp (shared by the
+// stored fill below and the fused mean sweep, predict_mean_kernel)
+__device__ __forceinline__ double cov_from_a_diff(double a, int kind, double amp, const double *tab /* LDS: 2^(j/64) */)
+{
+	if (kind == GPEMU_POWEREXP) return fast_exp_neg(-a, tab) * amp;                 // emulator.c:133,141
+	const double sdist = fast_sqrt(a);                                              // distance / rho
+	if (kind == GPEMU_MATERN32) {
+		const double root3 = 1.732050808;                                           // emulator.c:359 (literal)
+		return amp * (1 + root3 * sdist) * fast_exp_neg(-root3 * sdist, tab);
+	}
+	const double root5 = 2.236067978;                                               // emulator.c:452 (literal)
+	return amp * (1 + root5 * sdist + (5.0 / 3.0) * sdist * sdist) * fast_exp_neg(-root5 * sdist, tab);
+}
+
 // out[r][c] = cov(Xr[r], Xc[c]);  rows/cols beyond nr/nc (padding up to the
 // launch grid) get identity (square factorisation matrix) or zero.
 // p.w[k] is the per-dimension scale applied while staging: pow-exp sqrt(0.5)/r_k (so the exponent is
@@ -164,18 +178,7 @@ __device__ __forceinline__ void cov_fill_tile(double *out, long ld, const double
 		double v;
 		if (row < nr && colv) {
 			const double a = acc[t];
-			if (p.kind == GPEMU_POWEREXP) {
-				v = fast_exp_neg(-a, tab) * p.amp;                                  // emulator.c:133,141
-			} else {
-				const double sdist = fast_sqrt(a);                                  // distance / rho
-				if (p.kind == GPEMU_MATERN32) {
-					const double root3 = 1.732050808;                               // emulator.c:359 (literal)
-					v = p.amp * (1 + root3 * sdist) * fast_exp_neg(-root3 * sdist, tab);
-				} else {
-					const double root5 = 2.236067978;                               // emulator.c:452 (literal)
-					v = p.amp * (1 + root5 * sdist + (5.0 / 3.0) * sdist * sdist) * fast_exp_neg(-root5 * sdist, tab);
-				}
-			}
+			v = cov_from_a_diff(a, p.kind, p.amp, tab);
 			if (a <= p.cand) {
 				// rare: the two points may coincide in every coordinate -> exact test on the raw coordinates
 				// (emulator.c:136-150 / :368-384 / :462-478: nugget wherever ALL |x_k - y_k| < eps)
@@ -246,10 +249,16 @@ __device__ __forceinline__ void gram_tables(const CovParams &p, int d, double *t
 // RECT = true: k-vectors (makeKVector_fnptr, emulator.c:578-593): rows are query points, centred on the fly with the
 // design's per-dimension centre `mid`; a wave whose query rows lie so far outside the design that the Gram form's
 // cancellation bound no longer holds (|x'|^2 > 16) recomputes its elements from differences (the candidate path below).
-template <int KIND, bool RECT = false>
-__device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const double *Xa, const double *Xag, const double *mid,
-                                                     int na_rows, const double *Xb, const double *Xbg, int nb_cols, int d,
-                                                     const CovParams &p, int mode, int tr, int tc, const double *tab, const double *wsc)
+// First half, shared by the stored fills and the fused mean sweep (predict_mean_kernel): the lane's sixteen squared scaled
+// distances in acc (element (r, j) = tile row 16 wave + g + 4 r, tile column q + 16 j), candidates already recomputed from
+// differences; returns the mask of the elements (bit 4 r + j) that pass the exact "same point" test.
+// ROWFAR = false: one far query row sends the whole WAVE to exact distances (the stored k-vectors' rule, pinned bit for bit by
+// their tests).  ROWFAR = true: each of the lane's four rows decides for itself, so that an element's value never depends on
+// which other queries share its wave.
+template <int KIND, bool RECT, bool ROWFAR = false>
+__device__ __forceinline__ unsigned gram_tile_u2(d4g_t (&acc)[4], const double *Xa, const double *Xag, const double *mid,
+                                                 int na_rows, const double *Xb, const double *Xbg, int nb_cols, int d,
+                                                 const CovParams &p, int tr, int tc, const double *wsc)
 {
 	const int tid = threadIdx.x;
 	const double croot = gram_root(KIND);
@@ -267,7 +276,6 @@ __device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const
 		bv[j] = bc < nb_cols;
 		bp[j] = Xbg + (long)(bv[j] ? bc : 0) * d;
 	}
-	d4g_t acc[4];
 #pragma unroll
 	for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
 	double na = 0.0, nb[4] = {0.0, 0.0, 0.0, 0.0};
@@ -288,6 +296,12 @@ __device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const
 	na += __shfl_xor(na, 16); na += __shfl_xor(na, 32);
 #pragma unroll
 	for (int j = 0; j < 4; j++) { nb[j] += __shfl_xor(nb[j], 16); nb[j] += __shfl_xor(nb[j], 32); }
+	double thr[4] = {cand_g, cand_g, cand_g, cand_g};                     // ROWFAR: the threshold of the lane's row g + 4 r
+	if (ROWFAR) {
+#pragma unroll
+		for (int r = 0; r < 4; r++)
+			if (__shfl(na, g + 4 * r) > 16.0 * croot * croot) thr[r] = HUGE_VAL;   // (lane g + 4 r holds that row's |x'|^2)
+	} else
 	if (RECT && __any(na > 16.0 * croot * croot)) cand_g = HUGE_VAL;      // query rows far outside the design: exact distances
 	// one more matrix step adds |x'_row|^2 + |y'_col|^2: k slot 0 = (|x'|^2, 1), k slot 1 = (1, |y'|^2)
 	{
@@ -306,7 +320,7 @@ __device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const
 #pragma unroll
 	for (int r = 0; r < 4; r++)
 #pragma unroll
-		for (int j = 0; j < 4; j++) cand = cand || (acc[j][r] <= cand_g);
+		for (int j = 0; j < 4; j++) cand = cand || (acc[j][r] <= (ROWFAR ? thr[r] : cand_g));
 	if (__any(cand)) {
 		// (one copy of the slow code: the element index is a run-time value here, the accumulators go through LDS-free
 		// register selects -- this runs for the diagonal tiles and for duplicated design points only)
@@ -320,7 +334,12 @@ __device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const
 				for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
 			{
 				const int row = row0 + 4 * r, col = col0 + 16 * j;
-				if (ae <= cand_g && row < na_rows && col < nb_cols) {
+				double te = cand_g;
+				if (ROWFAR) {
+#pragma unroll
+					for (int rr = 0; rr < 4; rr++) te = (rr == r) ? thr[rr] : te;
+				}
+				if (ae <= te && row < na_rows && col < nb_cols) {
 					int cnt = 0;
 					double a = 0.0;
 					for (int k = 0; k < d; k++) {
@@ -343,6 +362,20 @@ __device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const
 			}
 		}
 	}
+	return same;
+}
+
+template <int KIND, bool RECT = false>
+__device__ __forceinline__ void cov_fill_tile_gram_k(double *out, long ld, const double *Xa, const double *Xag, const double *mid,
+                                                     int na_rows, const double *Xb, const double *Xbg, int nb_cols, int d,
+                                                     const CovParams &p, int mode, int tr, int tc, const double *tab, const double *wsc)
+{
+	d4g_t acc[4];
+	const unsigned same = gram_tile_u2<KIND, RECT>(acc, Xa, Xag, mid, na_rows, Xb, Xbg, nb_cols, d, p, tr, tc, wsc);
+	const int tid = threadIdx.x;
+	const int lane = tid & 63, wave = tid >> 6;
+	const int q = lane & 15, g = lane >> 4;
+	const int row0 = tr * FT + 16 * wave + g, col0 = tc * FT + q;
 	const bool full = (tr * FT + FT <= na_rows) && (tc * FT + FT <= nb_cols);
 	if (full && (RECT || !(mode & FILL_CLAMP)) && !__any(same != 0)) {
 		// the common tile: no coinciding points anywhere in the wave -- no nugget select in the element loop (it cost 7 of
@@ -739,6 +772,209 @@ __global__ __launch_bounds__(256) void predict_finish_kernel(const double *V, lo
 		mean[q] = m;
 		var[q] = kappa - ss + reg;
 	}
+}
+
+// ---------------------------------------------------------------------------
+// Mean-only sweep (makeEmulatedMean, emulator.c:672-704, with makeKVector_fnptr's clamp, :578-593):
+//   mean(x*) = h(x*)^T beta + sum_i k(x_i, x*) gamma_i
+// needs no product with L^-1, so the k-vector elements are used where they are made: one workgroup takes a 64-query tile and
+// one slice of the design (MEAN_TPW consecutive 64-point blocks), computes each 64 x 64 tile of k values exactly as the stored
+// k-vector kernels do (Gram form: gram_tile_u2 + cov_from_u2_gram; difference form: cov_from_a_diff; nugget rule, clamp, the
+// -700 exponent hold), multiplies by gamma (the slice's part staged in LDS) and accumulates per query row in registers.
+// Nothing of the tile goes to HBM: 8 bytes per (query, slice) leave the workgroup.  No atomics, no workgroup waits for
+// another: the slices' partial sums are added in slice order by predict_mean_finish_kernel.
+// One summation order per query, whatever else is in the call: a row's elements are added column by column within the lane
+// that holds them (tile after tile), the lanes of a row are combined by a fixed butterfly, the slices in index order; the
+// slicing depends on Np alone, and no decision about an element looks at another query (gram_tile_u2<.., ROWFAR = true>).
+// Columns i >= N carry gamma = 0 and are skipped explicitly on edge tiles; rows q >= M are computed on zero coordinates and
+// never stored.
+// ---------------------------------------------------------------------------
+constexpr int MEAN_TPW = GRAM_TPW;        // design blocks per slice
+
+int predict_mean_slices(int Np) { return (Np / FT + MEAN_TPW - 1) / MEAN_TPW; }
+
+template <int KIND, bool GRAM>
+__global__ __launch_bounds__(256, 4) void predict_mean_kernel(double *part, long pstride, const double *Xq, int M, const double *X,
+                                                            const double *Xg, const double *mid, const double *gamma, int N, int Np,
+                                                            int d, CovParams p)
+{
+	__shared__ double gam_s[MEAN_TPW * FT];
+	const int tid = threadIdx.x;
+	const int ntc = Np / FT, nsl = (ntc + MEAN_TPW - 1) / MEAN_TPW;
+	const int tr = blockIdx.x / nsl, slice = blockIdx.x % nsl, tc0 = slice * MEAN_TPW;
+	{
+		const int col = tc0 * FT + tid;
+		gam_s[tid] = (col < N) ? gamma[col] : 0.0;
+	}
+	static_assert(MEAN_TPW * FT == 256, "one gamma entry per thread");
+	if (GRAM) {
+		__shared__ double tab[EXP_TAB_G];
+		__shared__ double wsc[GPEMU_MAX_PARAMS];
+		__shared__ double mid_s[GPEMU_MAX_PARAMS];
+		gram_tables(p, d, tab, wsc);
+		if (tid < GPEMU_MAX_PARAMS) mid_s[tid] = (tid < d) ? mid[tid] : 0.0;
+		__syncthreads();
+		const int lane = tid & 63, wave = tid >> 6;
+		const int q = lane & 15, g = lane >> 4;
+		double sum[4] = {0.0, 0.0, 0.0, 0.0};
+		for (int i = 0; i < MEAN_TPW; i++) {
+			const int tc = tc0 + i;
+			if (tc >= ntc) break;
+			d4g_t acc[4];
+			const unsigned same = gram_tile_u2<KIND, true, true>(acc, Xq, nullptr, mid_s, M, X, Xg, N, d, p, tr, tc, wsc);
+			const double *gs = gam_s + i * FT + q;
+			if (tc * FT + FT <= N && !__any(same != 0)) {
+				// the common tile: no coinciding points in the wave, every column a design point
+#pragma unroll
+				for (int r = 0; r < 4; r++) {
+#pragma unroll
+					for (int j = 0; j < 4; j++) {
+						double v = cov_from_u2_gram<KIND>(acc[j][r], tab);
+						if (v < 1E-10) v = 0.0;                                           // emulator.c:588-590
+						sum[r] = fma(v, gs[16 * j], sum[r]);
+						if (j & 1) __builtin_amdgcn_sched_barrier(0);                 // two element chains at a time (cov_fill_tile_gram_k)
+					}
+				}
+				continue;
+			}
+			const double nug = p.nug;
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+#pragma unroll
+				for (int j = 0; j < 4; j++) {
+					double v = cov_from_u2_gram<KIND>(acc[j][r], tab);
+					if (same & (1u << (4 * r + j))) v += nug;
+					if (v < 1E-10) v = 0.0;                                               // emulator.c:588-590
+					// (a padding column's distance was not held at the exponent limit: its value may be anything)
+					if (tc * FT + q + 16 * j >= N) v = 0.0;
+					sum[r] = fma(v, gs[16 * j], sum[r]);
+					if (j & 1) __builtin_amdgcn_sched_barrier(0);
+				}
+			}
+		}
+		// the sixteen lanes q of a row: butterfly over the q bits, the same for every row
+#pragma unroll
+		for (int r = 0; r < 4; r++) {
+			double t = sum[r];
+			t += __shfl_xor(t, 1);
+			t += __shfl_xor(t, 2);
+			t += __shfl_xor(t, 4);
+			t += __shfl_xor(t, 8);
+			const int row = tr * FT + 16 * wave + g + 4 * r;
+			if (q == 0 && row < M) part[(long)slice * pstride + row] = t;
+		}
+	} else {
+		// difference form: the lane owns query row (tid & 63) of the tile, its wave the tile columns w, w + 4, ...; the design
+		// block is staged in LDS, scaled as cov_fill_tile scales it (every lane of a wave reads the same word: a broadcast)
+		__shared__ double xd_s[FT * (GPEMU_MAX_PARAMS + 1)];
+		__shared__ double tab[EXP_TAB];
+		__shared__ double red[4 * FT];
+		if (tid < EXP_TAB) tab[tid] = exp2((double)tid * (1.0 / EXP_TAB));
+		const int sd = d + 1;
+		const int row = tr * FT + (tid & 63), csub = tid >> 6;
+		const bool rowv = row < M;
+		const double *xq = Xq + (long)(rowv ? row : 0) * d;
+		double sum = 0.0;
+		for (int i = 0; i < MEAN_TPW; i++) {
+			const int tc = tc0 + i;
+			if (tc >= ntc) break;
+			__syncthreads();
+			for (int e = tid; e < FT * d; e += 256) {
+				const int c = e / d, k = e % d;
+				const int gc = tc * FT + c;
+				xd_s[c * sd + k] = (gc < N) ? X[(long)gc * d + k] * p.w[(KIND == GPEMU_POWEREXP) ? k : 0] : 0.0;
+			}
+			__syncthreads();
+			double acc[16];
+#pragma unroll
+			for (int t = 0; t < 16; t++) acc[t] = 0.0;
+			for (int k0 = 0; k0 < d; k0 += DCH) {
+				double xr[DCH];
+#pragma unroll
+				for (int k = 0; k < DCH; k++)
+					xr[k] = ((k0 + k) < d && rowv) ? xq[k0 + k] * p.w[(KIND == GPEMU_POWEREXP) ? (k0 + k) : 0] : 0.0;
+#pragma unroll
+				for (int t = 0; t < 16; t++) {
+					const double *xc = &xd_s[(csub + 4 * t) * sd + k0];
+#pragma unroll
+					for (int k = 0; k < DCH; k++) {
+						if (k0 + k < d) {
+							const double diff = xr[k] - xc[k];
+							acc[t] = fma(diff, diff, acc[t]);
+						}
+					}
+				}
+			}
+#pragma unroll
+			for (int t = 0; t < 16; t++) {
+				const int col = tc * FT + csub + 4 * t;
+				if (rowv && col < N) {
+					const double a = acc[t];
+					double v = cov_from_a_diff(a, KIND, p.amp, tab);
+					if (a <= p.cand) {
+						// rare: exact "same point" test on the raw coordinates (emulator.c:136-150 / :368-384 / :462-478)
+						int cnt = 0;
+						for (int k = 0; k < d; k++) cnt += (fabs(xq[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
+						if (cnt == d) v += p.nug;
+					}
+					if (v < 1E-10) v = 0.0;                                               // emulator.c:588-590
+					sum = fma(v, gam_s[i * FT + csub + 4 * t], sum);
+				}
+			}
+		}
+		red[tid] = sum;
+		__syncthreads();
+		if (tid < FT && rowv) part[(long)slice * pstride + row] = ((red[tid] + red[FT + tid]) + red[2 * FT + tid]) + red[3 * FT + tid];
+	}
+}
+
+// mean[q] = h(x*_q)^T beta + the slices' partial sums in slice order (regression.c:9-67, emulator.c:672-704)
+__global__ __launch_bounds__(256) void predict_mean_finish_kernel(const double *part, long pstride, int nslice, int M, int nreg, int d,
+                                                                  const double *Xq, const double *beta, double *mean)
+{
+	const int q = blockIdx.x * 256 + threadIdx.x;
+	if (q >= M) return;
+	double kg = 0.0;
+	for (int s = 0; s < nslice; s++) kg += part[(long)s * pstride + q];
+	const double *x = Xq + (long)q * d;
+	double hb = 0.0;
+	for (int a = 0; a < nreg; a++) hb = fma(hfun(a, x, d), beta[a], hb);
+	mean[q] = hb + kg;
+}
+
+template <bool GRAM>
+static void launch_predict_mean_kind(hipStream_t s, dim3 grid, double *part, long pstride, const double *Xq, int M, const double *X,
+                                     const double *Xg, const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p)
+{
+	if (p.kind == GPEMU_POWEREXP)
+		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	else if (p.kind == GPEMU_MATERN32)
+		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	else
+		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+}
+
+// part: predict_mean_slices(Np) rows of pstride >= M doubles.  gram: the Gram form (needs p.gram, Xg, mid), else differences.
+hipError_t launch_predict_mean(hipStream_t s, double *part, long pstride, const double *Xq, int M, const double *X, const double *Xg,
+                               const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p, bool gram)
+{
+	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
+	if (gram && (!p.gram || !Xg || !mid)) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
+	if (gram) {
+		const hipError_t e = ensure_exp_table(s);
+		if (e != hipSuccess) return e;
+		launch_predict_mean_kind<true>(s, grid, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	} else launch_predict_mean_kind<false>(s, grid, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	return hipGetLastError();
+}
+
+hipError_t launch_predict_mean_finish(hipStream_t s, const double *part, long pstride, int nslice, int M, int nreg, int d,
+                                      const double *Xq, const double *beta, double *mean)
+{
+	hipLaunchKernelGGL(predict_mean_finish_kernel, dim3((M + 255) / 256), dim3(256), 0, s, part, pstride, nslice, M, nreg, d, Xq, beta, mean);
+	return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

@@ -21,6 +21,9 @@ public:
 	// batch: one row per query point; Means[q], Errors[q] have number_outputs entries
 	void QueryEmulator(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
 	                   std::vector<std::vector<double> > &Errors);
+	// the means alone, one row per query point: the device's mean-only sweep (no variance, no product with L^-1); agrees
+	// with QueryEmulator's Means to rounding
+	void QueryEmulatorMeans(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

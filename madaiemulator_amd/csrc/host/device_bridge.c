@@ -924,6 +924,36 @@ void emulate_points_collect(emulator_struct *e, int npoints, double *mean, doubl
 	if (rc) die(en->ctx, rc, "emulate_point");
 }
 
+/* the mean alone (makeEmulatedMean, emulator.c:672-704, over the clamped k-vector): gpemu_predict_mean's fused sweep, no
+ * variance and none of its batch buffers */
+void emulate_points_mean(emulator_struct *e, gsl_matrix *points, double *mean)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	double *q = pack_matrix(points);
+	int rc = gpemu_predict_mean(en->ctx, (int)points->size1, q, mean);
+	free(q);
+	if (rc) die(en->ctx, rc, "emulate_points_mean");
+}
+
+void emulate_points_mean_enqueue(emulator_struct *e, gsl_matrix *points)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	double *q = pack_matrix(points);
+	int rc = gpemu_predict_mean_enqueue(en->ctx, (int)points->size1, q);
+	free(q);
+	if (rc) die(en->ctx, rc, "emulate_points_mean");
+}
+
+void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	int rc = gpemu_predict_mean_collect(en->ctx, npoints, mean);
+	if (rc) die(en->ctx, rc, "emulate_points_mean");
+}
+
 /* leave-one-out at every training point (gpemu_loo) */
 void emulate_loo(emulator_struct *e, double *mean, double *variance)
 {

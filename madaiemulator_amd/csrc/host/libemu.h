@@ -242,6 +242,11 @@ void emulate_points(emulator_struct *e, gsl_matrix *points, double *mean, double
 /* emulate_points in two halves (device work runs in between): used to query all PCA components at the same time */
 void emulate_points_enqueue(emulator_struct *e, gsl_matrix *points);
 void emulate_points_collect(emulator_struct *e, int npoints, double *mean, double *variance);
+/* the posterior mean alone (makeEmulatedMean, emulator.c:672-704): the device's fused k-vector . gamma sweep, no variance,
+ * no N^2 product; agrees with emulate_points' mean to rounding (another summation order).  Errors end in gpemu_host_fatal. */
+void emulate_points_mean(emulator_struct *e, gsl_matrix *points, double *mean);
+void emulate_points_mean_enqueue(emulator_struct *e, gsl_matrix *points);
+void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean);
 /* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
  * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
 void emulate_loo(emulator_struct *e, double *mean, double *variance);
@@ -265,6 +270,9 @@ void emulate_point_multi(multi_emulator *emu, gsl_vector *the_point, gsl_vector 
 void emulate_point_multi_pca(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance);
 /* extension: batched form of the two calls above; outputs are npoints x nt (or x nr) row-major */
 void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out);
+/* the means alone: npoints x nr (pca_space) or npoints x nt (training_mean + evecs diag(sqrt(evals)) mean_pca,
+ * multivar_support.c:118-137) */
+void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);

@@ -494,6 +494,33 @@ void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space
 	free(mp); free(vp); free(mc); free(vc);
 }
 
+/* the means alone: every component through its mean-only sweep (all enqueued, then collected, as above); observable space by
+ * the mean half of the reference's rule, training_mean + evecs diag(sqrt(evals)) mean_pca (multivar_support.c:118-137), which
+ * needs no variances */
+void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out)
+{
+	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt;
+	const multi_modelstruct *m = emu->model;
+	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
+	for (int c = 0; c < nr; c++) emulate_points_mean_enqueue(emu->emu_struct_array[c], points);
+	for (int c = 0; c < nr; c++) {
+		emulate_points_mean_collect(emu->emu_struct_array[c], np, mc);
+		for (int q = 0; q < np; q++) mp[(size_t)q * nr + c] = mc[q];
+	}
+	if (pca_space) {
+		memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
+	} else {
+		for (int q = 0; q < np; q++)
+			for (int i = 0; i < nt; i++) {
+				double ms = 0.0;
+				for (int j = 0; j < nr; j++)
+					ms += gsl_matrix_get(m->pca_evecs_r, i, j) * sqrt(gsl_vector_get(m->pca_evals_r, j)) * mp[(size_t)q * nr + j];
+				mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
+			}
+	}
+	free(mp); free(mc);
+}
+
 /* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
