@@ -336,6 +336,35 @@ typedef struct gpemu_gemm_launch_args {
 	int fa, fa_c0;
 } gpemu_gemm_launch_args;
 int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_gemm_launch_args *args, int *info_out);
+/* The gradient's reduction kernels -- beta on the device, alpha, the tile sums of the literal or the exact form, their
+ * second-stage sums: everything a value+gradient batch runs behind its C^-1 corners, through the routine production calls
+ * -- ONCE on caller-chosen operands, for the model (design, covariance function) and the mode the context holds, nb
+ * elements in lock-step.  Per element b:
+ *   thetas  nthetas values, used as they come (amplitude e^theta0 for pow-exp and, GPEMU_MODE_MATERN_LOG, the Matern kernels)
+ *   a       N x N, only the lower triangle is read: stands for C^-1
+ *   z       N x (1 + nreg): stands for C^-1 [y|H]
+ *   gram    (1 + nreg) x (1 + nreg), exact form only: gram[1+i][1+j] = (H^T C^-1 H)_ij, gram[1+i][0] = (H^T C^-1 y)_i
+ * form: 0 = literal, 1 = exact.  gram_dist (exact form): 1 / 0 = tile distances from the matrix unit / from coordinate
+ * differences, -1 = the context's GPEMU_GRAD_GRAM switch.  clamp (literal form): 1 / 0 = the kernel with / without the
+ * lower bound on the exp argument, -1 = production's rule (without, when 1/2 e^{-2 theta_k} range_k^2 < 600 for every
+ * direction and element).
+ * Outputs: alpha_out nb x N; beta_out nb x nreg (exact form); part_out nb x ntiles x (2d + 2), tile t = tr (tr + 1) / 2
+ * + tc of the 64 x 64 lower tiles; sums_out nb x (2d + 2).  Slots, literal: 2k = e^{-2 t_k} sum w a_ab D_k^2
+ * exp(-1/2 e^{-2 t_k} D_k^2), 2k + 1 = the same with alpha_a alpha_b, 2d = sum a_aa, 2d + 1 = sum alpha_a^2 (diagonal
+ * tiles); exact: k < nd = sum w (a_ab - alpha_a alpha_b) dC_ab/dtheta_k (nd = d for pow-exp, 1 for Matern), nd = the
+ * nugget direction; w = 1 on the diagonal, 2 below it.  Slots the form does not define come back NaN, as everything the
+ * kernels read beside their operands would make the outputs.  Uses device buffers of its own: the context's
+ * factorisation, prediction state and result ring are not touched.
+ * GPEMU_ERR_ARG, before anything runs: a NULL pointer, nb outside 1..GPEMU_MAX_BATCH, a switch outside its values, a
+ * Matern model without GPEMU_MODE_EXACT_GRAD | GPEMU_MODE_MATERN_LOG or with form = 0, gram_dist = 1 on a design without a
+ * centred copy, clamp = 0 where production's rule selects the clamped kernel. */
+typedef struct gpemu_grad_sums_args {
+	const double *thetas, *a, *z, *gram;
+	double *alpha_out, *beta_out, *part_out, *sums_out;
+	int nb, nthetas;
+	int form, gram_dist, clamp;
+} gpemu_grad_sums_args;
+int gpemu_test_grad_sums(gpemu_ctx *ctx, const gpemu_grad_sums_args *args);
 /* micro-benchmark of one GEMM shape on device-resident random operands: cfg 0 = the automatic tile choice, 2 = 64x64
  * tiles (4 waves), 8 = 128x128 tiles (8 waves); tri = lower-trapezoid update as in the factorisation; HIP-event timed. */
 int gpemu_test_gemm_bench(gpemu_ctx *ctx, int m, int n, int k, int ld, int cfg, int tri, int beta, int reps,

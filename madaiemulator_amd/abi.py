@@ -32,6 +32,12 @@ class GemmLaunchArgs(C.Structure):
                                         "kend_off", "nbatch", "ksplit", "force_cfg", "fa", "fa_c0")])
 
 
+class GradSumsArgs(C.Structure):
+    """gpemu_grad_sums_args of include/gpemu.h"""
+    _fields_ = ([(f, _dp) for f in ("thetas", "a", "z", "gram", "alpha_out", "beta_out", "part_out", "sums_out")] +
+                [(f, C.c_int) for f in ("nb", "nthetas", "form", "gram_dist", "clamp")])
+
+
 # every symbol include/gpemu.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gpemu_ctx_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -94,6 +100,7 @@ SYMBOLS = {
     "gpemu_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gpemu_test_gemm_nt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp]),
     "gpemu_test_gemm_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(GemmLaunchArgs), _ip]),
+    "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
     "gpemu_test_potrf": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
@@ -468,6 +475,26 @@ class Context:
         info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
         self._chk(self.L.gpemu_test_gemm_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
         return out, info
+
+    def test_grad_sums(self, thetas, a, z, gram=None, form=0, gram_dist=-1, clamp=-1):
+        """the gradient's reduction kernels once on caller-chosen operands (gpemu_test_grad_sums), for the model and mode of
+        the context.  thetas: nb x nthetas, a: nb x N x N (lower triangle read), z: nb x N x (1 + nreg), gram (exact form):
+        nb x (1 + nreg) x (1 + nreg) -> dict(alpha (nb, N), beta (nb, nreg), part (nb, ntiles, 2d + 2), sums (nb, 2d + 2));
+        what the form does not define is NaN.  GpemuError(ERR_ARG) for a refused call."""
+        N, d, nreg = self.N, self.d, self.nreg
+        th = _a(thetas)
+        th = th.reshape(-1, th.shape[-1])
+        nb = th.shape[0]
+        a, z = _a(a).reshape(nb, N, N), _a(z).reshape(nb, N, 1 + nreg)
+        g = None if gram is None else _a(gram).reshape(nb, 1 + nreg, 1 + nreg)
+        nt = (N + 63) // 64
+        out = dict(alpha=np.full((nb, N), np.nan), beta=np.full((nb, nreg), np.nan),
+                   part=np.full((nb, nt * (nt + 1) // 2, 2 * d + 2), np.nan), sums=np.full((nb, 2 * d + 2), np.nan))
+        args = GradSumsArgs(thetas=_p(th), a=_p(a), z=_p(z), gram=None if g is None else _p(g), alpha_out=_p(out["alpha"]),
+                            beta_out=_p(out["beta"]), part_out=_p(out["part"]), sums_out=_p(out["sums"]), nb=nb,
+                            nthetas=th.shape[1], form=int(form), gram_dist=int(gram_dist), clamp=int(clamp))
+        self._chk(self.L.gpemu_test_grad_sums(self.h, C.byref(args)))
+        return out
 
     def trace_dump(self, path):
         self._chk(self.L.gpemu_trace_dump(self.h, str(path).encode()))

@@ -1533,6 +1533,66 @@ static int grad_check_args(gpemu_ctx *ctx, int nthetas)
 	return GPEMU_OK;
 }
 
+// What the gradient reductions of a chunk of corners work on besides the model: a view, no owner.  Production points it at
+// the context's buffers (grad_enqueue_chunk), gpemu_test_grad_sums at buffers of its own.
+struct GradWork {
+	const double *S;        // nbc corners of side and leading dimension Np + Rp, one after the other
+	double *ag;             // nbc slots of Np + 2 GPEMU_MAX_PARAMS doubles: alpha scratch | length thetas | beta
+	double *part;           // nbc x ntiles x (2d + 2) tile sums
+	double *sums;           // nbc rows of second-stage sums,
+	long sums_stride;       //   this far apart
+	const double *res;      // exact form: the Gram matrices of the elements (Rp x Rp, as finish_kernel leaves them),
+	long rstride;           //   this far apart
+	const CovParams *pp;    // device: the nbc elements' hyper-parameters
+	double *gph;            // host staging of the length thetas, nbc x GPEMU_MAX_PARAMS: read by an asynchronous copy
+	hipEvent_t gph_ev;      // recorded behind that copy (nullptr: none)
+	bool exact;             // GPEMU_MODE_EXACT_GRAD form
+	bool gram;              // exact form: the tile distances from the matrix unit (needs the centred design)
+	int clamp;              // literal form: -1 = the rule below, 1 / 0 = grad_part_kernel<true> / <false> whatever it says
+};
+
+// literal form: exp(-1/2 e^{-2 theta_k} D_k^2) of every pair of design points -- when the largest such argument of the
+// chunk stays small (|D_k| <= the coordinate's range) the kernel's exp needs no lower clamp
+static bool grad_lit_noclamp(const gpemu_ctx *ctx, int nbc, const double *th, int nthetas)
+{
+	const int d = ctx->d, nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;
+	bool noclamp = (int)ctx->xhalf.size() == d;
+	for (int i = 0; noclamp && i < nbc; i++)
+		for (int k = 0; k < nlen; k++) {
+			const double range = 2.0 * ctx->xhalf[k];
+			if (!(0.5 * exp(-2.0 * th[(size_t)i * nthetas + 2 + k]) * range * range < 600.0)) noclamp = false;
+		}
+	return noclamp;
+}
+
+// everything of a chunk's gradient behind its corners, on the context's stream: the length thetas into the ag slots, beta
+// on the device (exact form), alpha, the tile sums and their second-stage sums.  th: the chunk's first theta vector.
+static int grad_sums_of_corners(gpemu_ctx *ctx, const GradWork &w, int nbc, const double *th, int nthetas)
+{
+	const int N = ctx->N, d = ctx->d, Rp = ctx->Rp;
+	const size_t dim = (size_t)ctx->Np + Rp, sstride = dim * dim;
+	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;           // length-scale directions
+	const size_t gslot = (size_t)ctx->Np + 2 * GPEMU_MAX_PARAMS;
+	const int nt = (N + 63) / 64, ntiles = nt * (nt + 1) / 2;
+	const int np = 2 * d + 2;
+	const size_t need = (size_t)ntiles * np;
+	for (int i = 0; i < nbc; i++)
+		for (int k = 0; k < GPEMU_MAX_PARAMS; k++)
+			w.gph[(size_t)i * GPEMU_MAX_PARAMS + k] = k < nlen ? th[(size_t)i * nthetas + 2 + k] : 0.0;
+	HIPCHK(ctx, hipMemcpy2DAsync(w.ag + ctx->Np, gslot * sizeof(double), w.gph, GPEMU_MAX_PARAMS * sizeof(double),
+	                             GPEMU_MAX_PARAMS * sizeof(double), nbc, hipMemcpyHostToDevice, ctx->stream));
+	if (w.gph_ev) HIPCHK(ctx, hipEventRecord(w.gph_ev, ctx->stream));
+	if (w.exact)
+		HIPCHK(ctx, launch_beta_solve(ctx->stream, w.res, w.rstride, Rp, ctx->nreg, nbc, w.ag, (long)gslot, ctx->Np));
+	int nparts = 0;
+	const bool noclamp = !w.exact && (w.clamp < 0 ? grad_lit_noclamp(ctx, nbc, th, nthetas) : w.clamp == 0);
+	HIPCHK(ctx, launch_grad_partials(ctx->stream, w.S, (long)dim, Rp, (long)sstride, nbc, ctx->dX, N, d, w.ag, ctx->Np,
+	                                 (long)gslot, w.part, (long)need, &nparts, w.exact ? ctx->kind : 0, ctx->nreg,
+	                                 w.pp, noclamp, w.gram ? ctx->dXg : nullptr));
+	HIPCHK(ctx, launch_grad_reduce(ctx->stream, w.part, (long)need, nparts, np, nbc, w.sums, w.sums_stride));
+	return GPEMU_OK;
+}
+
 // gradient reductions of the batch elements b0 .. b0+nbc-1 of the factorisation in the workspace, into dGradSum
 static int grad_enqueue_chunk(gpemu_ctx *ctx, int b0, int nbc, const double *th_all, int nthetas)
 {
@@ -1542,43 +1602,25 @@ static int grad_enqueue_chunk(gpemu_ctx *ctx, int b0, int nbc, const double *th_
 	if (rc) return rc;
 	ctx->S_dim = dim;
 	HIPCHK(ctx, build_corner(ctx, tall_of(ctx), ctx->dS, (long)dim, b0, nbc));
-	const bool exact = (ctx->mode & GPEMU_MODE_EXACT_GRAD) != 0;
-	const int nlen = ctx->kind == GPEMU_POWEREXP ? d : 1;           // length-scale directions
 	const size_t gslot = (size_t)ctx->Np + 2 * GPEMU_MAX_PARAMS;    // per corner: alpha scratch | length thetas | beta
 	rc = grow(ctx, ctx->dAlpha, (size_t)nbc * gslot);
 	if (rc) return rc;
 	const int nt = (N + 63) / 64, ntiles = nt * (nt + 1) / 2;
-	const int np = 2 * d + 2;
-	const size_t need = (size_t)ntiles * np;
-	rc = grow(ctx, ctx->dGradPart, need * nbc);
+	rc = grow(ctx, ctx->dGradPart, (size_t)ntiles * (2 * d + 2) * nbc);
 	if (rc) return rc;
-	// the length thetas of the chunk: from the pinned entry that belongs to this batch's hyper-parameter upload (reused
-	// only after the entry's event, re-recorded below behind this copy)
-	double *gph = ctx->pring.gph + ((size_t)ctx->pring.slot * GPEMU_MAX_BATCH + b0) * GPEMU_MAX_PARAMS;
-	for (int i = 0; i < nbc; i++)
-		for (int k = 0; k < GPEMU_MAX_PARAMS; k++)
-			gph[(size_t)i * GPEMU_MAX_PARAMS + k] = k < nlen ? th_all[(size_t)(b0 + i) * nthetas + 2 + k] : 0.0;
-	HIPCHK(ctx, hipMemcpy2DAsync(ctx->dAlpha + ctx->Np, gslot * sizeof(double), gph, GPEMU_MAX_PARAMS * sizeof(double),
-	                             GPEMU_MAX_PARAMS * sizeof(double), nbc, hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(ctx, hipEventRecord(ctx->pring.ev[ctx->pring.slot], ctx->stream));
-	if (exact)
-		HIPCHK(ctx, launch_beta_solve(ctx->stream, ctx->dRes + (size_t)b0 * ctx->res_len, (long)ctx->res_len, Rp, ctx->nreg, nbc,
-		                              ctx->dAlpha, (long)gslot, ctx->Np));
-	int nparts = 0;
-	// literal form: exp(-1/2 e^{-2 theta_k} D_k^2) of every pair of design points -- when the largest such argument of the
-	// chunk stays small (|D_k| <= the coordinate's range) the kernel's exp needs no lower clamp
-	bool noclamp = !exact && (int)ctx->xhalf.size() == d;
-	for (int i = 0; noclamp && i < nbc; i++)
-		for (int k = 0; k < nlen; k++) {
-			const double range = 2.0 * ctx->xhalf[k];
-			if (!(0.5 * exp(-2.0 * th_all[(size_t)(b0 + i) * nthetas + 2 + k]) * range * range < 600.0)) noclamp = false;
-		}
-	HIPCHK(ctx, launch_grad_partials(ctx->stream, ctx->dS, (long)dim, Rp, (long)sstride, nbc, ctx->dX, N, d, ctx->dAlpha, ctx->Np,
-	                                 (long)gslot, ctx->dGradPart, (long)need, &nparts, exact ? ctx->kind : 0, ctx->nreg,
-	                                 ctx->dParams + b0, noclamp, ctx->sched.grad_gram ? ctx->dXg : nullptr));
-	HIPCHK(ctx, launch_grad_reduce(ctx->stream, ctx->dGradPart, (long)need, nparts, np, nbc,
-	                               ctx->dGradSum + (size_t)b0 * gpemu_ctx::GRAD_NP_MAX, (long)gpemu_ctx::GRAD_NP_MAX));
-	return GPEMU_OK;
+	GradWork w{};
+	w.S = ctx->dS; w.ag = ctx->dAlpha; w.part = ctx->dGradPart;
+	w.sums = ctx->dGradSum + (size_t)b0 * gpemu_ctx::GRAD_NP_MAX; w.sums_stride = (long)gpemu_ctx::GRAD_NP_MAX;
+	w.res = ctx->dRes + (size_t)b0 * ctx->res_len; w.rstride = (long)ctx->res_len;
+	w.pp = ctx->dParams + b0;
+	// the length thetas of the chunk: through the pinned entry that belongs to this batch's hyper-parameter upload (reused
+	// only after the entry's event, re-recorded behind the copy out of it)
+	w.gph = ctx->pring.gph + ((size_t)ctx->pring.slot * GPEMU_MAX_BATCH + b0) * GPEMU_MAX_PARAMS;
+	w.gph_ev = ctx->pring.ev[ctx->pring.slot];
+	w.exact = (ctx->mode & GPEMU_MODE_EXACT_GRAD) != 0;
+	w.gram = ctx->sched.grad_gram != 0;
+	w.clamp = -1;
+	return grad_sums_of_corners(ctx, w, nbc, th_all + (size_t)b0 * nthetas, nthetas);
 }
 
 extern "C" int gpemu_loglik_grad_batch_enqueue(gpemu_ctx *ctx, int nb, const double *thetas, int nthetas)
@@ -2046,6 +2088,93 @@ extern "C" int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	if (info_out)
 		for (int b = 0; b < std::max(p->nbatch, 1); b++) info_out[b] = pivot_info(inf[(size_t)b]);
+	return GPEMU_OK;
+}
+
+// The gradient reductions behind the corners (grad_sums_of_corners: the routine grad_enqueue_chunk calls) ONCE, on corners,
+// [y|H] columns and Gram matrices the caller chose, for the model and mode the context holds.  The corners are laid out on
+// the host as production's S is -- side Np + Rp, S[Rp+i][Rp+j] = a[i][j] for j <= i, S[Rp+i][0 .. nreg] = z[i] -- and every
+// other element of them is NaN, as are the alpha slots beyond N, the beta slots beyond nreg, the Gram matrices outside
+// their (1 + nreg)^2 corner, the tile sums and the second-stage sums before the launch: what the kernels must not read
+// shows in the outputs, what they do not write stays NaN.  All device buffers are the call's own; of the context it
+// reads the design (dX, dXg), the model's sizes, the mode and the schedule switch, and uses the stream.
+extern "C" int gpemu_test_grad_sums(gpemu_ctx *ctx, const gpemu_grad_sums_args *p)
+{
+	if (!ctx || !p) return GPEMU_ERR_ARG;
+	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
+	if (p->nb < 1 || p->nb > GPEMU_MAX_BATCH) return fail(ctx, GPEMU_ERR_ARG, "grad_sums: batch size must be 1..GPEMU_MAX_BATCH");
+	if ((p->form != 0 && p->form != 1) || p->gram_dist < -1 || p->gram_dist > 1 || p->clamp < -1 || p->clamp > 1)
+		return fail(ctx, GPEMU_ERR_ARG, "grad_sums: form is 0/1, gram_dist and clamp are -1/0/1");
+	const bool exact = p->form == 1;
+	if (!p->thetas || !p->a || !p->z || !p->alpha_out || !p->part_out || !p->sums_out || (exact && (!p->gram || !p->beta_out)))
+		return fail(ctx, GPEMU_ERR_ARG, "grad_sums: NULL pointer");
+	if (ctx->kind != GPEMU_POWEREXP) {
+		if (!(ctx->mode & GPEMU_MODE_EXACT_GRAD) || !(ctx->mode & GPEMU_MODE_MATERN_LOG))
+			return fail(ctx, GPEMU_ERR_ARG, "grad_sums: a Matern model needs GPEMU_MODE_EXACT_GRAD | GPEMU_MODE_MATERN_LOG");
+		if (!exact) return fail(ctx, GPEMU_ERR_ARG, "grad_sums: there is no literal Matern gradient");
+	}
+	const int nb = p->nb, nthetas = p->nthetas;
+	if (nthetas < nthetas_for(ctx) || nthetas > GPEMU_MAX_PARAMS + 2) return fail(ctx, GPEMU_ERR_ARG, "grad_sums: nthetas");
+	const bool gram = exact && (p->gram_dist < 0 ? ctx->sched.grad_gram != 0 : p->gram_dist == 1);
+	if (exact && p->gram_dist == 1 && !ctx->dXg) return fail(ctx, GPEMU_ERR_ARG, "grad_sums: no centred design for the Gram form");
+	if (!exact && p->clamp == 0 && !grad_lit_noclamp(ctx, nb, p->thetas, nthetas))
+		return fail(ctx, GPEMU_ERR_ARG, "grad_sums: the unclamped literal kernel is defined only where production's rule selects it");
+	std::vector<CovParams> ps;
+	int rc = make_cov_params_batch(ctx, nb, p->thetas, nthetas, &ps);
+	if (rc) return rc;
+
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np, Rp = ctx->Rp, nreg = ctx->nreg, nz = 1 + nreg;
+	const size_t dim = (size_t)Np + Rp, sstride = dim * dim;
+	const size_t gslot = (size_t)Np + 2 * GPEMU_MAX_PARAMS;
+	const int nt = (N + 63) / 64, ntiles = nt * (nt + 1) / 2, np = 2 * d + 2;
+	const size_t need = (size_t)ntiles * np, rlen = (size_t)Rp * Rp;
+	std::vector<double> hS((size_t)nb * sstride, NAN), hAg((size_t)nb * gslot, NAN), hPart(need * nb, NAN), hSums((size_t)nb * np, NAN);
+	std::vector<double> hRes(exact ? (size_t)nb * rlen : 0, NAN), gph((size_t)nb * GPEMU_MAX_PARAMS, 0.0);
+	for (int b = 0; b < nb; b++) {
+		double *S = hS.data() + (size_t)b * sstride;
+		const double *a = p->a + (size_t)b * N * N, *z = p->z + (size_t)b * N * nz;
+		for (int i = 0; i < N; i++) {
+			for (int j = 0; j <= i; j++) S[(size_t)(Rp + i) * dim + Rp + j] = a[(size_t)i * N + j];
+			for (int c = 0; c < nz; c++) S[(size_t)(Rp + i) * dim + c] = z[(size_t)i * nz + c];
+		}
+		if (exact)
+			for (int i = 0; i < nz; i++)
+				for (int j = 0; j < nz; j++) hRes[(size_t)b * rlen + (size_t)i * Rp + j] = p->gram[((size_t)b * nz + i) * nz + j];
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dS, dAg, dPart, dSums, dRes;
+	DevBuf<CovParams> dPp;
+	HIPCHK(ctx, dS.grow(hS.size()));
+	HIPCHK(ctx, dAg.grow(hAg.size()));
+	HIPCHK(ctx, dPart.grow(hPart.size()));
+	HIPCHK(ctx, dSums.grow(hSums.size()));
+	HIPCHK(ctx, dRes.grow(std::max(hRes.size(), (size_t)1)));
+	HIPCHK(ctx, dPp.grow((size_t)nb));
+	HIPCHK(ctx, hipMemcpyAsync(dS, hS.data(), hS.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dAg, hAg.data(), hAg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dPart, hPart.data(), hPart.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dSums, hSums.data(), hSums.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	if (exact) HIPCHK(ctx, hipMemcpyAsync(dRes, hRes.data(), hRes.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dPp, ps.data(), (size_t)nb * sizeof(CovParams), hipMemcpyHostToDevice, ctx->stream));
+	GradWork w{};
+	w.S = dS; w.ag = dAg; w.part = dPart; w.sums = dSums; w.sums_stride = np;
+	w.res = dRes; w.rstride = (long)rlen; w.pp = dPp; w.gph = gph.data(); w.gph_ev = nullptr;
+	w.exact = exact; w.gram = gram; w.clamp = p->clamp;
+	rc = grad_sums_of_corners(ctx, w, nb, p->thetas, nthetas);
+	// (the copies above and inside the routine read host vectors of this frame: wait before any return)
+	const hipError_t es = hipStreamSynchronize(ctx->stream);
+	if (rc) return rc;
+	HIPCHK(ctx, es);
+	HIPCHK(ctx, hipMemcpyAsync(hAg.data(), dAg, hAg.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(hPart.data(), dPart, hPart.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(hSums.data(), dSums, hSums.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (int b = 0; b < nb; b++) {
+		memcpy(p->alpha_out + (size_t)b * N, hAg.data() + (size_t)b * gslot, (size_t)N * 8);
+		if (exact) memcpy(p->beta_out + (size_t)b * nreg, hAg.data() + (size_t)b * gslot + Np + GPEMU_MAX_PARAMS, (size_t)nreg * 8);
+	}
+	memcpy(p->part_out, hPart.data(), hPart.size() * 8);
+	memcpy(p->sums_out, hSums.data(), hSums.size() * 8);
 	return GPEMU_OK;
 }
 

@@ -89,6 +89,60 @@ def value_and_gradients(X, y, order, th):
     return dict(value=value, sigma2=sigma2, beta=beta, logdet=logdet, quad=quad, literal=lit, exact=exa)
 
 
+def matern_matrix(kind, X, th):
+    """emulator.c:344-386 (kind 2) / 438-480 (kind 3) with amplitude and nugget on the log scale (GPEMU_MODE_MATERN_LOG):
+    e^t0 (1 + c s [+ 5/3 s^2]) e^{-c s}, s = |x - x'| / e^{t2}, c = 1.732050808 / 2.236067978, + e^t1 where every
+    |D_k| < 1e-16; returns (C without the nugget, same, dC/dlog rho)"""
+    N, d = X.shape
+    r2 = np.zeros((N, N))
+    same = np.ones((N, N), dtype=bool)
+    for k in range(d):
+        D = X[:, k][:, None] - X[:, k][None, :]
+        same &= np.abs(D) < 1e-16
+        r2 += D * D
+    s = np.sqrt(r2) / np.exp(th[2])
+    amp = np.exp(th[0])
+    if kind == 2:
+        c = 1.732050808
+        e = amp * np.exp(-c * s)
+        return (1.0 + c * s) * e, same, c * c * s * s * e
+    c = 2.236067978
+    e = amp * np.exp(-c * s)
+    return (1.0 + c * s + (5.0 / 3.0) * s * s) * e, same, (s * s * (c * c - 10.0 / 3.0) + (5.0 / 3.0) * c * s ** 3) * e
+
+
+def value_and_gradients_matern(kind, X, y, order, th):
+    """-> dict(value, sigma2, beta, logdet, quad, exact (2: nugget and length direction), scale (2), cond_1) for a Matern kernel
+    (kind 2 or 3) at theta on the log scale (theta[0] taken as 0): the exact form d(-logL)/dtheta = 1/2 sum_ab W_ab dC_ab,
+    W = A - a a^T, a = A (y - H beta), with dC/dlog nug = nug [same point] and dC/dlog rho as matern_matrix gives it (the
+    derivative of the kernel above in log rho).  scale[i] = 1/2 sum_ab |W_ab dC_ab|: what a component is summed from."""
+    from scipy.linalg import lapack
+    N, d = X.shape
+    th = np.array(th, float)
+    th[0] = 0.0
+    C0, same, dCrho = matern_matrix(kind, X, th)
+    nug = np.exp(th[1])
+    Cm = C0
+    Cm[same] += nug
+    anorm = np.abs(Cm).sum(axis=0).max()
+    cf = sl.cho_factor(Cm, lower=True, overwrite_a=False, check_finite=False)
+    rcond, info = lapack.dpocon(cf[0], anorm, uplo="L")
+    A = sl.cho_solve(cf, np.eye(N), check_finite=False)
+    A = 0.5 * (A + A.T)
+    logdet = 2.0 * np.log(np.diag(cf[0])).sum()
+    H = hmatrix(order, X)
+    AH, Ay = A @ H, A @ y
+    beta = np.linalg.solve(H.T @ AH, H.T @ Ay)
+    r = y - H @ beta
+    Ar = A @ r
+    quad = r @ Ar
+    value = -(-0.5 * logdet - (N / 2.0) * 1.83788 - 0.5 * quad)
+    W = A - np.outer(Ar, Ar)
+    g = np.array([0.5 * nug * W[same].sum(), 0.5 * np.sum(W * dCrho)])
+    scale = np.array([0.5 * nug * np.abs(W[same]).sum(), 0.5 * np.sum(np.abs(W * dCrho))])
+    return dict(value=value, sigma2=(y @ Ar) / N, beta=beta, logdet=logdet, quad=quad, exact=g, scale=scale, cond_1=1.0 / rcond)
+
+
 def kvectors(X, th, Xq):
     """emulator.c:578-593 for a block of query rows: K[q, i] = cov(x_i, x*_q) of emulator.c:101-152 (amplitude e^t0 included,
     nugget where every |coordinate difference| < 1e-10), then the clamp `if (cov < 1e-10) cov = 0`"""
