@@ -233,6 +233,24 @@ int gpemu_predict_mean_collect(gpemu_ctx *ctx, int npoints, double *mean);
 /* device pointers: only enqueues on the context's stream, no host synchronisation (the first call sizes the scratch) */
 int gpemu_predict_mean_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev);
 
+/* ---- the mean and its gradient with respect to the query point ----
+ * grad[q*d + j] = d mean(x*_q) / d x*_j of the function gpemu_predict_mean evaluates: with D_j = x*_j - x_ij,
+ *   d k(x_i, x*) / d x*_j = -g_i s_j D_j      pow-exp  s_j = exp(-2 theta_{2+j}), g_i = k_i before the nugget
+ *                                             Matern 3/2  s_j = c^2 / rho^2, g_i = A exp(-u)          (c = 1.732050808)
+ *                                             Matern 5/2  s_j = 1 / rho^2, g_i = A exp(-u) ((c^2 - 10/3) + (5/3) u)  (c = 2.236067978)
+ * (u = c distance / rho), g_i = 0 where the k value, nugget included, falls under the < 1e-10 -> 0 clamp, plus the regression
+ * term sum_a beta_a dh_a/dx_j.  One fused sweep: the on-chip k tile is multiplied as weights with gamma_i [1, x_i - mid] on
+ * the matrix unit; nothing of size M x N is stored, the batch buffers of gpemu_predict_batch are neither touched nor
+ * allocated, the scratch is this entry's own.  mean (M values, may be NULL) agrees with gpemu_predict_mean to rounding, not
+ * bit for bit.  A query's bits do not depend on the rest of the call or on the entry used.  Sizes, errors and the
+ * enqueue / collect rules are those of gpemu_predict_mean: one batch of any kind per context is pending at a time and is
+ * collected by the collect of its own kind only (another: GPEMU_ERR_STATE, the batch stays enqueued). */
+int gpemu_predict_mean_grad(gpemu_ctx *ctx, int npoints, const double *xq, double *mean /* M, may be NULL */, double *grad /* M*d row-major */);
+int gpemu_predict_mean_grad_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
+int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int npoints, double *mean /* may be NULL */, double *grad);
+/* device pointers: only enqueues on the context's stream (the first call sizes the scratch) */
+int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */, double *grad_dev);
+
 /* ---- leave-one-out validation of a trained emulator -----------------
  * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
  * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
@@ -292,6 +310,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_GEMM_K512 6 /* only the GEMM launches with a contraction length >= 512 */
 #define GPEMU_PROF_LOO     7   /* the two launches of gpemu_loo[_dev]: column sums over L^-1 (bytes = 8 N (N+1) / 2), finish */
 #define GPEMU_PROF_MEAN    8   /* the two launches of the mean-only sweep: flops = M*N*(kernel + 2) with kernel = 3 d (the squared distance), bytes = 8*M*(d+1) */
+#define GPEMU_PROF_MEAN_GRAD 9 /* the two launches of the mean-gradient sweep: flops = M*N*(3 d + 2 + 2 (d + 1)), bytes = 8*M*(2 d + 1) */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

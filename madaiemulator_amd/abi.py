@@ -17,6 +17,7 @@ OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_PD, ERR_REGRESSION, ERR_STATE = ran
 PROF_NONE, PROF_GEMM, PROF_FILL, PROF_LEAF, PROF_POTRF, PROF_GEMM_BIG, PROF_GEMM_K512 = range(7)
 PROF_LOO = 7
 PROF_MEAN = 8
+PROF_MEAN_GRAD = 9
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -80,6 +81,10 @@ SYMBOLS = {
     "gpemu_predict_mean_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_mean_collect": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_mean_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_mean_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "gpemu_predict_mean_grad_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "gpemu_predict_mean_grad_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "gpemu_predict_mean_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -428,6 +433,29 @@ class Context:
         m = np.empty(self._npred)
         self._chk(self.L.gpemu_predict_mean_collect(self.h, self._npred, _p(m)))
         return m
+
+    # the posterior mean and its gradient with respect to the query point: one fused sweep
+    def predict_mean_grad(self, Xq, want_mean=True):
+        """-> (mean[M] or None, grad[M, d])"""
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        mean = np.empty(M) if want_mean else None
+        grad = np.empty((M, self.d))
+        self._chk(self.L.gpemu_predict_mean_grad(self.h, M, _p(Xq), _p(mean) if want_mean else None, _p(grad)))
+        return mean, grad
+
+    def predict_mean_grad_dev(self, M, xq_dev, mean_dev, grad_dev):
+        self._chk(self.L.gpemu_predict_mean_grad_dev(self.h, M, xq_dev, mean_dev, grad_dev))
+
+    def predict_mean_grad_enqueue(self, Xq):
+        Xq = _a(Xq).reshape(-1, self.d)
+        self._npred = Xq.shape[0]
+        self._chk(self.L.gpemu_predict_mean_grad_enqueue(self.h, Xq.shape[0], _p(Xq)))
+
+    def predict_mean_grad_collect(self):
+        m, g = np.empty(self._npred), np.empty((self._npred, self.d))
+        self._chk(self.L.gpemu_predict_mean_grad_collect(self.h, self._npred, _p(m), _p(g)))
+        return m, g
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

@@ -259,13 +259,15 @@ static void free_model(gpemu_ctx *ctx)
 	free_graphs(ctx);
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
 	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
-	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart})
+	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad})
 		b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
+	ctx->hMGrad.reset();
 	invalidate_prediction(ctx);
 	ctx->pred_pending = 0;
 	ctx->pred_pending_mean = false;
+	ctx->pred_pending_grad = false;
 	ctx->S_dim = 0;
 }
 
@@ -1296,6 +1298,7 @@ extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *
 	}
 	ctx->pred_pending = M;
 	ctx->pred_pending_mean = false;
+	ctx->pred_pending_grad = false;
 	return GPEMU_OK;
 }
 
@@ -1304,6 +1307,7 @@ extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, 
 	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
 	if (ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is mean-only: collect it with gpemu_predict_mean_collect");
+	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
 	memcpy(mean, hm, (size_t)M * sizeof(double));
@@ -1376,6 +1380,7 @@ extern "C" int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int M, const double *x
 	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	ctx->pred_pending = M;
 	ctx->pred_pending_mean = true;
+	ctx->pred_pending_grad = false;
 	return GPEMU_OK;
 }
 
@@ -1383,6 +1388,7 @@ extern "C" int gpemu_predict_mean_collect(gpemu_ctx *ctx, int M, double *mean)
 {
 	if (!ctx || !mean) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
 	if (!ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch has variances: collect it with gpemu_predict_batch_collect");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
@@ -1397,6 +1403,99 @@ extern "C" int gpemu_predict_mean(gpemu_ctx *ctx, int M, const double *xq, doubl
 	const int rc = gpemu_predict_mean_enqueue(ctx, M, xq);
 	if (rc) return rc;
 	return gpemu_predict_mean_collect(ctx, M, mean);
+}
+
+// ---------------------------------------------------------------------------
+// mean and its gradient with respect to the query point (gpemu.h): two launches per block of up to
+// PRED_BATCH_MAX queries -- the fused sweep (k tile as weights times gamma [1, x - mid] on the matrix unit) and the slice sum
+// with the regression term.  Reads what the mean-only sweep reads; scratch and staging are its own (dMGradPart, dMGrad,
+// hMGrad beside the shared coordinate / mean staging); dKq, dV and dMeanPart are not touched.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *grad_dev)
+{
+	if (!ctx || M < 1 || !xq_dev || !grad_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int Np = ctx->Np, N = ctx->N, d = ctx->d;
+	const int nslice = predict_mean_slices(Np), pw = predict_mean_grad_width(d);
+	const int cap = std::min(PRED_BATCH_MAX, round_up(M, 64));
+	int rc = grow(ctx, ctx->dMGradPart, (size_t)nslice * cap * (size_t)(1 + pw));
+	if (rc) return rc;
+	// (laid out with the row count it was sized for: a later, shorter call uses the same strides)
+	const long pstride = (long)(ctx->dMGradPart.size() / ((size_t)nslice * (size_t)(1 + pw)));
+	double *mpart = ctx->dMGradPart, *gpart = mpart + (size_t)nslice * pstride;
+	const CovParams &p = ctx->pred_cov;
+	const bool centred = ctx->dXg && ctx->dMid;
+	const bool gram = p.gram && ctx->sched.kvec_gram && centred;
+	const double *Xc = centred ? (const double *)ctx->dXg : (const double *)ctx->dX, *mid = centred ? (const double *)ctx->dMid : nullptr;
+	const double *gamma = ctx->dLinvAug + (size_t)Np * Np;
+	for (int q0 = 0; q0 < M; q0 += cap) {
+		const int mb = std::min(cap, M - q0);
+		const double *xq = xq_dev + (size_t)q0 * d;
+		if (prof_on(ctx, GPEMU_PROF_MEAN_GRAD)) { ctx->prof.tag.push_back("predict_mean_grad"); ctx->prof.tag.push_back("predict_mean_grad_finish"); }
+		{
+			// flops: per element the squared distance (3 d), the product with gamma (2) and the 1 + d columns of the second
+			// product (2 each); bytes: coordinates in, mean and gradient out
+			ProfScope ps(ctx, GPEMU_PROF_MEAN_GRAD, (double)mb * N * (3.0 * d + 2.0 + 2.0 * (d + 1)), 8.0 * (double)mb * (2 * d + 1));
+			HIPCHK(ctx, launch_predict_mean_grad(ctx->stream, mpart, gpart, pstride, xq, mb, ctx->dX, Xc, mid, gamma, N, Np, d, p, gram));
+		}
+		{
+			ProfScope ps(ctx, GPEMU_PROF_MEAN_GRAD, 2.0 * mb * ctx->nreg + 4.0 * mb * d, 0.0);
+			HIPCHK(ctx, launch_predict_mean_grad_finish(ctx->stream, mpart, gpart, pstride, nslice, mb, ctx->nreg, d, xq, mid, ctx->dBetaQ, p,
+			                                            mean_dev ? mean_dev + q0 : nullptr, grad_dev + (size_t)q0 * d));
+		}
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_mean_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq)
+{
+	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d;
+	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
+	if (ctx->mgrad_cap() < (size_t)M) {
+		const size_t gcap = (size_t)std::max(M, 64);
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		ctx->hMGrad.reset();
+		if (const int rc = grow(ctx, ctx->dMGrad, gcap * d)) return rc;
+		HIPCHK(ctx, ctx->hMGrad.grow(gcap * d));
+	}
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	const int rc = gpemu_predict_mean_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dMGrad);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->hMGrad, ctx->dMGrad, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	ctx->pred_pending = M;
+	ctx->pred_pending_mean = false;
+	ctx->pred_pending_grad = true;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *grad)
+{
+	if (!ctx || !grad) return GPEMU_ERR_ARG;
+	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (!ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is not a mean-gradient batch: collect it with the collect of its own kind");
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (mean) memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
+	memcpy(grad, ctx->hMGrad, (size_t)M * ctx->d * sizeof(double));
+	ctx->pred_pending = 0;
+	ctx->pred_pending_grad = false;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_mean_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *grad)
+{
+	if (!ctx || M < 1 || !xq || !grad) return GPEMU_ERR_ARG;
+	const int rc = gpemu_predict_mean_grad_enqueue(ctx, M, xq);
+	if (rc) return rc;
+	return gpemu_predict_mean_grad_collect(ctx, M, mean, grad);
 }
 
 // ---------------------------------------------------------------------------

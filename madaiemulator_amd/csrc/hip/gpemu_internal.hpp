@@ -244,6 +244,12 @@ struct gpemu_ctx {
 	int pred_pending = 0;        // queries of an enqueued, not yet collected prediction batch
 	bool pred_pending_mean = false;   // that batch came from gpemu_predict_mean_enqueue (no variances in the staging)
 	gpemu::DevBuf<double> dMeanPart;  // mean-only sweep: slice partial sums, predict_mean_slices(Np) x queries of a block
+	// mean-gradient sweep (gpemu_predict_mean_grad): its own scratch and staging.  dMGradPart: per slice and query of a block
+	// the mean's partial sum, then predict_mean_grad_width(d) gradient sums; dMGrad / hMGrad: mgrad_cap() x d gradients
+	bool pred_pending_grad = false;   // the enqueued batch came from gpemu_predict_mean_grad_enqueue
+	gpemu::DevBuf<double> dMGradPart, dMGrad;
+	gpemu::PinnedBuf<double> hMGrad;
+	size_t mgrad_cap() const { return d ? hMGrad.size() / (size_t)d : 0; }
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
@@ -309,6 +315,15 @@ hipError_t launch_predict_mean(hipStream_t s, double *part, long pstride, const 
                                const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p, bool gram);
 hipError_t launch_predict_mean_finish(hipStream_t s, const double *part, long pstride, int nslice, int M, int nreg, int d,
                                       const double *Xq, const double *beta, double *mean);
+// the mean and its gradient with respect to the query point (gpemu_predict_mean_grad): per (design slice,
+// query) the mean's partial sum and predict_mean_grad_width(d) sums [S_0, S_1 .. S_d], then the finish in slice order
+int predict_mean_grad_width(int d);
+hipError_t launch_predict_mean_grad(hipStream_t s, double *mpart, double *gpart, long pstride, const double *Xq, int M, const double *X,
+                                    const double *Xc, const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p,
+                                    bool gram);
+hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, const double *gpart, long pstride, int nslice, int M,
+                                           int nreg, int d, const double *Xq, const double *mid, const double *beta, const CovParams &p,
+                                           double *mean, double *grad);
 hipError_t launch_grad_partials(hipStream_t s, const double *S, long lds, int soff, long sstride, int nb, const double *X, int N,
                                 int d, double *ag, int np_pad, long gstride, double *part, long pstride, int *nparts,
                                 int exact_kind = 0, int nbeta = 0, const CovParams *pp_dev = nullptr, bool lit_noclamp = false,

@@ -978,6 +978,370 @@ hipError_t launch_predict_mean_finish(hipStream_t s, const double *part, long ps
 }
 
 // ---------------------------------------------------------------------------
+// Gradient of that mean with respect to the query point.  With D_j = x*_j - x_ij every covariance function
+// has  d k(x_i, x*) / d x*_j = -g_i s_j D_j  (one weight g_i per element, one constant s_j per dimension), so
+//   d mean / d x*_j = sum_a beta_a dh_a/dx_j  -  s_j ((x*_j - mid_j) S_0 - S_j),   S_0 = sum_i gamma_i g_i,
+//                                                                                  S_j = sum_i gamma_i g_i x'_ij
+// on the centred design x' = x - mid.  The sums are a second small matrix product behind the distance product: the tile is
+// made with the DESIGN as the A operand and the queries as B (gram_tile_u2_qcol), so accumulator register r of lane (q, g)
+// holds (design point 4 r + g of a 16-block, query q) -- already the A operand of a 16x16x4 step over the four design points
+// {4 r + g}.  B is gamma_i [1, x'_i1 .. x'_id] from LDS (ncb = ceil((1 + d) / 16) column blocks, staged per tile).  The k
+// values, the nugget rule and the clamp are those of predict_mean_kernel; where the k value (nugget included) falls under
+// the clamp its weight is zero too: the gradient of the function gpemu_predict_mean evaluates.
+// Slicing, the absence of atomics and the per-query summation order are predict_mean_kernel's: a query's four lanes g each
+// add their sixteen design points per tile in a fixed order, the matrix unit adds an output row from that row of A alone.
+// ---------------------------------------------------------------------------
+
+// cov_from_u2_gram with the weight g beside the value (the value by the same operations)
+template <int KIND>
+__device__ __forceinline__ double cov_grad_from_u2_gram(double a, const double *tab_amp, double &gw)
+{
+	if (KIND == GPEMU_POWEREXP) { gw = fast_exp_neg_g(-a, tab_amp); return gw; }
+	const double u = fast_sqrt_g(a);
+	const double e = fast_exp_neg_g(-u, tab_amp);
+	if (KIND == GPEMU_MATERN32) { gw = e; return e * (1.0 + u); }
+	const double c2 = (5.0 / 3.0) / (2.236067978 * 2.236067978);
+	gw = e * fma(5.0 / 3.0, u, 2.236067978 * 2.236067978 - 10.0 / 3.0);
+	return e * fma(u, fma(u, c2, 1.0), 1.0);
+}
+
+// cov_from_a_diff likewise
+template <int KIND>
+__device__ __forceinline__ double cov_grad_from_a_diff(double a, double amp, const double *tab, double &gw)
+{
+	if (KIND == GPEMU_POWEREXP) { gw = fast_exp_neg(-a, tab) * amp; return gw; }
+	const double sdist = fast_sqrt(a);
+	if (KIND == GPEMU_MATERN32) {
+		const double root3 = 1.732050808;
+		const double e = fast_exp_neg(-root3 * sdist, tab);
+		gw = amp * e;
+		return amp * (1 + root3 * sdist) * e;
+	}
+	const double root5 = 2.236067978;
+	const double e = fast_exp_neg(-root5 * sdist, tab);
+	gw = amp * e * fma(5.0 / 3.0, root5 * sdist, root5 * root5 - 10.0 / 3.0);
+	return amp * (1 + root5 * sdist + (5.0 / 3.0) * sdist * sdist) * e;
+}
+
+// gram_tile_u2<KIND, RECT = true, ROWFAR = true> with the operands exchanged: element (r, j) of the lane is (design point
+// 16 j + g + 4 r of the tile, query 16 wave + q).  The products, their order and the candidate rule are the same, so the
+// squared distances are; the far-query rule needs no shuffle here (the lane's one query).  Bit 4 r + j of the result: the
+// element passed the exact "same point" test.
+template <int KIND>
+__device__ __forceinline__ unsigned gram_tile_u2_qcol(d4g_t (&acc)[4], const double *Xq, const double *mid, int M, const double *X,
+                                                      const double *Xg, int N, int d, const CovParams &p, int tr, int tc,
+                                                      const double *wsc)
+{
+	const int tid = threadIdx.x;
+	const double croot = gram_root(KIND);
+	const double cand_g = p.cand_g * croot * croot;
+	const int lane = tid & 63, wave = tid >> 6;
+	const int q = lane & 15, g = lane >> 4;
+	const int qrow = tr * FT + 16 * wave + q;
+	const bool qv = qrow < M;
+	const double *qp = Xq + (long)(qv ? qrow : 0) * d;
+	const double *dp[4];
+	bool dv[4];
+#pragma unroll
+	for (int j = 0; j < 4; j++) {
+		const int dr = tc * FT + 16 * j + q;
+		dv[j] = dr < N;
+		dp[j] = Xg + (long)(dv[j] ? dr : 0) * d;
+	}
+#pragma unroll
+	for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+	double nq = 0.0, nd[4] = {0.0, 0.0, 0.0, 0.0};
+	for (int k0 = 0; k0 < d; k0 += 4) {
+		const int k = k0 + g;
+		const bool kv = k < d;
+		const double wk = wsc[kv ? k : 0];
+		const double xq = (kv && qv) ? (qp[k] - mid[k]) * wk : 0.0;
+		nq = fma(xq, xq, nq);
+		const double xq2 = -2.0 * xq;
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const double xd = (kv && dv[j]) ? dp[j][k] * wk : 0.0;
+			nd[j] = fma(xd, xd, nd[j]);
+			acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xd, xq2, acc[j], 0, 0, 0);
+		}
+	}
+	nq += __shfl_xor(nq, 16); nq += __shfl_xor(nq, 32);
+#pragma unroll
+	for (int j = 0; j < 4; j++) { nd[j] += __shfl_xor(nd[j], 16); nd[j] += __shfl_xor(nd[j], 32); }
+	const double thr = (nq > 16.0 * croot * croot) ? HUGE_VAL : cand_g;   // a far query: every element from differences
+	// k slot 0 = (1, |x*'|^2), k slot 1 = (|x'|^2, 1): the order of gram_tile_u2's last step
+	{
+		const double eb = (g == 0) ? nq : (g == 1 ? 1.0 : 0.0);
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const double ea = (g == 0) ? 1.0 : (g == 1 ? nd[j] : 0.0);
+			acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ea, eb, acc[j], 0, 0, 0);
+		}
+	}
+	const int dcol0 = tc * FT + g;
+	unsigned same = 0;
+	bool cand = false;
+#pragma unroll
+	for (int r = 0; r < 4; r++)
+#pragma unroll
+		for (int j = 0; j < 4; j++) cand = cand || (acc[j][r] <= thr);
+	if (__any(cand)) {
+#pragma unroll 1
+		for (int e = 0; e < 16; e++) {
+			const int r = e >> 2, j = e & 3;
+			double ae = 0.0;
+#pragma unroll
+			for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+				for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
+			const int col = dcol0 + 16 * j + 4 * r;
+			if (ae <= thr && qv && col < N) {
+				int cnt = 0;
+				double a = 0.0;
+				for (int k = 0; k < d; k++) {
+					const double D = Xq[(long)qrow * d + k] - X[(long)col * d + k];
+					const double t = D * wsc[k];
+					a = fma(t, t, a);
+					cnt += (fabs(D) < p.eps) ? 1 : 0;
+				}
+				a = fmin(a, KIND == GPEMU_POWEREXP ? 700.0 : 490000.0);       // (the exponent hold of gram_tile_u2)
+#pragma unroll
+				for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+					for (int jj = 0; jj < 4; jj++) acc[jj][rr] = (rr == r && jj == j) ? a : acc[jj][rr];
+				if (cnt == d) same |= 1u << e;
+			}
+		}
+	}
+	return same;
+}
+
+constexpr int MGRAD_NCB = (GPEMU_MAX_PARAMS + 1 + 15) / 16;      // column blocks of [1 | x'] at the largest d
+
+int predict_mean_grad_width(int d) { return 16 * ((d + 1 + 15) / 16); }
+
+// mpart: slices x pstride partial sums gamma . k; gpart: slices x pstride rows of pw = 16 ncb partial sums [S_0, S_1 .. S_d, 0 ..]
+template <int KIND, bool GRAM>
+__global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart, double *gpart, long pstride, const double *Xq, int M,
+                                                                 const double *X, const double *Xc, const double *mid,
+                                                                 const double *gamma, int N, int Np, int d, CovParams p)
+{
+	extern __shared__ double ys[];                 // FT x pw: gamma_i [1, x'_i1 .. x'_id, 0 ..] of the current tile
+	__shared__ double gam_s[MEAN_TPW * FT];
+	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
+	__shared__ double wsc[GPEMU_MAX_PARAMS];
+	__shared__ double mid_s[GPEMU_MAX_PARAMS];
+	const int tid = threadIdx.x;
+	const int ntc = Np / FT, nsl = (ntc + MEAN_TPW - 1) / MEAN_TPW;
+	const int tr = blockIdx.x / nsl, slice = blockIdx.x % nsl, tc0 = slice * MEAN_TPW;
+	const int ncb = (d + 1 + 15) / 16, pw = 16 * ncb;
+	{
+		const int col = tc0 * FT + tid;
+		gam_s[tid] = (col < N) ? gamma[col] : 0.0;
+	}
+	if (GRAM) {
+		gram_tables(p, d, tab, wsc);
+		if (tid < GPEMU_MAX_PARAMS) mid_s[tid] = (tid < d) ? mid[tid] : 0.0;
+	} else {
+		if (tid < EXP_TAB) tab[tid] = exp2((double)tid * (1.0 / EXP_TAB));
+		if (tid < GPEMU_MAX_PARAMS) wsc[tid] = (tid < d) ? p.w[(KIND == GPEMU_POWEREXP) ? tid : 0] : 0.0;
+	}
+	const int lane = tid & 63, wave = tid >> 6;
+	const int q = lane & 15, g = lane >> 4;
+	const int qrow = tr * FT + 16 * wave + q;
+	const bool qv = qrow < M;
+	double msum = 0.0;
+	d4g_t G[MGRAD_NCB];
+#pragma unroll
+	for (int cb = 0; cb < MGRAD_NCB; cb++) G[cb] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+	for (int i = 0; i < MEAN_TPW; i++) {
+		const int tc = tc0 + i;
+		if (tc >= ntc) break;
+		__syncthreads();                           // the tables (first tile); the previous tile's ys has been read
+		for (int rr = 0; rr < 4; rr++) {
+			const int r = (tid >> 4) + 16 * rr, gi = tc * FT + r;
+			const double gm = (gi < N) ? gam_s[i * FT + r] : 0.0;
+			for (int cb = 0; cb < ncb; cb++) {
+				const int c = 16 * cb + (tid & 15);
+				double v = 0.0;
+				if (gi < N && c <= d) v = (c == 0) ? gm : gm * Xc[(long)gi * d + c - 1];
+				ys[r * pw + c] = v;
+			}
+		}
+		__syncthreads();
+		d4g_t acc[4];
+		unsigned same = 0;
+		if (GRAM) {
+			same = gram_tile_u2_qcol<KIND>(acc, Xq, mid_s, M, X, Xc, N, d, p, tr, tc, wsc);
+		} else {
+			// squared scaled distances from differences, by the operations of predict_mean_kernel's difference form
+			// (x* w - x w, squared and added in dimension order); the design from global memory (each address shared by
+			// sixteen lanes): this form runs for extreme length scales only
+#pragma unroll
+			for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+			const double *qp = Xq + (long)(qv ? qrow : 0) * d;
+			const double *xp[4];
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const int col = tc * FT + g + 4 * r;              // (+ 16 j below: a tile of Np / FT lies inside the Np rows ...
+				xp[r] = X + (long)col * d;                        //  ... of the padded size, not of X: clamped per element)
+			}
+			for (int k = 0; k < d; k++) {
+				const double wk = wsc[k];
+				const double xr = qv ? qp[k] * wk : 0.0;
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+#pragma unroll
+					for (int r = 0; r < 4; r++) {
+						const bool cv = tc * FT + 16 * j + g + 4 * r < N;
+						const double xc = cv ? xp[r][(long)16 * j * d + k] * wk : 0.0;
+						const double diff = xr - xc;
+						acc[j][r] = fma(diff, diff, acc[j][r]);
+					}
+			}
+			bool cand = false;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) cand = cand || (acc[j][r] <= p.cand);
+			if (__any(cand)) {
+#pragma unroll 1
+				for (int e = 0; e < 16; e++) {
+					const int r = e >> 2, j = e & 3;
+					double ae = HUGE_VAL;
+#pragma unroll
+					for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+						for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
+					const int col = tc * FT + 16 * j + g + 4 * r;
+					if (ae <= p.cand && qv && col < N) {
+						int cnt = 0;
+						for (int k = 0; k < d; k++) cnt += (fabs(qp[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
+						if (cnt == d) same |= 1u << e;
+					}
+				}
+			}
+		}
+		const bool plain = (tc * FT + FT <= N) && !__any(same != 0);
+		const double *gs = gam_s + i * FT + g;
+		const double *yb = ys + g * pw + q;
+#pragma unroll
+		for (int r = 0; r < 4; r++) {
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				double gw;
+				double v = GRAM ? cov_grad_from_u2_gram<KIND>(acc[j][r], tab, gw) : cov_grad_from_a_diff<KIND>(acc[j][r], p.amp, tab, gw);
+				if (!plain) {
+					if (same & (1u << (4 * r + j))) v += p.nug;
+					// (a padding column's distance was not held at the exponent limit: its value may be anything)
+					if (tc * FT + 16 * j + g + 4 * r >= N) { v = 0.0; gw = 0.0; }
+				}
+				if (v < 1E-10) { v = 0.0; gw = 0.0; }                             // emulator.c:588-590, and its derivative
+				msum = fma(v, gs[16 * j + 4 * r], msum);
+#pragma unroll
+				for (int cb = 0; cb < MGRAD_NCB; cb++)
+					if (cb < ncb) G[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(gw, yb[(16 * j + 4 * r) * pw + 16 * cb], G[cb], 0, 0, 0);
+				if (j & 1) __builtin_amdgcn_sched_barrier(0);
+			}
+		}
+	}
+	// the mean's partial sum: the query's four lanes g, a fixed butterfly
+	msum += __shfl_xor(msum, 16);
+	msum += __shfl_xor(msum, 32);
+	if (g == 0 && qv) mpart[(long)slice * pstride + qrow] = msum;
+	// D register r of block cb: (query 16 wave + g + 4 r, column 16 cb + q)
+#pragma unroll
+	for (int cb = 0; cb < MGRAD_NCB; cb++)
+		if (cb < ncb) {
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const int row = tr * FT + 16 * wave + g + 4 * r;
+				if (row < M) gpart[((long)slice * pstride + row) * pw + 16 * cb + q] = G[cb][r];
+			}
+		}
+}
+
+// grad[q][j] = sum_a beta_a dh_a/dx_j - s_j ((x*_j - mid_j) S_0 - S_j), the slices added in index order; the basis is
+// 1, x_j, x_j^2, x_j^3 with coefficient 1 + (o - 1) d + j on x_j^o (hfun).  mean (optional) as predict_mean_finish_kernel.
+__global__ __launch_bounds__(256) void predict_mean_grad_finish_kernel(const double *mpart, const double *gpart, long pstride, int pw,
+                                                                       int nslice, int M, int nreg, int d, const double *Xq,
+                                                                       const double *mid, const double *beta, CovParams p,
+                                                                       double *mean, double *grad)
+{
+	const int e = blockIdx.x * 256 + threadIdx.x;
+	if (e >= M * d) return;
+	const int q = e / d, j = e % d;
+	double S0 = 0.0, Sj = 0.0;
+	for (int s = 0; s < nslice; s++) {
+		const double *row = gpart + ((long)s * pstride + q) * pw;
+		S0 += row[0];
+		Sj += row[1 + j];
+	}
+	const double *x = Xq + (long)q * d;
+	const double xj = x[j];
+	double sj;
+	if (p.kind == GPEMU_POWEREXP) sj = 2.0 * p.w[j] * p.w[j];                       // w = sqrt(1/2) / r_j: 1 / r_j^2
+	else if (p.kind == GPEMU_MATERN32) sj = (1.732050808 * 1.732050808) * (p.w[0] * p.w[0]);
+	else sj = p.w[0] * p.w[0];
+	const int order = (nreg - 1) / d;
+	double dh = 0.0;
+	for (int o = 1; o <= order; o++) {
+		const double b = beta[1 + (o - 1) * d + j];
+		dh = fma(o == 1 ? 1.0 : (o == 2 ? 2.0 * xj : 3.0 * xj * xj), b, dh);
+	}
+	grad[e] = dh - sj * ((xj - (mid ? mid[j] : 0.0)) * S0 - Sj);
+	if (j == 0 && mean) {
+		double kg = 0.0;
+		for (int s = 0; s < nslice; s++) kg += mpart[(long)s * pstride + q];
+		double hb = 0.0;
+		for (int a = 0; a < nreg; a++) hb = fma(hfun(a, x, d), beta[a], hb);
+		mean[q] = hb + kg;
+	}
+}
+
+template <bool GRAM>
+static void launch_predict_mean_grad_kind(hipStream_t s, dim3 grid, size_t lds, double *mpart, double *gpart, long pstride, const double *Xq,
+                                          int M, const double *X, const double *Xc, const double *mid, const double *gamma, int N, int Np,
+                                          int d, const CovParams &p)
+{
+	if (p.kind == GPEMU_POWEREXP)
+		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	else if (p.kind == GPEMU_MATERN32)
+		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	else
+		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+}
+
+// mpart: predict_mean_slices(Np) x pstride; gpart: predict_mean_slices(Np) x pstride x predict_mean_grad_width(d); pstride >= M.
+// Xc: the design the sums S_j run on (the centred one, or X itself with mid = nullptr when the context has none).
+// gram: the Gram form (needs p.gram, the centred design and mid), else differences.
+hipError_t launch_predict_mean_grad(hipStream_t s, double *mpart, double *gpart, long pstride, const double *Xq, int M, const double *X,
+                                    const double *Xc, const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p,
+                                    bool gram)
+{
+	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS || !Xc) return hipErrorInvalidValue;
+	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
+	if (gram && (!p.gram || !mid)) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
+	const size_t lds = (size_t)FT * predict_mean_grad_width(d) * sizeof(double);
+	if (gram) {
+		const hipError_t e = ensure_exp_table(s);
+		if (e != hipSuccess) return e;
+		launch_predict_mean_grad_kind<true>(s, grid, lds, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	} else launch_predict_mean_grad_kind<false>(s, grid, lds, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	return hipGetLastError();
+}
+
+hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, const double *gpart, long pstride, int nslice, int M,
+                                           int nreg, int d, const double *Xq, const double *mid, const double *beta, const CovParams &p,
+                                           double *mean, double *grad)
+{
+	hipLaunchKernelGGL(predict_mean_grad_finish_kernel, dim3(((long)M * d + 255) / 256), dim3(256), 0, s, mpart, gpart, pstride,
+	                   predict_mean_grad_width(d), nslice, M, nreg, d, Xq, mid, beta, p, mean, grad);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // A handful of queries (emulate_point: ONE -- the call an MCMC driver makes per sample, emulator_struct.c:124-143): the
 // 64-row tiles of the batch path would spend a table set-up and 63 padding rows on it.  One thread per design point instead
 // computes k_i = cov(x_i, x*_q) for the up to 16 queries (difference form, exact nugget test, clamp: makeKVector_fnptr,

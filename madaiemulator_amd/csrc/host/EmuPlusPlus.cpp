@@ -68,6 +68,29 @@ void emulator::QueryEmulatorMeans(const std::vector<std::vector<double> > &xpoin
 		for (int i = 0; i < number_outputs; i++) Means[q][i] = m[q * number_outputs + i];
 }
 
+void emulator::QueryEmulatorMeanGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+                                          std::vector<std::vector<double> > &Gradients)
+{
+	const size_t np = xpoints.size(), ng = (size_t)number_outputs * number_params;
+	std::vector<double> flat(np * number_params), m(np * number_outputs), g(np * ng);
+	for (size_t q = 0; q < np; q++) {
+		if ((int)xpoints[q].size() != number_params) {
+			std::cerr << "Error::QueryEmulatorMeanGradients called with incorrect number of dimensions in xpoint" << std::endl;
+			gpemu_host_exit(EXIT_FAILURE);
+		}
+		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
+	}
+	gsl_matrix view;
+	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	emulate_points_multi_mean_grad(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), g.data());
+	Means.assign(np, std::vector<double>(number_outputs));
+	Gradients.assign(np, std::vector<double>(ng));
+	for (size_t q = 0; q < np; q++) {
+		for (int i = 0; i < number_outputs; i++) Means[q][i] = m[q * number_outputs + i];
+		for (size_t i = 0; i < ng; i++) Gradients[q][i] = g[q * ng + i];
+	}
+}
+
 void emulator::QueryEmulator(const std::vector<double> &xpoint, std::vector<double> &Means, std::vector<double> &Errors)
 {
 	if ((int)xpoint.size() != number_params) {

@@ -24,6 +24,10 @@ public:
 	// the means alone, one row per query point: the device's mean-only sweep (no variance, no product with L^-1); agrees
 	// with QueryEmulator's Means to rounding
 	void QueryEmulatorMeans(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means);
+	// the means and their gradients with respect to the query point: Gradients[q] has number_outputs x number_params entries,
+	// row-major (output i, parameter j at i * number_params + j)
+	void QueryEmulatorMeanGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+	                                std::vector<std::vector<double> > &Gradients);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

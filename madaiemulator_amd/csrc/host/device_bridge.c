@@ -954,6 +954,35 @@ void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean)
 	if (rc) die(en->ctx, rc, "emulate_points_mean");
 }
 
+/* the mean and its gradient with respect to the query point: gpemu_predict_mean_grad's fused sweep */
+void emulate_points_mean_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *grad)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	double *q = pack_matrix(points);
+	int rc = gpemu_predict_mean_grad(en->ctx, (int)points->size1, q, mean, grad);
+	free(q);
+	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+}
+
+void emulate_points_mean_grad_enqueue(emulator_struct *e, gsl_matrix *points)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	double *q = pack_matrix(points);
+	int rc = gpemu_predict_mean_grad_enqueue(en->ctx, (int)points->size1, q);
+	free(q);
+	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+}
+
+void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *mean, double *grad)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	int rc = gpemu_predict_mean_grad_collect(en->ctx, npoints, mean, grad);
+	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+}
+
 /* leave-one-out at every training point (gpemu_loo) */
 void emulate_loo(emulator_struct *e, double *mean, double *variance)
 {

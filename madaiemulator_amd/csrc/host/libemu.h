@@ -247,6 +247,11 @@ void emulate_points_collect(emulator_struct *e, int npoints, double *mean, doubl
 void emulate_points_mean(emulator_struct *e, gsl_matrix *points, double *mean);
 void emulate_points_mean_enqueue(emulator_struct *e, gsl_matrix *points);
 void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean);
+/* the posterior mean and its gradient with respect to the query point (gpemu_predict_mean_grad in gpemu.h): grad is
+ * npoints x nparams row-major, mean may be NULL.  Errors end in gpemu_host_fatal, as emulate_points_mean's do. */
+void emulate_points_mean_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *grad);
+void emulate_points_mean_grad_enqueue(emulator_struct *e, gsl_matrix *points);
+void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *mean, double *grad);
 /* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
  * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
 void emulate_loo(emulator_struct *e, double *mean, double *variance);
@@ -273,6 +278,10 @@ void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space
 /* the means alone: npoints x nr (pca_space) or npoints x nt (training_mean + evecs diag(sqrt(evals)) mean_pca,
  * multivar_support.c:118-137) */
 void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out);
+/* means (npoints x nr or nt, may be NULL) and their gradients: grad_out is npoints x (nr or nt) x nparams; in observable
+ * space grad_Y[t][j] = sum_c evecs[t][c] sqrt(evals[c]) grad_c[j], the back-projection of multivar_support.c:118-137 without
+ * the training mean */
+void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *grad_out);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);

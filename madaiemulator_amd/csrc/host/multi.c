@@ -521,6 +521,43 @@ void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_
 	free(mp); free(mc);
 }
 
+/* means and their gradients with respect to the query point: every component through its fused sweep (all enqueued, then
+ * collected); observable space by the linear part of the reference's rule (multivar_support.c:118-137), which for the
+ * gradient is grad_Y[t][j] = sum_c evecs[t][c] sqrt(evals[c]) grad_c[j] -- the training mean is a constant */
+void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *grad_out)
+{
+	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt, d = (int)points->size2;
+	const multi_modelstruct *m = emu->model;
+	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
+	double *gp = (double *)malloc(sizeof(double) * (size_t)np * nr * d), *gc = (double *)malloc(sizeof(double) * (size_t)np * d);
+	for (int c = 0; c < nr; c++) emulate_points_mean_grad_enqueue(emu->emu_struct_array[c], points);
+	for (int c = 0; c < nr; c++) {
+		emulate_points_mean_grad_collect(emu->emu_struct_array[c], np, mc, gc);
+		for (int q = 0; q < np; q++) {
+			mp[(size_t)q * nr + c] = mc[q];
+			memcpy(gp + ((size_t)q * nr + c) * d, gc + (size_t)q * d, sizeof(double) * (size_t)d);
+		}
+	}
+	if (pca_space) {
+		if (mean_out) memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
+		memcpy(grad_out, gp, sizeof(double) * (size_t)np * nr * d);
+	} else {
+		for (int q = 0; q < np; q++)
+			for (int i = 0; i < nt; i++) {
+				double ms = 0.0;
+				double *go = grad_out + ((size_t)q * nt + i) * d;
+				for (int j = 0; j < d; j++) go[j] = 0.0;
+				for (int c = 0; c < nr; c++) {
+					const double f = gsl_matrix_get(m->pca_evecs_r, i, c) * sqrt(gsl_vector_get(m->pca_evals_r, c));
+					ms += f * mp[(size_t)q * nr + c];
+					for (int j = 0; j < d; j++) go[j] += f * gp[((size_t)q * nr + c) * d + j];
+				}
+				if (mean_out) mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
+			}
+	}
+	free(mp); free(mc); free(gp); free(gc);
+}
+
 /* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
