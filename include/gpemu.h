@@ -251,6 +251,33 @@ int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int npoints, double *mean /*
 /* device pointers: only enqueues on the context's stream (the first call sizes the scratch) */
 int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */, double *grad_dev);
 
+/* ---- mean, variance and the variance's gradient with respect to the query point ----
+ * grad[q*d + j] = d var(x*_q) / d x*_j of the variance gpemu_predict_batch evaluates, var = kappa - |u|^2 + r^T Q r with
+ * u = L^-1 k, r = h(x*) - W^T k, W = C^-1 H (kappa is constant: the nugget's add is constant on its box).  With the weights g_i
+ * and constants s_j of gpemu_predict_mean_grad (g_i = 0 where the k value falls under the clamp), x' = x - mid:
+ *   a = L^-T u + W (Q r)                                  one N-vector per query: a second N^2 product
+ *   T_0 = sum_i a_i g_i,  T_j = sum_i a_i g_i x'_ij
+ *   d var / d x*_j = 2 s_j ((x*_j - mid_j) T_0 - T_j) + 2 sum_a (Q r)_a dh_a/dx_j
+ * Cost: two triangular products of M N^2 flops each (gpemu_predict_batch runs one) and one fused sweep.  Unlike the mean
+ * sweeps this entry uses the batch buffers of gpemu_predict_batch (k-vectors and products, 8 M' (2 Np + 64) bytes for blocks of
+ * M' <= 16384 queries), and the first call after a set-up makes a transposed copy of L^-1 with gamma and W: 8 Np (Np + 64)
+ * bytes (0.54 GB at N = 8192), kept until the model is freed and rebuilt after every gpemu_predict_setup[_batch],
+ * gpemu_set_model or gpemu_set_training.  Callers that never ask for this gradient allocate nothing for it.
+ * mean and var (M values each, either may be NULL) agree with gpemu_predict_batch to rounding, not bit for bit.  Two
+ * identical calls return the same bits; the host, _dev and enqueue / collect entries return the same bits.  Few queries take
+ * the same kernels on one 64-row tile: there is no fast path for them.  Where the variance rounds to <= 0 the gradient is
+ * still that of the expression above.
+ * Errors are those of gpemu_predict_mean_grad (grad required; mean, var optional).  One batch of any kind per context is
+ * pending at a time; a variance-gradient batch is a fourth kind and is collected by gpemu_predict_var_grad_collect only
+ * (another collect: GPEMU_ERR_STATE, the batch stays enqueued). */
+int gpemu_predict_var_grad(gpemu_ctx *ctx, int npoints, const double *xq, double *mean /* M, may be NULL */, double *var /* M, may be NULL */,
+                           double *grad /* M*d row-major */);
+int gpemu_predict_var_grad_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
+int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int npoints, double *mean /* may be NULL */, double *var /* may be NULL */, double *grad);
+/* device pointers: only enqueues on the context's stream (the first call sizes the scratch and makes the transposed copy) */
+int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */,
+                               double *var_dev /* may be NULL */, double *grad_dev);
+
 /* ---- leave-one-out validation of a trained emulator -----------------
  * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
  * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
@@ -311,6 +338,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_LOO     7   /* the two launches of gpemu_loo[_dev]: column sums over L^-1 (bytes = 8 N (N+1) / 2), finish */
 #define GPEMU_PROF_MEAN    8   /* the two launches of the mean-only sweep: flops = M*N*(kernel + 2) with kernel = 3 d (the squared distance), bytes = 8*M*(d+1) */
 #define GPEMU_PROF_MEAN_GRAD 9 /* the two launches of the mean-gradient sweep: flops = M*N*(3 d + 2 + 2 (d + 1)), bytes = 8*M*(2 d + 1) */
+#define GPEMU_PROF_VAR_GRAD 10 /* the fused sweep of the variance-gradient entry and its finish: flops = M*N*(3 d + 1 + 2 (d + 1)), bytes = 8*M*(N + 2 d); its two products report under GPEMU_PROF_GEMM */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

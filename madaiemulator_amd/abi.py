@@ -18,6 +18,7 @@ PROF_NONE, PROF_GEMM, PROF_FILL, PROF_LEAF, PROF_POTRF, PROF_GEMM_BIG, PROF_GEMM
 PROF_LOO = 7
 PROF_MEAN = 8
 PROF_MEAN_GRAD = 9
+PROF_VAR_GRAD = 10
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -85,6 +86,10 @@ SYMBOLS = {
     "gpemu_predict_mean_grad_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_mean_grad_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "gpemu_predict_mean_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_var_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpemu_predict_var_grad_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "gpemu_predict_var_grad_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "gpemu_predict_var_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -456,6 +461,32 @@ class Context:
         m, g = np.empty(self._npred), np.empty((self._npred, self.d))
         self._chk(self.L.gpemu_predict_mean_grad_collect(self.h, self._npred, _p(m), _p(g)))
         return m, g
+
+    # mean, variance and the variance's gradient with respect to the query point: two N^2 products and a fused sweep
+    # (DESIGN.md 4.10); uses the batch buffers of predict_batch
+    def predict_var_grad(self, Xq, want_mean=True, want_var=True):
+        """-> (mean[M] or None, var[M] or None, grad[M, d])"""
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        mean = np.empty(M) if want_mean else None
+        var = np.empty(M) if want_var else None
+        grad = np.empty((M, self.d))
+        self._chk(self.L.gpemu_predict_var_grad(self.h, M, _p(Xq), _p(mean) if want_mean else None,
+                                                _p(var) if want_var else None, _p(grad)))
+        return mean, var, grad
+
+    def predict_var_grad_dev(self, M, xq_dev, mean_dev, var_dev, grad_dev):
+        self._chk(self.L.gpemu_predict_var_grad_dev(self.h, M, xq_dev, mean_dev, var_dev, grad_dev))
+
+    def predict_var_grad_enqueue(self, Xq):
+        Xq = _a(Xq).reshape(-1, self.d)
+        self._npred = Xq.shape[0]
+        self._chk(self.L.gpemu_predict_var_grad_enqueue(self.h, Xq.shape[0], _p(Xq)))
+
+    def predict_var_grad_collect(self):
+        m, v, g = np.empty(self._npred), np.empty(self._npred), np.empty((self._npred, self.d))
+        self._chk(self.L.gpemu_predict_var_grad_collect(self.h, self._npred, _p(m), _p(v), _p(g)))
+        return m, v, g
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

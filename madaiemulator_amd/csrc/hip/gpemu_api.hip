@@ -34,7 +34,7 @@ static int fail(gpemu_ctx *ctx, int code, const char *msg)
 }
 
 // the prediction state and the explicit inverse no longer belong to what the workspace, the model or the mode now say
-static void invalidate_prediction(gpemu_ctx *ctx) { ctx->pred_ready = false; ctx->cinv_ready = false; }
+static void invalidate_prediction(gpemu_ctx *ctx) { ctx->pred_ready = false; ctx->cinv_ready = false; ctx->linvT_ready = false; }
 
 // ---------------------------------------------------------------------------
 // profiling helpers
@@ -259,7 +259,7 @@ static void free_model(gpemu_ctx *ctx)
 	free_graphs(ctx);
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
 	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
-	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad})
+	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad, &ctx->dLinvAugT, &ctx->dVGradPart})
 		b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
@@ -268,6 +268,7 @@ static void free_model(gpemu_ctx *ctx)
 	ctx->pred_pending = 0;
 	ctx->pred_pending_mean = false;
 	ctx->pred_pending_grad = false;
+	ctx->pred_pending_vgrad = false;
 	ctx->S_dim = 0;
 }
 
@@ -1056,6 +1057,7 @@ static int build_prediction_state(gpemu_ctx *src, int b, gpemu_ctx *dst, const C
 	dst->kappa = p.amp + p.nug;                       // cov(x*,x*): emulator_struct.c:135 (nugget included)
 	dst->pred_ready = true;
 	dst->cinv_ready = false;
+	dst->linvT_ready = false;
 	dst->last_thetas.assign(thetas, thetas + nthetas);
 	return GPEMU_OK;
 }
@@ -1306,6 +1308,7 @@ extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, 
 {
 	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
 	if (ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is mean-only: collect it with gpemu_predict_mean_collect");
 	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1388,6 +1391,7 @@ extern "C" int gpemu_predict_mean_collect(gpemu_ctx *ctx, int M, double *mean)
 {
 	if (!ctx || !mean) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
 	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
 	if (!ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch has variances: collect it with gpemu_predict_batch_collect");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1481,6 +1485,7 @@ extern "C" int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int M, double *me
 {
 	if (!ctx || !grad) return GPEMU_ERR_ARG;
 	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
 	if (!ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is not a mean-gradient batch: collect it with the collect of its own kind");
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	if (mean) memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
@@ -1496,6 +1501,151 @@ extern "C" int gpemu_predict_mean_grad(gpemu_ctx *ctx, int M, const double *xq, 
 	const int rc = gpemu_predict_mean_grad_enqueue(ctx, M, xq);
 	if (rc) return rc;
 	return gpemu_predict_mean_grad_collect(ctx, M, mean, grad);
+}
+
+// ---------------------------------------------------------------------------
+// mean, variance and the variance's gradient with respect to the query point (gpemu.h).  Per block of up to
+// PRED_BATCH_MAX queries: the k-vectors and V = Kq LinvAug^T as in gpemu_predict_batch_dev (K never split: the u rows must be
+// whole), the finish, Q r per query into V's columns Np .., the second product A^T = LinvAugT [u | Q r]^T into dKq (its
+// k-vectors are dead by then; row starts skipped: L^-T is upper triangular), the fused sweep and its finish.  Uses dKq and dV
+// -- unlike the mean sweeps --, its own dVGradPart and, made by the first call after a set-up, dLinvAugT.
+// ---------------------------------------------------------------------------
+static int ensure_linv_transposed(gpemu_ctx *ctx)
+{
+	if (ctx->linvT_ready) return GPEMU_OK;
+	const int Np = ctx->Np, Rp = ctx->Rp;
+	const long ldt = (long)Np + Rp;
+	const int rc = grow(ctx, ctx->dLinvAugT, (size_t)Np * ldt, false, "out of device memory for the transposed copy of L^-1 (8 Np (Np + Rp) bytes)");
+	if (rc) return rc;
+	HIPCHK(ctx, launch_transpose(ctx->stream, ctx->dLinvAugT, ldt, ctx->dLinvAug, Np, Np));
+	HIPCHK(ctx, launch_transpose_rect(ctx->stream, ctx->dLinvAugT + Np, ldt, ctx->dLinvAug + (size_t)Np * Np, Np, Rp, Np));
+	ctx->linvT_ready = true;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *var_dev, double *grad_dev)
+{
+	if (!ctx || M < 1 || !xq_dev || !grad_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int Np = ctx->Np, Rp = ctx->Rp, N = ctx->N, d = ctx->d;
+	const int nslice = predict_mean_slices(Np), pw = predict_mean_grad_width(d);
+	const int cap = std::min(PRED_BATCH_MAX, round_up(M, 64));
+	int rc = ensure_pred_batch(ctx, cap);
+	if (!rc) rc = grow(ctx, ctx->dVGradPart, (size_t)nslice * cap * (size_t)pw + 2 * (size_t)cap);
+	if (!rc) rc = ensure_linv_transposed(ctx);
+	if (rc) return rc;
+	double *gpart = ctx->dVGradPart, *spare = gpart + (size_t)nslice * cap * (size_t)pw;
+	const long ldv = (long)Np + Rp;
+	const CovParams &p = ctx->pred_cov;
+	const bool centred = ctx->dXg && ctx->dMid;
+	const bool gram = p.gram && ctx->sched.kvec_gram && centred;
+	const double *Xc = centred ? (const double *)ctx->dXg : (const double *)ctx->dX, *mid = centred ? (const double *)ctx->dMid : nullptr;
+	for (int q0 = 0; q0 < M; q0 += cap) {
+		const int mb = std::min(cap, M - q0);
+		const int mbp = round_up(mb, 64);
+		const double *xq = xq_dev + (size_t)q0 * d;
+		{
+			ProfScope ps(ctx, GPEMU_PROF_FILL, 0.0, 8.0 * (double)mbp * Np);
+			HIPCHK(ctx, fill_kvectors(ctx, ctx->dKq, xq, mb, mbp, p));
+		}
+		GemmArgs g{};
+		g.C = ctx->dV; g.ldc = ldv;
+		g.A = ctx->dKq; g.lda = Np;
+		g.B = ctx->dLinvAug; g.ldb = Np;
+		g.m = mb; g.n = Np + Rp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+		g.kend_mode = 1; g.kend_off = 0;
+		apply_sched(ctx->sched, g);
+		if (ctx->sched.split_rhs_rows && gemm_uses_big_tiles(g)) {
+			// (the gamma and W^T columns in a 64x64-tile launch of their own, as in gpemu_predict_batch_dev)
+			GemmArgs a = g;
+			a.n = Np;
+			HIPCHK(ctx, gemm(ctx, a));
+			GemmArgs b = g;
+			b.C = ctx->dV + Np; b.B = ctx->dLinvAug + (size_t)Np * Np;
+			b.n = Rp; b.kend_mode = 0; b.force_cfg = 2;
+			HIPCHK(ctx, gemm(ctx, b));
+		} else
+			HIPCHK(ctx, gemm(ctx, g));
+		HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, ldv, mb, Np, ctx->nreg, ctx->order, d, xq, ctx->dBetaQ, ctx->kappa,
+		                                  mean_dev ? mean_dev + q0 : spare, var_dev ? var_dev + q0 : spare + cap, 1, (long)mbp * ldv));
+		HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, mb, Np, Rp, ctx->nreg, d, xq, ctx->dBetaQ));
+		// A^T (Np x mbp) = LinvAugT (Np x (Np + Rp), row i zero before column i) . V^T
+		GemmArgs t{};
+		t.C = ctx->dKq; t.ldc = mbp;
+		t.A = ctx->dLinvAugT; t.lda = ldv;
+		t.B = ctx->dV; t.ldb = ldv;
+		t.m = Np; t.n = mb; t.k0 = 0; t.k1 = Np + Rp; t.alpha = 1.0; t.beta = 0;
+		t.kstart_mode = 1; t.kstart_off = 0;
+		HIPCHK(ctx, gemm(ctx, t));
+		if (prof_on(ctx, GPEMU_PROF_VAR_GRAD)) { ctx->prof.tag.push_back("predict_var_grad"); ctx->prof.tag.push_back("predict_var_grad_finish"); }
+		{
+			// flops: per element the squared distance (3 d), the product with a (1) and the 1 + d columns of the matrix
+			// product (2 each); bytes: A^T and the coordinates in, the gradient out
+			ProfScope ps(ctx, GPEMU_PROF_VAR_GRAD, (double)mb * N * (3.0 * d + 1.0 + 2.0 * (d + 1)), 8.0 * (double)mb * (N + 2 * d));
+			HIPCHK(ctx, launch_predict_var_grad(ctx->stream, gpart, cap, xq, mb, ctx->dX, Xc, mid, ctx->dKq, mbp, N, Np, d, p, gram));
+		}
+		{
+			ProfScope ps(ctx, GPEMU_PROF_VAR_GRAD, 2.0 * mb * d * (nslice + 3.0), 0.0);
+			HIPCHK(ctx, launch_predict_var_grad_finish(ctx->stream, gpart, cap, nslice, mb, ctx->nreg, d, xq, mid, ctx->dV, ldv, Np, p,
+			                                           grad_dev + (size_t)q0 * d));
+		}
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_var_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq)
+{
+	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d;
+	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
+	if (ctx->mgrad_cap() < (size_t)M) {
+		const size_t gcap = (size_t)std::max(M, 64);
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+		ctx->hMGrad.reset();
+		if (const int rc = grow(ctx, ctx->dMGrad, gcap * d)) return rc;
+		HIPCHK(ctx, ctx->hMGrad.grow(gcap * d));
+	}
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d, *hv = hm + cap;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	const int rc = gpemu_predict_var_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar(), ctx->dMGrad);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->hMGrad, ctx->dMGrad, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	ctx->pred_pending = M;
+	ctx->pred_pending_mean = false;
+	ctx->pred_pending_grad = false;
+	ctx->pred_pending_vgrad = true;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *var, double *grad)
+{
+	if (!ctx || !grad) return GPEMU_ERR_ARG;
+	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (!ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is not a variance-gradient batch: collect it with the collect of its own kind");
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
+	if (mean) memcpy(mean, hm, (size_t)M * sizeof(double));
+	if (var) memcpy(var, hv, (size_t)M * sizeof(double));
+	memcpy(grad, ctx->hMGrad, (size_t)M * ctx->d * sizeof(double));
+	ctx->pred_pending = 0;
+	ctx->pred_pending_vgrad = false;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_var_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *var, double *grad)
+{
+	if (!ctx || M < 1 || !xq || !grad) return GPEMU_ERR_ARG;
+	const int rc = gpemu_predict_var_grad_enqueue(ctx, M, xq);
+	if (rc) return rc;
+	return gpemu_predict_var_grad_collect(ctx, M, mean, var, grad);
 }
 
 // ---------------------------------------------------------------------------

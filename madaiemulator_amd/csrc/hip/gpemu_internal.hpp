@@ -246,10 +246,18 @@ struct gpemu_ctx {
 	gpemu::DevBuf<double> dMeanPart;  // mean-only sweep: slice partial sums, predict_mean_slices(Np) x queries of a block
 	// mean-gradient sweep (gpemu_predict_mean_grad): its own scratch and staging.  dMGradPart: per slice and query of a block
 	// the mean's partial sum, then predict_mean_grad_width(d) gradient sums; dMGrad / hMGrad: mgrad_cap() x d gradients
+	// (dMGrad / hMGrad also stage the gradients of the variance-gradient entry's host forms: one batch is pending at a time)
 	bool pred_pending_grad = false;   // the enqueued batch came from gpemu_predict_mean_grad_enqueue
 	gpemu::DevBuf<double> dMGradPart, dMGrad;
 	gpemu::PinnedBuf<double> hMGrad;
 	size_t mgrad_cap() const { return d ? hMGrad.size() / (size_t)d : 0; }
+	// variance-gradient entry (gpemu_predict_var_grad).  dLinvAugT: dLinvAug transposed, Np x (Np + Rp), made by
+	// the first call after a set-up (linvT_ready; cleared with pred_ready); dVGradPart: per slice and query of a block
+	// predict_mean_grad_width(d) gradient sums, then two rows of scratch for a mean or variance the caller did not ask for.
+	// The entry also uses dKq and dV, as gpemu_predict_batch does.
+	bool pred_pending_vgrad = false;  // the enqueued batch came from gpemu_predict_var_grad_enqueue
+	bool linvT_ready = false;
+	gpemu::DevBuf<double> dLinvAugT, dVGradPart;
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
@@ -324,6 +332,16 @@ hipError_t launch_predict_mean_grad(hipStream_t s, double *mpart, double *gpart,
 hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, const double *gpart, long pstride, int nslice, int M,
                                            int nreg, int d, const double *Xq, const double *mid, const double *beta, const CovParams &p,
                                            double *mean, double *grad);
+// the variance's gradient (gpemu_predict_var_grad): (Q r) per query into V's columns Np .. Np + Rp, the fused
+// sweep over A^T (Np x lda, the second product's output), the finish in slice order
+hipError_t launch_predict_qr(hipStream_t s, double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
+                             const double *betaQ);
+hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const double *src, long lds, int rows, int cols);
+hipError_t launch_predict_var_grad(hipStream_t s, double *gpart, long pstride, const double *Xq, int M, const double *X, const double *Xc,
+                                   const double *mid, const double *At, long lda, int N, int Np, int d, const CovParams &p, bool gram);
+hipError_t launch_predict_var_grad_finish(hipStream_t s, const double *gpart, long pstride, int nslice, int M, int nreg, int d,
+                                          const double *Xq, const double *mid, const double *V, long ldv, int Np, const CovParams &p,
+                                          double *grad);
 hipError_t launch_grad_partials(hipStream_t s, const double *S, long lds, int soff, long sstride, int nb, const double *X, int N,
                                 int d, double *ag, int np_pad, long gstride, double *part, long pstride, int *nparts,
                                 int exact_kind = 0, int nbeta = 0, const CovParams *pp_dev = nullptr, bool lit_noclamp = false,

@@ -1342,6 +1342,264 @@ hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, c
 }
 
 // ---------------------------------------------------------------------------
+// Gradient of the posterior variance with respect to the query point.  predict_finish_kernel evaluates
+//   var = kappa - |u|^2 + r^T Q r,   u = L^-1 k,  r = h(x*) - W^T k,
+// so with a = L^-T u + W (Q r) (one N-vector per query, gpemu_predict_var_grad_dev's second product) and the weights g_i and
+// constants s_j of the mean's gradient
+//   d var / d x*_j = 2 s_j ((x*_j - mid_j) T_0 - T_j) + 2 sum_a (Q r)_a dh_a/dx_j,   T_0 = sum_i a_i g_i,  T_j = sum_i a_i g_i x'_ij.
+// The reduction is predict_mean_grad_kernel's with the shared gamma_i replaced by a per-query a_qi: the weight tile is made on
+// chip, multiplied element by element with a loaded tile of A and fed to the matrix unit against [1, x'_i].
+// ---------------------------------------------------------------------------
+
+// V[q][Np + c], c in [0, Rp): 0 for c = 0 (the column that pairs with gamma in the second product), (Q r)_q[c - 1] for
+// 1 <= c <= nreg (the columns that pair with W^T), 0 beyond.  r is read from the same columns (W^T k, left there by the
+// first product) before anything is written: one wave per query, reads and writes on either side of the barrier.
+__global__ __launch_bounds__(256) void predict_qr_kernel(double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
+                                                         const double *betaQ)
+{
+	__shared__ double r_s[4][64];
+	const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+	const int q = blockIdx.x * 4 + w;
+	const bool qv = q < M;
+	double *v = V + (long)(qv ? q : 0) * ldv + Np;
+	r_s[w][c] = (qv && c < nreg) ? hfun(c, Xq + (long)q * d, d) - v[1 + c] : 0.0;
+	__syncthreads();
+	if (!qv) return;
+	const double *Q = betaQ + nreg;
+	for (int col = c; col < Rp; col += 64) {
+		double t = 0.0;
+		if (col >= 1 && col <= nreg)
+			for (int b = 0; b < nreg; b++) t += Q[(col - 1) * nreg + b] * r_s[w][b];
+		v[col] = t;
+	}
+}
+
+hipError_t launch_predict_qr(hipStream_t s, double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
+                             const double *betaQ)
+{
+	if (M < 1 || nreg < 1 || nreg > 63 || nreg + 1 > Rp) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(predict_qr_kernel, dim3((M + 3) / 4), dim3(256), 0, s, V, ldv, M, Np, Rp, nreg, d, Xq, betaQ);
+	return hipGetLastError();
+}
+
+// transpose_kernel on a rows x cols block (multiples of 64): dst[j][i] = src[i][j]
+hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const double *src, long lds_, int rows, int cols)
+{
+	if (rows % 64 || cols % 64 || rows < 64 || cols < 64) return hipErrorInvalidValue;
+	dim3 grid(cols / 64, rows / 64);
+	hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, s, dst, ldd, src, lds_, rows);
+	return hipGetLastError();
+}
+
+// gpart: slices x pstride rows of pw = 16 ncb partial sums [T_0, T_1 .. T_d, 0 ..].  At: a as A^T, Np rows of lda >= the
+// query count rounded up to 64 (a multiple of 16): element (design i, query q) at At[i * lda + q].  The lane that holds
+// (design 16 j + g + 4 r of the tile, query 16 wave + q) loads its sixteen a values at the top of the tile, under the
+// distance product: per load instruction the sixteen lanes q of one g read one 128-byte run of row i, four runs a wave.
+// The tiling, the tile, the candidate / far-query / same-point rules, the clamp and the summation order are
+// predict_mean_grad_kernel's; there is no mean accumulator.  Padding columns i >= N and clamped entries have weight 0, rows
+// q >= M weight 0 as well (their a is not read as a number) and are never stored.
+template <int KIND, bool GRAM>
+__global__ __launch_bounds__(256, 2) void predict_var_grad_kernel(double *gpart, long pstride, const double *Xq, int M, const double *X,
+                                                                const double *Xc, const double *mid, const double *At, long lda, int N,
+                                                                int Np, int d, CovParams p)
+{
+	extern __shared__ double ys[];                 // FT x pw: [1, x'_i1 .. x'_id, 0 ..] of the current tile
+	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
+	__shared__ double wsc[GPEMU_MAX_PARAMS];
+	__shared__ double mid_s[GPEMU_MAX_PARAMS];
+	const int tid = threadIdx.x;
+	const int ntc = Np / FT, nsl = (ntc + MEAN_TPW - 1) / MEAN_TPW;
+	const int tr = blockIdx.x / nsl, slice = blockIdx.x % nsl, tc0 = slice * MEAN_TPW;
+	const int ncb = (d + 1 + 15) / 16, pw = 16 * ncb;
+	if (GRAM) {
+		gram_tables(p, d, tab, wsc);
+		if (tid < GPEMU_MAX_PARAMS) mid_s[tid] = (tid < d) ? mid[tid] : 0.0;
+	} else {
+		if (tid < EXP_TAB) tab[tid] = exp2((double)tid * (1.0 / EXP_TAB));
+		if (tid < GPEMU_MAX_PARAMS) wsc[tid] = (tid < d) ? p.w[(KIND == GPEMU_POWEREXP) ? tid : 0] : 0.0;
+	}
+	const int lane = tid & 63, wave = tid >> 6;
+	const int q = lane & 15, g = lane >> 4;
+	const int qrow = tr * FT + 16 * wave + q;
+	const bool qv = qrow < M;
+	d4g_t G[MGRAD_NCB];
+#pragma unroll
+	for (int cb = 0; cb < MGRAD_NCB; cb++) G[cb] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+	for (int i = 0; i < MEAN_TPW; i++) {
+		const int tc = tc0 + i;
+		if (tc >= ntc) break;
+		// (rows tc FT + .. < Np and columns qrow < lda lie inside the block whatever N and M are)
+		d4g_t av[4];
+		{
+			const double *ap = At + (long)(tc * FT + g) * lda + qrow;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) av[j][r] = ap[(long)(16 * j + 4 * r) * lda];
+		}
+		__syncthreads();                           // the tables (first tile); the previous tile's ys has been read
+		for (int rr = 0; rr < 4; rr++) {
+			const int r = (tid >> 4) + 16 * rr, gi = tc * FT + r;
+			for (int cb = 0; cb < ncb; cb++) {
+				const int c = 16 * cb + (tid & 15);
+				double v = 0.0;
+				if (gi < N && c <= d) v = (c == 0) ? 1.0 : Xc[(long)gi * d + c - 1];
+				ys[r * pw + c] = v;
+			}
+		}
+		__syncthreads();
+		d4g_t acc[4];
+		unsigned same = 0;
+		if (GRAM) {
+			same = gram_tile_u2_qcol<KIND>(acc, Xq, mid_s, M, X, Xc, N, d, p, tr, tc, wsc);
+		} else {
+			// squared scaled distances from differences, as in predict_mean_grad_kernel's difference form
+#pragma unroll
+			for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+			const double *qp = Xq + (long)(qv ? qrow : 0) * d;
+			const double *xp[4];
+#pragma unroll
+			for (int r = 0; r < 4; r++) xp[r] = X + (long)(tc * FT + g + 4 * r) * d;      // (+ 16 j below, clamped per element)
+			for (int k = 0; k < d; k++) {
+				const double wk = wsc[k];
+				const double xr = qv ? qp[k] * wk : 0.0;
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+#pragma unroll
+					for (int r = 0; r < 4; r++) {
+						const bool cv = tc * FT + 16 * j + g + 4 * r < N;
+						const double xc = cv ? xp[r][(long)16 * j * d + k] * wk : 0.0;
+						const double diff = xr - xc;
+						acc[j][r] = fma(diff, diff, acc[j][r]);
+					}
+			}
+			bool cand = false;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) cand = cand || (acc[j][r] <= p.cand);
+			if (__any(cand)) {
+#pragma unroll 1
+				for (int e = 0; e < 16; e++) {
+					const int r = e >> 2, j = e & 3;
+					double ae = HUGE_VAL;
+#pragma unroll
+					for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+						for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
+					const int col = tc * FT + 16 * j + g + 4 * r;
+					if (ae <= p.cand && qv && col < N) {
+						int cnt = 0;
+						for (int k = 0; k < d; k++) cnt += (fabs(qp[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
+						if (cnt == d) same |= 1u << e;
+					}
+				}
+			}
+		}
+		const bool plain = (tc * FT + FT <= N) && !__any(same != 0);
+		const double *yb = ys + g * pw + q;
+#pragma unroll
+		for (int r = 0; r < 4; r++) {
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				double gw;
+				double v = GRAM ? cov_grad_from_u2_gram<KIND>(acc[j][r], tab, gw) : cov_grad_from_a_diff<KIND>(acc[j][r], p.amp, tab, gw);
+				if (!plain && (same & (1u << (4 * r + j)))) v += p.nug;
+				// emulator.c:588-590 and its derivative; a padding column's distance was not held at the exponent limit and a
+				// padding row's a is whatever the buffer held: neither is used as a number
+				const bool live = qv && (plain || tc * FT + 16 * j + g + 4 * r < N) && !(v < 1E-10);
+				const double wgt = live ? gw * av[j][r] : 0.0;
+#pragma unroll
+				for (int cb = 0; cb < MGRAD_NCB; cb++)
+					if (cb < ncb) G[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(wgt, yb[(16 * j + 4 * r) * pw + 16 * cb], G[cb], 0, 0, 0);
+				if (j & 1) __builtin_amdgcn_sched_barrier(0);
+			}
+		}
+	}
+	// D register r of block cb: (query 16 wave + g + 4 r, column 16 cb + q)
+#pragma unroll
+	for (int cb = 0; cb < MGRAD_NCB; cb++)
+		if (cb < ncb) {
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const int row = tr * FT + 16 * wave + g + 4 * r;
+				if (row < M) gpart[((long)slice * pstride + row) * pw + 16 * cb + q] = G[cb][r];
+			}
+		}
+}
+
+// grad[q][j] = 2 s_j ((x*_j - mid_j) T_0 - T_j) + 2 sum_a (Q r)_a dh_a/dx_j, the slices added in index order; (Q r)_a from
+// V[q][Np + 1 + a] (predict_qr_kernel); basis and s_j as in predict_mean_grad_finish_kernel
+__global__ __launch_bounds__(256) void predict_var_grad_finish_kernel(const double *gpart, long pstride, int pw, int nslice, int M, int nreg,
+                                                                      int d, const double *Xq, const double *mid, const double *V, long ldv,
+                                                                      int Np, CovParams p, double *grad)
+{
+	const int e = blockIdx.x * 256 + threadIdx.x;
+	if (e >= M * d) return;
+	const int q = e / d, j = e % d;
+	double T0 = 0.0, Tj = 0.0;
+	for (int s = 0; s < nslice; s++) {
+		const double *row = gpart + ((long)s * pstride + q) * pw;
+		T0 += row[0];
+		Tj += row[1 + j];
+	}
+	const double xj = Xq[(long)q * d + j];
+	double sj;
+	if (p.kind == GPEMU_POWEREXP) sj = 2.0 * p.w[j] * p.w[j];                       // w = sqrt(1/2) / r_j: 1 / r_j^2
+	else if (p.kind == GPEMU_MATERN32) sj = (1.732050808 * 1.732050808) * (p.w[0] * p.w[0]);
+	else sj = p.w[0] * p.w[0];
+	const double *qr = V + (long)q * ldv + Np + 1;
+	const int order = (nreg - 1) / d;
+	double dh = 0.0;
+	for (int o = 1; o <= order; o++) {
+		const double b = qr[1 + (o - 1) * d + j];
+		dh = fma(o == 1 ? 1.0 : (o == 2 ? 2.0 * xj : 3.0 * xj * xj), b, dh);
+	}
+	grad[e] = 2.0 * (sj * ((xj - (mid ? mid[j] : 0.0)) * T0 - Tj) + dh);
+}
+
+template <bool GRAM>
+static void launch_predict_var_grad_kind(hipStream_t s, dim3 grid, size_t lds, double *gpart, long pstride, const double *Xq, int M,
+                                         const double *X, const double *Xc, const double *mid, const double *At, long lda, int N, int Np,
+                                         int d, const CovParams &p)
+{
+	if (p.kind == GPEMU_POWEREXP)
+		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+	else if (p.kind == GPEMU_MATERN32)
+		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+	else
+		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+}
+
+// gpart: predict_mean_slices(Np) x pstride x predict_mean_grad_width(d); pstride >= M; At: Np x lda, lda >= M rounded up to 64.
+// Xc, mid, gram as in launch_predict_mean_grad.
+hipError_t launch_predict_var_grad(hipStream_t s, double *gpart, long pstride, const double *Xq, int M, const double *X, const double *Xc,
+                                   const double *mid, const double *At, long lda, int N, int Np, int d, const CovParams &p, bool gram)
+{
+	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS || !Xc || !At) return hipErrorInvalidValue;
+	if (lda % 16 || lda < (long)((M + FT - 1) / FT) * FT) return hipErrorInvalidValue;
+	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
+	if (gram && (!p.gram || !mid)) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
+	const size_t lds = (size_t)FT * predict_mean_grad_width(d) * sizeof(double);
+	if (gram) {
+		const hipError_t e = ensure_exp_table(s);
+		if (e != hipSuccess) return e;
+		launch_predict_var_grad_kind<true>(s, grid, lds, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+	} else launch_predict_var_grad_kind<false>(s, grid, lds, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+	return hipGetLastError();
+}
+
+hipError_t launch_predict_var_grad_finish(hipStream_t s, const double *gpart, long pstride, int nslice, int M, int nreg, int d,
+                                          const double *Xq, const double *mid, const double *V, long ldv, int Np, const CovParams &p,
+                                          double *grad)
+{
+	hipLaunchKernelGGL(predict_var_grad_finish_kernel, dim3(((long)M * d + 255) / 256), dim3(256), 0, s, gpart, pstride,
+	                   predict_mean_grad_width(d), nslice, M, nreg, d, Xq, mid, V, ldv, Np, p, grad);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // A handful of queries (emulate_point: ONE -- the call an MCMC driver makes per sample, emulator_struct.c:124-143): the
 // 64-row tiles of the batch path would spend a table set-up and 63 padding rows on it.  One thread per design point instead
 // computes k_i = cov(x_i, x*_q) for the up to 16 queries (difference form, exact nugget test, clamp: makeKVector_fnptr,

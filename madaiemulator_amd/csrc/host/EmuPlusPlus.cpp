@@ -91,6 +91,32 @@ void emulator::QueryEmulatorMeanGradients(const std::vector<std::vector<double> 
 	}
 }
 
+void emulator::QueryEmulatorGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+                                      std::vector<std::vector<double> > &Variances, std::vector<std::vector<double> > &MeanGradients,
+                                      std::vector<std::vector<double> > &VarianceGradients)
+{
+	const size_t np = xpoints.size(), ng = (size_t)number_outputs * number_params;
+	std::vector<double> flat(np * number_params), m(np * number_outputs), v(np * number_outputs), gm(np * ng), gv(np * ng);
+	for (size_t q = 0; q < np; q++) {
+		if ((int)xpoints[q].size() != number_params) {
+			std::cerr << "Error::QueryEmulatorGradients called with incorrect number of dimensions in xpoint" << std::endl;
+			gpemu_host_exit(EXIT_FAILURE);
+		}
+		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
+	}
+	gsl_matrix view;
+	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	emulate_points_multi_grad(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), v.data(), gm.data(), gv.data());
+	Means.assign(np, std::vector<double>(number_outputs));
+	Variances.assign(np, std::vector<double>(number_outputs));
+	MeanGradients.assign(np, std::vector<double>(ng));
+	VarianceGradients.assign(np, std::vector<double>(ng));
+	for (size_t q = 0; q < np; q++) {
+		for (int i = 0; i < number_outputs; i++) { Means[q][i] = m[q * number_outputs + i]; Variances[q][i] = v[q * number_outputs + i]; }
+		for (size_t i = 0; i < ng; i++) { MeanGradients[q][i] = gm[q * ng + i]; VarianceGradients[q][i] = gv[q * ng + i]; }
+	}
+}
+
 void emulator::QueryEmulator(const std::vector<double> &xpoint, std::vector<double> &Means, std::vector<double> &Errors)
 {
 	if ((int)xpoint.size() != number_params) {

@@ -28,6 +28,13 @@ public:
 	// row-major (output i, parameter j at i * number_params + j)
 	void QueryEmulatorMeanGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
 	                                std::vector<std::vector<double> > &Gradients);
+	// means, variances and the gradients of both with respect to the query point.  Variances, NOT their square roots
+	// (QueryEmulator returns Errors = sqrt(variance)): the derivative of an error bar is undefined where the variance rounds
+	// to <= 0, so the caller forms grad(sqrt(var)) = VarianceGradients / (2 sqrt(Variances)) where it is positive.
+	// MeanGradients[q] and VarianceGradients[q] have number_outputs x number_params entries, row-major
+	void QueryEmulatorGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+	                            std::vector<std::vector<double> > &Variances, std::vector<std::vector<double> > &MeanGradients,
+	                            std::vector<std::vector<double> > &VarianceGradients);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -116,6 +116,7 @@ struct entry {
 	unsigned long long xsum, ysum;    /* ... and a 64-bit checksum of every value: callers rewrite the buffers in place */
 	int N, d, kind, order;
 	struct vcache vc;                 /* (callers with a context of their own; group members have theirs in the group) */
+	double *grad_q;                   /* emulate_points_grad_enqueue: the packed points, kept for the mean gradient at collect */
 	struct entry *next;
 };
 
@@ -216,6 +217,7 @@ void gpemu_host_release(void *key)
 			struct entry *e = *pp;
 			*pp = e->next;
 			gpemu_ctx_destroy(e->ctx);
+			free(e->grad_q);
 			free(e);
 			continue;
 		}
@@ -981,6 +983,50 @@ void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *m
 	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
 	int rc = gpemu_predict_mean_grad_collect(en->ctx, npoints, mean, grad);
 	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+}
+
+/* mean, variance and both gradients with respect to the query point (libemu.h).  The variance-gradient entry of the device
+ * library gives mean, variance and the variance's gradient (two N^2 products and a sweep); the mean's gradient comes from
+ * gpemu_predict_mean_grad's fused sweep, a small fraction of that.  A context holds one pending batch, so the pair starts the
+ * variance-gradient batch at enqueue and runs the mean-gradient sweep at collect, on the points kept since. */
+void emulate_points_grad_enqueue(emulator_struct *e, gsl_matrix *points)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	free(en->grad_q);
+	en->grad_q = pack_matrix(points);
+	int rc = gpemu_predict_var_grad_enqueue(en->ctx, (int)points->size1, en->grad_q);
+	if (rc) die(en->ctx, rc, "emulate_points_grad");
+}
+
+void emulate_points_grad_collect(emulator_struct *e, int npoints, double *mean, double *variance, double *grad_mean, double *grad_variance)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	if (!mean && !variance && !grad_mean && !grad_variance) gpemu_host_fatal("emulate_points_grad: every output is NULL\n");
+	if (!en->grad_q) gpemu_host_fatal("emulate_points_grad_collect: nothing was enqueued\n");
+	/* (the device entry requires its gradient output: a scratch row when the caller does not want it) */
+	double *gv = grad_variance ? grad_variance : (double *)malloc(sizeof(double) * (size_t)npoints * en->d);
+	int rc = gpemu_predict_var_grad_collect(en->ctx, npoints, mean, variance, gv);
+	if (!grad_variance) free(gv);
+	if (!rc && grad_mean) rc = gpemu_predict_mean_grad(en->ctx, npoints, en->grad_q, NULL, grad_mean);
+	free(en->grad_q);
+	en->grad_q = NULL;
+	if (rc) die(en->ctx, rc, "emulate_points_grad");
+}
+
+void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *variance, double *grad_mean, double *grad_variance)
+{
+	if (!mean && !variance && !grad_mean && !grad_variance) gpemu_host_fatal("emulate_points_grad: every output is NULL\n");
+	if (!variance && !grad_variance) {
+		/* neither the variance nor its gradient: the mean-gradient sweep alone answers, without the N^2 products */
+		double *gm = grad_mean ? grad_mean : (double *)malloc(sizeof(double) * points->size1 * points->size2);
+		emulate_points_mean_grad(e, points, mean, gm);
+		if (!grad_mean) free(gm);
+		return;
+	}
+	emulate_points_grad_enqueue(e, points);
+	emulate_points_grad_collect(e, (int)points->size1, mean, variance, grad_mean, grad_variance);
 }
 
 /* leave-one-out at every training point (gpemu_loo) */

@@ -252,6 +252,16 @@ void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean);
 void emulate_points_mean_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *grad);
 void emulate_points_mean_grad_enqueue(emulator_struct *e, gsl_matrix *points);
 void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *mean, double *grad);
+/* mean, variance and the gradients of both with respect to the query point: grad_mean and grad_variance are npoints x
+ * nparams row-major.  Any output may be NULL, but not all of them.  mean, variance and grad_variance come from
+ * gpemu_predict_var_grad (gpemu.h: two N^2 products, the batch buffers of emulate_points, and on the first call a transposed
+ * copy of L^-1 of 8 N (N + 64) bytes), grad_mean from gpemu_predict_mean_grad; with variance and grad_variance both NULL
+ * emulate_points_grad is emulate_points_mean_grad.  The pair: enqueue starts the variance-gradient batch and returns, collect
+ * waits for it and then runs the (much shorter) mean-gradient sweep if grad_mean is asked for.  Errors end in
+ * gpemu_host_fatal. */
+void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *variance, double *grad_mean, double *grad_variance);
+void emulate_points_grad_enqueue(emulator_struct *e, gsl_matrix *points);
+void emulate_points_grad_collect(emulator_struct *e, int npoints, double *mean, double *variance, double *grad_mean, double *grad_variance);
 /* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
  * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
 void emulate_loo(emulator_struct *e, double *mean, double *variance);
@@ -282,6 +292,12 @@ void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_
  * space grad_Y[t][j] = sum_c evecs[t][c] sqrt(evals[c]) grad_c[j], the back-projection of multivar_support.c:118-137 without
  * the training mean */
 void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *grad_out);
+/* means, variances (npoints x nr or nt) and their gradients (npoints x (nr or nt) x nparams); any output may be NULL, but
+ * not all.  In observable space the mean and its gradient as in emulate_points_multi_mean_grad, the variance and its gradient
+ * by the reference's variance rule: grad_var_Y[t][j] = sum_c evecs[t][c]^2 evals[c] grad_var_c[j].  All components are started
+ * before the first is collected. */
+void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out,
+                               double *grad_mean_out, double *grad_var_out);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);

@@ -558,6 +558,65 @@ void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int
 	free(mp); free(mc); free(gp); free(gc);
 }
 
+/* means, variances and the gradients of both: every component's variance-gradient batch is started before the first is
+ * collected (its mean-gradient sweep, when asked for, runs at its collect); observable space by the reference's two rules
+ * (multivar_support.c:118-137): factor evecs sqrt(evals) on the mean and its gradient, evecs^2 evals on the variance and its */
+void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out,
+                               double *grad_mean_out, double *grad_var_out)
+{
+	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt, d = (int)points->size2;
+	const multi_modelstruct *m = emu->model;
+	if (!mean_out && !var_out && !grad_mean_out && !grad_var_out) gpemu_host_fatal("emulate_points_multi_grad: every output is NULL\n");
+	if (!var_out && !grad_var_out) {                     /* no variance asked for: the mean-gradient sweeps alone */
+		double *g = grad_mean_out ? grad_mean_out : (double *)malloc(sizeof(double) * (size_t)np * (pca_space ? nr : nt) * d);
+		emulate_points_multi_mean_grad(emu, points, pca_space, mean_out, g);
+		if (!grad_mean_out) free(g);
+		return;
+	}
+	const size_t ns = (size_t)np * nr, ng = ns * d;
+	double *mp = (double *)malloc(sizeof(double) * ns), *vp = (double *)malloc(sizeof(double) * ns);
+	double *gm = (double *)malloc(sizeof(double) * ng), *gv = (double *)malloc(sizeof(double) * ng);
+	double *mc = (double *)malloc(sizeof(double) * (size_t)np), *vc = (double *)malloc(sizeof(double) * (size_t)np);
+	double *gmc = (double *)malloc(sizeof(double) * (size_t)np * d), *gvc = (double *)malloc(sizeof(double) * (size_t)np * d);
+	for (int c = 0; c < nr; c++) emulate_points_grad_enqueue(emu->emu_struct_array[c], points);
+	for (int c = 0; c < nr; c++) {
+		emulate_points_grad_collect(emu->emu_struct_array[c], np, mc, vc, grad_mean_out ? gmc : NULL, gvc);
+		for (int q = 0; q < np; q++) {
+			mp[(size_t)q * nr + c] = mc[q];
+			vp[(size_t)q * nr + c] = vc[q];
+			if (grad_mean_out) memcpy(gm + ((size_t)q * nr + c) * d, gmc + (size_t)q * d, sizeof(double) * (size_t)d);
+			memcpy(gv + ((size_t)q * nr + c) * d, gvc + (size_t)q * d, sizeof(double) * (size_t)d);
+		}
+	}
+	if (pca_space) {
+		if (mean_out) memcpy(mean_out, mp, sizeof(double) * ns);
+		if (var_out) memcpy(var_out, vp, sizeof(double) * ns);
+		if (grad_mean_out) memcpy(grad_mean_out, gm, sizeof(double) * ng);
+		if (grad_var_out) memcpy(grad_var_out, gv, sizeof(double) * ng);
+	} else {
+		for (int q = 0; q < np; q++)
+			for (int i = 0; i < nt; i++) {
+				double ms = 0.0, vs = 0.0;
+				double *gmo = grad_mean_out ? grad_mean_out + ((size_t)q * nt + i) * d : NULL;
+				double *gvo = grad_var_out ? grad_var_out + ((size_t)q * nt + i) * d : NULL;
+				for (int j = 0; j < d; j++) { if (gmo) gmo[j] = 0.0; if (gvo) gvo[j] = 0.0; }
+				for (int c = 0; c < nr; c++) {
+					const double u = gsl_matrix_get(m->pca_evecs_r, i, c), lam = gsl_vector_get(m->pca_evals_r, c);
+					const double f = u * sqrt(lam), f2 = pow(u, 2.0) * lam;
+					ms += f * mp[(size_t)q * nr + c];
+					vs += f2 * vp[(size_t)q * nr + c];
+					for (int j = 0; j < d; j++) {
+						if (gmo) gmo[j] += f * gm[((size_t)q * nr + c) * d + j];
+						if (gvo) gvo[j] += f2 * gv[((size_t)q * nr + c) * d + j];
+					}
+				}
+				if (mean_out) mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
+				if (var_out) var_out[(size_t)q * nt + i] = vs;
+			}
+	}
+	free(mp); free(vp); free(gm); free(gv); free(mc); free(vc); free(gmc); free(gvc);
+}
+
 /* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
