@@ -383,6 +383,45 @@ typedef struct gpemu_gemm_launch_args {
 	int fa, fa_c0;
 } gpemu_gemm_launch_args;
 int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_gemm_launch_args *args, int *info_out);
+/* ONE call of the Cholesky leaf launchers (the 64-column kernels of every factorisation) on a matrix inside one host
+ * buffer (the arena), element offset off, row stride ld; nbatch > 1: that many matrices, bstride elements apart.
+ *   GPEMU_LEAF_FACTOR        the 64x64 block at (c0, c0) leaves as its Cholesky factor: the lower triangle is L, the upper
+ *                            16x16 blocks (0,1) (1,2) (2,3) (0,3) of it hold the inverses of L's diagonal 16x16 blocks
+ *                            0, 1, 2, 3 (each a full 16x16 block, zero above its diagonal); blocks (0,2) (1,3) and the strict
+ *                            upper triangles of the four diagonal 16x16 blocks are neither read nor written.  m_below = 0.
+ *   GPEMU_LEAF_SOLVE         X L^T = B in place on rows c0+64 .. c0+64+m_below-1 of columns c0 .. c0+63, L the factored
+ *                            block at (c0, c0).  staged: 1 / 0 = rows move as whole 512-byte pieces / as doubles, -1 = the
+ *                            launch-size rule; pre: 1 = the diagonal inverses are read from the block's upper part, 0 = they
+ *                            are computed from L (the upper part is not read).  c0b >= 0: one more workgroup solves the 64
+ *                            rows under the factored block at (c0b, c0b), columns c0b .. c0b+63, the same way.
+ *   GPEMU_LEAF_FACTOR_SOLVE  both, the plain leaf.
+ *   GPEMU_LEAF_PAIR          the first block of a 128-column pair, m_below a multiple of 64: rows 64.. of the m_below rows
+ *                            under the factored block (with its inverses) at (c0, c0) are solved as above; the FIRST 64 rows
+ *                            of columns c0 .. c0+63 keep their bits (a later solve with c0b = c0 stores them); columns
+ *                            c0+64 .. c0+127 of all m_below rows become C2 - X1 X0^T, X0 the solved first 64 rows.  fa: the
+ *                            first 64 rows of those columns leave as the factor of the updated block, as GPEMU_LEAF_FACTOR
+ *                            leaves it; without fa everything above that block's diagonal is unspecified.
+ * A pivot <= 0 or NaN at row r (1-based) of the block being factored gives info_out[b] = c0 + r (the pair's tile:
+ * c0 + 64 + r) for matrix b, the first such row; otherwise 0.  Everything in a matrix whose pivot failed is unspecified.
+ * Alignment contract: the staged solve and the pair move 16-byte pieces of rows, so off, ld, bstride, c0 and c0b must be
+ * even (and the device allocation is 16-byte aligned).
+ * The whole arena is uploaded, and downloaded after the launch; the device buffers are the call's own.
+ * GPEMU_ERR_ARG, before anything runs: a NULL pointer; op, staged, pre, fa or c0b outside their values; nbatch outside
+ * 0..GPEMU_MAX_BATCH; the pair with m_below < 64 or no multiple of 64; a solve with m_below < 1; the factor alone with
+ * m_below != 0; an odd off, ld, bstride, c0 or c0b; c0b with an op that launches no solve; fa without the pair; columns
+ * beyond ld; or any matrix whose footprint -- rows c0 .. c0+64+m_below-1 of columns c0 .. c0+63 (pair: .. c0+127), and rows
+ * c0b .. c0b+127 of columns c0b .. c0b+63 -- leaves [0, arena_len).  info_out: max(nbatch, 1) words. */
+#define GPEMU_LEAF_FACTOR 0
+#define GPEMU_LEAF_SOLVE 1
+#define GPEMU_LEAF_FACTOR_SOLVE 2
+#define GPEMU_LEAF_PAIR 3
+typedef struct gpemu_leaf_launch_args {
+	long off, ld, bstride;
+	int nbatch, c0, m_below;
+	int op;
+	int staged, pre, c0b, fa;
+} gpemu_leaf_launch_args;
+int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_leaf_launch_args *args, int *info_out);
 /* The gradient's reduction kernels -- beta on the device, alpha, the tile sums of the literal or the exact form, their
  * second-stage sums: everything a value+gradient batch runs behind its C^-1 corners, through the routine production calls
  * -- ONCE on caller-chosen operands, for the model (design, covariance function) and the mode the context holds, nb

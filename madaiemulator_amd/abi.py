@@ -34,6 +34,15 @@ class GemmLaunchArgs(C.Structure):
                                         "kend_off", "nbatch", "ksplit", "force_cfg", "fa", "fa_c0")])
 
 
+class LeafLaunchArgs(C.Structure):
+    """gpemu_leaf_launch_args of include/gpemu.h"""
+    _fields_ = ([(f, C.c_long) for f in ("off", "ld", "bstride")] +
+                [(f, C.c_int) for f in ("nbatch", "c0", "m_below", "op", "staged", "pre", "c0b", "fa")])
+
+
+LEAF_FACTOR, LEAF_SOLVE, LEAF_FACTOR_SOLVE, LEAF_PAIR = 0, 1, 2, 3
+
+
 class GradSumsArgs(C.Structure):
     """gpemu_grad_sums_args of include/gpemu.h"""
     _fields_ = ([(f, _dp) for f in ("thetas", "a", "z", "gram", "alpha_out", "beta_out", "part_out", "sums_out")] +
@@ -110,6 +119,7 @@ SYMBOLS = {
     "gpemu_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gpemu_test_gemm_nt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp]),
     "gpemu_test_gemm_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(GemmLaunchArgs), _ip]),
+    "gpemu_test_leaf_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(LeafLaunchArgs), _ip]),
     "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
@@ -533,6 +543,16 @@ class Context:
         a = GemmLaunchArgs(**{k: float(v) if k == "alpha" else int(v) for k, v in args.items()})
         info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
         self._chk(self.L.gpemu_test_gemm_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
+        return out, info
+
+    def test_leaf_launch(self, arena, **args):
+        """one call of the Cholesky leaf launchers on a matrix inside `arena` (gpemu_test_leaf_launch; args: the fields of
+        LeafLaunchArgs, defaults staged = -1, pre = 1, c0b = -1) -> (the arena after the launch, info word per matrix).
+        GpemuError(ERR_ARG) for a refused launch."""
+        out = _a(arena).ravel().copy()
+        a = LeafLaunchArgs(**{k: int(v) for k, v in dict(dict(staged=-1, pre=1, c0b=-1), **args).items()})
+        info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
+        self._chk(self.L.gpemu_test_leaf_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
         return out, info
 
     def test_grad_sums(self, thetas, a, z, gram=None, form=0, gram_dist=-1, clamp=-1):

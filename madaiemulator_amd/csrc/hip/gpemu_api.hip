@@ -2340,6 +2340,72 @@ extern "C" int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_
 	return GPEMU_OK;
 }
 
+// One launch_leaf / launch_leaf_pair call -- the launchers production calls, unchanged -- with caller-chosen arguments on a
+// matrix (or a lock-step batch of them, bstride elements apart) inside ONE host buffer, the arena: uploads the whole arena,
+// launches, downloads the whole arena, so that a test sees every element the launch must and must not have touched.
+//   GPEMU_LEAF_FACTOR        leaf_factor_kernel on the 64x64 block at (c0, c0)                       (m_below = 0)
+//   GPEMU_LEAF_SOLVE         leaf_solve_kernel<staged, pre> on the m_below rows under a FACTORED block (skip_factor)
+//   GPEMU_LEAF_FACTOR_SOLVE  both, the plain leaf
+//   GPEMU_LEAF_PAIR          leaf_pair_kernel: solve of columns [c0, c0+64) and K = 64 update of [c0+64, c0+128), fa: with
+//                            the factor-ahead tile
+// What the kernels may address is computed here first and anything outside [0, arena_len) is refused: per matrix rows
+// c0 .. c0+64+m_below-1 of columns c0 .. c0+63 (the pair: .. c0+127; the row clamps of the solve stay inside m_below), and
+// with c0b >= 0 rows c0b .. c0b+127 of columns c0b .. c0b+63.  The staged solve and the pair move 16-byte pieces of rows:
+// off, ld, bstride, c0 and c0b must be even (production: Np and the strides are multiples of 64).
+// Info: one word per matrix, INFO_NONE before the launch, decoded by pivot_info afterwards.
+extern "C" int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_leaf_launch_args *p, int *info_out)
+{
+	if (!ctx || !arena || !p || !info_out) return GPEMU_ERR_ARG;
+	constexpr long DIM_MAX = 1L << 20, LD_MAX = 1L << 24, LEN_MAX = 1L << 32, STRIDE_MAX = 1L << 32;   // no product below leaves 63 bits
+	if (arena_len < 1 || arena_len > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: arena length");
+	if (p->op != GPEMU_LEAF_FACTOR && p->op != GPEMU_LEAF_SOLVE && p->op != GPEMU_LEAF_FACTOR_SOLVE && p->op != GPEMU_LEAF_PAIR)
+		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: op");
+	if (p->staged < -1 || p->staged > 1 || (p->pre != 0 && p->pre != 1) || (p->fa != 0 && p->fa != 1) || p->c0b < -1 || p->c0b > DIM_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: staged is -1/0/1, pre and fa are 0/1, c0b is -1 or a column");
+	if (p->nbatch < 0 || p->nbatch > GPEMU_MAX_BATCH) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: nbatch");
+	if (p->off < 0 || p->off > arena_len || p->ld < 1 || p->ld > LD_MAX || p->c0 < 0 || p->c0 > DIM_MAX || p->m_below < 0 ||
+	    p->m_below > DIM_MAX || std::labs(p->bstride) > STRIDE_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: off, ld, c0, m_below, bstride");
+	const bool pair = p->op == GPEMU_LEAF_PAIR, solves = p->op == GPEMU_LEAF_SOLVE || p->op == GPEMU_LEAF_FACTOR_SOLVE;
+	if (p->op == GPEMU_LEAF_FACTOR && p->m_below != 0) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the factor alone takes m_below = 0");
+	if (pair && (p->m_below < LEAF || p->m_below % LEAF)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the pair takes m_below = 64, 128, ...");
+	if (solves && p->m_below < 1) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: a solve needs m_below >= 1");
+	if ((p->off & 1) || (p->ld & 1) || (p->bstride & 1) || (p->c0 & 1) || (p->c0b >= 0 && (p->c0b & 1)))
+		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: off, ld, bstride, c0 and c0b must be even (16-byte row pieces)");
+	if (p->c0b >= 0 && !solves) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: c0b needs an op that launches the solve");
+	if (p->fa && !pair) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: fa belongs to the pair");
+	const int width = pair ? 2 * LEAF : LEAF;
+	if (p->c0 + width > p->ld || (p->c0b >= 0 && p->c0b + LEAF > p->ld)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the columns leave the row");
+	const int nblk = std::max(p->nbatch, 1);
+	// smallest and largest element index over all matrices (the stride may have either sign)
+	auto inside = [&](long first, long last) {
+		const long s0 = 0, s1 = (long)(nblk - 1) * p->bstride;
+		return p->off + first + std::min(s0, s1) >= 0 && p->off + last + std::max(s0, s1) < arena_len;
+	};
+	if (!inside((long)p->c0 * p->ld + p->c0, (long)(p->c0 + LEAF + p->m_below - 1) * p->ld + p->c0 + width - 1) ||
+	    (p->c0b >= 0 && !inside((long)p->c0b * p->ld + p->c0b, (long)(p->c0b + 2 * LEAF - 1) * p->ld + p->c0b + LEAF - 1)))
+		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the launch would address memory outside the arena");
+
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dArena;
+	DevBuf<int> dInfo;
+	HIPCHK(ctx, dArena.grow((size_t)arena_len));
+	HIPCHK(ctx, dInfo.grow((size_t)nblk));
+	std::vector<int> inf((size_t)nblk, INFO_NONE);
+	HIPCHK(ctx, hipMemcpyAsync(dArena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dInfo, inf.data(), (size_t)nblk * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	double *T = dArena + p->off;
+	if (pair) HIPCHK(ctx, launch_leaf_pair(ctx->stream, T, p->ld, p->c0, p->m_below, dInfo, nullptr, p->nbatch, p->bstride, p->fa != 0));
+	else HIPCHK(ctx, launch_leaf(ctx->stream, T, p->ld, p->c0, p->m_below, dInfo, nullptr, nullptr, p->nbatch, p->bstride,
+	                             p->op == GPEMU_LEAF_SOLVE, p->staged, p->pre != 0, p->c0b));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(arena, dArena, (size_t)arena_len * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(inf.data(), dInfo, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (int b = 0; b < nblk; b++) info_out[b] = pivot_info(inf[(size_t)b]);
+	return GPEMU_OK;
+}
+
 // The gradient reductions behind the corners (grad_sums_of_corners: the routine grad_enqueue_chunk calls) ONCE, on corners,
 // [y|H] columns and Gram matrices the caller chose, for the model and mode the context holds.  The corners are laid out on
 // the host as production's S is -- side Np + Rp, S[Rp+i][Rp+j] = a[i][j] for j <= i, S[Rp+i][0 .. nreg] = z[i] -- and every
