@@ -462,6 +462,47 @@ int gpemu_test_potrf(gpemu_ctx *ctx, int n, double *a, int *info);
  * staging kernel, lower tiles only) and copies the N x N block of matrix b to out[N*N] without factorising; tiles
  * strictly above the diagonal are not written by that path. */
 int gpemu_test_staged_matrix(gpemu_ctx *ctx, int nb, const double *thetas, int nthetas, int b, double *out);
+/* ONE call of a covariance fill launcher -- the launchers every likelihood, gradient and prediction starts from, unchanged --
+ * for the model (design, its centred copy, covariance function) and the mode the context holds, into the host buffer out.
+ * Np = N rounded up to 64; every region has Np columns and row stride Np.
+ *   GPEMU_FILL_STAGE  the staging launch of a lock-step batch, lower tiles with identity padding: nb matrices with nb theta
+ *                     vectors (nthetas apart); per matrix (Np + Rp + guard) rows, one matrix after the other.  Rows [0, Np):
+ *                     the 64 x 64 tiles (tr, tc <= tr) hold cov(x_i, x_j) for i, j < N, 1 on the diagonal beyond N and 0
+ *                     elsewhere; tiles strictly above the diagonal are not written.  Rows [Np, Np + Rp): a copy of the
+ *                     right-hand-side rows rrows (Rp x Np, row stride Np): rstride = 0 the same block for every matrix,
+ *                     otherwise matrix b takes rrows + b * rstride (0 <= rstride <= 4 * Rp * Np); rrows must hold
+ *                     (nb - 1) * rstride + Rp * Np doubles, all of which are read.  Rp = 0: the context's 64; other values up to 256 are
+ *                     staged the same way (in 64-row blocks of which rows >= Rp are not written).  The guard rows are not
+ *                     written.  form: -1 = production's rule (the Gram-form kernel if every theta is admitted to the Gram
+ *                     form, else the batch kernel, each matrix in its own form), 0 = the batch kernel, every matrix from
+ *                     coordinate differences, 1 = the Gram-form kernel, 2 = the batch kernel, each matrix in its own form.
+ *   GPEMU_FILL_KVEC   k-vectors of the M query rows xq (M x d) with the 1e-10 clamp: an Mp x Np block (Mp = M rounded up to
+ *                     64), rows >= M and columns >= N zero, then guard rows that are not written.  nb = 1.  form: 1 = the
+ *                     Gram-form kernel, 0 = the difference form, -1 = the prediction sweep's rule.
+ *   GPEMU_FILL_FULL   the full matrix as gpemu_cov_matrix fills it (difference form, both triangles, zero padding): Np x Np,
+ *                     then guard rows that are not written.  nb = 1, form = 0.
+ * A theta is admitted to the Gram form while norm2 = sum_k (w_k * half range_k)^2 <= 16 (w_k the coordinate scale of its
+ * length scale).  Per matrix, form_out[b] = 1 / 0: its elements came from the Gram form / from differences, and
+ * norm2_out[b] = that norm2 (NaN for a design without a centred copy).
+ * The whole region (out_len >= nb * rows per matrix * Np doubles) is uploaded before the launch and downloaded after it,
+ * so the caller's prefill shows what was written.  Uses device buffers of its own: the context's factorisation workspace,
+ * prediction state and result ring are not touched.
+ * GPEMU_ERR_ARG, before anything runs: a NULL pointer (rrows for the staging, xq for k-vectors, thetas, out, form_out,
+ * norm2_out); op or form outside their values; nb outside 1..GPEMU_MAX_BATCH, or not 1 for k-vectors and the full matrix;
+ * nthetas too small for the covariance function; form = 1 with a theta that is not admitted or a design without a centred
+ * copy; M < 1; guard or Rp negative or out of range; rstride outside 0 .. 4 * Rp * Np; out_len shorter than the footprint. */
+#define GPEMU_FILL_STAGE 0
+#define GPEMU_FILL_KVEC 1
+#define GPEMU_FILL_FULL 2
+typedef struct gpemu_fill_launch_args {
+	const double *thetas, *rrows, *xq;
+	double *out, *norm2_out;
+	int *form_out;
+	long out_len, rstride;
+	int op, form, nb, nthetas;
+	int M, Rp, guard;
+} gpemu_fill_launch_args;
+int gpemu_test_fill_launch(gpemu_ctx *ctx, const gpemu_fill_launch_args *args);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

@@ -49,6 +49,16 @@ class GradSumsArgs(C.Structure):
                 [(f, C.c_int) for f in ("nb", "nthetas", "form", "gram_dist", "clamp")])
 
 
+class FillLaunchArgs(C.Structure):
+    """gpemu_fill_launch_args of include/gpemu.h"""
+    _fields_ = ([(f, _dp) for f in ("thetas", "rrows", "xq", "out", "norm2_out")] + [("form_out", _ip)] +
+                [(f, C.c_long) for f in ("out_len", "rstride")] +
+                [(f, C.c_int) for f in ("op", "form", "nb", "nthetas", "M", "Rp", "guard")])
+
+
+FILL_STAGE, FILL_KVEC, FILL_FULL = 0, 1, 2
+
+
 # every symbol include/gpemu.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gpemu_ctx_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -121,6 +131,7 @@ SYMBOLS = {
     "gpemu_test_gemm_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(GemmLaunchArgs), _ip]),
     "gpemu_test_leaf_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(LeafLaunchArgs), _ip]),
     "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
+    "gpemu_test_fill_launch": (C.c_int, [C.c_void_p, C.POINTER(FillLaunchArgs)]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
     "gpemu_test_potrf": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
@@ -574,6 +585,36 @@ class Context:
                             nthetas=th.shape[1], form=int(form), gram_dist=int(gram_dist), clamp=int(clamp))
         self._chk(self.L.gpemu_test_grad_sums(self.h, C.byref(args)))
         return out
+
+    def test_fill_launch(self, op, thetas, out, form=-1, rrows=None, rstride=0, Rp=64, guard=0, Xq=None):
+        """one call of a covariance fill launcher for the context's model (gpemu_test_fill_launch): `out` is the caller's
+        prefilled region (STAGE: nb x (Np + Rp + guard) x Np, KVEC: (Mp + guard) x Np, FULL: (Np + guard) x Np) -> (the
+        region after the launch, form per matrix, norm2 per matrix).  Rp is always passed explicitly (production's is 64), so
+        the length the entry reads from rrows, (nb - 1) * rstride + Rp * Np, is checked here against what was given.
+        GpemuError(ERR_ARG) for a refused launch; the exception carries the region as the entry left it (`region`)."""
+        th = _a(thetas)
+        th = th.reshape(-1, th.shape[-1])
+        nb = th.shape[0]
+        res = _a(out).copy()
+        rr = None if rrows is None else _a(rrows)
+        xq = None if Xq is None else _a(Xq).reshape(-1, self.d)
+        if Rp == 0:
+            raise ValueError("Rp = 0 (the context's own) is not offered here: pass the number of rows")
+        if rr is not None and op == FILL_STAGE and Rp > 0 and rstride >= 0:
+            need = (nb - 1) * int(rstride) + int(Rp) * ((self.N + 63) // 64 * 64)
+            if rr.size < need:
+                raise ValueError(f"rrows holds {rr.size} values, the launch reads {need}")
+        form_out, norm2 = np.full(nb, -1, dtype=np.int32), np.full(nb, np.nan)
+        args = FillLaunchArgs(thetas=_p(th), rrows=None if rr is None else _p(rr), xq=None if xq is None else _p(xq),
+                              out=_p(res), norm2_out=_p(norm2), form_out=form_out.ctypes.data_as(_ip), out_len=res.size,
+                              rstride=int(rstride), op=int(op), form=int(form), nb=nb, nthetas=th.shape[1],
+                              M=0 if xq is None else xq.shape[0], Rp=int(Rp), guard=int(guard))
+        try:
+            self._chk(self.L.gpemu_test_fill_launch(self.h, C.byref(args)))
+        except GpemuError as e:
+            e.region = res
+            raise
+        return res, form_out, norm2
 
     def trace_dump(self, path):
         self._chk(self.L.gpemu_trace_dump(self.h, str(path).encode()))

@@ -440,8 +440,10 @@ static int nthetas_for(const gpemu_ctx *ctx) { return ctx->kind == GPEMU_POWEREX
 
 // theta layout: modelstruct.c:300-308.  pow-exp exponentiates everything
 // (emulator.c:115-123); the Matern kernels take amp and nugget raw (:355-357).
-static int make_cov_params(gpemu_ctx *ctx, const double *thetas, int nthetas, CovParams *p)
+// norm2_out (optional): the admission rule's sum_k (w_k halfrange_k)^2, NaN for a design without a centred copy
+static int make_cov_params(gpemu_ctx *ctx, const double *thetas, int nthetas, CovParams *p, double *norm2_out = nullptr)
 {
+	if (norm2_out) *norm2_out = NAN;
 	if (!thetas) return fail(ctx, GPEMU_ERR_ARG, "thetas is NULL");
 	if (nthetas < nthetas_for(ctx)) return fail(ctx, GPEMU_ERR_ARG, "nthetas too small for this covariance function");
 	memset(p, 0, sizeof *p);
@@ -478,6 +480,7 @@ static int make_cov_params(gpemu_ctx *ctx, const double *thetas, int nthetas, Co
 			const double t = ctx->xhalf[k] * p->w[ctx->kind == GPEMU_POWEREXP ? k : 0];
 			norm2 += t * t;
 		}
+		if (norm2_out) *norm2_out = norm2;
 		// the candidates of the nugget rule in a Gram-form distance: below the difference form's bound plus the form's own
 		// cancellation error (a few ulp of |x'|^2 + |y'|^2 <= 2 norm2, 64 ulp allowed), whatever the length scales
 		p->cand_w = p->cand + 64.0 * 2.220446049250313e-16 * (2.0 * norm2 + 1.0);
@@ -2511,6 +2514,89 @@ extern "C" int gpemu_test_staged_matrix(gpemu_ctx *ctx, int nb, const double *th
 	const int N = ctx->N, Np = ctx->Np;
 	HIPCHK(ctx, hipMemcpy2DAsync(out, (size_t)N * sizeof(double), ctx->dT + (size_t)b * ctx->T_stride, (size_t)Np * sizeof(double),
 	                             (size_t)N * sizeof(double), N, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// ONE call of a covariance fill launcher -- the launchers production calls, unchanged -- for the model the context holds
+// (design, centred copy, covariance function, mode) into a host buffer of the caller's: the whole output region is
+// uploaded, the launch runs, the whole region is downloaded, so that the caller's prefill shows what was and was not written.
+//   GPEMU_FILL_STAGE  launch_cov_stage_batch as stage_matrices calls it (FILL_LOWER | FILL_IDENT_PAD): per matrix
+//                     (Np + Rp + guard) rows of Np columns, the matrices that many rows apart
+//   GPEMU_FILL_KVEC   M query rows to an Mp x Np block (Mp = M rounded up to 64), guard rows behind it
+//   GPEMU_FILL_FULL   the 2-D launch_cov_fill with mode 0 as gpemu_cov_matrix runs it: Np x Np, guard rows behind it
+// What the kernels may address is fixed by these shapes: lower tiles of rows [0, Np), rows [Np, Np + Rp) of a staged matrix,
+// all of an Mp x Np or Np x Np block -- the footprint out_len has to cover, checked before anything runs.
+// All device buffers are the call's own; of the context it reads the design (dX, dXg, dMid), the model's sizes, the mode
+// and the schedule switches, and uses the stream.
+extern "C" int gpemu_test_fill_launch(gpemu_ctx *ctx, const gpemu_fill_launch_args *p)
+{
+	if (!ctx || !p) return GPEMU_ERR_ARG;
+	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
+	if (p->op != GPEMU_FILL_STAGE && p->op != GPEMU_FILL_KVEC && p->op != GPEMU_FILL_FULL) return fail(ctx, GPEMU_ERR_ARG, "fill_launch: op");
+	const bool stage = p->op == GPEMU_FILL_STAGE, kvec = p->op == GPEMU_FILL_KVEC;
+	if (!p->thetas || !p->out || !p->form_out || !p->norm2_out || (stage && !p->rrows) || (kvec && !p->xq))
+		return fail(ctx, GPEMU_ERR_ARG, "fill_launch: NULL pointer");
+	if (p->nb < 1 || p->nb > GPEMU_MAX_BATCH || (!stage && p->nb != 1))
+		return fail(ctx, GPEMU_ERR_ARG, "fill_launch: batch size must be 1..GPEMU_MAX_BATCH (1 for k-vectors and the full matrix)");
+	if (p->form < -1 || p->form > (stage ? 2 : (kvec ? 1 : 0)) || (!stage && !kvec && p->form != 0))
+		return fail(ctx, GPEMU_ERR_ARG, "fill_launch: form is -1/0/1/2 for the staging, -1/0/1 for k-vectors, 0 for the full matrix");
+	if (kvec && p->M < 1) return fail(ctx, GPEMU_ERR_ARG, "fill_launch: M < 1");
+	constexpr long ROWS_MAX = 1L << 20;
+	if (p->guard < 0 || p->guard > ROWS_MAX || p->Rp < 0 || p->Rp > 4 * LEAF || p->M > ROWS_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "fill_launch: guard, Rp or M out of range");
+	const int nb = p->nb, nthetas = p->nthetas, N = ctx->N, d = ctx->d, Np = ctx->Np;
+	if (nthetas < nthetas_for(ctx) || nthetas > GPEMU_MAX_PARAMS + 2) return fail(ctx, GPEMU_ERR_ARG, "fill_launch: nthetas");
+	const int Rp = stage ? (p->Rp ? p->Rp : ctx->Rp) : 0, Mp = kvec ? round_up(p->M, LEAF) : 0;
+	const long rows_each = (stage ? (long)Np + Rp : (kvec ? (long)Mp : (long)Np)) + p->guard;
+	const long bstride = rows_each * Np, footprint = bstride * nb;
+	// (the caller's rrows holds (nb - 1) * rstride + Rp * Np doubles: the stride is held to a few blocks so that a wrong one cannot ask for much)
+	if (stage && (p->rstride < 0 || p->rstride > 4L * Rp * Np)) return fail(ctx, GPEMU_ERR_ARG, "fill_launch: rstride must be 0 .. 4 * Rp * Np");
+	if (p->out_len < footprint) return fail(ctx, GPEMU_ERR_ARG, "fill_launch: the output buffer is shorter than the launch's footprint");
+	std::vector<CovParams> ps((size_t)nb);
+	for (int b = 0; b < nb; b++)
+		if (const int rc = make_cov_params(ctx, p->thetas + (size_t)b * nthetas, nthetas, &ps[(size_t)b], p->norm2_out + b)) return rc;
+	bool all_gram = ctx->dXg != nullptr;
+	for (int b = 0; b < nb; b++) all_gram = all_gram && ps[(size_t)b].gram;
+	if (p->form == 1 && (!all_gram || !ctx->dXg || !ctx->dMid))
+		return fail(ctx, GPEMU_ERR_ARG, "fill_launch: the Gram form needs a centred design and hyper-parameters the admission rule accepts");
+	if (p->form == 0)
+		for (auto &q : ps) { q.gram = 0; q.cand_g = 0.0; }
+	const bool gram_kernel = stage ? (p->form == 1 || (p->form == -1 && all_gram))
+	                               : (kvec && (p->form == 1 || (p->form == -1 && ps[0].gram && ctx->sched.kvec_gram && ctx->dXg && ctx->dMid)));
+	for (int b = 0; b < nb; b++)
+		p->form_out[b] = stage ? ((gram_kernel || (ps[(size_t)b].gram && ctx->dXg)) ? 1 : 0) : (gram_kernel ? 1 : 0);
+
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dOut, dRr, dQ;
+	DevBuf<CovParams> dPp;
+	const size_t rlen = stage ? (size_t)(nb - 1) * (size_t)p->rstride + (size_t)Rp * Np : 0;
+	// every allocation first; from the first copy on nothing returns before the stream has been waited for (the copies read
+	// ps, a vector of this frame, and the caller's buffers)
+	HIPCHK(ctx, dOut.grow((size_t)footprint));
+	if (stage) {
+		HIPCHK(ctx, dRr.grow(rlen));
+		HIPCHK(ctx, dPp.grow((size_t)nb));
+	} else if (kvec)
+		HIPCHK(ctx, dQ.grow((size_t)p->M * d));
+	hipError_t e = hipMemcpyAsync(dOut, p->out, (size_t)footprint * 8, hipMemcpyHostToDevice, ctx->stream);
+	if (stage) {
+		if (e == hipSuccess) e = hipMemcpyAsync(dRr, p->rrows, rlen * 8, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipMemcpyAsync(dPp, ps.data(), (size_t)nb * sizeof(CovParams), hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess)
+			e = launch_cov_stage_batch(ctx->stream, dOut, Np, bstride, nb, ctx->dX, N, Np, d, dPp, FILL_LOWER | FILL_IDENT_PAD, dRr, Rp,
+			                           ctx->dXg, gram_kernel, ctx->kind, p->rstride);
+	} else if (kvec) {
+		if (e == hipSuccess) e = hipMemcpyAsync(dQ, p->xq, (size_t)p->M * d * 8, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess)
+			e = gram_kernel ? launch_cov_kvec_gram(ctx->stream, dOut, Np, dQ, p->M, Mp, ctx->dX, ctx->dXg, ctx->dMid, N, Np, d, ps[0])
+			                : launch_cov_fill(ctx->stream, dOut, Np, dQ, p->M, Mp, ctx->dX, N, Np, d, ps[0], FILL_CLAMP);
+	} else if (e == hipSuccess)
+		e = launch_cov_fill(ctx->stream, dOut, Np, ctx->dX, N, Np, ctx->dX, N, Np, d, ps[0], 0);
+	const hipError_t es = hipStreamSynchronize(ctx->stream);
+	HIPCHK(ctx, e);
+	HIPCHK(ctx, es);
+	HIPCHK(ctx, hipMemcpyAsync(p->out, dOut, (size_t)footprint * 8, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
