@@ -401,6 +401,11 @@ int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const 
  *                            c0+64 .. c0+127 of all m_below rows become C2 - X1 X0^T, X0 the solved first 64 rows.  fa: the
  *                            first 64 rows of those columns leave as the factor of the updated block, as GPEMU_LEAF_FACTOR
  *                            leaves it; without fa everything above that block's diagonal is unspecified.
+ *   GPEMU_LEAF_PANEL_ROWS    the m_far rows from r_far on (m_far a multiple of 64, r_far >= c0 + 256) under the FINISHED
+ *                            256-column group at c0 -- rows and columns c0 .. c0+255 hold L with the diagonal inverses of its
+ *                            four 64x64 diagonal blocks -- leave, in columns c0 .. c0+255, with the bits the group's five
+ *                            launches (pair, solve, K = 128 update, pair, solve) over those rows give them.  m_below = 0,
+ *                            c0b = -1, fa = 0; the square is only read.
  * A pivot <= 0 or NaN at row r (1-based) of the block being factored gives info_out[b] = c0 + r (the pair's tile:
  * c0 + 64 + r) for matrix b, the first such row; otherwise 0.  Everything in a matrix whose pivot failed is unspecified.
  * Alignment contract: the staged solve and the pair move 16-byte pieces of rows, so off, ld, bstride, c0 and c0b must be
@@ -409,17 +414,21 @@ int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const 
  * GPEMU_ERR_ARG, before anything runs: a NULL pointer; op, staged, pre, fa or c0b outside their values; nbatch outside
  * 0..GPEMU_MAX_BATCH; the pair with m_below < 64 or no multiple of 64; a solve with m_below < 1; the factor alone with
  * m_below != 0; an odd off, ld, bstride, c0 or c0b; c0b with an op that launches no solve; fa without the pair; columns
- * beyond ld; or any matrix whose footprint -- rows c0 .. c0+64+m_below-1 of columns c0 .. c0+63 (pair: .. c0+127), and rows
- * c0b .. c0b+127 of columns c0b .. c0b+63 -- leaves [0, arena_len).  info_out: max(nbatch, 1) words. */
+ * beyond ld; the panel rows with m_far < 64 or no multiple of 64, r_far < c0 + 256, m_below != 0, c0b or fa; r_far or m_far
+ * != 0 with any other op; or any matrix whose footprint -- rows c0 .. c0+64+m_below-1 of columns c0 .. c0+63 (pair:
+ * .. c0+127), rows c0b .. c0b+127 of columns c0b .. c0b+63, the panel rows: rows c0 .. c0+255 and r_far .. r_far+m_far-1 of
+ * columns c0 .. c0+255 -- leaves [0, arena_len).  info_out: max(nbatch, 1) words. */
 #define GPEMU_LEAF_FACTOR 0
 #define GPEMU_LEAF_SOLVE 1
 #define GPEMU_LEAF_FACTOR_SOLVE 2
 #define GPEMU_LEAF_PAIR 3
+#define GPEMU_LEAF_PANEL_ROWS 4
 typedef struct gpemu_leaf_launch_args {
 	long off, ld, bstride;
 	int nbatch, c0, m_below;
 	int op;
 	int staged, pre, c0b, fa;
+	int r_far, m_far;    /* GPEMU_LEAF_PANEL_ROWS only, otherwise 0 */
 } gpemu_leaf_launch_args;
 int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_leaf_launch_args *args, int *info_out);
 /* The gradient's reduction kernels -- beta on the device, alpha, the tile sums of the literal or the exact form, their

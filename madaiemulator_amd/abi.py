@@ -37,10 +37,10 @@ class GemmLaunchArgs(C.Structure):
 class LeafLaunchArgs(C.Structure):
     """gpemu_leaf_launch_args of include/gpemu.h"""
     _fields_ = ([(f, C.c_long) for f in ("off", "ld", "bstride")] +
-                [(f, C.c_int) for f in ("nbatch", "c0", "m_below", "op", "staged", "pre", "c0b", "fa")])
+                [(f, C.c_int) for f in ("nbatch", "c0", "m_below", "op", "staged", "pre", "c0b", "fa", "r_far", "m_far")])
 
 
-LEAF_FACTOR, LEAF_SOLVE, LEAF_FACTOR_SOLVE, LEAF_PAIR = 0, 1, 2, 3
+LEAF_FACTOR, LEAF_SOLVE, LEAF_FACTOR_SOLVE, LEAF_PAIR, LEAF_PANEL_ROWS = 0, 1, 2, 3, 4
 
 
 class GradSumsArgs(C.Structure):

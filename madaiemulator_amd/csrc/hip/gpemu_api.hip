@@ -183,6 +183,10 @@ static Sched read_environment()
 	v = geti("GPEMU_NB_TOP", 0);
 	sc.nb_top = v >= LEAF ? (v / LEAF) * LEAF : 0;
 	sc.split_rhs_rows = geti("GPEMU_SPLIT_RHS_ROWS", 1) != 0;
+	v = geti("GPEMU_PANEL_ROWS", 1);
+	sc.panel_rows = v >= 0 && v <= 2 ? v : 1;
+	v = geti("GPEMU_PANEL_SPLIT", 1);
+	sc.panel_split = v >= 0 && v <= (1 << 16) ? v : 1;
 	return sc;
 }
 
@@ -514,12 +518,13 @@ static Tall tall_of(gpemu_ctx *ctx) { return Tall{ctx->dT, ctx->dInfo, ctx->Np, 
 
 // *fa_done: set when the update ran with the factor-ahead tile, i.e. the 64x64 diagonal block at c0+k is already
 // factored when the update has finished and the next leaf must not factor it again
-static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, int ncols, int inv, bool *fa_done)
+// row_cut > 0 (without inverse rows): the update stops at that row -- the rows from there on are panel_rows_kernel's
+static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, int ncols, int inv, bool *fa_done, int row_cut = 0)
 {
 	// C[rows >= r0, cols r0 .. r0+ncols) -= P P^T with P = the factored panel columns [c0, c0+k) and r0 = c0 + k
 	const long ld = t.Np;
 	const int r0 = c0 + k;
-	const int row_end = t.Np + t.Rp + (inv ? c0 + k : 0);         // identity rows < c0+k have fill-in in the panel
+	const int row_end = row_cut > 0 ? row_cut : t.Np + t.Rp + (inv ? c0 + k : 0);   // identity rows < c0+k have fill-in in the panel
 	GemmArgs g{};
 	g.C = t.T + (long)r0 * ld + r0;
 	g.A = t.T + (long)r0 * ld + c0;
@@ -568,10 +573,14 @@ static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, 
 // diag_done: the 64x64 diagonal block at (c0,c0) is already factored (by the factor-ahead tile of the update before)
 // defer_c0 >= 0: the leaf solve of this block also solves, in place, the 64 rows under the diagonal block at defer_c0 (the
 // pair's first block, which leaf_pair_kernel leaves untouched there)
-static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int inv, bool diag_done = false, int defer_c0 = -1)
+// panel_end: the end of the diagonal square of the outer panel this node lies in (0: this node is the outer panel)
+// row_cut > 0 (without inverse rows): the node's launches stop at that row -- a 256-column group whose rows from there on
+// go through panel_rows_kernel
+static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int inv, bool diag_done = false, int defer_c0 = -1,
+                            int panel_end = 0, int row_cut = 0)
 {
 	const long ld = t.Np;
-	const int base_end = t.Np + t.Rp;
+	const int base_end = row_cut > 0 ? row_cut : t.Np + t.Rp;
 	if (n <= LEAF) {
 		const int row_end = base_end + (inv ? c0 + LEAF : 0);
 		ProfScope ps(ctx, GPEMU_PROF_LEAF, 0.0, 0.0);
@@ -595,7 +604,7 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int in
 		const bool fa = ctx->sched.factor_ahead != 0;
 		hipError_t e = launch_leaf_pair(ctx->stream, t.T, ld, c0, m_below, t.info, trp, t.nb, t.stride, fa);
 		if (e != hipSuccess) return e;
-		return potrf_rec(ctx, t, c0 + LEAF, LEAF, inv, fa, c0);
+		return potrf_rec(ctx, t, c0 + LEAF, LEAF, inv, fa, c0, panel_end, row_cut);
 	}
 	// automatic outer panel width: a batch has enough tiles per launch to afford the longer panel chain of a wider
 	// panel and gains from the larger K of its trailing updates and the fewer read-modify-write passes over the
@@ -613,7 +622,7 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int in
 		bool next_done = diag_done;
 		for (int c = c0; c < c0 + n; c += nb_top) {
 			const int nb = std::min(nb_top, c0 + n - c);
-			hipError_t e = potrf_rec(ctx, t, c, nb, inv, next_done);
+			hipError_t e = potrf_rec(ctx, t, c, nb, inv, next_done, -1, c + nb);
 			next_done = false;
 			if (e != hipSuccess) return e;
 			const int rest = c0 + n - (c + nb);
@@ -623,13 +632,33 @@ static hipError_t potrf_rec(gpemu_ctx *ctx, const Tall &t, int c0, int n, int in
 		}
 		return hipSuccess;
 	}
+	if (panel_end == 0) panel_end = c0 + n;
+	if (n == 4 * LEAF && !inv && row_cut == 0 && ctx->sched.panel_rows && ctx->sched.leaf_pair && ctx->sched.diag_inv_ahead) {
+		// a 256-column group: its five launches (pair, solve, K = 128 update, pair, solve) stop at r_split, and the rows from
+		// there on -- operands of later updates only, the right-hand sides among them -- take the group's whole arithmetic in
+		// one pass (panel_rows_kernel; same bits).  Every cut launch keeps arguments it accepts today: at least 64 rows under
+		// the group for the last solve (with the cut at the end of the outer panel's square the panel's last group stays as
+		// it is).  The cut 64 rows under the group, the most rows the one pass can take, measured best.
+		// Automatic: lock-step batches whose launch fills the chip's resident workgroups once (two per CU); one matrix is
+		// latency-bound and must not get a launch more per group.
+		const int r_split = ctx->sched.panel_split > 0 ? c0 + 4 * LEAF + LEAF * ctx->sched.panel_split : panel_end;
+		const int m_far = base_end - r_split;
+		const bool big = ctx->sched.panel_rows == 2 || (t.nb >= 2 && (long)(m_far / LEAF) * t.nb >= 512);
+		if (big && r_split >= c0 + 5 * LEAF && m_far >= LEAF && m_far % LEAF == 0) {
+			hipError_t e = potrf_rec(ctx, t, c0, n, inv, diag_done, -1, panel_end, r_split);
+			if (e != hipSuccess) return e;
+			ProfScope ps(ctx, GPEMU_PROF_LEAF, 0.0, 0.0);
+			unsigned long long *trp = trace_slot(ctx, "panel_rows cg=%d m=%d", c0, m_far);
+			return launch_panel_rows(ctx->stream, t.T, ld, c0, r_split, m_far, trp, t.nb, t.stride);
+		}
+	}
 	const int n1 = ((n / LEAF + 1) / 2) * LEAF;
-	hipError_t e = potrf_rec(ctx, t, c0, n1, inv, diag_done);
+	hipError_t e = potrf_rec(ctx, t, c0, n1, inv, diag_done, -1, panel_end, row_cut);
 	if (e != hipSuccess) return e;
 	bool right_done = false;
-	e = trailing_update(ctx, t, c0, n1, n - n1, inv, &right_done);
+	e = trailing_update(ctx, t, c0, n1, n - n1, inv, &right_done, row_cut);
 	if (e != hipSuccess) return e;
-	return potrf_rec(ctx, t, c0 + n1, n - n1, inv, right_done);
+	return potrf_rec(ctx, t, c0 + n1, n - n1, inv, right_done, -1, panel_end, row_cut);
 }
 
 // the whole factorisation with plain launches (or under capture), its trace tags from slot 0
@@ -2351,6 +2380,9 @@ extern "C" int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_
 //   GPEMU_LEAF_FACTOR_SOLVE  both, the plain leaf
 //   GPEMU_LEAF_PAIR          leaf_pair_kernel: solve of columns [c0, c0+64) and K = 64 update of [c0+64, c0+128), fa: with
 //                            the factor-ahead tile
+//   GPEMU_LEAF_PANEL_ROWS    panel_rows_kernel (launch_panel_rows): the m_far rows from r_far on under the finished 256-column
+//                            group at c0; footprint per matrix: the square, rows and columns c0 .. c0+255, and rows
+//                            r_far .. r_far+m_far-1 of those columns
 // What the kernels may address is computed here first and anything outside [0, arena_len) is refused: per matrix rows
 // c0 .. c0+64+m_below-1 of columns c0 .. c0+63 (the pair: .. c0+127; the row clamps of the solve stay inside m_below), and
 // with c0b >= 0 rows c0b .. c0b+127 of columns c0b .. c0b+63.  The staged solve and the pair move 16-byte pieces of rows:
@@ -2361,8 +2393,14 @@ extern "C" int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_
 	if (!ctx || !arena || !p || !info_out) return GPEMU_ERR_ARG;
 	constexpr long DIM_MAX = 1L << 20, LD_MAX = 1L << 24, LEN_MAX = 1L << 32, STRIDE_MAX = 1L << 32;   // no product below leaves 63 bits
 	if (arena_len < 1 || arena_len > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: arena length");
-	if (p->op != GPEMU_LEAF_FACTOR && p->op != GPEMU_LEAF_SOLVE && p->op != GPEMU_LEAF_FACTOR_SOLVE && p->op != GPEMU_LEAF_PAIR)
+	if (p->op != GPEMU_LEAF_FACTOR && p->op != GPEMU_LEAF_SOLVE && p->op != GPEMU_LEAF_FACTOR_SOLVE && p->op != GPEMU_LEAF_PAIR &&
+	    p->op != GPEMU_LEAF_PANEL_ROWS)
 		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: op");
+	const bool far = p->op == GPEMU_LEAF_PANEL_ROWS;
+	if (!far && (p->r_far != 0 || p->m_far != 0)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: r_far and m_far belong to the panel rows");
+	if (far && (p->m_below != 0 || p->c0b >= 0 || p->fa)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the panel rows take m_below = 0, no c0b, no fa");
+	if (far && (p->m_far < LEAF || p->m_far > DIM_MAX || p->m_far % LEAF)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the panel rows take m_far = 64, 128, ...");
+	if (far && (p->r_far > DIM_MAX || p->r_far < p->c0 + 4 * LEAF)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the panel rows start at r_far >= c0 + 256");
 	if (p->staged < -1 || p->staged > 1 || (p->pre != 0 && p->pre != 1) || (p->fa != 0 && p->fa != 1) || p->c0b < -1 || p->c0b > DIM_MAX)
 		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: staged is -1/0/1, pre and fa are 0/1, c0b is -1 or a column");
 	if (p->nbatch < 0 || p->nbatch > GPEMU_MAX_BATCH) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: nbatch");
@@ -2377,7 +2415,7 @@ extern "C" int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_
 		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: off, ld, bstride, c0 and c0b must be even (16-byte row pieces)");
 	if (p->c0b >= 0 && !solves) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: c0b needs an op that launches the solve");
 	if (p->fa && !pair) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: fa belongs to the pair");
-	const int width = pair ? 2 * LEAF : LEAF;
+	const int width = far ? 4 * LEAF : pair ? 2 * LEAF : LEAF;
 	if (p->c0 + width > p->ld || (p->c0b >= 0 && p->c0b + LEAF > p->ld)) return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the columns leave the row");
 	const int nblk = std::max(p->nbatch, 1);
 	// smallest and largest element index over all matrices (the stride may have either sign)
@@ -2385,7 +2423,8 @@ extern "C" int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_
 		const long s0 = 0, s1 = (long)(nblk - 1) * p->bstride;
 		return p->off + first + std::min(s0, s1) >= 0 && p->off + last + std::max(s0, s1) < arena_len;
 	};
-	if (!inside((long)p->c0 * p->ld + p->c0, (long)(p->c0 + LEAF + p->m_below - 1) * p->ld + p->c0 + width - 1) ||
+	const long last_row = far ? (long)p->r_far + p->m_far - 1 : (long)p->c0 + LEAF + p->m_below - 1;
+	if (!inside((long)p->c0 * p->ld + p->c0, last_row * p->ld + p->c0 + width - 1) ||
 	    (p->c0b >= 0 && !inside((long)p->c0b * p->ld + p->c0b, (long)(p->c0b + 2 * LEAF - 1) * p->ld + p->c0b + LEAF - 1)))
 		return fail(ctx, GPEMU_ERR_ARG, "leaf_launch: the launch would address memory outside the arena");
 
@@ -2398,7 +2437,8 @@ extern "C" int gpemu_test_leaf_launch(gpemu_ctx *ctx, double *arena, long arena_
 	HIPCHK(ctx, hipMemcpyAsync(dArena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(dInfo, inf.data(), (size_t)nblk * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
 	double *T = dArena + p->off;
-	if (pair) HIPCHK(ctx, launch_leaf_pair(ctx->stream, T, p->ld, p->c0, p->m_below, dInfo, nullptr, p->nbatch, p->bstride, p->fa != 0));
+	if (far) HIPCHK(ctx, launch_panel_rows(ctx->stream, T, p->ld, p->c0, p->r_far, p->m_far, nullptr, p->nbatch, p->bstride));
+	else if (pair) HIPCHK(ctx, launch_leaf_pair(ctx->stream, T, p->ld, p->c0, p->m_below, dInfo, nullptr, p->nbatch, p->bstride, p->fa != 0));
 	else HIPCHK(ctx, launch_leaf(ctx->stream, T, p->ld, p->c0, p->m_below, dInfo, nullptr, nullptr, p->nbatch, p->bstride,
 	                             p->op == GPEMU_LEAF_SOLVE, p->staged, p->pre != 0, p->c0b));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

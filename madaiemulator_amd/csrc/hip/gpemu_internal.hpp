@@ -100,6 +100,8 @@ struct Sched {
 	int leaf_pair = 1;           // GPEMU_LEAF_PAIR: first block of a 128-column pair in one launch (leaf solve + K=64 update, leaf_pair_kernel); 0: two launches
 	int corner_row_table = 1;    // GPEMU_CORNER_ROW_TABLE: C^-1 = U U^T with whole tile rows per XCD (0: row-major enumeration, round-robin over the XCDs)
 	int stagger_us = 20;         // GPEMU_STAGGER_US: first-round offset between the two workgroups of a CU in the 128x128 GEMM (0 = none)
+	int panel_rows = 1;          // GPEMU_PANEL_ROWS: the rows under a 256-column group's cut in one pass (panel_rows_kernel): 0 never, 1 lock-step batches by launch size, 2 always
+	int panel_split = 1;         // GPEMU_PANEL_SPLIT: the cut: k > 0 = 64 k rows under the group (1 measured best), 0 = the end of the outer panel's diagonal square
 };
 
 // The one owner of device or pinned host memory in this library: move-only, released by the destructor, knows its element
@@ -367,6 +369,11 @@ hipError_t launch_leaf(hipStream_t s, double *T, long ld, int c0, int m_below, i
                        int nbatch = 1, long bstride = 0, bool skip_factor = false, int staged = -1, bool pre = true, int c0b = -1);
 hipError_t launch_leaf_pair(hipStream_t s, double *T, long ld, int c0, int m_below, int *info, unsigned long long *trace, int nbatch,
                             long bstride, bool fa);
+// the m_far rows from r_far on under the finished 256-column group at cg, all of the group's arithmetic in one pass
+// (panel_rows_kernel).  hipErrorInvalidValue, before anything runs: m_far no positive multiple of 64, r_far < cg + 256, an odd
+// ld, bstride or cg, T not 16-byte aligned
+hipError_t launch_panel_rows(hipStream_t s, double *T, long ld, int cg, int r_far, int m_far, unsigned long long *trace, int nbatch,
+                             long bstride);
 bool gemm_factor_ahead_ok(const GemmArgs &a);
 bool gemm_uses_big_tiles(const GemmArgs &a);
 hipError_t launch_gram_partials(hipStream_t s, const double *Z, long ld, int Np, int nrhs, int Rp, double *part,

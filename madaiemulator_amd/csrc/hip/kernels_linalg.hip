@@ -1422,6 +1422,173 @@ hipError_t launch_leaf(hipStream_t s, double *T, long ld, int c0, int m_below, i
 }
 
 // ---------------------------------------------------------------------------
+// panel_rows_kernel: the rows UNDER a finished 256-column group in one pass.  The group's diagonal square at (cg, cg) --
+// L, the parked diagonal inverses, the 64 rows under each diagonal block -- is complete; a row further down holds no
+// diagonal block of the group, is read by no leaf and no factor-ahead tile, and its substitution depends on no other row.
+// The five launches of a group (pair, solve, K = 128 update, pair, solve) make 18 passes over 64-column pieces of such a
+// row; here a wave takes 16 rows x 256 columns, reads each piece once, does per row exactly those launches' operations in
+// their order, and writes each piece once: 8 passes.
+//   X0 = solve(B0, L00);  B1 -= X0 L10^T;  X1 = solve(B1, L11);  [B2 B3] -= [X0 X1] [L20 L21; L30 L31]^T;
+//   X2 = solve(B2, L22);  B3 -= X2 L32^T;  X3 = solve(B3, L33)
+// Bits: the solve is leaf_chain.  An update runs per accumulator over the chunks of 16 in ascending k, inside a chunk
+// k = 8 t + 2 g + h for (t, h) = (0,0) (0,1) (1,0) (1,1) in lane group g, the product negated by the instruction, the
+// accumulator starting from the stored C -- what gemm_nt_kernel and leaf_pair_kernel feed the matrix unit, with the two
+// operands of the instruction exchanged: the unit then delivers the TRANSPOSED tile, i.e. the layout the chain starts from,
+// and every element is the same sequence of fused multiply-adds on the same pairs of factors (a product does not depend
+// on the order of its factors, nor -(l x) on which of them carries the sign).  Where the launches store a block and load it
+// again, the value stays in registers: exact, as at leaf_pair_kernel.
+// The ten 64x64 blocks of L pass through ONE 33 KB LDS image, the next block requested (L2) into registers before the work
+// on the current one; the solved blocks stay in registers as the updates' fragments.  LDS 33 KB + four 4.25 KB strips;
+// 216 vector registers, no scratch: two workgroups per CU (three would need 168: the four blocks of a row and the block of
+// L on its way are 96 of them before any fragment).  Measured: a workgroup lives 46 us for 15 us of
+// matrix instructions per wave -- the chain's operands come from LDS right in front of the instructions that use them.
+// ---------------------------------------------------------------------------
+// T -= Xa Lb^T for a solved block Xa (fragments af: doubles 16 c + 8 t + 2 g, + 1 of the lane's row q) and the 64x64 block
+// Lb in M (row-major, stride LP); T in the chain's layout (lane (q, g): row q, doubles 16 j + g + 4 r)
+__device__ __forceinline__ void rows_update64(d4_t (&R)[4], const d2_t (&af)[8], const double *M, int lane)
+{
+	const int g = lane >> 4, q = lane & 15;
+#pragma unroll
+	for (int c = 0; c < 4; c++)
+#pragma unroll
+		for (int t = 0; t < 2; t++) {
+			d2_t bf[4];
+#pragma unroll
+			for (int j = 0; j < 4; j++) bf[j] = *reinterpret_cast<const d2_t *>(&M[(16 * j + q) * LP + 16 * c + 8 * t + 2 * g]);
+#pragma unroll
+			for (int h = 0; h < 2; h++)
+#pragma unroll
+				for (int j = 0; j < 4; j++) R[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j][h], af[2 * c + t][h], R[j], 0, 0, 1);
+		}
+}
+// a wave-uniform address the compiler knows nothing else about: a scalar register pair.  Row r of a wave's tile is then
+// addressed as (scalar base of row r) + (the lane's 32-bit byte offset), one vector register for all rows; left to itself
+// the compiler keeps a 64-bit vector address per row alive across the kernel (16 register pairs, spilled)
+// (global address space spelled out: behind the asm statement the compiler has forgotten it and would use flat accesses)
+typedef __attribute__((address_space(1))) char gchar_t;
+typedef __attribute__((address_space(1))) d2_t gd2_t;
+typedef __attribute__((address_space(1))) double gdouble_t;
+__device__ __forceinline__ gchar_t *scalar_base(const void *p)
+{
+	gchar_t *c = (gchar_t *)p;
+	asm("" : "+s"(c));
+	return c;
+}
+// a solved tile (chain layout) through the wave's strip: to HBM in whole row pieces (dst: the wave's first row at the
+// block's first column, vbyte: the lane's byte offset in the coalesced shape), and, AF, into the fragments of the updates it feeds
+template <bool AF>
+__device__ __forceinline__ void tile_to_rows(char *strip, const d4_t (&X)[4], int lane, double *dst, long ld, unsigned vbyte, d2_t (&af)[8])
+{
+	const int g = lane >> 4, q = lane & 15, crow = lane >> 5, ccol = 2 * (lane & 31);
+#pragma unroll
+	for (int h = 0; h < 16 / LEAF_SROWS; h++) {
+		if ((q / LEAF_SROWS) == h) {
+			char *sp = strip + (q % LEAF_SROWS) * LEAF_SPITCH + 8 * g;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) *reinterpret_cast<double *>(sp + 8 * (16 * j + 4 * r)) = X[j][r];
+		}
+		asm volatile("" ::: "memory");
+#pragma unroll
+		for (int u = 0; u < LEAF_SROWS / 2; u++) {
+			const d2_t v = *reinterpret_cast<const d2_t *>(strip + (2 * u + crow) * LEAF_SPITCH + 8 * ccol);
+			*(gd2_t *)(scalar_base(dst + (long)(h * LEAF_SROWS + 2 * u) * ld) + vbyte) = v;
+		}
+		if (AF && (q / LEAF_SROWS) == h) {
+			const char *sp = strip + (q % LEAF_SROWS) * LEAF_SPITCH + 16 * g;
+#pragma unroll
+			for (int c = 0; c < 4; c++)
+#pragma unroll
+				for (int t = 0; t < 2; t++) af[2 * c + t] = *reinterpret_cast<const d2_t *>(sp + 8 * (16 * c + 8 * t));
+		}
+		asm volatile("" ::: "memory");
+	}
+}
+
+__global__ __launch_bounds__(256, 2) void panel_rows_kernel(double *T, long ld, int cg, int r_far, unsigned long long *trace, long bstride)
+{
+	T += (long)blockIdx.y * bstride;
+	__shared__ __attribute__((aligned(16))) double M[LEAF * LP];
+	__shared__ __attribute__((aligned(16))) char strip_all[4 * LEAF_SROWS * LEAF_SPITCH];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int crow = lane >> 5, ccol = 2 * (lane & 31);
+	const TraceT0 tr0 = trace_begin(trace);
+	const int uw = __builtin_amdgcn_readfirstlane(wave);
+	char *strip = strip_all + uw * LEAF_SROWS * LEAF_SPITCH;
+	// (m_far is a multiple of 64 -- launch_panel_rows refuses anything else -- so every row of every workgroup exists)
+	double *wrow = T + (long)(r_far + ((int)blockIdx.x * 4 + uw) * 16) * ld + cg;     // the wave's first row, column cg (scalar)
+	const unsigned voff = 8u * (unsigned)(crow * ld + ccol);                         // bytes: row crow of a row pair, doubles ccol, ccol + 1
+	const double *Lsq = T + (long)cg * ld + cg;
+	// block (a, b) of the square: requested into registers (fetch), written to the image once nobody reads the last one (land)
+	double lv[16];
+	auto fetch = [&](int a, int b) {
+		const double *D = Lsq + (long)(LEAF * a) * ld + LEAF * b;
+#pragma unroll
+		for (int u = 0; u < 16; u++) lv[u] = *(const gdouble_t *)(scalar_base(D + (long)(uw + 4 * u) * ld) + 8u * (unsigned)lane);
+	};
+	auto land = [&]() {
+#pragma unroll
+		for (int u = 0; u < 16; u++) M[(uw + 4 * u) * LP + lane] = lv[u];
+		__syncthreads();
+	};
+	fetch(0, 0);
+	// the wave's 16 rows x 256 columns as whole row pieces (2 rows x 512 bytes per wave-instruction): blocks 0 and 1 requested
+	// up front, blocks 2 and 3 each a step or two (a microsecond of matrix instructions) before their use -- all four at once,
+	// beside the block of L on its way, are more registers than two workgroups per CU leave a wave
+	d2_t in[4][8];
+	auto request = [&](int k) {
+#pragma unroll
+		for (int u = 0; u < 8; u++) in[k][u] = *(const gd2_t *)(scalar_base(wrow + (long)(2 * u) * ld + LEAF * k) + voff);
+	};
+	request(0); request(1);
+	d4_t R[4], R3[4], X[4];
+	d2_t af0[8], af1[8], af2[8];
+	land(); fetch(1, 0);
+	strip_rows_to_tile(strip, in[0], lane, R);
+	leaf_chain(R, M, lane, X);
+	tile_to_rows<true>(strip, X, lane, wrow, ld, voff, af0);
+	__syncthreads(); land(); fetch(1, 1); request(2);
+	strip_rows_to_tile(strip, in[1], lane, R);
+	rows_update64(R, af0, M, lane);
+	__syncthreads(); land(); fetch(2, 0);
+	leaf_chain(R, M, lane, X);
+	tile_to_rows<true>(strip, X, lane, wrow + LEAF, ld, voff, af1);
+	__syncthreads(); land(); fetch(2, 1); request(3);
+	strip_rows_to_tile(strip, in[2], lane, R);
+	rows_update64(R, af0, M, lane);
+	__syncthreads(); land(); fetch(3, 0);
+	rows_update64(R, af1, M, lane);
+	__syncthreads(); land(); fetch(3, 1);
+	strip_rows_to_tile(strip, in[3], lane, R3);
+	rows_update64(R3, af0, M, lane);
+	__syncthreads(); land(); fetch(2, 2);
+	rows_update64(R3, af1, M, lane);
+	__syncthreads(); land(); fetch(3, 2);
+	leaf_chain(R, M, lane, X);
+	tile_to_rows<true>(strip, X, lane, wrow + 2 * LEAF, ld, voff, af2);
+	__syncthreads(); land(); fetch(3, 3);
+	rows_update64(R3, af2, M, lane);
+	__syncthreads(); land();
+	leaf_chain(R3, M, lane, X);
+	tile_to_rows<false>(strip, X, lane, wrow + 3 * LEAF, ld, voff, af2);
+	trace_end(trace, tr0);
+}
+
+// the m_far rows from r_far on under the finished 256-column group at cg (r_far >= cg + 256: none of them holds a diagonal
+// block of the group).  Rows move as 16-byte pieces: ld, bstride and cg even, T 16-byte aligned
+hipError_t launch_panel_rows(hipStream_t s, double *T, long ld, int cg, int r_far, int m_far, unsigned long long *tr, int nbatch,
+                             long bstride)
+{
+	if (nbatch < 1) nbatch = 1;
+	if (m_far < LEAF || m_far % LEAF) return hipErrorInvalidValue;
+	if (cg < 0 || r_far < cg + 4 * LEAF || ld < cg + 4 * LEAF) return hipErrorInvalidValue;
+	if ((ld & 1) || (bstride & 1) || (cg & 1) || (reinterpret_cast<uintptr_t>(T) & 15)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(panel_rows_kernel, dim3(m_far / LEAF, nbatch), dim3(256), 0, s, T, ld, cg, r_far, tr, bstride);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Gram partials: part[blk][a][b] = sum_{j in 64-column chunk blk} Z[a][j] Z[b][j]
 // Z rows are the solved right-hand sides (rows Np.. of T): Z = L^-1 [y|H].
 // ---------------------------------------------------------------------------
