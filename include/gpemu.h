@@ -207,9 +207,13 @@ int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out);
  * mean[q], var[q] for M query rows xq[M*d].  Host buffers. */
 int gpemu_predict_batch(gpemu_ctx *ctx, int npoints, const double *xq, double *mean, double *var);
 /* the same in two halves: enqueue stages the queries through pinned memory and returns at once (the device work
- * runs on the context's stream), collect waits and copies the M means/variances out.  One batch per context at a
- * time; different contexts -- the PCA components of a multi-output emulator (multivar_support.c:103-157) --
- * work on their batches concurrently. */
+ * runs on the context's stream), collect waits and copies the M means/variances out.  Different contexts -- the PCA
+ * components of a multi-output emulator (multivar_support.c:103-157) -- work on their batches concurrently.
+ * The one-batch-per-context rule, for this pair and the enqueue / collect pairs of gpemu_predict_mean, _mean_grad and
+ * _var_grad below, which share its staging: a context has at most ONE batch pending, of whichever kind (an enqueue of any
+ * kind while one is pending: GPEMU_ERR_STATE).  Only the collect of the batch's own kind takes it, with the npoints it was
+ * enqueued with and the outputs that kind requires.  A refused collect -- another kind's or another npoints
+ * (GPEMU_ERR_STATE), a required output NULL (GPEMU_ERR_ARG) -- leaves the batch pending.  gpemu_set_model drops it. */
 int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
 int gpemu_predict_batch_collect(gpemu_ctx *ctx, int npoints, double *mean, double *var);
 /* same with query / result buffers already resident in HBM (device pointers) */
@@ -224,9 +228,8 @@ int gpemu_predict_batch_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev,
  * gpemu_predict_batch's mean to rounding, NOT bit for bit: the sum over the design runs in another order.  That order is the
  * same for a query whatever else the call holds: two calls, a query alone or among others, any entry below -- same bits.
  * Any M (blocks of 16 384 internally).  GPEMU_ERR_STATE without a prediction set-up (gpemu_predict_setup or
- * gpemu_predict_setup_batch); GPEMU_ERR_ARG on a NULL pointer or npoints < 1.  The enqueue / collect pair shares the
- * staging and the one-batch-per-context rule with gpemu_predict_batch_enqueue / _collect; a batch is collected by the
- * collect of its own kind (the other one: GPEMU_ERR_STATE, the batch stays enqueued). */
+ * gpemu_predict_setup_batch); GPEMU_ERR_ARG on a NULL pointer or npoints < 1.  The enqueue / collect pair follows the
+ * one-batch-per-context rule stated at gpemu_predict_batch_enqueue. */
 int gpemu_predict_mean(gpemu_ctx *ctx, int npoints, const double *xq, double *mean);
 int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
 int gpemu_predict_mean_collect(gpemu_ctx *ctx, int npoints, double *mean);
@@ -243,8 +246,7 @@ int gpemu_predict_mean_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, do
  * the matrix unit; nothing of size M x N is stored, the batch buffers of gpemu_predict_batch are neither touched nor
  * allocated, the scratch is this entry's own.  mean (M values, may be NULL) agrees with gpemu_predict_mean to rounding, not
  * bit for bit.  A query's bits do not depend on the rest of the call or on the entry used.  Sizes, errors and the
- * enqueue / collect rules are those of gpemu_predict_mean: one batch of any kind per context is pending at a time and is
- * collected by the collect of its own kind only (another: GPEMU_ERR_STATE, the batch stays enqueued). */
+ * enqueue / collect rule (the one stated at gpemu_predict_batch_enqueue) are those of gpemu_predict_mean. */
 int gpemu_predict_mean_grad(gpemu_ctx *ctx, int npoints, const double *xq, double *mean /* M, may be NULL */, double *grad /* M*d row-major */);
 int gpemu_predict_mean_grad_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);
 int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int npoints, double *mean /* may be NULL */, double *grad);
@@ -267,9 +269,8 @@ int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int npoints, const double *xq_de
  * identical calls return the same bits; the host, _dev and enqueue / collect entries return the same bits.  Few queries take
  * the same kernels on one 64-row tile: there is no fast path for them.  Where the variance rounds to <= 0 the gradient is
  * still that of the expression above.
- * Errors are those of gpemu_predict_mean_grad (grad required; mean, var optional).  One batch of any kind per context is
- * pending at a time; a variance-gradient batch is a fourth kind and is collected by gpemu_predict_var_grad_collect only
- * (another collect: GPEMU_ERR_STATE, the batch stays enqueued). */
+ * Errors are those of gpemu_predict_mean_grad (grad required; mean, var optional); the enqueue / collect pair follows the
+ * one-batch-per-context rule stated at gpemu_predict_batch_enqueue. */
 int gpemu_predict_var_grad(gpemu_ctx *ctx, int npoints, const double *xq, double *mean /* M, may be NULL */, double *var /* M, may be NULL */,
                            double *grad /* M*d row-major */);
 int gpemu_predict_var_grad_enqueue(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */);

@@ -369,15 +369,24 @@ class Context:
                        allow=(ERR_NOT_PD, ERR_REGRESSION))
         return beta, rc
 
-    def predict_enqueue(self, Xq):
+    # the two halves of the four host-buffer prediction entries (gpemu_predict_<kind>_enqueue / _collect): one batch of any
+    # kind is pending per context; _npred is its size, the collect's outputs are allocated by kind
+    def _pred_enqueue(self, kind, Xq):
         Xq = _a(Xq).reshape(-1, self.d)
         self._npred = Xq.shape[0]
-        self._chk(self.L.gpemu_predict_batch_enqueue(self.h, Xq.shape[0], _p(Xq)))
+        self._chk(getattr(self.L, f"gpemu_predict_{kind}_enqueue")(self.h, Xq.shape[0], _p(Xq)))
+
+    def _pred_collect(self, kind, outputs):
+        """outputs: the collect's arrays in argument order, "m" / "v" (M values) or "g" (M x d) -> a tuple of them"""
+        out = tuple(np.empty((self._npred, self.d) if o == "g" else self._npred) for o in outputs)
+        self._chk(getattr(self.L, f"gpemu_predict_{kind}_collect")(self.h, self._npred, *map(_p, out)))
+        return out
+
+    def predict_enqueue(self, Xq):
+        self._pred_enqueue("batch", Xq)
 
     def predict_collect(self):
-        m, v = np.empty(self._npred), np.empty(self._npred)
-        self._chk(self.L.gpemu_predict_batch_collect(self.h, self._npred, _p(m), _p(v)))
-        return m, v
+        return self._pred_collect("batch", "mv")
 
     def loo(self):
         """leave-one-out mean and variance at every training point, from the resident prediction state -> (mean, var)"""
@@ -451,14 +460,10 @@ class Context:
         self._chk(self.L.gpemu_predict_mean_dev(self.h, M, xq_dev, mean_dev))
 
     def predict_mean_enqueue(self, Xq):
-        Xq = _a(Xq).reshape(-1, self.d)
-        self._npred = Xq.shape[0]
-        self._chk(self.L.gpemu_predict_mean_enqueue(self.h, Xq.shape[0], _p(Xq)))
+        self._pred_enqueue("mean", Xq)
 
     def predict_mean_collect(self):
-        m = np.empty(self._npred)
-        self._chk(self.L.gpemu_predict_mean_collect(self.h, self._npred, _p(m)))
-        return m
+        return self._pred_collect("mean", "m")[0]
 
     # the posterior mean and its gradient with respect to the query point: one fused sweep
     def predict_mean_grad(self, Xq, want_mean=True):
@@ -474,14 +479,10 @@ class Context:
         self._chk(self.L.gpemu_predict_mean_grad_dev(self.h, M, xq_dev, mean_dev, grad_dev))
 
     def predict_mean_grad_enqueue(self, Xq):
-        Xq = _a(Xq).reshape(-1, self.d)
-        self._npred = Xq.shape[0]
-        self._chk(self.L.gpemu_predict_mean_grad_enqueue(self.h, Xq.shape[0], _p(Xq)))
+        self._pred_enqueue("mean_grad", Xq)
 
     def predict_mean_grad_collect(self):
-        m, g = np.empty(self._npred), np.empty((self._npred, self.d))
-        self._chk(self.L.gpemu_predict_mean_grad_collect(self.h, self._npred, _p(m), _p(g)))
-        return m, g
+        return self._pred_collect("mean_grad", "mg")
 
     # mean, variance and the variance's gradient with respect to the query point: two N^2 products and a fused sweep
     # (DESIGN.md 4.10); uses the batch buffers of predict_batch
@@ -500,14 +501,10 @@ class Context:
         self._chk(self.L.gpemu_predict_var_grad_dev(self.h, M, xq_dev, mean_dev, var_dev, grad_dev))
 
     def predict_var_grad_enqueue(self, Xq):
-        Xq = _a(Xq).reshape(-1, self.d)
-        self._npred = Xq.shape[0]
-        self._chk(self.L.gpemu_predict_var_grad_enqueue(self.h, Xq.shape[0], _p(Xq)))
+        self._pred_enqueue("var_grad", Xq)
 
     def predict_var_grad_collect(self):
-        m, v, g = np.empty(self._npred), np.empty(self._npred), np.empty((self._npred, self.d))
-        self._chk(self.L.gpemu_predict_var_grad_collect(self.h, self._npred, _p(m), _p(v), _p(g)))
-        return m, v, g
+        return self._pred_collect("var_grad", "mvg")
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

@@ -269,10 +269,7 @@ static void free_model(gpemu_ctx *ctx)
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
 	invalidate_prediction(ctx);
-	ctx->pred_pending = 0;
-	ctx->pred_pending_mean = false;
-	ctx->pred_pending_grad = false;
-	ctx->pred_pending_vgrad = false;
+	ctx->pred_pending = {};
 	ctx->S_dim = 0;
 }
 
@@ -1131,7 +1128,7 @@ extern "C" int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const do
 		if (x->device != lead->device || x->kind != lead->kind || x->order != lead->order || x->N != lead->N || x->d != lead->d ||
 		    x->mode != lead->mode || x->hX != lead->hX)
 			return fail(lead, GPEMU_ERR_ARG, "the contexts of a batched set-up share device, design, covariance function, regression order and modes");
-		if (x->pred_pending) return fail(lead, GPEMU_ERR_STATE, "a prediction batch is enqueued in one of the contexts: collect it first");
+		if (x->pred_pending.kind != PRED_NONE) return fail(lead, GPEMU_ERR_STATE, "a prediction batch is enqueued in one of the contexts: collect it first");
 		invalidate_prediction(x);
 	}
 	std::vector<CovParams> ps;
@@ -1218,6 +1215,60 @@ static int ensure_pred_batch(gpemu_ctx *ctx, int mb)
 
 constexpr int PRED_BATCH_MAX = 16384;
 
+// V = Kq LinvAug^T for the mb query rows in dKq: Np columns against the triangular rows of L^-1, then Rp against gamma and W^T
+// (gpemu_predict_batch_dev and gpemu_predict_var_grad_dev).  The schedule switches are applied here already -- gemm() does it
+// again -- for the tile-shape question of launch_aug_product and the callers' own questions about the call.
+static GemmArgs aug_product_args(gpemu_ctx *ctx, int mb)
+{
+	const int Np = ctx->Np, Rp = ctx->Rp;
+	GemmArgs g{};
+	g.C = ctx->dV; g.ldc = Np + Rp;
+	g.A = ctx->dKq; g.lda = Np;
+	g.B = ctx->dLinvAug; g.ldb = Np;
+	g.m = mb; g.n = Np + Rp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+	g.kend_mode = 1; g.kend_off = 0;
+	apply_sched(ctx->sched, g);
+	return g;
+}
+
+// launches what aug_product_args made (the caller may have split K since)
+static hipError_t launch_aug_product(gpemu_ctx *ctx, const GemmArgs &g)
+{
+	if (g.ksplit <= 1 && ctx->sched.split_rhs_rows && gemm_uses_big_tiles(g)) {
+		// 128x128 tiles: the 64 columns of gamma and W^T behind the Np triangular ones would make a 65th tile column that is
+		// half empty at the full contraction length (1.5 % of the sweep's tile time): they go to a 64x64-tile launch of
+		// their own, as the right-hand-side rows of the factorisation's updates do.  Same chain per element, same bits.
+		const int Np = ctx->Np;
+		GemmArgs a = g;
+		a.n = Np;
+		const hipError_t e = gemm(ctx, a);
+		if (e != hipSuccess) return e;
+		GemmArgs b = g;
+		b.C = ctx->dV + Np; b.B = ctx->dLinvAug + (size_t)Np * Np;
+		b.n = ctx->Rp; b.kend_mode = 0; b.force_cfg = 2;
+		return gemm(ctx, b);
+	}
+	return gemm(ctx, g);
+}
+
+// what the fused sweeps read of the model besides dX: the design centred per dimension with its centres where the model has
+// them (else as given, mid = NULL), the gamma row of dLinvAug, and whether the k-vectors are taken in Gram form
+struct SweepInputs {
+	const double *Xc, *mid, *gamma;
+	bool gram;
+};
+
+static SweepInputs sweep_inputs(gpemu_ctx *ctx)
+{
+	const bool centred = ctx->dXg && ctx->dMid;
+	SweepInputs s;
+	s.Xc = centred ? (const double *)ctx->dXg : (const double *)ctx->dX;
+	s.mid = centred ? (const double *)ctx->dMid : nullptr;
+	s.gamma = ctx->dLinvAug + (size_t)ctx->Np * ctx->Np;
+	s.gram = ctx->pred_cov.gram && ctx->sched.kvec_gram && centred;
+	return s;
+}
+
 extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *var_dev)
 {
 	if (!ctx || M < 1 || !xq_dev || !mean_dev || !var_dev) return GPEMU_ERR_ARG;
@@ -1230,13 +1281,7 @@ extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_d
 	for (int q0 = 0; q0 < M; q0 += cap) {
 		const int mb = std::min(cap, M - q0);
 		const int mbp = round_up(mb, 64);
-		GemmArgs g{};
-		g.C = ctx->dV; g.ldc = Np + Rp;
-		g.A = ctx->dKq; g.lda = Np;
-		g.B = ctx->dLinvAug; g.ldb = Np;
-		g.m = mb; g.n = Np + Rp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
-		g.kend_mode = 1; g.kend_off = 0;
-		apply_sched(ctx->sched, g);                     // (gemm() does too: here for the tile-shape question below)
+		GemmArgs g = aug_product_args(ctx, mb);
 		// a few queries (emulate_point: ONE) give one or two tile rows with K = N each: split K over the chip
 		// (0.46 -> 0.1 ms per call at N=8192); the slices are summed in order by the finishing kernel
 		int nslice = 1;
@@ -1260,7 +1305,8 @@ extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_d
 			// up to 16 queries (emulate_point: one): the skinny kernel, one 16-row query tile, instead of 64-row GEMM
 			// tiles (97 vs 115 us at N=8192; from 17 queries on the split-K GEMM is as fast)
 			const int klen = (((Np + nslice - 1) / nslice) + 15) & ~15;
-			ProfScope ps(ctx, GPEMU_PROF_GEMM, gemm_flops(g), 0.0);
+			// (the count walks the Np + Rp columns on the host: only for a profile, as in gemm())
+			ProfScope ps(ctx, GPEMU_PROF_GEMM, prof_on(ctx, GPEMU_PROF_GEMM) ? gemm_flops(g) : 0.0, 0.0);
 			if (mb == 1 && ctx->sched.gemv_point)
 				// ONE query: a matrix-vector stream over whole rows of L^-1 instead of the matrix unit's 16-row reads
 				HIPCHK(ctx, launch_gemv_tri(ctx->stream, ctx->dKq, Np, ctx->dLinvAug, Np, ctx->dV, Np + Rp, (long)mbp * (Np + Rp),
@@ -1271,92 +1317,13 @@ extern "C" int gpemu_predict_batch_dev(gpemu_ctx *ctx, int M, const double *xq_d
 			HIPCHK(ctx, launch_predict_finish_small(ctx->stream, ctx->dV, Np + Rp, (long)mbp * (Np + Rp), nslice, mb, Np, ctx->nreg, d,
 			                                        xq_dev + (size_t)q0 * d, ctx->dBetaQ, ctx->kappa, mean_dev + q0, var_dev + q0));
 			continue;
-		} else if (nslice == 1 && ctx->sched.split_rhs_rows && gemm_uses_big_tiles(g)) {
-			// 128x128 tiles: the 64 columns of gamma and W^T behind the Np triangular ones would make a 65th tile column that is
-			// half empty at the full contraction length (1.5 % of the sweep's tile time): they go to a 64x64-tile launch of
-			// their own, as the right-hand-side rows of the factorisation's updates do.  Same chain per element, same bits.
-			GemmArgs a = g;
-			a.n = Np;
-			HIPCHK(ctx, gemm(ctx, a));
-			GemmArgs b = g;
-			b.C = ctx->dV + Np; b.B = ctx->dLinvAug + (size_t)Np * Np;
-			b.n = Rp; b.kend_mode = 0; b.force_cfg = 2;
-			HIPCHK(ctx, gemm(ctx, b));
-		} else
-		HIPCHK(ctx, gemm(ctx, g));
+		}
+		HIPCHK(ctx, launch_aug_product(ctx, g));
 		HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, Np + Rp, mb, Np, ctx->nreg, ctx->order, d,
 		                                  xq_dev + (size_t)q0 * d, ctx->dBetaQ, ctx->kappa, mean_dev + q0, var_dev + q0,
 		                                  nslice, (long)mbp * (Np + Rp)));
 	}
 	return GPEMU_OK;
-}
-
-// the staging of the host-buffer entries (mean+variance and mean-only share it), for at least M queries
-static int ensure_pred_stage(gpemu_ctx *ctx, int M)
-{
-	if (ctx->stage_cap() >= (size_t)M) return GPEMU_OK;
-	const int d = ctx->d;
-	const size_t cap = (size_t)std::max(M, 64);
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->hStage.reset();                           // (the capacity is zero until all three are there again)
-	int rc = grow(ctx, ctx->dXq, cap * d);
-	if (!rc) rc = grow(ctx, ctx->dMean, 2 * cap);
-	if (rc) return rc;
-	HIPCHK(ctx, ctx->hStage.grow(cap * (d + 2)));
-	return GPEMU_OK;
-}
-
-// host-buffer entry, asynchronous form: the queries are staged through pinned memory, the batch runs on the context's
-// stream and the results come back into pinned memory; nothing blocks until gpemu_predict_batch_collect.  Several
-// contexts (the PCA components of a multi-output emulator) can so work on one query at the same time.
-extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *xq)
-{
-	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const int d = ctx->d;
-	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
-	const size_t cap = ctx->stage_cap();
-	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d, *hv = hm + cap;
-	memcpy(hx, xq, (size_t)M * d * sizeof(double));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	int rc = gpemu_predict_batch_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar());
-	if (rc) return rc;
-	if (cap <= 1024) {
-		// (hm | hv on the host and dMean | dVar on the device have the same layout, cap entries apart)
-		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (cap + M) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	} else {
-		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	}
-	ctx->pred_pending = M;
-	ctx->pred_pending_mean = false;
-	ctx->pred_pending_grad = false;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, double *var)
-{
-	if (!ctx || !mean || !var) return GPEMU_ERR_ARG;
-	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
-	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
-	if (ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is mean-only: collect it with gpemu_predict_mean_collect");
-	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
-	memcpy(mean, hm, (size_t)M * sizeof(double));
-	memcpy(var, hv, (size_t)M * sizeof(double));
-	ctx->pred_pending = 0;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_batch(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *var)
-{
-	if (!ctx || M < 1 || !xq || !mean || !var) return GPEMU_ERR_ARG;
-	int rc = gpemu_predict_batch_enqueue(ctx, M, xq);
-	if (rc) return rc;
-	return gpemu_predict_batch_collect(ctx, M, mean, var);
 }
 
 // ---------------------------------------------------------------------------
@@ -1377,8 +1344,7 @@ extern "C" int gpemu_predict_mean_dev(gpemu_ctx *ctx, int M, const double *xq_de
 	if (rc) return rc;
 	const long pstride = (long)(ctx->dMeanPart.size() / (size_t)nslice);
 	const CovParams &p = ctx->pred_cov;
-	const bool gram = p.gram && ctx->sched.kvec_gram && ctx->dXg && ctx->dMid;
-	const double *gamma = ctx->dLinvAug + (size_t)Np * Np;
+	const SweepInputs in = sweep_inputs(ctx);        // (the kernel takes dXg and dMid as they are: it reads them in Gram form only)
 	for (int q0 = 0; q0 < M; q0 += cap) {
 		const int mb = std::min(cap, M - q0);
 		const double *xq = xq_dev + (size_t)q0 * d;
@@ -1386,7 +1352,7 @@ extern "C" int gpemu_predict_mean_dev(gpemu_ctx *ctx, int M, const double *xq_de
 		{
 			// flops: per element the squared distance (3 d) and the product with gamma (2); bytes: coordinates in, mean out
 			ProfScope ps(ctx, GPEMU_PROF_MEAN, (double)mb * N * (3.0 * d + 2.0), 8.0 * (double)mb * (d + 1));
-			HIPCHK(ctx, launch_predict_mean(ctx->stream, ctx->dMeanPart, pstride, xq, mb, ctx->dX, ctx->dXg, ctx->dMid, gamma, N, Np, d, p, gram));
+			HIPCHK(ctx, launch_predict_mean(ctx->stream, ctx->dMeanPart, pstride, xq, mb, ctx->dX, ctx->dXg, ctx->dMid, in.gamma, N, Np, d, p, in.gram));
 		}
 		{
 			ProfScope ps(ctx, GPEMU_PROF_MEAN, 2.0 * mb * ctx->nreg, 0.0);
@@ -1395,50 +1361,6 @@ extern "C" int gpemu_predict_mean_dev(gpemu_ctx *ctx, int M, const double *xq_de
 		}
 	}
 	return GPEMU_OK;
-}
-
-// host buffers, in two halves: the staging (and the one-batch-per-context rule) is the mean+variance pair's
-extern "C" int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int M, const double *xq)
-{
-	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const int d = ctx->d;
-	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
-	const size_t cap = ctx->stage_cap();
-	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d;
-	memcpy(hx, xq, (size_t)M * d * sizeof(double));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	const int rc = gpemu_predict_mean_dev(ctx, M, ctx->dXq, ctx->dMean);
-	if (rc) return rc;
-	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	ctx->pred_pending = M;
-	ctx->pred_pending_mean = true;
-	ctx->pred_pending_grad = false;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_mean_collect(gpemu_ctx *ctx, int M, double *mean)
-{
-	if (!ctx || !mean) return GPEMU_ERR_ARG;
-	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
-	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
-	if (ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a mean-gradient batch: collect it with gpemu_predict_mean_grad_collect");
-	if (!ctx->pred_pending_mean) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch has variances: collect it with gpemu_predict_batch_collect");
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
-	ctx->pred_pending = 0;
-	ctx->pred_pending_mean = false;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_mean(gpemu_ctx *ctx, int M, const double *xq, double *mean)
-{
-	if (!ctx || M < 1 || !xq || !mean) return GPEMU_ERR_ARG;
-	const int rc = gpemu_predict_mean_enqueue(ctx, M, xq);
-	if (rc) return rc;
-	return gpemu_predict_mean_collect(ctx, M, mean);
 }
 
 // ---------------------------------------------------------------------------
@@ -1461,10 +1383,7 @@ extern "C" int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int M, const double *
 	const long pstride = (long)(ctx->dMGradPart.size() / ((size_t)nslice * (size_t)(1 + pw)));
 	double *mpart = ctx->dMGradPart, *gpart = mpart + (size_t)nslice * pstride;
 	const CovParams &p = ctx->pred_cov;
-	const bool centred = ctx->dXg && ctx->dMid;
-	const bool gram = p.gram && ctx->sched.kvec_gram && centred;
-	const double *Xc = centred ? (const double *)ctx->dXg : (const double *)ctx->dX, *mid = centred ? (const double *)ctx->dMid : nullptr;
-	const double *gamma = ctx->dLinvAug + (size_t)Np * Np;
+	const SweepInputs in = sweep_inputs(ctx);
 	for (int q0 = 0; q0 < M; q0 += cap) {
 		const int mb = std::min(cap, M - q0);
 		const double *xq = xq_dev + (size_t)q0 * d;
@@ -1473,66 +1392,15 @@ extern "C" int gpemu_predict_mean_grad_dev(gpemu_ctx *ctx, int M, const double *
 			// flops: per element the squared distance (3 d), the product with gamma (2) and the 1 + d columns of the second
 			// product (2 each); bytes: coordinates in, mean and gradient out
 			ProfScope ps(ctx, GPEMU_PROF_MEAN_GRAD, (double)mb * N * (3.0 * d + 2.0 + 2.0 * (d + 1)), 8.0 * (double)mb * (2 * d + 1));
-			HIPCHK(ctx, launch_predict_mean_grad(ctx->stream, mpart, gpart, pstride, xq, mb, ctx->dX, Xc, mid, gamma, N, Np, d, p, gram));
+			HIPCHK(ctx, launch_predict_mean_grad(ctx->stream, mpart, gpart, pstride, xq, mb, ctx->dX, in.Xc, in.mid, in.gamma, N, Np, d, p, in.gram));
 		}
 		{
 			ProfScope ps(ctx, GPEMU_PROF_MEAN_GRAD, 2.0 * mb * ctx->nreg + 4.0 * mb * d, 0.0);
-			HIPCHK(ctx, launch_predict_mean_grad_finish(ctx->stream, mpart, gpart, pstride, nslice, mb, ctx->nreg, d, xq, mid, ctx->dBetaQ, p,
+			HIPCHK(ctx, launch_predict_mean_grad_finish(ctx->stream, mpart, gpart, pstride, nslice, mb, ctx->nreg, d, xq, in.mid, ctx->dBetaQ, p,
 			                                            mean_dev ? mean_dev + q0 : nullptr, grad_dev + (size_t)q0 * d));
 		}
 	}
 	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_mean_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq)
-{
-	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const int d = ctx->d;
-	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
-	if (ctx->mgrad_cap() < (size_t)M) {
-		const size_t gcap = (size_t)std::max(M, 64);
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		ctx->hMGrad.reset();
-		if (const int rc = grow(ctx, ctx->dMGrad, gcap * d)) return rc;
-		HIPCHK(ctx, ctx->hMGrad.grow(gcap * d));
-	}
-	const size_t cap = ctx->stage_cap();
-	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d;
-	memcpy(hx, xq, (size_t)M * d * sizeof(double));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	const int rc = gpemu_predict_mean_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dMGrad);
-	if (rc) return rc;
-	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->hMGrad, ctx->dMGrad, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	ctx->pred_pending = M;
-	ctx->pred_pending_mean = false;
-	ctx->pred_pending_grad = true;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *grad)
-{
-	if (!ctx || !grad) return GPEMU_ERR_ARG;
-	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
-	if (ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is a variance-gradient batch: collect it with gpemu_predict_var_grad_collect");
-	if (!ctx->pred_pending_grad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is not a mean-gradient batch: collect it with the collect of its own kind");
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	if (mean) memcpy(mean, ctx->hStage + ctx->stage_cap() * ctx->d, (size_t)M * sizeof(double));
-	memcpy(grad, ctx->hMGrad, (size_t)M * ctx->d * sizeof(double));
-	ctx->pred_pending = 0;
-	ctx->pred_pending_grad = false;
-	return GPEMU_OK;
-}
-
-extern "C" int gpemu_predict_mean_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *grad)
-{
-	if (!ctx || M < 1 || !xq || !grad) return GPEMU_ERR_ARG;
-	const int rc = gpemu_predict_mean_grad_enqueue(ctx, M, xq);
-	if (rc) return rc;
-	return gpemu_predict_mean_grad_collect(ctx, M, mean, grad);
 }
 
 // ---------------------------------------------------------------------------
@@ -1570,9 +1438,7 @@ extern "C" int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int M, const double *x
 	double *gpart = ctx->dVGradPart, *spare = gpart + (size_t)nslice * cap * (size_t)pw;
 	const long ldv = (long)Np + Rp;
 	const CovParams &p = ctx->pred_cov;
-	const bool centred = ctx->dXg && ctx->dMid;
-	const bool gram = p.gram && ctx->sched.kvec_gram && centred;
-	const double *Xc = centred ? (const double *)ctx->dXg : (const double *)ctx->dX, *mid = centred ? (const double *)ctx->dMid : nullptr;
+	const SweepInputs in = sweep_inputs(ctx);
 	for (int q0 = 0; q0 < M; q0 += cap) {
 		const int mb = std::min(cap, M - q0);
 		const int mbp = round_up(mb, 64);
@@ -1581,24 +1447,7 @@ extern "C" int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int M, const double *x
 			ProfScope ps(ctx, GPEMU_PROF_FILL, 0.0, 8.0 * (double)mbp * Np);
 			HIPCHK(ctx, fill_kvectors(ctx, ctx->dKq, xq, mb, mbp, p));
 		}
-		GemmArgs g{};
-		g.C = ctx->dV; g.ldc = ldv;
-		g.A = ctx->dKq; g.lda = Np;
-		g.B = ctx->dLinvAug; g.ldb = Np;
-		g.m = mb; g.n = Np + Rp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
-		g.kend_mode = 1; g.kend_off = 0;
-		apply_sched(ctx->sched, g);
-		if (ctx->sched.split_rhs_rows && gemm_uses_big_tiles(g)) {
-			// (the gamma and W^T columns in a 64x64-tile launch of their own, as in gpemu_predict_batch_dev)
-			GemmArgs a = g;
-			a.n = Np;
-			HIPCHK(ctx, gemm(ctx, a));
-			GemmArgs b = g;
-			b.C = ctx->dV + Np; b.B = ctx->dLinvAug + (size_t)Np * Np;
-			b.n = Rp; b.kend_mode = 0; b.force_cfg = 2;
-			HIPCHK(ctx, gemm(ctx, b));
-		} else
-			HIPCHK(ctx, gemm(ctx, g));
+		HIPCHK(ctx, launch_aug_product(ctx, aug_product_args(ctx, mb)));
 		HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, ldv, mb, Np, ctx->nreg, ctx->order, d, xq, ctx->dBetaQ, ctx->kappa,
 		                                  mean_dev ? mean_dev + q0 : spare, var_dev ? var_dev + q0 : spare + cap, 1, (long)mbp * ldv));
 		HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, mb, Np, Rp, ctx->nreg, d, xq, ctx->dBetaQ));
@@ -1615,69 +1464,165 @@ extern "C" int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int M, const double *x
 			// flops: per element the squared distance (3 d), the product with a (1) and the 1 + d columns of the matrix
 			// product (2 each); bytes: A^T and the coordinates in, the gradient out
 			ProfScope ps(ctx, GPEMU_PROF_VAR_GRAD, (double)mb * N * (3.0 * d + 1.0 + 2.0 * (d + 1)), 8.0 * (double)mb * (N + 2 * d));
-			HIPCHK(ctx, launch_predict_var_grad(ctx->stream, gpart, cap, xq, mb, ctx->dX, Xc, mid, ctx->dKq, mbp, N, Np, d, p, gram));
+			HIPCHK(ctx, launch_predict_var_grad(ctx->stream, gpart, cap, xq, mb, ctx->dX, in.Xc, in.mid, ctx->dKq, mbp, N, Np, d, p, in.gram));
 		}
 		{
 			ProfScope ps(ctx, GPEMU_PROF_VAR_GRAD, 2.0 * mb * d * (nslice + 3.0), 0.0);
-			HIPCHK(ctx, launch_predict_var_grad_finish(ctx->stream, gpart, cap, nslice, mb, ctx->nreg, d, xq, mid, ctx->dV, ldv, Np, p,
+			HIPCHK(ctx, launch_predict_var_grad_finish(ctx->stream, gpart, cap, nslice, mb, ctx->nreg, d, xq, in.mid, ctx->dV, ldv, Np, p,
 			                                           grad_dev + (size_t)q0 * d));
 		}
 	}
 	return GPEMU_OK;
 }
 
-extern "C" int gpemu_predict_var_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq)
+// ---------------------------------------------------------------------------
+// host-buffer entries of the four kinds above, in two halves each: the queries are staged through pinned memory, the kind's
+// _dev entry runs on the context's stream and the results come back into pinned memory; nothing blocks until the collect.
+// Several contexts (the PCA components of a multi-output emulator) can so work on one query at the same time.  One batch of
+// any kind is pending per context (ctx->pred_pending); only the collect of its own kind takes it.
+// ---------------------------------------------------------------------------
+// the staging every kind uses (coordinates, means, variances), for at least M queries
+static int ensure_pred_stage(gpemu_ctx *ctx, int M)
 {
-	if (!ctx || M < 1 || !xq) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	if (ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (ctx->stage_cap() >= (size_t)M) return GPEMU_OK;
 	const int d = ctx->d;
-	if (const int rc = ensure_pred_stage(ctx, M)) return rc;
-	if (ctx->mgrad_cap() < (size_t)M) {
-		const size_t gcap = (size_t)std::max(M, 64);
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-		ctx->hMGrad.reset();
-		if (const int rc = grow(ctx, ctx->dMGrad, gcap * d)) return rc;
-		HIPCHK(ctx, ctx->hMGrad.grow(gcap * d));
-	}
-	const size_t cap = ctx->stage_cap();
-	double *hx = ctx->hStage, *hm = ctx->hStage + cap * d, *hv = hm + cap;
-	memcpy(hx, xq, (size_t)M * d * sizeof(double));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	const int rc = gpemu_predict_var_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar(), ctx->dMGrad);
+	const size_t cap = (size_t)std::max(M, 64);
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->hStage.reset();                           // (the capacity is zero until all three are there again)
+	int rc = grow(ctx, ctx->dXq, cap * d);
+	if (!rc) rc = grow(ctx, ctx->dMean, 2 * cap);
 	if (rc) return rc;
-	HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipMemcpyAsync(ctx->hMGrad, ctx->dMGrad, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	ctx->pred_pending = M;
-	ctx->pred_pending_mean = false;
-	ctx->pred_pending_grad = false;
-	ctx->pred_pending_vgrad = true;
+	HIPCHK(ctx, ctx->hStage.grow(cap * (d + 2)));
 	return GPEMU_OK;
 }
 
-extern "C" int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *var, double *grad)
+// the gradient staging of the two gradient kinds, for at least M queries
+static int ensure_pred_grad_stage(gpemu_ctx *ctx, int M)
 {
-	if (!ctx || !grad) return GPEMU_ERR_ARG;
-	if (!ctx->pred_pending || M != ctx->pred_pending) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
-	if (!ctx->pred_pending_vgrad) return fail(ctx, GPEMU_ERR_STATE, "the enqueued batch is not a variance-gradient batch: collect it with the collect of its own kind");
+	if (ctx->mgrad_cap() >= (size_t)M) return GPEMU_OK;
+	const size_t gcap = (size_t)std::max(M, 64);
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->hMGrad.reset();
+	if (const int rc = grow(ctx, ctx->dMGrad, gcap * ctx->d)) return rc;
+	HIPCHK(ctx, ctx->hMGrad.grow(gcap * ctx->d));
+	return GPEMU_OK;
+}
+
+// per PredKind: what the kind stages back to the host besides the means, which every kind does; which outputs its collect
+// refuses to go without (the others may be NULL); its name and its collect function for the error texts
+struct PredKindInfo {
+	bool var, grad;
+	bool need_mean, need_var, need_grad;
+	const char *name, *collect;
+};
+static constexpr PredKindInfo PRED_KINDS[] = {
+	{false, false, false, false, false, "", ""},                                              // PRED_NONE
+	{true, false, true, true, false, "mean+variance", "gpemu_predict_batch_collect"},         // PRED_MEAN_VAR
+	{false, false, true, false, false, "mean-only", "gpemu_predict_mean_collect"},            // PRED_MEAN
+	{false, true, false, false, true, "mean-gradient", "gpemu_predict_mean_grad_collect"},    // PRED_MEAN_GRAD
+	{true, true, false, false, true, "variance-gradient", "gpemu_predict_var_grad_collect"},  // PRED_VAR_GRAD
+};
+
+static bool pred_outputs_ok(PredKind kind, const double *mean, const double *var, const double *grad)
+{
+	const PredKindInfo &k = PRED_KINDS[kind];
+	return (mean || !k.need_mean) && (var || !k.need_var) && (grad || !k.need_grad);
+}
+
+static int pred_enqueue(gpemu_ctx *ctx, PredKind kind, int M, const double *xq)
+{
+	if (!ctx || kind == PRED_NONE || M < 1 || !xq) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending.kind != PRED_NONE) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is already enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const PredKindInfo &k = PRED_KINDS[kind];
+	const int d = ctx->d;
+	int rc = ensure_pred_stage(ctx, M);
+	if (!rc && k.grad) rc = ensure_pred_grad_stage(ctx, M);
+	if (rc) return rc;
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = hx + cap * d, *hv = hm + cap;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	switch (kind) {
+	case PRED_MEAN_VAR: rc = gpemu_predict_batch_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar()); break;
+	case PRED_MEAN: rc = gpemu_predict_mean_dev(ctx, M, ctx->dXq, ctx->dMean); break;
+	case PRED_MEAN_GRAD: rc = gpemu_predict_mean_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dMGrad); break;
+	case PRED_VAR_GRAD: rc = gpemu_predict_var_grad_dev(ctx, M, ctx->dXq, ctx->dMean, ctx->dVar(), ctx->dMGrad); break;
+	case PRED_NONE: break;                           // (refused above; here for the compiler's list of cases)
+	}
+	if (rc) return rc;
+	if (k.var && cap <= 1024) {
+		// ONE copy for a small batch, which keeps the latency of a single query low: hm | hv on the host and dMean | dVar on
+		// the device have the same layout, cap entries apart
+		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (cap + M) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	} else {
+		HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+		if (k.var) HIPCHK(ctx, hipMemcpyAsync(hv, ctx->dVar(), (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	if (k.grad) HIPCHK(ctx, hipMemcpyAsync(ctx->hMGrad, ctx->dMGrad, (size_t)M * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	ctx->pred_pending = {kind, M};
+	return GPEMU_OK;
+}
+
+// a refused collect, for whatever reason, leaves the batch pending
+static int pred_collect(gpemu_ctx *ctx, PredKind kind, int M, double *mean, double *var, double *grad)
+{
+	if (!ctx || !pred_outputs_ok(kind, mean, var, grad)) return GPEMU_ERR_ARG;
+	const PredPending pend = ctx->pred_pending;
+	if (pend.kind == PRED_NONE || M != pend.M) return fail(ctx, GPEMU_ERR_STATE, "no enqueued prediction batch of this size");
+	if (pend.kind != kind) {
+		char buf[160];
+		snprintf(buf, sizeof buf, "the enqueued batch is a %s batch: collect it with %s", PRED_KINDS[pend.kind].name, PRED_KINDS[pend.kind].collect);
+		return fail(ctx, GPEMU_ERR_STATE, buf);
+	}
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	// (an output the kind does not have is NULL: the wrappers below pass it so)
 	const double *hm = ctx->hStage + ctx->stage_cap() * ctx->d, *hv = hm + ctx->stage_cap();
 	if (mean) memcpy(mean, hm, (size_t)M * sizeof(double));
 	if (var) memcpy(var, hv, (size_t)M * sizeof(double));
-	memcpy(grad, ctx->hMGrad, (size_t)M * ctx->d * sizeof(double));
-	ctx->pred_pending = 0;
-	ctx->pred_pending_vgrad = false;
+	if (grad) memcpy(grad, ctx->hMGrad, (size_t)M * ctx->d * sizeof(double));
+	ctx->pred_pending = {};
 	return GPEMU_OK;
 }
 
+// both halves in one call (the outputs are looked at first: nothing is enqueued that the collect would then refuse)
+static int pred_sync(gpemu_ctx *ctx, PredKind kind, int M, const double *xq, double *mean, double *var, double *grad)
+{
+	if (!pred_outputs_ok(kind, mean, var, grad)) return GPEMU_ERR_ARG;
+	const int rc = pred_enqueue(ctx, kind, M, xq);
+	return rc ? rc : pred_collect(ctx, kind, M, mean, var, grad);
+}
+
+extern "C" int gpemu_predict_batch_enqueue(gpemu_ctx *ctx, int M, const double *xq) { return pred_enqueue(ctx, PRED_MEAN_VAR, M, xq); }
+extern "C" int gpemu_predict_batch_collect(gpemu_ctx *ctx, int M, double *mean, double *var) { return pred_collect(ctx, PRED_MEAN_VAR, M, mean, var, nullptr); }
+extern "C" int gpemu_predict_batch(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *var)
+{
+	return pred_sync(ctx, PRED_MEAN_VAR, M, xq, mean, var, nullptr);
+}
+
+extern "C" int gpemu_predict_mean_enqueue(gpemu_ctx *ctx, int M, const double *xq) { return pred_enqueue(ctx, PRED_MEAN, M, xq); }
+extern "C" int gpemu_predict_mean_collect(gpemu_ctx *ctx, int M, double *mean) { return pred_collect(ctx, PRED_MEAN, M, mean, nullptr, nullptr); }
+extern "C" int gpemu_predict_mean(gpemu_ctx *ctx, int M, const double *xq, double *mean)
+{
+	return pred_sync(ctx, PRED_MEAN, M, xq, mean, nullptr, nullptr);
+}
+
+extern "C" int gpemu_predict_mean_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq) { return pred_enqueue(ctx, PRED_MEAN_GRAD, M, xq); }
+extern "C" int gpemu_predict_mean_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *grad) { return pred_collect(ctx, PRED_MEAN_GRAD, M, mean, nullptr, grad); }
+extern "C" int gpemu_predict_mean_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *grad)
+{
+	return pred_sync(ctx, PRED_MEAN_GRAD, M, xq, mean, nullptr, grad);
+}
+
+extern "C" int gpemu_predict_var_grad_enqueue(gpemu_ctx *ctx, int M, const double *xq) { return pred_enqueue(ctx, PRED_VAR_GRAD, M, xq); }
+extern "C" int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int M, double *mean, double *var, double *grad)
+{
+	return pred_collect(ctx, PRED_VAR_GRAD, M, mean, var, grad);
+}
 extern "C" int gpemu_predict_var_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *var, double *grad)
 {
-	if (!ctx || M < 1 || !xq || !grad) return GPEMU_ERR_ARG;
-	const int rc = gpemu_predict_var_grad_enqueue(ctx, M, xq);
-	if (rc) return rc;
-	return gpemu_predict_var_grad_collect(ctx, M, mean, var, grad);
+	return pred_sync(ctx, PRED_VAR_GRAD, M, xq, mean, var, grad);
 }
 
 // ---------------------------------------------------------------------------

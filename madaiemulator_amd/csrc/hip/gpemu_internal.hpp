@@ -181,6 +181,14 @@ struct ParamRing {
 	unsigned slot = 0;               // entry of the batch being enqueued
 };
 
+// The host-buffer prediction entries (gpemu_predict_batch, _mean, _mean_grad, _var_grad and their halves) and the one batch a
+// context can have enqueued through any of them: its kind and its number of queries.  PRED_NONE: nothing pending.
+enum PredKind { PRED_NONE = 0, PRED_MEAN_VAR, PRED_MEAN, PRED_MEAN_GRAD, PRED_VAR_GRAD };
+struct PredPending {
+	PredKind kind = PRED_NONE;
+	int M = 0;
+};
+
 } // namespace gpemu
 
 struct gpemu_ctx {
@@ -237,19 +245,17 @@ struct gpemu_ctx {
 	gpemu::CovParams pred_cov;
 	std::vector<double> h_beta, h_Q;
 	gpemu::DevBuf<double> dKq, dV;   // batch buffers
-	// staging for the host-buffer entry, stage_cap() queries: dXq coordinates; dMean means, then variances (one allocation: a
-	// small batch comes back in ONE copy); hStage pinned, coordinates, then means, then variances
+	// staging of the host-buffer entries of every kind, stage_cap() queries: dXq coordinates; dMean means, then variances (one
+	// allocation: a small batch comes back in ONE copy); hStage pinned, coordinates, then means, then variances
 	gpemu::DevBuf<double> dXq, dMean;
 	gpemu::PinnedBuf<double> hStage;
 	size_t stage_cap() const { return hStage.size() / (size_t)(d + 2); }   // (hStage is allocated last, and gone with the model)
 	double *dVar() const { return dMean + stage_cap(); }
-	int pred_pending = 0;        // queries of an enqueued, not yet collected prediction batch
-	bool pred_pending_mean = false;   // that batch came from gpemu_predict_mean_enqueue (no variances in the staging)
+	gpemu::PredPending pred_pending;  // the enqueued, not yet collected prediction batch; gone with the model (free_model)
 	gpemu::DevBuf<double> dMeanPart;  // mean-only sweep: slice partial sums, predict_mean_slices(Np) x queries of a block
 	// mean-gradient sweep (gpemu_predict_mean_grad): its own scratch and staging.  dMGradPart: per slice and query of a block
 	// the mean's partial sum, then predict_mean_grad_width(d) gradient sums; dMGrad / hMGrad: mgrad_cap() x d gradients
 	// (dMGrad / hMGrad also stage the gradients of the variance-gradient entry's host forms: one batch is pending at a time)
-	bool pred_pending_grad = false;   // the enqueued batch came from gpemu_predict_mean_grad_enqueue
 	gpemu::DevBuf<double> dMGradPart, dMGrad;
 	gpemu::PinnedBuf<double> hMGrad;
 	size_t mgrad_cap() const { return d ? hMGrad.size() / (size_t)d : 0; }
@@ -257,7 +263,6 @@ struct gpemu_ctx {
 	// the first call after a set-up (linvT_ready; cleared with pred_ready); dVGradPart: per slice and query of a block
 	// predict_mean_grad_width(d) gradient sums, then two rows of scratch for a mean or variance the caller did not ask for.
 	// The entry also uses dKq and dV, as gpemu_predict_batch does.
-	bool pred_pending_vgrad = false;  // the enqueued batch came from gpemu_predict_var_grad_enqueue
 	bool linvT_ready = false;
 	gpemu::DevBuf<double> dLinvAugT, dVGradPart;
 	bool cinv_ready = false;
