@@ -10,6 +10,7 @@
 #include <cmath>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 namespace gpemu {
@@ -551,6 +552,25 @@ static hipError_t ensure_exp_table(hipStream_t s)
 	return e;
 }
 
+// A run-time covariance function (checked by the caller) as a template argument: f(std::integral_constant<int, KIND>)
+template <class F>
+static void dispatch_kind(int kind, F &&f)
+{
+	if (kind == GPEMU_POWEREXP) f(std::integral_constant<int, GPEMU_POWEREXP>{});
+	else if (kind == GPEMU_MATERN32) f(std::integral_constant<int, GPEMU_MATERN32>{});
+	else f(std::integral_constant<int, GPEMU_MATERN52>{});
+}
+
+// ... and the Gram / difference form beside it: f(kind constant, std::bool_constant<GRAM>)
+template <class F>
+static void dispatch_kind_form(int kind, bool gram, F &&f)
+{
+	dispatch_kind(kind, [&](auto K) {
+		if (gram) f(K, std::true_type{});
+		else f(K, std::false_type{});
+	});
+}
+
 // (every matrix of a batch has the model's covariance function: `kind` selects the instantiation)
 hipError_t launch_cov_stage_batch(hipStream_t s, double *T, long ld, long bstride, int nb, const double *X, int N, int Np, int d,
                                   const CovParams *pp_dev, int mode, const double *Rrows, int Rp, const double *Xg, bool all_gram,
@@ -567,22 +587,16 @@ hipError_t launch_cov_stage_batch(hipStream_t s, double *T, long ld, long bstrid
 		const long ntiles = nt * (nt + 1) / 2;
 		const long blocks = (ntiles + GRAM_TPW - 1) / GRAM_TPW + ((Rp + FT - 1) / FT) * nt;
 		const dim3 grid((unsigned)blocks, nb);
-		if (kind == GPEMU_POWEREXP)
-			hipLaunchKernelGGL(cov_stage_gram_kernel<GPEMU_POWEREXP>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
-		else if (kind == GPEMU_MATERN32)
-			hipLaunchKernelGGL(cov_stage_gram_kernel<GPEMU_MATERN32>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
-		else
-			hipLaunchKernelGGL(cov_stage_gram_kernel<GPEMU_MATERN52>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
+		dispatch_kind(kind, [&](auto K) {
+			hipLaunchKernelGGL(cov_stage_gram_kernel<K()>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
+		});
 		return hipGetLastError();
 	}
 	const long blocks = nt * (nt + 1) / 2 + ((Rp + FT - 1) / FT) * nt;
 	const dim3 grid((unsigned)blocks, nb);
-	if (kind == GPEMU_POWEREXP)
-		hipLaunchKernelGGL(cov_stage_batch_kernel<GPEMU_POWEREXP>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
-	else if (kind == GPEMU_MATERN32)
-		hipLaunchKernelGGL(cov_stage_batch_kernel<GPEMU_MATERN32>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
-	else
-		hipLaunchKernelGGL(cov_stage_batch_kernel<GPEMU_MATERN52>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
+	dispatch_kind(kind, [&](auto K) {
+		hipLaunchKernelGGL(cov_stage_batch_kernel<K()>, grid, dim3(256), 0, s, T, ld, bstride, X, N, Np, d, pp_dev, mode, Rrows, Rp, Xg, rstride);
+	});
 	return hipGetLastError();
 }
 
@@ -631,12 +645,9 @@ hipError_t launch_cov_kvec_gram(hipStream_t s, double *out, long ld, const doubl
 	if (e != hipSuccess) return e;
 	const int ntc = Np / FT, ngc = (ntc + GRAM_TPW - 1) / GRAM_TPW;
 	const dim3 grid((unsigned)((Mp / FT) * ngc));
-	if (p.kind == GPEMU_POWEREXP)
-		hipLaunchKernelGGL(cov_kvec_gram_kernel<GPEMU_POWEREXP>, grid, dim3(256), 0, s, out, ld, Xq, M, Mp, X, Xg, mid, N, Np, d, p);
-	else if (p.kind == GPEMU_MATERN32)
-		hipLaunchKernelGGL(cov_kvec_gram_kernel<GPEMU_MATERN32>, grid, dim3(256), 0, s, out, ld, Xq, M, Mp, X, Xg, mid, N, Np, d, p);
-	else
-		hipLaunchKernelGGL(cov_kvec_gram_kernel<GPEMU_MATERN52>, grid, dim3(256), 0, s, out, ld, Xq, M, Mp, X, Xg, mid, N, Np, d, p);
+	dispatch_kind(p.kind, [&](auto K) {
+		hipLaunchKernelGGL(cov_kvec_gram_kernel<K()>, grid, dim3(256), 0, s, out, ld, Xq, M, Mp, X, Xg, mid, N, Np, d, p);
+	});
 	return hipGetLastError();
 }
 
@@ -942,18 +953,6 @@ __global__ __launch_bounds__(256) void predict_mean_finish_kernel(const double *
 	mean[q] = hb + kg;
 }
 
-template <bool GRAM>
-static void launch_predict_mean_kind(hipStream_t s, dim3 grid, double *part, long pstride, const double *Xq, int M, const double *X,
-                                     const double *Xg, const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p)
-{
-	if (p.kind == GPEMU_POWEREXP)
-		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
-	else if (p.kind == GPEMU_MATERN32)
-		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
-	else
-		hipLaunchKernelGGL((predict_mean_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
-}
-
 // part: predict_mean_slices(Np) rows of pstride >= M doubles.  gram: the Gram form (needs p.gram, Xg, mid), else differences.
 hipError_t launch_predict_mean(hipStream_t s, double *part, long pstride, const double *Xq, int M, const double *X, const double *Xg,
                                const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p, bool gram)
@@ -965,8 +964,10 @@ hipError_t launch_predict_mean(hipStream_t s, double *part, long pstride, const 
 	if (gram) {
 		const hipError_t e = ensure_exp_table(s);
 		if (e != hipSuccess) return e;
-		launch_predict_mean_kind<true>(s, grid, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
-	} else launch_predict_mean_kind<false>(s, grid, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	}
+	dispatch_kind_form(p.kind, gram, [&](auto K, auto G) {
+		hipLaunchKernelGGL((predict_mean_kernel<K(), G()>), grid, dim3(256), 0, s, part, pstride, Xq, M, X, Xg, mid, gamma, N, Np, d, p);
+	});
 	return hipGetLastError();
 }
 
@@ -990,6 +991,8 @@ hipError_t launch_predict_mean_finish(hipStream_t s, const double *part, long ps
 // the clamp its weight is zero too: the gradient of the function gpemu_predict_mean evaluates.
 // Slicing, the absence of atomics and the per-query summation order are predict_mean_kernel's: a query's four lanes g each
 // add their sixteen design points per tile in a fixed order, the matrix unit adds an output row from that row of A alone.
+// The variance's gradient (further down) is the same reduction with a per-query vector in gamma's place:
+// both kernels are query_grad_sweep.
 // ---------------------------------------------------------------------------
 
 // cov_from_u2_gram with the weight g beside the value (the value by the same operations)
@@ -1116,28 +1119,100 @@ __device__ __forceinline__ unsigned gram_tile_u2_qcol(d4g_t (&acc)[4], const dou
 	return same;
 }
 
+// The difference-form counterpart, with the same element map and result convention: squared scaled distances by the
+// operations of predict_mean_kernel's difference form (x* w - x w, squared and added in dimension order; the kind is in
+// wsc), the design from global memory (each address shared by sixteen lanes): this form runs for extreme length scales only.
+// The exact "same point" test runs for the elements at or under p.cand.
+__device__ __forceinline__ unsigned diff_tile_u2_qcol(d4g_t (&acc)[4], const double *Xq, int M, const double *X, int N, int d,
+                                                      const CovParams &p, int tr, int tc, const double *wsc)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int q = lane & 15, g = lane >> 4;
+	const int qrow = tr * FT + 16 * wave + q;
+	const bool qv = qrow < M;
+#pragma unroll
+	for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
+	const double *qp = Xq + (long)(qv ? qrow : 0) * d;
+	const double *xp[4];
+#pragma unroll
+	for (int r = 0; r < 4; r++) {
+		const int col = tc * FT + g + 4 * r;              // (+ 16 j below: a tile of Np / FT lies inside the Np rows ...
+		xp[r] = X + (long)col * d;                        //  ... of the padded size, not of X: clamped per element)
+	}
+	for (int k = 0; k < d; k++) {
+		const double wk = wsc[k];
+		const double xr = qv ? qp[k] * wk : 0.0;
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const bool cv = tc * FT + 16 * j + g + 4 * r < N;
+				const double xc = cv ? xp[r][(long)16 * j * d + k] * wk : 0.0;
+				const double diff = xr - xc;
+				acc[j][r] = fma(diff, diff, acc[j][r]);
+			}
+	}
+	unsigned same = 0;
+	bool cand = false;
+#pragma unroll
+	for (int j = 0; j < 4; j++)
+#pragma unroll
+		for (int r = 0; r < 4; r++) cand = cand || (acc[j][r] <= p.cand);
+	if (__any(cand)) {
+#pragma unroll 1
+		for (int e = 0; e < 16; e++) {
+			const int r = e >> 2, j = e & 3;
+			double ae = HUGE_VAL;
+#pragma unroll
+			for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+				for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
+			const int col = tc * FT + 16 * j + g + 4 * r;
+			if (ae <= p.cand && qv && col < N) {
+				int cnt = 0;
+				for (int k = 0; k < d; k++) cnt += (fabs(qp[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
+				if (cnt == d) same |= 1u << e;
+			}
+		}
+	}
+	return same;
+}
+
 constexpr int MGRAD_NCB = (GPEMU_MAX_PARAMS + 1 + 15) / 16;      // column blocks of [1 | x'] at the largest d
 
 int predict_mean_grad_width(int d) { return 16 * ((d + 1 + 15) / 16); }
 
-// mpart: slices x pstride partial sums gamma . k; gpart: slices x pstride rows of pw = 16 ncb partial sums [S_0, S_1 .. S_d, 0 ..]
-template <int KIND, bool GRAM>
-__global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart, double *gpart, long pstride, const double *Xq, int M,
-                                                                 const double *X, const double *Xc, const double *mid,
-                                                                 const double *gamma, int N, int Np, int d, CovParams p)
+// The sweep behind both query gradients: per (64-query tile, slice of MEAN_TPW design tiles) the sums
+//   sum_i w_qi g_qi [1, x'_i1 .. x'_id]   (pw = 16 ncb columns, zeros beyond 1 + d)
+// over the slice's design points, g_qi the weight of the element's covariance value (above).  The two gradients differ in
+// w alone, and PERQ says which:
+//   PERQ = false (the mean): w_qi = gamma_i, one vector for all queries (wv).  The slice of gamma is staged
+//     in gam_s, the B block in LDS is gamma_i [1, x'_i] and the element weight is g; the sweep also keeps the mean
+//     gamma . k itself (msum, to mpart), a query's four lanes g adding their sixteen design points per tile in a fixed order.
+//   PERQ = true (the variance): w_qi = a_qi, given as A^T (wv: Np rows of lda >= the query count rounded up
+//     to 64, a multiple of 16; element (design i, query q) at wv[i * lda + q]).  The lane that holds (design 16 j + g + 4 r
+//     of the tile, query 16 wave + q) loads its sixteen a values at the top of the tile, under the distance product: per
+//     load instruction the sixteen lanes q of one g read one 128-byte run of row i, four runs a wave.  The B block is
+//     [1, x'_i], the element weight g a; there is no mean (mpart, gam_s unused).
+// Everything else is one text: the tables, the distance tile with its candidate / far-query / same-point rules, the nugget
+// on a same-point hit, the 1e-10 clamp with its zero derivative, the matrix-unit accumulation and the store.  Padding
+// columns i >= N have weight 0 in both; the mean path zeroes the VALUE of such an element and of a clamped one (it adds
+// them), the variance path only selects: a row q >= M's a is whatever the buffer held and is never used as a number.
+// Static LDS comes from the kernel (tab: EXP_TAB_G or EXP_TAB doubles by form; mid_s is read in the Gram form only).
+// p is taken by value: by reference the Matern kinds of the mean's Gram form come out three registers larger.
+template <int KIND, bool GRAM, bool PERQ>
+__device__ __forceinline__ void query_grad_sweep(double *mpart, double *gpart, long pstride, const double *Xq, int M, const double *X,
+                                                 const double *Xc, const double *mid, const double *wv, long lda, int N, int Np, int d,
+                                                 const CovParams p, double *tab, double *wsc, double *mid_s, double *gam_s)
 {
-	extern __shared__ double ys[];                 // FT x pw: gamma_i [1, x'_i1 .. x'_id, 0 ..] of the current tile
-	__shared__ double gam_s[MEAN_TPW * FT];
-	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
-	__shared__ double wsc[GPEMU_MAX_PARAMS];
-	__shared__ double mid_s[GPEMU_MAX_PARAMS];
+	extern __shared__ double ys[];                 // FT x pw: the B block of the current tile
 	const int tid = threadIdx.x;
 	const int ntc = Np / FT, nsl = (ntc + MEAN_TPW - 1) / MEAN_TPW;
 	const int tr = blockIdx.x / nsl, slice = blockIdx.x % nsl, tc0 = slice * MEAN_TPW;
 	const int ncb = (d + 1 + 15) / 16, pw = 16 * ncb;
-	{
+	if constexpr (!PERQ) {
 		const int col = tc0 * FT + tid;
-		gam_s[tid] = (col < N) ? gamma[col] : 0.0;
+		gam_s[tid] = (col < N) ? wv[col] : 0.0;
 	}
 	if (GRAM) {
 		gram_tables(p, d, tab, wsc);
@@ -1150,80 +1225,43 @@ __global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart
 	const int q = lane & 15, g = lane >> 4;
 	const int qrow = tr * FT + 16 * wave + q;
 	const bool qv = qrow < M;
-	double msum = 0.0;
+	[[maybe_unused]] double msum = 0.0;
 	d4g_t G[MGRAD_NCB];
 #pragma unroll
 	for (int cb = 0; cb < MGRAD_NCB; cb++) G[cb] = (d4g_t){0.0, 0.0, 0.0, 0.0};
 	for (int i = 0; i < MEAN_TPW; i++) {
 		const int tc = tc0 + i;
 		if (tc >= ntc) break;
+		[[maybe_unused]] d4g_t av[4];
+		if constexpr (PERQ) {
+			// (rows tc FT + .. < Np and columns qrow < lda lie inside the block whatever N and M are)
+			const double *ap = wv + (long)(tc * FT + g) * lda + qrow;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+#pragma unroll
+				for (int r = 0; r < 4; r++) av[j][r] = ap[(long)(16 * j + 4 * r) * lda];
+		}
 		__syncthreads();                           // the tables (first tile); the previous tile's ys has been read
 		for (int rr = 0; rr < 4; rr++) {
 			const int r = (tid >> 4) + 16 * rr, gi = tc * FT + r;
-			const double gm = (gi < N) ? gam_s[i * FT + r] : 0.0;
+			[[maybe_unused]] double gm = 0.0;
+			if constexpr (!PERQ) gm = (gi < N) ? gam_s[i * FT + r] : 0.0;
 			for (int cb = 0; cb < ncb; cb++) {
 				const int c = 16 * cb + (tid & 15);
 				double v = 0.0;
-				if (gi < N && c <= d) v = (c == 0) ? gm : gm * Xc[(long)gi * d + c - 1];
+				if (gi < N && c <= d) {
+					if constexpr (PERQ) v = (c == 0) ? 1.0 : Xc[(long)gi * d + c - 1];
+					else v = (c == 0) ? gm : gm * Xc[(long)gi * d + c - 1];
+				}
 				ys[r * pw + c] = v;
 			}
 		}
 		__syncthreads();
 		d4g_t acc[4];
-		unsigned same = 0;
-		if (GRAM) {
-			same = gram_tile_u2_qcol<KIND>(acc, Xq, mid_s, M, X, Xc, N, d, p, tr, tc, wsc);
-		} else {
-			// squared scaled distances from differences, by the operations of predict_mean_kernel's difference form
-			// (x* w - x w, squared and added in dimension order); the design from global memory (each address shared by
-			// sixteen lanes): this form runs for extreme length scales only
-#pragma unroll
-			for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
-			const double *qp = Xq + (long)(qv ? qrow : 0) * d;
-			const double *xp[4];
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const int col = tc * FT + g + 4 * r;              // (+ 16 j below: a tile of Np / FT lies inside the Np rows ...
-				xp[r] = X + (long)col * d;                        //  ... of the padded size, not of X: clamped per element)
-			}
-			for (int k = 0; k < d; k++) {
-				const double wk = wsc[k];
-				const double xr = qv ? qp[k] * wk : 0.0;
-#pragma unroll
-				for (int j = 0; j < 4; j++)
-#pragma unroll
-					for (int r = 0; r < 4; r++) {
-						const bool cv = tc * FT + 16 * j + g + 4 * r < N;
-						const double xc = cv ? xp[r][(long)16 * j * d + k] * wk : 0.0;
-						const double diff = xr - xc;
-						acc[j][r] = fma(diff, diff, acc[j][r]);
-					}
-			}
-			bool cand = false;
-#pragma unroll
-			for (int j = 0; j < 4; j++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) cand = cand || (acc[j][r] <= p.cand);
-			if (__any(cand)) {
-#pragma unroll 1
-				for (int e = 0; e < 16; e++) {
-					const int r = e >> 2, j = e & 3;
-					double ae = HUGE_VAL;
-#pragma unroll
-					for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-						for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
-					const int col = tc * FT + 16 * j + g + 4 * r;
-					if (ae <= p.cand && qv && col < N) {
-						int cnt = 0;
-						for (int k = 0; k < d; k++) cnt += (fabs(qp[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
-						if (cnt == d) same |= 1u << e;
-					}
-				}
-			}
-		}
+		const unsigned same = GRAM ? gram_tile_u2_qcol<KIND>(acc, Xq, mid_s, M, X, Xc, N, d, p, tr, tc, wsc)
+		                           : diff_tile_u2_qcol(acc, Xq, M, X, N, d, p, tr, tc, wsc);
 		const bool plain = (tc * FT + FT <= N) && !__any(same != 0);
-		const double *gs = gam_s + i * FT + g;
+		[[maybe_unused]] const double *gs = gam_s + i * FT + g;
 		const double *yb = ys + g * pw + q;
 #pragma unroll
 		for (int r = 0; r < 4; r++) {
@@ -1231,24 +1269,35 @@ __global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart
 			for (int j = 0; j < 4; j++) {
 				double gw;
 				double v = GRAM ? cov_grad_from_u2_gram<KIND>(acc[j][r], tab, gw) : cov_grad_from_a_diff<KIND>(acc[j][r], p.amp, tab, gw);
-				if (!plain) {
-					if (same & (1u << (4 * r + j))) v += p.nug;
-					// (a padding column's distance was not held at the exponent limit: its value may be anything)
-					if (tc * FT + 16 * j + g + 4 * r >= N) { v = 0.0; gw = 0.0; }
+				// (a padding column's distance was not held at the exponent limit: its value may be anything)
+				const bool pad = tc * FT + 16 * j + g + 4 * r >= N;
+				double wgt;
+				if constexpr (PERQ) {
+					if (!plain && (same & (1u << (4 * r + j)))) v += p.nug;
+					const bool live = qv && (plain || !pad) && !(v < 1E-10);          // emulator.c:588-590, and its derivative
+					wgt = live ? gw * av[j][r] : 0.0;
+				} else {
+					if (!plain) {
+						if (same & (1u << (4 * r + j))) v += p.nug;
+						if (pad) { v = 0.0; gw = 0.0; }
+					}
+					if (v < 1E-10) { v = 0.0; gw = 0.0; }                             // emulator.c:588-590, and its derivative
+					msum = fma(v, gs[16 * j + 4 * r], msum);
+					wgt = gw;
 				}
-				if (v < 1E-10) { v = 0.0; gw = 0.0; }                             // emulator.c:588-590, and its derivative
-				msum = fma(v, gs[16 * j + 4 * r], msum);
 #pragma unroll
 				for (int cb = 0; cb < MGRAD_NCB; cb++)
-					if (cb < ncb) G[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(gw, yb[(16 * j + 4 * r) * pw + 16 * cb], G[cb], 0, 0, 0);
+					if (cb < ncb) G[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(wgt, yb[(16 * j + 4 * r) * pw + 16 * cb], G[cb], 0, 0, 0);
 				if (j & 1) __builtin_amdgcn_sched_barrier(0);
 			}
 		}
 	}
-	// the mean's partial sum: the query's four lanes g, a fixed butterfly
-	msum += __shfl_xor(msum, 16);
-	msum += __shfl_xor(msum, 32);
-	if (g == 0 && qv) mpart[(long)slice * pstride + qrow] = msum;
+	if constexpr (!PERQ) {
+		// the mean's partial sum: the query's four lanes g, a fixed butterfly
+		msum += __shfl_xor(msum, 16);
+		msum += __shfl_xor(msum, 32);
+		if (g == 0 && qv) mpart[(long)slice * pstride + qrow] = msum;
+	}
 	// D register r of block cb: (query 16 wave + g + 4 r, column 16 cb + q)
 #pragma unroll
 	for (int cb = 0; cb < MGRAD_NCB; cb++)
@@ -1261,8 +1310,54 @@ __global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart
 		}
 }
 
-// grad[q][j] = sum_a beta_a dh_a/dx_j - s_j ((x*_j - mid_j) S_0 - S_j), the slices added in index order; the basis is
-// 1, x_j, x_j^2, x_j^3 with coefficient 1 + (o - 1) d + j on x_j^o (hfun).  mean (optional) as predict_mean_finish_kernel.
+// mpart: slices x pstride partial sums gamma . k; gpart: slices x pstride rows of pw = 16 ncb partial sums [S_0, S_1 .. S_d, 0 ..]
+template <int KIND, bool GRAM>
+__global__ __launch_bounds__(256, 2) void predict_mean_grad_kernel(double *mpart, double *gpart, long pstride, const double *Xq, int M,
+                                                                 const double *X, const double *Xc, const double *mid,
+                                                                 const double *gamma, int N, int Np, int d, CovParams p)
+{
+	__shared__ double gam_s[MEAN_TPW * FT];
+	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
+	__shared__ double wsc[GPEMU_MAX_PARAMS];
+	__shared__ double mid_s[GPEMU_MAX_PARAMS];
+	query_grad_sweep<KIND, GRAM, false>(mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, 0, N, Np, d, p, tab, wsc, mid_s, gam_s);
+}
+
+// gpart: slices x pstride rows of pw = 16 ncb partial sums [T_0, T_1 .. T_d, 0 ..] (below); rows q >= M are
+// never stored
+template <int KIND, bool GRAM>
+__global__ __launch_bounds__(256, 2) void predict_var_grad_kernel(double *gpart, long pstride, const double *Xq, int M, const double *X,
+                                                                const double *Xc, const double *mid, const double *At, long lda, int N,
+                                                                int Np, int d, CovParams p)
+{
+	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
+	__shared__ double wsc[GPEMU_MAX_PARAMS];
+	__shared__ double mid_s[GPEMU_MAX_PARAMS];
+	query_grad_sweep<KIND, GRAM, true>(nullptr, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p, tab, wsc, mid_s, nullptr);
+}
+
+// s_j of  d k(x_i, x*) / d x*_j = -g_i s_j D_j
+__device__ __forceinline__ double grad_dim_scale(const CovParams &p, int j)
+{
+	if (p.kind == GPEMU_POWEREXP) return 2.0 * p.w[j] * p.w[j];                       // w = sqrt(1/2) / r_j: 1 / r_j^2
+	if (p.kind == GPEMU_MATERN32) return (1.732050808 * 1.732050808) * (p.w[0] * p.w[0]);
+	return p.w[0] * p.w[0];
+}
+
+// sum_a coeff_a dh_a/dx_j at x_j = xj: the basis is 1, x_j, x_j^2, x_j^3 with coefficient 1 + (o - 1) d + j on x_j^o (hfun)
+__device__ __forceinline__ double hfun_grad_dot(const double *coeff, int nreg, int d, int j, double xj)
+{
+	const int order = (nreg - 1) / d;
+	double dh = 0.0;
+	for (int o = 1; o <= order; o++) {
+		const double b = coeff[1 + (o - 1) * d + j];
+		dh = fma(o == 1 ? 1.0 : (o == 2 ? 2.0 * xj : 3.0 * xj * xj), b, dh);
+	}
+	return dh;
+}
+
+// grad[q][j] = sum_a beta_a dh_a/dx_j - s_j ((x*_j - mid_j) S_0 - S_j), the slices added in index order.  mean (optional) as
+// predict_mean_finish_kernel.
 __global__ __launch_bounds__(256) void predict_mean_grad_finish_kernel(const double *mpart, const double *gpart, long pstride, int pw,
                                                                        int nslice, int M, int nreg, int d, const double *Xq,
                                                                        const double *mid, const double *beta, CovParams p,
@@ -1279,16 +1374,8 @@ __global__ __launch_bounds__(256) void predict_mean_grad_finish_kernel(const dou
 	}
 	const double *x = Xq + (long)q * d;
 	const double xj = x[j];
-	double sj;
-	if (p.kind == GPEMU_POWEREXP) sj = 2.0 * p.w[j] * p.w[j];                       // w = sqrt(1/2) / r_j: 1 / r_j^2
-	else if (p.kind == GPEMU_MATERN32) sj = (1.732050808 * 1.732050808) * (p.w[0] * p.w[0]);
-	else sj = p.w[0] * p.w[0];
-	const int order = (nreg - 1) / d;
-	double dh = 0.0;
-	for (int o = 1; o <= order; o++) {
-		const double b = beta[1 + (o - 1) * d + j];
-		dh = fma(o == 1 ? 1.0 : (o == 2 ? 2.0 * xj : 3.0 * xj * xj), b, dh);
-	}
+	const double sj = grad_dim_scale(p, j);
+	const double dh = hfun_grad_dot(beta, nreg, d, j, xj);
 	grad[e] = dh - sj * ((xj - (mid ? mid[j] : 0.0)) * S0 - Sj);
 	if (j == 0 && mean) {
 		double kg = 0.0;
@@ -1299,17 +1386,17 @@ __global__ __launch_bounds__(256) void predict_mean_grad_finish_kernel(const dou
 	}
 }
 
-template <bool GRAM>
-static void launch_predict_mean_grad_kind(hipStream_t s, dim3 grid, size_t lds, double *mpart, double *gpart, long pstride, const double *Xq,
-                                          int M, const double *X, const double *Xc, const double *mid, const double *gamma, int N, int Np,
-                                          int d, const CovParams &p)
+// What the two sweeps' launchers share: the argument checks, the grid, the dynamic LDS size (ys) and, for the Gram form,
+// the exp table on the device.
+static hipError_t query_grad_launch_shape(hipStream_t s, long pstride, int M, const double *Xc, const double *mid, int Np, int d,
+                                          const CovParams &p, bool gram, dim3 &grid, size_t &lds)
 {
-	if (p.kind == GPEMU_POWEREXP)
-		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
-	else if (p.kind == GPEMU_MATERN32)
-		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
-	else
-		hipLaunchKernelGGL((predict_mean_grad_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS || !Xc) return hipErrorInvalidValue;
+	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
+	if (gram && (!p.gram || !mid)) return hipErrorInvalidValue;
+	grid = dim3((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
+	lds = (size_t)FT * predict_mean_grad_width(d) * sizeof(double);
+	return gram ? ensure_exp_table(s) : hipSuccess;
 }
 
 // mpart: predict_mean_slices(Np) x pstride; gpart: predict_mean_slices(Np) x pstride x predict_mean_grad_width(d); pstride >= M.
@@ -1319,16 +1406,14 @@ hipError_t launch_predict_mean_grad(hipStream_t s, double *mpart, double *gpart,
                                     const double *Xc, const double *mid, const double *gamma, int N, int Np, int d, const CovParams &p,
                                     bool gram)
 {
-	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS || !Xc) return hipErrorInvalidValue;
-	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
-	if (gram && (!p.gram || !mid)) return hipErrorInvalidValue;
-	const dim3 grid((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
-	const size_t lds = (size_t)FT * predict_mean_grad_width(d) * sizeof(double);
-	if (gram) {
-		const hipError_t e = ensure_exp_table(s);
-		if (e != hipSuccess) return e;
-		launch_predict_mean_grad_kind<true>(s, grid, lds, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
-	} else launch_predict_mean_grad_kind<false>(s, grid, lds, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N, Np, d, p);
+	dim3 grid;
+	size_t lds;
+	const hipError_t e = query_grad_launch_shape(s, pstride, M, Xc, mid, Np, d, p, gram, grid, lds);
+	if (e != hipSuccess) return e;
+	dispatch_kind_form(p.kind, gram, [&](auto K, auto G) {
+		hipLaunchKernelGGL((predict_mean_grad_kernel<K(), G()>), grid, dim3(256), lds, s, mpart, gpart, pstride, Xq, M, X, Xc, mid, gamma, N,
+		                   Np, d, p);
+	});
 	return hipGetLastError();
 }
 
@@ -1347,8 +1432,9 @@ hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, c
 // so with a = L^-T u + W (Q r) (one N-vector per query, gpemu_predict_var_grad_dev's second product) and the weights g_i and
 // constants s_j of the mean's gradient
 //   d var / d x*_j = 2 s_j ((x*_j - mid_j) T_0 - T_j) + 2 sum_a (Q r)_a dh_a/dx_j,   T_0 = sum_i a_i g_i,  T_j = sum_i a_i g_i x'_ij.
-// The reduction is predict_mean_grad_kernel's with the shared gamma_i replaced by a per-query a_qi: the weight tile is made on
-// chip, multiplied element by element with a loaded tile of A and fed to the matrix unit against [1, x'_i].
+// The reduction is the mean gradient's with the shared gamma_i replaced by a per-query a_qi (query_grad_sweep<.., PERQ = true>,
+// predict_var_grad_kernel above): the weight tile is made on chip, multiplied element by element with a loaded tile of A
+// and fed to the matrix unit against [1, x'_i].
 // ---------------------------------------------------------------------------
 
 // V[q][Np + c], c in [0, Rp): 0 for c = 0 (the column that pairs with gamma in the second product), (Q r)_q[c - 1] for
@@ -1391,145 +1477,8 @@ hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const dou
 	return hipGetLastError();
 }
 
-// gpart: slices x pstride rows of pw = 16 ncb partial sums [T_0, T_1 .. T_d, 0 ..].  At: a as A^T, Np rows of lda >= the
-// query count rounded up to 64 (a multiple of 16): element (design i, query q) at At[i * lda + q].  The lane that holds
-// (design 16 j + g + 4 r of the tile, query 16 wave + q) loads its sixteen a values at the top of the tile, under the
-// distance product: per load instruction the sixteen lanes q of one g read one 128-byte run of row i, four runs a wave.
-// The tiling, the tile, the candidate / far-query / same-point rules, the clamp and the summation order are
-// predict_mean_grad_kernel's; there is no mean accumulator.  Padding columns i >= N and clamped entries have weight 0, rows
-// q >= M weight 0 as well (their a is not read as a number) and are never stored.
-template <int KIND, bool GRAM>
-__global__ __launch_bounds__(256, 2) void predict_var_grad_kernel(double *gpart, long pstride, const double *Xq, int M, const double *X,
-                                                                const double *Xc, const double *mid, const double *At, long lda, int N,
-                                                                int Np, int d, CovParams p)
-{
-	extern __shared__ double ys[];                 // FT x pw: [1, x'_i1 .. x'_id, 0 ..] of the current tile
-	__shared__ double tab[GRAM ? EXP_TAB_G : EXP_TAB];
-	__shared__ double wsc[GPEMU_MAX_PARAMS];
-	__shared__ double mid_s[GPEMU_MAX_PARAMS];
-	const int tid = threadIdx.x;
-	const int ntc = Np / FT, nsl = (ntc + MEAN_TPW - 1) / MEAN_TPW;
-	const int tr = blockIdx.x / nsl, slice = blockIdx.x % nsl, tc0 = slice * MEAN_TPW;
-	const int ncb = (d + 1 + 15) / 16, pw = 16 * ncb;
-	if (GRAM) {
-		gram_tables(p, d, tab, wsc);
-		if (tid < GPEMU_MAX_PARAMS) mid_s[tid] = (tid < d) ? mid[tid] : 0.0;
-	} else {
-		if (tid < EXP_TAB) tab[tid] = exp2((double)tid * (1.0 / EXP_TAB));
-		if (tid < GPEMU_MAX_PARAMS) wsc[tid] = (tid < d) ? p.w[(KIND == GPEMU_POWEREXP) ? tid : 0] : 0.0;
-	}
-	const int lane = tid & 63, wave = tid >> 6;
-	const int q = lane & 15, g = lane >> 4;
-	const int qrow = tr * FT + 16 * wave + q;
-	const bool qv = qrow < M;
-	d4g_t G[MGRAD_NCB];
-#pragma unroll
-	for (int cb = 0; cb < MGRAD_NCB; cb++) G[cb] = (d4g_t){0.0, 0.0, 0.0, 0.0};
-	for (int i = 0; i < MEAN_TPW; i++) {
-		const int tc = tc0 + i;
-		if (tc >= ntc) break;
-		// (rows tc FT + .. < Np and columns qrow < lda lie inside the block whatever N and M are)
-		d4g_t av[4];
-		{
-			const double *ap = At + (long)(tc * FT + g) * lda + qrow;
-#pragma unroll
-			for (int j = 0; j < 4; j++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) av[j][r] = ap[(long)(16 * j + 4 * r) * lda];
-		}
-		__syncthreads();                           // the tables (first tile); the previous tile's ys has been read
-		for (int rr = 0; rr < 4; rr++) {
-			const int r = (tid >> 4) + 16 * rr, gi = tc * FT + r;
-			for (int cb = 0; cb < ncb; cb++) {
-				const int c = 16 * cb + (tid & 15);
-				double v = 0.0;
-				if (gi < N && c <= d) v = (c == 0) ? 1.0 : Xc[(long)gi * d + c - 1];
-				ys[r * pw + c] = v;
-			}
-		}
-		__syncthreads();
-		d4g_t acc[4];
-		unsigned same = 0;
-		if (GRAM) {
-			same = gram_tile_u2_qcol<KIND>(acc, Xq, mid_s, M, X, Xc, N, d, p, tr, tc, wsc);
-		} else {
-			// squared scaled distances from differences, as in predict_mean_grad_kernel's difference form
-#pragma unroll
-			for (int j = 0; j < 4; j++) acc[j] = (d4g_t){0.0, 0.0, 0.0, 0.0};
-			const double *qp = Xq + (long)(qv ? qrow : 0) * d;
-			const double *xp[4];
-#pragma unroll
-			for (int r = 0; r < 4; r++) xp[r] = X + (long)(tc * FT + g + 4 * r) * d;      // (+ 16 j below, clamped per element)
-			for (int k = 0; k < d; k++) {
-				const double wk = wsc[k];
-				const double xr = qv ? qp[k] * wk : 0.0;
-#pragma unroll
-				for (int j = 0; j < 4; j++)
-#pragma unroll
-					for (int r = 0; r < 4; r++) {
-						const bool cv = tc * FT + 16 * j + g + 4 * r < N;
-						const double xc = cv ? xp[r][(long)16 * j * d + k] * wk : 0.0;
-						const double diff = xr - xc;
-						acc[j][r] = fma(diff, diff, acc[j][r]);
-					}
-			}
-			bool cand = false;
-#pragma unroll
-			for (int j = 0; j < 4; j++)
-#pragma unroll
-				for (int r = 0; r < 4; r++) cand = cand || (acc[j][r] <= p.cand);
-			if (__any(cand)) {
-#pragma unroll 1
-				for (int e = 0; e < 16; e++) {
-					const int r = e >> 2, j = e & 3;
-					double ae = HUGE_VAL;
-#pragma unroll
-					for (int rr = 0; rr < 4; rr++)
-#pragma unroll
-						for (int jj = 0; jj < 4; jj++) ae = (rr == r && jj == j) ? acc[jj][rr] : ae;
-					const int col = tc * FT + 16 * j + g + 4 * r;
-					if (ae <= p.cand && qv && col < N) {
-						int cnt = 0;
-						for (int k = 0; k < d; k++) cnt += (fabs(qp[k] - X[(long)col * d + k]) < p.eps) ? 1 : 0;
-						if (cnt == d) same |= 1u << e;
-					}
-				}
-			}
-		}
-		const bool plain = (tc * FT + FT <= N) && !__any(same != 0);
-		const double *yb = ys + g * pw + q;
-#pragma unroll
-		for (int r = 0; r < 4; r++) {
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				double gw;
-				double v = GRAM ? cov_grad_from_u2_gram<KIND>(acc[j][r], tab, gw) : cov_grad_from_a_diff<KIND>(acc[j][r], p.amp, tab, gw);
-				if (!plain && (same & (1u << (4 * r + j)))) v += p.nug;
-				// emulator.c:588-590 and its derivative; a padding column's distance was not held at the exponent limit and a
-				// padding row's a is whatever the buffer held: neither is used as a number
-				const bool live = qv && (plain || tc * FT + 16 * j + g + 4 * r < N) && !(v < 1E-10);
-				const double wgt = live ? gw * av[j][r] : 0.0;
-#pragma unroll
-				for (int cb = 0; cb < MGRAD_NCB; cb++)
-					if (cb < ncb) G[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(wgt, yb[(16 * j + 4 * r) * pw + 16 * cb], G[cb], 0, 0, 0);
-				if (j & 1) __builtin_amdgcn_sched_barrier(0);
-			}
-		}
-	}
-	// D register r of block cb: (query 16 wave + g + 4 r, column 16 cb + q)
-#pragma unroll
-	for (int cb = 0; cb < MGRAD_NCB; cb++)
-		if (cb < ncb) {
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const int row = tr * FT + 16 * wave + g + 4 * r;
-				if (row < M) gpart[((long)slice * pstride + row) * pw + 16 * cb + q] = G[cb][r];
-			}
-		}
-}
-
 // grad[q][j] = 2 s_j ((x*_j - mid_j) T_0 - T_j) + 2 sum_a (Q r)_a dh_a/dx_j, the slices added in index order; (Q r)_a from
-// V[q][Np + 1 + a] (predict_qr_kernel); basis and s_j as in predict_mean_grad_finish_kernel
+// V[q][Np + 1 + a] (predict_qr_kernel)
 __global__ __launch_bounds__(256) void predict_var_grad_finish_kernel(const double *gpart, long pstride, int pw, int nslice, int M, int nreg,
                                                                       int d, const double *Xq, const double *mid, const double *V, long ldv,
                                                                       int Np, CovParams p, double *grad)
@@ -1544,31 +1493,9 @@ __global__ __launch_bounds__(256) void predict_var_grad_finish_kernel(const doub
 		Tj += row[1 + j];
 	}
 	const double xj = Xq[(long)q * d + j];
-	double sj;
-	if (p.kind == GPEMU_POWEREXP) sj = 2.0 * p.w[j] * p.w[j];                       // w = sqrt(1/2) / r_j: 1 / r_j^2
-	else if (p.kind == GPEMU_MATERN32) sj = (1.732050808 * 1.732050808) * (p.w[0] * p.w[0]);
-	else sj = p.w[0] * p.w[0];
-	const double *qr = V + (long)q * ldv + Np + 1;
-	const int order = (nreg - 1) / d;
-	double dh = 0.0;
-	for (int o = 1; o <= order; o++) {
-		const double b = qr[1 + (o - 1) * d + j];
-		dh = fma(o == 1 ? 1.0 : (o == 2 ? 2.0 * xj : 3.0 * xj * xj), b, dh);
-	}
+	const double sj = grad_dim_scale(p, j);
+	const double dh = hfun_grad_dot(V + (long)q * ldv + Np + 1, nreg, d, j, xj);
 	grad[e] = 2.0 * (sj * ((xj - (mid ? mid[j] : 0.0)) * T0 - Tj) + dh);
-}
-
-template <bool GRAM>
-static void launch_predict_var_grad_kind(hipStream_t s, dim3 grid, size_t lds, double *gpart, long pstride, const double *Xq, int M,
-                                         const double *X, const double *Xc, const double *mid, const double *At, long lda, int N, int Np,
-                                         int d, const CovParams &p)
-{
-	if (p.kind == GPEMU_POWEREXP)
-		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_POWEREXP, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
-	else if (p.kind == GPEMU_MATERN32)
-		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_MATERN32, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
-	else
-		hipLaunchKernelGGL((predict_var_grad_kernel<GPEMU_MATERN52, GRAM>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
 }
 
 // gpart: predict_mean_slices(Np) x pstride x predict_mean_grad_width(d); pstride >= M; At: Np x lda, lda >= M rounded up to 64.
@@ -1576,17 +1503,15 @@ static void launch_predict_var_grad_kind(hipStream_t s, dim3 grid, size_t lds, d
 hipError_t launch_predict_var_grad(hipStream_t s, double *gpart, long pstride, const double *Xq, int M, const double *X, const double *Xc,
                                    const double *mid, const double *At, long lda, int N, int Np, int d, const CovParams &p, bool gram)
 {
-	if (Np % FT || M < 1 || pstride < M || d < 1 || d > GPEMU_MAX_PARAMS || !Xc || !At) return hipErrorInvalidValue;
-	if (lda % 16 || lda < (long)((M + FT - 1) / FT) * FT) return hipErrorInvalidValue;
-	if (p.kind < GPEMU_POWEREXP || p.kind > GPEMU_MATERN52) return hipErrorInvalidValue;
-	if (gram && (!p.gram || !mid)) return hipErrorInvalidValue;
-	const dim3 grid((unsigned)(((M + FT - 1) / FT) * predict_mean_slices(Np)));
-	const size_t lds = (size_t)FT * predict_mean_grad_width(d) * sizeof(double);
-	if (gram) {
-		const hipError_t e = ensure_exp_table(s);
-		if (e != hipSuccess) return e;
-		launch_predict_var_grad_kind<true>(s, grid, lds, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
-	} else launch_predict_var_grad_kind<false>(s, grid, lds, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np, d, p);
+	if (!At || lda % 16 || lda < (long)((M + FT - 1) / FT) * FT) return hipErrorInvalidValue;
+	dim3 grid;
+	size_t lds;
+	const hipError_t e = query_grad_launch_shape(s, pstride, M, Xc, mid, Np, d, p, gram, grid, lds);
+	if (e != hipSuccess) return e;
+	dispatch_kind_form(p.kind, gram, [&](auto K, auto G) {
+		hipLaunchKernelGGL((predict_var_grad_kernel<K(), G()>), grid, dim3(256), lds, s, gpart, pstride, Xq, M, X, Xc, mid, At, lda, N, Np,
+		                   d, p);
+	});
 	return hipGetLastError();
 }
 
