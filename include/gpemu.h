@@ -279,6 +279,30 @@ int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int npoints, double *mean /* 
 int gpemu_predict_var_grad_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */,
                                double *var_dev /* may be NULL */, double *grad_dev);
 
+/* ---- joint posterior covariance between the query points of one call ----
+ * cov[p*M + q] = Sigma_pq, the covariance between the emulator's errors at x*_p and x*_q (the "full predictive covariance"):
+ *   Sigma_pq = c(x*_p, x*_q) - u_p . u_q + r_p^T Q r_q,   u_p = L^-1 k_p,  r_p = h(x*_p) - W^T k_p,
+ * k_p the clamped k-vector of gpemu_predict_batch, c(.,.) the covariance function as gpemu_cov_matrix evaluates it on two
+ * design rows: not clamped, with the reference's nugget rule (the nugget is added when every coordinate differs by less than
+ * 1e-10, pow-exp, or 1e-16, Matern), GPEMU_MODE_MATERN_LOG honoured.  So Sigma_pp is gpemu_predict_batch's variance to
+ * rounding; two identical query rows give identical rows and columns (Sigma is then singular, as the reference's C is for a
+ * duplicated design row); Sigma is symmetric bit for bit (the upper triangle is a copy of the lower) and positive
+ * semi-definite up to rounding.  mean (M values, may be NULL) agrees with gpemu_predict_batch to rounding.
+ * Cost: the prediction sweep's M N^2 flops plus M^2 N for the symmetric product, 8 M^2 bytes of result; few queries take the
+ * same kernels on one 64-row tile.  1 <= npoints <= 16384 (one block: 2 GB of result at the top); a larger npoints, a NULL
+ * xq or cov: GPEMU_ERR_ARG before anything is allocated or launched.  GPEMU_ERR_STATE without a prediction set-up, and from
+ * the host-buffer entry while a host-buffer batch of any kind is pending on the context (it stages through the same buffers;
+ * the pending batch stays collectable).  Regression limits as for gpemu_predict_var_grad.  No enqueue / collect pair: the
+ * result is M^2 numbers, not M.  The host-buffer entry keeps its 8 M^2-byte device copy until the model is freed.
+ * Two identical calls return the same bits; the host and _dev entries and a context set up by gpemu_predict_setup_batch
+ * return the same bits; no atomics.  The entry uses the batch buffers of gpemu_predict_batch and leaves nothing the other
+ * prediction entries read. */
+int gpemu_predict_cov(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */, double *mean /* M, may be NULL */,
+                      double *cov /* M*M row-major, both triangles */);
+/* device pointers: only enqueues on the context's stream (the first call sizes the scratch) */
+int gpemu_predict_cov_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */,
+                          double *cov_dev /* M*M */);
+
 /* ---- leave-one-out validation of a trained emulator -----------------
  * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
  * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
@@ -340,6 +364,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_MEAN    8   /* the two launches of the mean-only sweep: flops = M*N*(kernel + 2) with kernel = 3 d (the squared distance), bytes = 8*M*(d+1) */
 #define GPEMU_PROF_MEAN_GRAD 9 /* the two launches of the mean-gradient sweep: flops = M*N*(3 d + 2 + 2 (d + 1)), bytes = 8*M*(2 d + 1) */
 #define GPEMU_PROF_VAR_GRAD 10 /* the fused sweep of the variance-gradient entry and its finish: flops = M*N*(3 d + 1 + 2 (d + 1)), bytes = 8*M*(N + 2 d); its two products report under GPEMU_PROF_GEMM */
+#define GPEMU_PROF_COV     11  /* the prior and mirror launches of gpemu_predict_cov[_dev]: bytes = 8*M*M (the lower triangle written once, mirrored once); its symmetric product reports under GPEMU_PROF_GEMM */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

@@ -19,6 +19,7 @@ PROF_LOO = 7
 PROF_MEAN = 8
 PROF_MEAN_GRAD = 9
 PROF_VAR_GRAD = 10
+PROF_COV = 11
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -109,6 +110,8 @@ SYMBOLS = {
     "gpemu_predict_var_grad_enqueue": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "gpemu_predict_var_grad_collect": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "gpemu_predict_var_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_cov": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "gpemu_predict_cov_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -505,6 +508,20 @@ class Context:
 
     def predict_var_grad_collect(self):
         return self._pred_collect("var_grad", "mvg")
+
+    # the joint posterior covariance between the query points of one call: the sweep of predict_batch plus
+    # one symmetric M^2 N product; uses the batch buffers of predict_batch
+    def predict_cov(self, Xq, want_mean=True):
+        """-> (mean[M] or None, cov[M, M]); cov is the covariance itself, both triangles"""
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        mean = np.empty(M) if want_mean else None
+        cov = np.empty((M, M))
+        self._chk(self.L.gpemu_predict_cov(self.h, M, _p(Xq), _p(mean) if want_mean else None, _p(cov)))
+        return mean, cov
+
+    def predict_cov_dev(self, M, xq_dev, mean_dev, cov_dev):
+        self._chk(self.L.gpemu_predict_cov_dev(self.h, M, xq_dev, mean_dev, cov_dev))
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

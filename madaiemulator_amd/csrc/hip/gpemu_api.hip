@@ -263,7 +263,8 @@ static void free_model(gpemu_ctx *ctx)
 	free_graphs(ctx);
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
 	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
-	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad, &ctx->dLinvAugT, &ctx->dVGradPart})
+	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad, &ctx->dLinvAugT, &ctx->dVGradPart, &ctx->dCovR,
+	                &ctx->dCov})
 		b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
@@ -1623,6 +1624,82 @@ extern "C" int gpemu_predict_var_grad_collect(gpemu_ctx *ctx, int M, double *mea
 extern "C" int gpemu_predict_var_grad(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *var, double *grad)
 {
 	return pred_sync(ctx, PRED_VAR_GRAD, M, xq, mean, var, grad);
+}
+
+// ---------------------------------------------------------------------------
+// joint posterior covariance between the M query points of one call (gpemu.h):
+//   Sigma_pq = c(x*_p, x*_q) - u_p . u_q + r_p^T Q r_q,   u = L^-1 k,  r = h(x*) - W^T k.
+// ONE block of up to PRED_BATCH_MAX queries.  The k-vectors, V = Kq LinvAug^T (K never split: the u rows must be whole), the
+// finish and Q r per query as in gpemu_predict_var_grad_dev, r kept beside; then the prior tiles c + r . (Q r) on the lower
+// triangle of Sigma, the symmetric product Sigma -= U U^T on the GEMM of the factorisation's trailing update (tri, alpha = -1,
+// beta = 1, A = B = dV, k over the Np columns of u) and the mirror.  The product works on Sigma in place with ldc = M: the GEMM
+// moves C by single elements, so an odd M needs no padded scratch (its A and B rows are rows of dV, whose leading dimension
+// Np + Rp is a multiple of 64).  Uses dKq, dV and its own dCovR; everything only enqueued on the context's stream.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_predict_cov_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *cov_dev)
+{
+	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq_dev || !cov_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int Np = ctx->Np, Rp = ctx->Rp, d = ctx->d;
+	const int mbp = round_up(M, 64);
+	int rc = ensure_pred_batch(ctx, mbp);
+	if (!rc) rc = grow(ctx, ctx->dCovR, (size_t)mbp * Rp + 2 * (size_t)mbp);
+	if (rc) return rc;
+	double *rkeep = ctx->dCovR, *spare = rkeep + (size_t)mbp * Rp;
+	const long ldv = (long)Np + Rp;
+	const CovParams &p = ctx->pred_cov;
+	{
+		ProfScope ps(ctx, GPEMU_PROF_FILL, 0.0, 8.0 * (double)mbp * Np);
+		HIPCHK(ctx, fill_kvectors(ctx, ctx->dKq, xq_dev, M, mbp, p));
+	}
+	HIPCHK(ctx, launch_aug_product(ctx, aug_product_args(ctx, M)));
+	HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, ldv, M, Np, ctx->nreg, ctx->order, d, xq_dev, ctx->dBetaQ, ctx->kappa,
+	                                  mean_dev ? mean_dev : spare, spare + mbp, 1, (long)mbp * ldv));
+	HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, M, Np, Rp, ctx->nreg, d, xq_dev, ctx->dBetaQ, rkeep));
+	if (prof_on(ctx, GPEMU_PROF_COV)) { ctx->prof.tag.push_back("predict_cov_prior"); ctx->prof.tag.push_back("predict_cov_mirror"); }
+	{
+		// flops: per element of the lower triangle the squared distance (3 d) and the regression sum (2 nreg); bytes: the lower
+		// triangle written once here, mirrored once below
+		ProfScope ps(ctx, GPEMU_PROF_COV, 0.5 * M * (double)M * (3.0 * d + 2.0 * ctx->nreg), 4.0 * M * (double)M);
+		HIPCHK(ctx, launch_predict_cov_prior(ctx->stream, cov_dev, M, xq_dev, M, d, p, rkeep, Rp, ctx->dV, ldv, Np, ctx->nreg));
+	}
+	GemmArgs g{};
+	g.C = cov_dev; g.ldc = M;
+	g.A = ctx->dV; g.lda = ldv;
+	g.B = ctx->dV; g.ldb = ldv;
+	g.m = M; g.n = M; g.k0 = 0; g.k1 = Np; g.alpha = -1.0; g.beta = 1; g.tri = 1;
+	HIPCHK(ctx, gemm(ctx, g));
+	{
+		ProfScope ps(ctx, GPEMU_PROF_COV, 0.0, 4.0 * M * (double)M);
+		HIPCHK(ctx, launch_predict_cov_mirror(ctx->stream, cov_dev, M, M));
+	}
+	return GPEMU_OK;
+}
+
+// host buffers: the queries go through the staging of the other host-buffer entries (hence not while one of their batches is
+// pending), the result through dCov; every copy on the context's stream.  No enqueue / collect pair: the result is M^2 numbers.
+extern "C" int gpemu_predict_cov(gpemu_ctx *ctx, int M, const double *xq, double *mean, double *cov)
+{
+	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq || !cov) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending.kind != PRED_NONE) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d;
+	int rc = ensure_pred_stage(ctx, M);
+	if (!rc) rc = grow(ctx, ctx->dCov, (size_t)M * M, false, "out of device memory for the joint covariance (8 M^2 bytes)");
+	if (rc) return rc;
+	const size_t cap = ctx->stage_cap();
+	double *hx = ctx->hStage, *hm = hx + cap * d;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	rc = gpemu_predict_cov_dev(ctx, M, ctx->dXq, mean ? (double *)ctx->dMean : nullptr, ctx->dCov);
+	if (rc) return rc;
+	if (mean) HIPCHK(ctx, hipMemcpyAsync(hm, ctx->dMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(cov, ctx->dCov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (mean) memcpy(mean, hm, (size_t)M * sizeof(double));
+	return GPEMU_OK;
 }
 
 // ---------------------------------------------------------------------------

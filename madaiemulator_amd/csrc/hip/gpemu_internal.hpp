@@ -265,6 +265,10 @@ struct gpemu_ctx {
 	// The entry also uses dKq and dV, as gpemu_predict_batch does.
 	bool linvT_ready = false;
 	gpemu::DevBuf<double> dLinvAugT, dVGradPart;
+	// joint-covariance entry (gpemu_predict_cov).  dCovR: the r rows of a call (M' x Rp, M' = M rounded up to 64),
+	// then two rows of M' for a mean the caller did not ask for and the variance nobody reads; dCov: the M x M result of the
+	// host-buffer entry before it is copied out.  The entry also uses dKq and dV, as gpemu_predict_batch does.
+	gpemu::DevBuf<double> dCovR, dCov;
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
@@ -342,7 +346,13 @@ hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, c
 // the variance's gradient (gpemu_predict_var_grad): (Q r) per query into V's columns Np .. Np + Rp, the fused
 // sweep over A^T (Np x lda, the second product's output), the finish in slice order
 hipError_t launch_predict_qr(hipStream_t s, double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
-                             const double *betaQ);
+                             const double *betaQ, double *rkeep = nullptr);
+// the joint posterior covariance (gpemu_predict_cov): c(x*_p, x*_q) + r_p . (Q r)_q on the lower 64 x 64 tiles of
+// S (M x M, leading dimension lds) -- R: the r rows predict_qr kept (M x ldr), V: its Q r in columns Np + 1 .. --, and the copy
+// of the strict lower triangle into the upper one
+hipError_t launch_predict_cov_prior(hipStream_t s, double *S, long lds, const double *Xq, int M, int d, const CovParams &p,
+                                    const double *R, long ldr, const double *V, long ldv, int Np, int nreg);
+hipError_t launch_predict_cov_mirror(hipStream_t s, double *S, long lds, int M);
 hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const double *src, long lds, int rows, int cols);
 hipError_t launch_predict_var_grad(hipStream_t s, double *gpart, long pstride, const double *Xq, int M, const double *X, const double *Xc,
                                    const double *mid, const double *At, long lda, int N, int Np, int d, const CovParams &p, bool gram);

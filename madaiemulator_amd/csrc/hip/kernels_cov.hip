@@ -129,9 +129,12 @@ __device__ __forceinline__ void lower_tile(long t, int &tr, int &tc)
 	tc = (int)(t - (long)r * (r + 1) / 2);
 }
 
-// one FT x FT tile (tr, tc) of the fill
-__device__ __forceinline__ void cov_fill_tile(double *out, long ld, const double *Xr, int nr, const double *Xc, int nc, int d,
-                                              const CovParams &p, int mode, int tr, int tc)
+// the elements of one FT x FT tile (tr, tc) of the fill: emit(t, row, col, v) receives element (row tr * FT + (tid >> 6) + 4 t,
+// column tc * FT + (tid & 63)), t = 0 .. 15, where the value is made.  Shared by the stored fill (cov_fill_tile) and the prior
+// tile of the joint posterior covariance (predict_cov_prior_kernel).
+template <class Emit>
+__device__ __forceinline__ void cov_tile_values(const double *Xr, int nr, const double *Xc, int nc, int d, const CovParams &p, int mode,
+                                                int tr, int tc, Emit &&emit)
 {
 	__shared__ double xr_s[FT * (GPEMU_MAX_PARAMS + 1)];
 	__shared__ double tab[EXP_TAB];
@@ -192,8 +195,15 @@ __device__ __forceinline__ void cov_fill_tile(double *out, long ld, const double
 		} else {
 			v = ((mode & FILL_IDENT_PAD) && row == col) ? 1.0 : 0.0;
 		}
-		out[(long)row * ld + col] = v;
+		emit(t, row, col, v);
 	}
+}
+
+// one FT x FT tile (tr, tc) of the fill
+__device__ __forceinline__ void cov_fill_tile(double *out, long ld, const double *Xr, int nr, const double *Xc, int nc, int d,
+                                              const CovParams &p, int mode, int tr, int tc)
+{
+	cov_tile_values(Xr, nr, Xc, nc, d, p, mode, tr, tc, [&](int, int row, int col, double v) { out[(long)row * ld + col] = v; });
 }
 
 // ---------------------------------------------------------------------------
@@ -1440,8 +1450,9 @@ hipError_t launch_predict_mean_grad_finish(hipStream_t s, const double *mpart, c
 // V[q][Np + c], c in [0, Rp): 0 for c = 0 (the column that pairs with gamma in the second product), (Q r)_q[c - 1] for
 // 1 <= c <= nreg (the columns that pair with W^T), 0 beyond.  r is read from the same columns (W^T k, left there by the
 // first product) before anything is written: one wave per query, reads and writes on either side of the barrier.
+// rkeep (optional, M x Rp): r itself, which the joint covariance needs beside Q r (gpemu_predict_cov_dev).
 __global__ __launch_bounds__(256) void predict_qr_kernel(double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
-                                                         const double *betaQ)
+                                                         const double *betaQ, double *rkeep)
 {
 	__shared__ double r_s[4][64];
 	const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
@@ -1451,6 +1462,7 @@ __global__ __launch_bounds__(256) void predict_qr_kernel(double *V, long ldv, in
 	r_s[w][c] = (qv && c < nreg) ? hfun(c, Xq + (long)q * d, d) - v[1 + c] : 0.0;
 	__syncthreads();
 	if (!qv) return;
+	if (rkeep) rkeep[(long)q * Rp + c] = r_s[w][c];
 	const double *Q = betaQ + nreg;
 	for (int col = c; col < Rp; col += 64) {
 		double t = 0.0;
@@ -1461,10 +1473,96 @@ __global__ __launch_bounds__(256) void predict_qr_kernel(double *V, long ldv, in
 }
 
 hipError_t launch_predict_qr(hipStream_t s, double *V, long ldv, int M, int Np, int Rp, int nreg, int d, const double *Xq,
-                             const double *betaQ)
+                             const double *betaQ, double *rkeep)
 {
-	if (M < 1 || nreg < 1 || nreg > 63 || nreg + 1 > Rp) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(predict_qr_kernel, dim3((M + 3) / 4), dim3(256), 0, s, V, ldv, M, Np, Rp, nreg, d, Xq, betaQ);
+	if (M < 1 || nreg < 1 || nreg > 63 || nreg + 1 > Rp || (rkeep && Rp < 64)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(predict_qr_kernel, dim3((M + 3) / 4), dim3(256), 0, s, V, ldv, M, Np, Rp, nreg, d, Xq, betaQ, rkeep);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Joint posterior covariance between the M query points of a call (gpemu_predict_cov):
+//   Sigma_pq = c(x*_p, x*_q) - u_p . u_q + r_p^T Q r_q
+// predict_cov_prior_kernel writes c + r_p . (Q r)_q on the lower 64 x 64 tiles of Sigma (one workgroup per tile, one pass),
+// the symmetric product Sigma -= U U^T follows on the GEMM, predict_cov_mirror_kernel copies the strict lower triangle into
+// the upper one.  c is the element of the unclamped fill (cov_tile_values with mode 0: what gpemu_cov_matrix evaluates on two
+// design rows -- difference form, nugget rule, exponent hold); r (rkeep of predict_qr_kernel, M x ldr) and Q r (V's columns
+// Np + 1 ..) of the tile's 64 row and 64 column queries are staged in LDS, Q r transposed so that the lanes of a wave read
+// consecutive words and r is a broadcast; the regression sum runs in index order.  Dynamic LDS: 2 * 64 * nreg doubles.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void predict_cov_prior_kernel(double *S, long lds_, const double *Xq, int M, int d, CovParams p,
+                                                                const double *R, long ldr, const double *V, long ldv, int Np, int nreg)
+{
+	extern __shared__ double cov_reg_s[];
+	double *r_s = cov_reg_s;                    // [row of the tile][a]
+	double *qr_s = cov_reg_s + FT * nreg;       // [a][column of the tile]
+	int tr, tc;
+	lower_tile(blockIdx.x, tr, tc);
+	const int tid = threadIdx.x;
+	for (int e = tid; e < FT * nreg; e += 256) {
+		const int i = e / nreg, a = e % nreg;
+		const int gr = tr * FT + i, gc = tc * FT + i;
+		r_s[i * nreg + a] = gr < M ? R[(long)gr * ldr + a] : 0.0;
+		qr_s[a * FT + i] = gc < M ? V[(long)gc * ldv + Np + 1 + a] : 0.0;
+	}
+	double v[16];
+	cov_tile_values(Xq, M, Xq, M, d, p, 0, tr, tc, [&](int t, int, int, double c) { v[t] = c; });       // (its barrier also covers the staging above)
+	const int cl = tid & 63, rsub = tid >> 6;
+	double reg[16];
+#pragma unroll
+	for (int t = 0; t < 16; t++) reg[t] = 0.0;
+	for (int a = 0; a < nreg; a++) {
+		const double qr = qr_s[a * FT + cl];
+#pragma unroll
+		for (int t = 0; t < 16; t++) reg[t] = fma(r_s[(rsub + 4 * t) * nreg + a], qr, reg[t]);
+	}
+	const int col = tc * FT + cl;
+	if (col >= M) return;
+#pragma unroll
+	for (int t = 0; t < 16; t++) {
+		const int row = tr * FT + rsub + 4 * t;
+		if (row < M) S[(long)row * lds_ + col] = v[t] + reg[t];
+	}
+}
+
+// Sigma_qp = Sigma_pq for p > q: the workgroup of lower tile (tr, tc) reads it as whole row pieces into LDS and writes the
+// transposed tile (tc, tr) as whole row pieces; a diagonal tile writes its strict upper part only, after the barrier.
+__global__ __launch_bounds__(256) void predict_cov_mirror_kernel(double *S, long lds_, int M)
+{
+	__shared__ double t_s[FT * (FT + 1)];
+	int tr, tc;
+	lower_tile(blockIdx.x, tr, tc);
+	const int cl = threadIdx.x & 63, rsub = threadIdx.x >> 6;
+#pragma unroll
+	for (int t = 0; t < 16; t++) {
+		const int i = rsub + 4 * t;
+		const int row = tr * FT + i, col = tc * FT + cl;
+		t_s[i * (FT + 1) + cl] = (row < M && col < M) ? S[(long)row * lds_ + col] : 0.0;
+	}
+	__syncthreads();
+#pragma unroll
+	for (int t = 0; t < 16; t++) {
+		const int i = rsub + 4 * t;
+		const int row = tc * FT + i, col = tr * FT + cl;       // of the upper tile: element (i, cl) = lower element (cl, i)
+		if (row < col && col < M) S[(long)row * lds_ + col] = t_s[cl * (FT + 1) + i];
+	}
+}
+
+hipError_t launch_predict_cov_prior(hipStream_t s, double *S, long lds_, const double *Xq, int M, int d, const CovParams &p,
+                                    const double *R, long ldr, const double *V, long ldv, int Np, int nreg)
+{
+	if (M < 1 || nreg < 1 || nreg > 63 || ldr < nreg || lds_ < M) return hipErrorInvalidValue;
+	const long nt = (long)((M + FT - 1) / FT);
+	hipLaunchKernelGGL(predict_cov_prior_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 2 * FT * nreg * sizeof(double), s, S, lds_,
+	                   Xq, M, d, p, R, ldr, V, ldv, Np, nreg);
+	return hipGetLastError();
+}
+
+hipError_t launch_predict_cov_mirror(hipStream_t s, double *S, long lds_, int M)
+{
+	if (M < 1 || lds_ < M) return hipErrorInvalidValue;
+	const long nt = (long)((M + FT - 1) / FT);
+	hipLaunchKernelGGL(predict_cov_mirror_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, S, lds_, M);
 	return hipGetLastError();
 }
 

@@ -117,6 +117,28 @@ void emulator::QueryEmulatorGradients(const std::vector<std::vector<double> > &x
 	}
 }
 
+void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+                                       std::vector<std::vector<double> > &Covariances)
+{
+	const size_t np = xpoints.size();
+	std::vector<double> flat(np * number_params), m(np * number_outputs), c((size_t)number_outputs * np * np);
+	for (size_t q = 0; q < np; q++) {
+		if ((int)xpoints[q].size() != number_params) {
+			std::cerr << "Error::QueryEmulatorCovariance called with incorrect number of dimensions in xpoint" << std::endl;
+			gpemu_host_exit(EXIT_FAILURE);
+		}
+		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
+	}
+	gsl_matrix view;
+	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	emulate_points_multi_cov(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), c.data());
+	Means.assign(np, std::vector<double>(number_outputs));
+	for (size_t q = 0; q < np; q++)
+		for (int i = 0; i < number_outputs; i++) Means[q][i] = m[q * number_outputs + i];
+	Covariances.assign(number_outputs, std::vector<double>());
+	for (int i = 0; i < number_outputs; i++) Covariances[i].assign(c.begin() + (size_t)i * np * np, c.begin() + (size_t)(i + 1) * np * np);
+}
+
 void emulator::QueryEmulator(const std::vector<double> &xpoint, std::vector<double> &Means, std::vector<double> &Errors)
 {
 	if ((int)xpoint.size() != number_params) {

@@ -35,6 +35,12 @@ public:
 	void QueryEmulatorGradients(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
 	                            std::vector<std::vector<double> > &Variances, std::vector<std::vector<double> > &MeanGradients,
 	                            std::vector<std::vector<double> > &VarianceGradients);
+	// the means and, per output, the joint posterior covariance between the query points: Covariances[t] is the flattened
+	// xpoints.size() x xpoints.size() matrix of output t, row-major (points p, q at p * xpoints.size() + q).  The COVARIANCE,
+	// not a square root: QueryEmulator returns Errors = sqrt(variance), so Covariances[t][q * (np + 1)] = Errors[q][t]^2 to
+	// rounding.  Covariances between different outputs are not modelled (libemu.h: emulate_points_multi_cov).
+	void QueryEmulatorCovariance(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+	                             std::vector<std::vector<double> > &Covariances);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -1029,6 +1029,47 @@ void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, d
 	emulate_points_grad_collect(e, (int)points->size1, mean, variance, grad_mean, grad_variance);
 }
 
+/* the joint posterior covariance between the query points (gpemu_predict_cov in gpemu.h): cov is npoints x npoints row-major,
+ * both triangles; mean may be NULL */
+void emulate_points_cov(emulator_struct *e, gsl_matrix *points, double *mean, double *cov)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	double *q = pack_matrix(points);
+	int rc = gpemu_predict_cov(en->ctx, (int)points->size1, q, mean, cov);
+	free(q);
+	if (rc) die(en->ctx, rc, "emulate_points_cov");
+}
+
+/* its two halves, like emulate_loo_enqueue / _collect: the queries go up, gpemu_predict_cov_dev is enqueued on the component's
+ * own stream and the results wait in a device buffer (queries, means, the matrix); collect downloads them, which waits for
+ * that stream only, and releases the buffer */
+void emulate_points_cov_enqueue(emulator_struct *e, gsl_matrix *points, void **dev_out)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	const size_t np = points->size1, d = points->size2;
+	double *q = pack_matrix(points);
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(en->ctx, (np * d + np + np * np) * sizeof(double), &dev);
+	if (!rc) rc = gpemu_dev_upload(en->ctx, dev, q, np * d * sizeof(double));
+	free(q);
+	if (!rc) rc = gpemu_predict_cov_dev(en->ctx, (int)np, (const double *)dev, (double *)dev + np * d, (double *)dev + np * d + np);
+	if (rc) die(en->ctx, rc, "emulate_points_cov");
+	*dev_out = dev;
+}
+
+void emulate_points_cov_collect(emulator_struct *e, void *dev, int npoints, double *mean, double *cov)
+{
+	struct entry *en = lookup(e, 0);
+	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	const size_t np = (size_t)npoints, d = (size_t)en->d;
+	int rc = mean ? gpemu_dev_download(en->ctx, mean, (const double *)dev + np * d, np * sizeof(double)) : 0;
+	if (!rc) rc = gpemu_dev_download(en->ctx, cov, (const double *)dev + np * d + np, np * np * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	if (rc) die(en->ctx, rc, "emulate_points_cov");
+}
+
 /* leave-one-out at every training point (gpemu_loo) */
 void emulate_loo(emulator_struct *e, double *mean, double *variance)
 {

@@ -262,6 +262,14 @@ void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *m
 void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *variance, double *grad_mean, double *grad_variance);
 void emulate_points_grad_enqueue(emulator_struct *e, gsl_matrix *points);
 void emulate_points_grad_collect(emulator_struct *e, int npoints, double *mean, double *variance, double *grad_mean, double *grad_variance);
+/* extension: the joint posterior covariance between the query points (gpemu_predict_cov in gpemu.h): cov[p * npoints + q] is
+ * the covariance between the emulator's errors at rows p and q of points (both triangles; its diagonal is emulate_points'
+ * variance to rounding), mean (npoints, may be NULL) the posterior mean.  At most 16384 points.  Errors end in
+ * gpemu_host_fatal. */
+void emulate_points_cov(emulator_struct *e, gsl_matrix *points, double *mean, double *cov);
+/* emulate_points_cov in two halves, like emulate_loo_enqueue / _collect: *dev_out is the device buffer the results wait in */
+void emulate_points_cov_enqueue(emulator_struct *e, gsl_matrix *points, void **dev_out);
+void emulate_points_cov_collect(emulator_struct *e, void *dev, int npoints, double *mean, double *cov);
 /* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
  * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
 void emulate_loo(emulator_struct *e, double *mean, double *variance);
@@ -298,6 +306,15 @@ void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int
  * before the first is collected. */
 void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out,
                                double *grad_mean_out, double *grad_var_out);
+/* the joint posterior covariance between the query points, one npoints x npoints matrix per output: cov_out is nr x npoints x
+ * npoints in PCA space (component c's matrix, the bits of emulate_points_cov on it), nt x npoints x npoints in observable space
+ * by the reference's variance rule (multivar_support.c:118-157) applied to every element,
+ *   cov_Y[t] = sum_c evecs[t][c]^2 evals[c] Sigma_c,
+ * whose diagonal is what emulate_points_multi returns as variance (to rounding: that entry sums in another order).  mean_out
+ * (may be NULL) is npoints x nr or nt as emulate_points_multi lays it out.  Every component's device call is started before
+ * the first is waited for.  Covariances BETWEEN outputs are not modelled here, as they are not in the reference: its PCA
+ * components are independent emulators and its rule keeps only each output's own variance. */
+void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *cov_out);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);

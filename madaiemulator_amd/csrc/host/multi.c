@@ -617,6 +617,48 @@ void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_
 	free(mp); free(vp); free(gm); free(gv); free(mc); free(vc); free(gmc); free(gvc);
 }
 
+/* the joint posterior covariance between the query points, per output (libemu.h): every component's gpemu_predict_cov_dev is
+ * enqueued on its own stream before the first is collected; observable space by the variance half of the reference's rule
+ * (multivar_support.c:118-157) on every element, the mean by its mean half */
+void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *cov_out)
+{
+	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt;
+	const multi_modelstruct *m = emu->model;
+	const size_t mm = (size_t)np * np;
+	if (!cov_out) gpemu_host_fatal("emulate_points_multi_cov: cov_out is NULL\n");
+	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
+	double *cp = pca_space ? cov_out : (double *)malloc(sizeof(double) * mm * nr);
+	void **dev = (void **)malloc(sizeof(void *) * (size_t)nr);
+	for (int c = 0; c < nr; c++) emulate_points_cov_enqueue(emu->emu_struct_array[c], points, &dev[c]);
+	for (int c = 0; c < nr; c++) {
+		emulate_points_cov_collect(emu->emu_struct_array[c], dev[c], np, mc, cp + mm * c);
+		for (int q = 0; q < np; q++) mp[(size_t)q * nr + c] = mc[q];
+	}
+	if (pca_space) {
+		if (mean_out) memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
+	} else {
+		for (int i = 0; i < nt; i++) {
+			double *co = cov_out + mm * i;
+			for (size_t e = 0; e < mm; e++) co[e] = 0.0;
+			for (int c = 0; c < nr; c++) {
+				const double f2 = pow(gsl_matrix_get(m->pca_evecs_r, i, c), 2.0) * gsl_vector_get(m->pca_evals_r, c);
+				const double *cc = cp + mm * c;
+				for (size_t e = 0; e < mm; e++) co[e] += f2 * cc[e];
+			}
+		}
+		if (mean_out)
+			for (int q = 0; q < np; q++)
+				for (int i = 0; i < nt; i++) {
+					double ms = 0.0;
+					for (int c = 0; c < nr; c++)
+						ms += gsl_matrix_get(m->pca_evecs_r, i, c) * sqrt(gsl_vector_get(m->pca_evals_r, c)) * mp[(size_t)q * nr + c];
+					mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
+				}
+		free(cp);
+	}
+	free(mp); free(mc); free(dev);
+}
+
 /* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
