@@ -25,20 +25,33 @@ emulator::emulator(std::string path) { init(path, false); }
 emulator::emulator(std::string path, bool PcaOnly) { init(path, PcaOnly); }
 emulator::~emulator() { free_multi_emulator(the_emulator); }
 
-void emulator::QueryEmulator(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
-                             std::vector<std::vector<double> > &Errors)
+// the one complaint of the Query* methods about a point's length, under the name of the method that was called
+static void wrong_dimensions(const char *method)
 {
-	const size_t np = xpoints.size();
-	std::vector<double> flat(np * number_params), m(np * number_outputs), v(np * number_outputs);
-	for (size_t q = 0; q < np; q++) {
+	std::cerr << "Error::" << method << " called with incorrect number of dimensions in xpoint" << std::endl;
+}
+
+// xpoints, every row checked to have number_params entries, as packed row-major doubles (the data of the gsl_matrix view)
+static std::vector<double> flatten(const char *method, const std::vector<std::vector<double> > &xpoints, int number_params)
+{
+	std::vector<double> flat(xpoints.size() * number_params);
+	for (size_t q = 0; q < xpoints.size(); q++) {
 		if ((int)xpoints[q].size() != number_params) {
-			std::cerr << "Error::QueryEmulator called with incorrect number of dimensions in xpoint" << std::endl;
+			wrong_dimensions(method);
 			gpemu_host_exit(EXIT_FAILURE);
 		}
 		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
 	}
-	gsl_matrix view;
-	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	return flat;
+}
+
+void emulator::QueryEmulator(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
+                             std::vector<std::vector<double> > &Errors)
+{
+	const size_t np = xpoints.size();
+	std::vector<double> m(np * number_outputs), v(np * number_outputs);
+	std::vector<double> flat = flatten("QueryEmulator", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
 	emulate_points_multi(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), v.data());
 	Means.assign(np, std::vector<double>(number_outputs));
 	Errors.assign(np, std::vector<double>(number_outputs));
@@ -52,16 +65,9 @@ void emulator::QueryEmulator(const std::vector<std::vector<double> > &xpoints, s
 void emulator::QueryEmulatorMeans(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means)
 {
 	const size_t np = xpoints.size();
-	std::vector<double> flat(np * number_params), m(np * number_outputs);
-	for (size_t q = 0; q < np; q++) {
-		if ((int)xpoints[q].size() != number_params) {
-			std::cerr << "Error::QueryEmulatorMeans called with incorrect number of dimensions in xpoint" << std::endl;
-			gpemu_host_exit(EXIT_FAILURE);
-		}
-		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
-	}
-	gsl_matrix view;
-	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	std::vector<double> m(np * number_outputs);
+	std::vector<double> flat = flatten("QueryEmulatorMeans", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
 	emulate_points_multi_mean(the_emulator, &view, outputPCAValues ? 1 : 0, m.data());
 	Means.assign(np, std::vector<double>(number_outputs));
 	for (size_t q = 0; q < np; q++)
@@ -72,16 +78,9 @@ void emulator::QueryEmulatorMeanGradients(const std::vector<std::vector<double> 
                                           std::vector<std::vector<double> > &Gradients)
 {
 	const size_t np = xpoints.size(), ng = (size_t)number_outputs * number_params;
-	std::vector<double> flat(np * number_params), m(np * number_outputs), g(np * ng);
-	for (size_t q = 0; q < np; q++) {
-		if ((int)xpoints[q].size() != number_params) {
-			std::cerr << "Error::QueryEmulatorMeanGradients called with incorrect number of dimensions in xpoint" << std::endl;
-			gpemu_host_exit(EXIT_FAILURE);
-		}
-		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
-	}
-	gsl_matrix view;
-	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	std::vector<double> m(np * number_outputs), g(np * ng);
+	std::vector<double> flat = flatten("QueryEmulatorMeanGradients", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
 	emulate_points_multi_mean_grad(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), g.data());
 	Means.assign(np, std::vector<double>(number_outputs));
 	Gradients.assign(np, std::vector<double>(ng));
@@ -96,16 +95,9 @@ void emulator::QueryEmulatorGradients(const std::vector<std::vector<double> > &x
                                       std::vector<std::vector<double> > &VarianceGradients)
 {
 	const size_t np = xpoints.size(), ng = (size_t)number_outputs * number_params;
-	std::vector<double> flat(np * number_params), m(np * number_outputs), v(np * number_outputs), gm(np * ng), gv(np * ng);
-	for (size_t q = 0; q < np; q++) {
-		if ((int)xpoints[q].size() != number_params) {
-			std::cerr << "Error::QueryEmulatorGradients called with incorrect number of dimensions in xpoint" << std::endl;
-			gpemu_host_exit(EXIT_FAILURE);
-		}
-		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
-	}
-	gsl_matrix view;
-	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	std::vector<double> m(np * number_outputs), v(np * number_outputs), gm(np * ng), gv(np * ng);
+	std::vector<double> flat = flatten("QueryEmulatorGradients", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
 	emulate_points_multi_grad(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), v.data(), gm.data(), gv.data());
 	Means.assign(np, std::vector<double>(number_outputs));
 	Variances.assign(np, std::vector<double>(number_outputs));
@@ -121,16 +113,9 @@ void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &
                                        std::vector<std::vector<double> > &Covariances)
 {
 	const size_t np = xpoints.size();
-	std::vector<double> flat(np * number_params), m(np * number_outputs), c((size_t)number_outputs * np * np);
-	for (size_t q = 0; q < np; q++) {
-		if ((int)xpoints[q].size() != number_params) {
-			std::cerr << "Error::QueryEmulatorCovariance called with incorrect number of dimensions in xpoint" << std::endl;
-			gpemu_host_exit(EXIT_FAILURE);
-		}
-		for (int k = 0; k < number_params; k++) flat[q * number_params + k] = xpoints[q][k];
-	}
-	gsl_matrix view;
-	view.size1 = np; view.size2 = number_params; view.tda = number_params; view.data = flat.data(); view.block = NULL; view.owner = 0;
+	std::vector<double> m(np * number_outputs), c((size_t)number_outputs * np * np);
+	std::vector<double> flat = flatten("QueryEmulatorCovariance", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
 	emulate_points_multi_cov(the_emulator, &view, outputPCAValues ? 1 : 0, m.data(), c.data());
 	Means.assign(np, std::vector<double>(number_outputs));
 	for (size_t q = 0; q < np; q++)
@@ -142,7 +127,7 @@ void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &
 void emulator::QueryEmulator(const std::vector<double> &xpoint, std::vector<double> &Means, std::vector<double> &Errors)
 {
 	if ((int)xpoint.size() != number_params) {
-		std::cerr << "Error::QueryEmulator called with incorrect number of dimensions in xpoint" << std::endl;
+		wrong_dimensions("QueryEmulator");
 		std::cerr << "xpoint.length: " << xpoint.size() << " emulator->number_params: " << number_params << std::endl;
 		gpemu_host_exit(EXIT_FAILURE);
 	}

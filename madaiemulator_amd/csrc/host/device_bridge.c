@@ -897,92 +897,91 @@ void free_emulator_struct(emulator_struct *e)
 	free(e);
 }
 
-void emulate_points(emulator_struct *e, gsl_matrix *points, double *mean, double *variance)
+/* what every emulate_* entry below opens and closes with: the entry alloc_emulator_struct registered for e, or the message and
+ * the layer's exit; and the end of a device call that failed.  `who` is the name the entry reports under. */
+static struct entry *entry_of(emulator_struct *e, const char *who)
 {
 	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_point: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	if (!en) { fprintf(stderr, "%s: emulator_struct was not made by alloc_emulator_struct\n", who); gpemu_host_exit(EXIT_FAILURE); }
+	return en;
+}
+
+static void check(const struct entry *en, int rc, const char *who) { if (rc) die(en->ctx, rc, who); }
+
+void emulate_points(emulator_struct *e, gsl_matrix *points, double *mean, double *variance)
+{
+	struct entry *en = entry_of(e, "emulate_point");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_batch(en->ctx, (int)points->size1, q, mean, variance);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_point");
+	check(en, rc, "emulate_point");
 }
 
 /* the two halves of emulate_points: all components of a multi-output emulator enqueue, then all collect */
 void emulate_points_enqueue(emulator_struct *e, gsl_matrix *points)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_point: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_point");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_batch_enqueue(en->ctx, (int)points->size1, q);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_point");
+	check(en, rc, "emulate_point");
 }
 
 void emulate_points_collect(emulator_struct *e, int npoints, double *mean, double *variance)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_point: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
-	int rc = gpemu_predict_batch_collect(en->ctx, npoints, mean, variance);
-	if (rc) die(en->ctx, rc, "emulate_point");
+	struct entry *en = entry_of(e, "emulate_point");
+	check(en, gpemu_predict_batch_collect(en->ctx, npoints, mean, variance), "emulate_point");
 }
 
 /* the mean alone (makeEmulatedMean, emulator.c:672-704, over the clamped k-vector): gpemu_predict_mean's fused sweep, no
  * variance and none of its batch buffers */
 void emulate_points_mean(emulator_struct *e, gsl_matrix *points, double *mean)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_mean");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_mean(en->ctx, (int)points->size1, q, mean);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_points_mean");
+	check(en, rc, "emulate_points_mean");
 }
 
 void emulate_points_mean_enqueue(emulator_struct *e, gsl_matrix *points)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_mean");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_mean_enqueue(en->ctx, (int)points->size1, q);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_points_mean");
+	check(en, rc, "emulate_points_mean");
 }
 
 void emulate_points_mean_collect(emulator_struct *e, int npoints, double *mean)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
-	int rc = gpemu_predict_mean_collect(en->ctx, npoints, mean);
-	if (rc) die(en->ctx, rc, "emulate_points_mean");
+	struct entry *en = entry_of(e, "emulate_points_mean");
+	check(en, gpemu_predict_mean_collect(en->ctx, npoints, mean), "emulate_points_mean");
 }
 
 /* the mean and its gradient with respect to the query point: gpemu_predict_mean_grad's fused sweep */
 void emulate_points_mean_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *grad)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_mean_grad");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_mean_grad(en->ctx, (int)points->size1, q, mean, grad);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+	check(en, rc, "emulate_points_mean_grad");
 }
 
 void emulate_points_mean_grad_enqueue(emulator_struct *e, gsl_matrix *points)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_mean_grad");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_mean_grad_enqueue(en->ctx, (int)points->size1, q);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+	check(en, rc, "emulate_points_mean_grad");
 }
 
 void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *mean, double *grad)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_mean_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
-	int rc = gpemu_predict_mean_grad_collect(en->ctx, npoints, mean, grad);
-	if (rc) die(en->ctx, rc, "emulate_points_mean_grad");
+	struct entry *en = entry_of(e, "emulate_points_mean_grad");
+	check(en, gpemu_predict_mean_grad_collect(en->ctx, npoints, mean, grad), "emulate_points_mean_grad");
 }
 
 /* mean, variance and both gradients with respect to the query point (libemu.h).  The variance-gradient entry of the device
@@ -991,18 +990,15 @@ void emulate_points_mean_grad_collect(emulator_struct *e, int npoints, double *m
  * variance-gradient batch at enqueue and runs the mean-gradient sweep at collect, on the points kept since. */
 void emulate_points_grad_enqueue(emulator_struct *e, gsl_matrix *points)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_grad");
 	free(en->grad_q);
 	en->grad_q = pack_matrix(points);
-	int rc = gpemu_predict_var_grad_enqueue(en->ctx, (int)points->size1, en->grad_q);
-	if (rc) die(en->ctx, rc, "emulate_points_grad");
+	check(en, gpemu_predict_var_grad_enqueue(en->ctx, (int)points->size1, en->grad_q), "emulate_points_grad");
 }
 
 void emulate_points_grad_collect(emulator_struct *e, int npoints, double *mean, double *variance, double *grad_mean, double *grad_variance)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_grad: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_grad");
 	if (!mean && !variance && !grad_mean && !grad_variance) gpemu_host_fatal("emulate_points_grad: every output is NULL\n");
 	if (!en->grad_q) gpemu_host_fatal("emulate_points_grad_collect: nothing was enqueued\n");
 	/* (the device entry requires its gradient output: a scratch row when the caller does not want it) */
@@ -1012,7 +1008,7 @@ void emulate_points_grad_collect(emulator_struct *e, int npoints, double *mean, 
 	if (!rc && grad_mean) rc = gpemu_predict_mean_grad(en->ctx, npoints, en->grad_q, NULL, grad_mean);
 	free(en->grad_q);
 	en->grad_q = NULL;
-	if (rc) die(en->ctx, rc, "emulate_points_grad");
+	check(en, rc, "emulate_points_grad");
 }
 
 void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, double *variance, double *grad_mean, double *grad_variance)
@@ -1033,12 +1029,11 @@ void emulate_points_grad(emulator_struct *e, gsl_matrix *points, double *mean, d
  * both triangles; mean may be NULL */
 void emulate_points_cov(emulator_struct *e, gsl_matrix *points, double *mean, double *cov)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_cov");
 	double *q = pack_matrix(points);
 	int rc = gpemu_predict_cov(en->ctx, (int)points->size1, q, mean, cov);
 	free(q);
-	if (rc) die(en->ctx, rc, "emulate_points_cov");
+	check(en, rc, "emulate_points_cov");
 }
 
 /* its two halves, like emulate_loo_enqueue / _collect: the queries go up, gpemu_predict_cov_dev is enqueued on the component's
@@ -1046,8 +1041,7 @@ void emulate_points_cov(emulator_struct *e, gsl_matrix *points, double *mean, do
  * that stream only, and releases the buffer */
 void emulate_points_cov_enqueue(emulator_struct *e, gsl_matrix *points, void **dev_out)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_cov");
 	const size_t np = points->size1, d = points->size2;
 	double *q = pack_matrix(points);
 	void *dev = NULL;
@@ -1055,61 +1049,55 @@ void emulate_points_cov_enqueue(emulator_struct *e, gsl_matrix *points, void **d
 	if (!rc) rc = gpemu_dev_upload(en->ctx, dev, q, np * d * sizeof(double));
 	free(q);
 	if (!rc) rc = gpemu_predict_cov_dev(en->ctx, (int)np, (const double *)dev, (double *)dev + np * d, (double *)dev + np * d + np);
-	if (rc) die(en->ctx, rc, "emulate_points_cov");
+	check(en, rc, "emulate_points_cov");
 	*dev_out = dev;
 }
 
 void emulate_points_cov_collect(emulator_struct *e, void *dev, int npoints, double *mean, double *cov)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_points_cov: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_points_cov");
 	const size_t np = (size_t)npoints, d = (size_t)en->d;
 	int rc = mean ? gpemu_dev_download(en->ctx, mean, (const double *)dev + np * d, np * sizeof(double)) : 0;
 	if (!rc) rc = gpemu_dev_download(en->ctx, cov, (const double *)dev + np * d + np, np * np * sizeof(double));
 	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
-	if (rc) die(en->ctx, rc, "emulate_points_cov");
+	check(en, rc, "emulate_points_cov");
 }
 
 /* leave-one-out at every training point (gpemu_loo) */
 void emulate_loo(emulator_struct *e, double *mean, double *variance)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
-	int rc = gpemu_loo(en->ctx, mean, variance);
-	if (rc) die(en->ctx, rc, "emulate_loo");
+	struct entry *en = entry_of(e, "emulate_loo");
+	check(en, gpemu_loo(en->ctx, mean, variance), "emulate_loo");
 }
 
 /* its two halves: the launches go onto the component's own stream and the results wait in a device buffer (means, then
  * variances); collect downloads them, which waits for that stream only, and releases the buffer */
 void emulate_loo_enqueue(emulator_struct *e, void **dev_out)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_loo");
 	const size_t n = (size_t)e->nmodel_points;
 	void *dev = NULL;
 	int rc = gpemu_dev_alloc(en->ctx, 2 * n * sizeof(double), &dev);
 	if (!rc) rc = gpemu_loo_dev(en->ctx, (double *)dev, (double *)dev + n);
-	if (rc) die(en->ctx, rc, "emulate_loo");
+	check(en, rc, "emulate_loo");
 	*dev_out = dev;
 }
 
 void emulate_loo_collect(emulator_struct *e, void *dev, double *mean, double *variance)
 {
-	struct entry *en = lookup(e, 0);
-	if (!en) { fprintf(stderr, "emulate_loo: emulator_struct was not made by alloc_emulator_struct\n"); gpemu_host_exit(EXIT_FAILURE); }
+	struct entry *en = entry_of(e, "emulate_loo");
 	const size_t n = (size_t)e->nmodel_points;
 	int rc = gpemu_dev_download(en->ctx, mean, dev, n * sizeof(double));
 	if (!rc) rc = gpemu_dev_download(en->ctx, variance, (const double *)dev + n, n * sizeof(double));
 	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
-	if (rc) die(en->ctx, rc, "emulate_loo");
+	check(en, rc, "emulate_loo");
 }
 
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {
-	gsl_matrix view;
 	double *q = pack_vector(point);
-	view.size1 = 1; view.size2 = point->size; view.tda = point->size; view.data = q; view.block = NULL; view.owner = 0;
+	gsl_matrix view = gpemu_matrix_view(q, 1, point->size);
 	emulate_points(e, &view, mean, variance);
 	free(q);
 }

@@ -90,4 +90,12 @@ void gsl_rng_free(gsl_rng *r);
 }
 #endif
 #endif /* GPEMU_USE_SYSTEM_GSL */
+
+/* a gsl_matrix over n1 x n2 packed row-major doubles the caller keeps: owns nothing, is never freed (either GSL) */
+static inline gsl_matrix gpemu_matrix_view(double *data, size_t n1, size_t n2)
+{
+	gsl_matrix view;
+	view.size1 = n1; view.size2 = n2; view.tda = n2; view.data = data; view.block = NULL; view.owner = 0;
+	return view;
+}
 #endif

@@ -129,8 +129,7 @@ struct emu_call { multi_emulator *emu; int pca_space, d; };
 static void emu_points(void *user, int np, const double *pts, double *mean, double *var)
 {
 	struct emu_call *c = (struct emu_call *)user;
-	gsl_matrix view;
-	view.size1 = (size_t)np; view.size2 = (size_t)c->d; view.tda = (size_t)c->d; view.data = (double *)pts; view.block = NULL; view.owner = 0;
+	gsl_matrix view = gpemu_matrix_view((double *)pts, (size_t)np, (size_t)c->d);
 	emulate_points_multi(c->emu, &view, c->pca_space, mean, var);
 }
 

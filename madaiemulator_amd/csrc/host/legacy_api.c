@@ -307,10 +307,9 @@ void emulateAtPointList(modelstruct *the_model, gsl_matrix *point_list, optstruc
 /* emulate-fns.c:138-190 */
 void emulateAtPoint(modelstruct *the_model, gsl_vector *the_point, optstruct *options, double *the_mean, double *the_variance)
 {
-	gsl_matrix one;
 	double *q = (double *)malloc(sizeof(double) * (size_t)options->nparams);
 	for (int k = 0; k < options->nparams; k++) q[k] = gsl_vector_get(the_point, k);
-	one.size1 = 1; one.size2 = (size_t)options->nparams; one.tda = one.size2; one.data = q; one.block = NULL; one.owner = 0;
+	gsl_matrix one = gpemu_matrix_view(q, 1, (size_t)options->nparams);
 	emulate_list(the_model, options, &one, 1, the_mean, the_variance, 0);
 	free(q);
 }

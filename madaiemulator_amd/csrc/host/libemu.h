@@ -378,6 +378,13 @@ void gpemu_host_eval_stats(long *value_evals, long *valgrad_evals, long *cached,
 int gpemu_host_modes(void);
 void gpemu_host_set_modes(int flags);
 void gpemu_host_release(void *params_or_emulator); /* drop the device context cached for a params / emulator pointer */
+/* the PCA -> observable rule of the emulate_*_multi entries (multivar_support.c:118-157), host arithmetic only (multi.c):
+ *   out[q][t][j] = (add_mean && j == 0 ? training_mean[t] : 0) + sum_c F[t][c] * in[q][c][j],   q < nrows, j < width
+ * F = evecs * sqrt(evals) (squared = 0: means, mean gradients) or evecs^2 * evals (squared = 1: variances, their gradients,
+ * covariances; a component-major [c][M x M] buffer is nrows = 1, width = M x M).  in is nrows x nr x width, out nrows x nt x
+ * width, both row-major and distinct.  The sum runs over c in index order from 0.0; the training mean is added last. */
+void gpemu_host_backproject(const multi_modelstruct *m, int squared, int add_mean, size_t nrows, size_t width,
+                            const double *in, double *out);
 /* lock-step group: n restart threads (one struct estimate_thetas_params each, same model) share one device context;
  * their concurrent evalFnMulti / gradFnMulti / evalFnGradMulti / estimateSigmaFull calls are gathered into device
  * batches.  A member's thread calls gpemu_host_group_leave(params) when it will make no further calls. */

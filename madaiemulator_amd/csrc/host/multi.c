@@ -455,207 +455,146 @@ void free_multi_emulator(multi_emulator *e)
 	free(e);
 }
 
-/* npoints x nr PCA-space results -> npoints x nt observable-space results (multivar_support.c:126-151) */
-static void backproject(const multi_emulator *emu, int npoints, const double *mp, const double *vp, double *mean_out, double *var_out)
+/* The PCA -> observable rule of the reference (multivar_support.c:118-157), written once for every entry below:
+ *   out[q][t][j] = (add_mean && j == 0 ? training_mean[t] : 0) + sum_c F[t][c] * in[q][c][j],   q < nrows, j < width
+ * with F = evecs * sqrt(evals) (squared = 0: means and their gradients) or evecs^2 * evals (squared = 1: variances, their
+ * gradients, covariances).  This is the summation order of every observable-space number the library returns: the factor is
+ * formed first and then multiplied by the input element, the sum runs over c in index order from 0.0, and the training mean
+ * is added to the finished sum.  j is the innermost loop, so a component-major [c][M^2] covariance buffer (nrows = 1,
+ * width = M^2) is streamed with unit stride. */
+void gpemu_host_backproject(const multi_modelstruct *m, int squared, int add_mean, size_t nrows, size_t width,
+                            const double *in, double *out)
 {
-	const int nt = emu->nt, nr = emu->nr;
-	const multi_modelstruct *m = emu->model;
-	for (int q = 0; q < npoints; q++)
-		for (int i = 0; i < nt; i++) {
-			double ms = 0.0, vs = 0.0;
-			for (int j = 0; j < nr; j++) {
-				const double u = gsl_matrix_get(m->pca_evecs_r, i, j), lam = gsl_vector_get(m->pca_evals_r, j);
-				ms += u * sqrt(lam) * mp[(size_t)q * nr + j];
-				vs += pow(u, 2.0) * lam * vp[(size_t)q * nr + j];
+	const size_t nt = (size_t)m->nt, nr = (size_t)m->nr;
+	for (size_t q = 0; q < nrows; q++)
+		for (size_t t = 0; t < nt; t++) {
+			double *o = out + (q * nt + t) * width;
+			for (size_t j = 0; j < width; j++) o[j] = 0.0;
+			for (size_t c = 0; c < nr; c++) {
+				const double u = gsl_matrix_get(m->pca_evecs_r, t, c), lam = gsl_vector_get(m->pca_evals_r, c);
+				const double f = squared ? pow(u, 2.0) * lam : u * sqrt(lam);
+				const double *ic = in + (q * nr + c) * width;
+				for (size_t j = 0; j < width; j++) o[j] += f * ic[j];
 			}
-			mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
-			var_out[(size_t)q * nt + i] = vs;
+			if (add_mean && width) o[0] = gsl_vector_get(m->training_mean, t) + o[0];
 		}
+}
+
+static double *doubles(size_t n) { return (double *)malloc(sizeof(double) * n); }
+
+/* component c's np x w result into the [q][c][w] layout of the PCA-space outputs, which the back-projection reads */
+static void place_component(double *all, const double *one, size_t np, size_t nr, size_t c, size_t w)
+{
+	for (size_t q = 0; q < np; q++) memcpy(all + (q * nr + c) * w, one + q * w, sizeof(double) * w);
+}
+
+/* np x nr x w PCA-space results to the caller: as they are, or np x nt x w through the back-projection */
+static void deliver(const multi_emulator *emu, int pca_space, int squared, int add_mean, size_t np, size_t w, const double *in, double *out)
+{
+	if (pca_space) memcpy(out, in, sizeof(double) * np * (size_t)emu->nr * w);
+	else gpemu_host_backproject(emu->model, squared, add_mean, np, w, in, out);
 }
 
 void emulate_points_multi(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out)
 {
-	const int np = (int)points->size1, nr = emu->nr;
-	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *vp = (double *)malloc(sizeof(double) * (size_t)np * nr);
-	double *mc = (double *)malloc(sizeof(double) * (size_t)np), *vc = (double *)malloc(sizeof(double) * (size_t)np);
+	const size_t np = points->size1, nr = (size_t)emu->nr;
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *mc = doubles(np), *vc = doubles(np);
 	/* the nr scalar emulators are independent (multivar_support.c:116 loops over them): each has its own device
 	 * context, so all of them are started before the first result is waited for */
-	for (int c = 0; c < nr; c++) emulate_points_enqueue(emu->emu_struct_array[c], points);
-	for (int c = 0; c < nr; c++) {
-		emulate_points_collect(emu->emu_struct_array[c], np, mc, vc);
-		for (int q = 0; q < np; q++) { mp[(size_t)q * nr + c] = mc[q]; vp[(size_t)q * nr + c] = vc[q]; }
+	for (size_t c = 0; c < nr; c++) emulate_points_enqueue(emu->emu_struct_array[c], points);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_collect(emu->emu_struct_array[c], (int)np, mc, vc);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
 	}
-	if (pca_space) {
-		memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
-		memcpy(var_out, vp, sizeof(double) * (size_t)np * nr);
-	} else {
-		backproject(emu, np, mp, vp, mean_out, var_out);
-	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
+	deliver(emu, pca_space, 1, 0, np, 1, vp, var_out);
 	free(mp); free(vp); free(mc); free(vc);
 }
 
 /* the means alone: every component through its mean-only sweep (all enqueued, then collected, as above); observable space by
- * the mean half of the reference's rule, training_mean + evecs diag(sqrt(evals)) mean_pca (multivar_support.c:118-137), which
- * needs no variances */
+ * the mean half of the rule, which needs no variances */
 void emulate_points_multi_mean(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out)
 {
-	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt;
-	const multi_modelstruct *m = emu->model;
-	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
-	for (int c = 0; c < nr; c++) emulate_points_mean_enqueue(emu->emu_struct_array[c], points);
-	for (int c = 0; c < nr; c++) {
-		emulate_points_mean_collect(emu->emu_struct_array[c], np, mc);
-		for (int q = 0; q < np; q++) mp[(size_t)q * nr + c] = mc[q];
+	const size_t np = points->size1, nr = (size_t)emu->nr;
+	double *mp = doubles(np * nr), *mc = doubles(np);
+	for (size_t c = 0; c < nr; c++) emulate_points_mean_enqueue(emu->emu_struct_array[c], points);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_mean_collect(emu->emu_struct_array[c], (int)np, mc);
+		place_component(mp, mc, np, nr, c, 1);
 	}
-	if (pca_space) {
-		memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
-	} else {
-		for (int q = 0; q < np; q++)
-			for (int i = 0; i < nt; i++) {
-				double ms = 0.0;
-				for (int j = 0; j < nr; j++)
-					ms += gsl_matrix_get(m->pca_evecs_r, i, j) * sqrt(gsl_vector_get(m->pca_evals_r, j)) * mp[(size_t)q * nr + j];
-				mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
-			}
-	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
 	free(mp); free(mc);
 }
 
 /* means and their gradients with respect to the query point: every component through its fused sweep (all enqueued, then
- * collected); observable space by the linear part of the reference's rule (multivar_support.c:118-137), which for the
- * gradient is grad_Y[t][j] = sum_c evecs[t][c] sqrt(evals[c]) grad_c[j] -- the training mean is a constant */
+ * collected); in observable space the gradient takes the mean's factor without the training mean, which is a constant */
 void emulate_points_multi_mean_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *grad_out)
 {
-	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt, d = (int)points->size2;
-	const multi_modelstruct *m = emu->model;
-	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
-	double *gp = (double *)malloc(sizeof(double) * (size_t)np * nr * d), *gc = (double *)malloc(sizeof(double) * (size_t)np * d);
-	for (int c = 0; c < nr; c++) emulate_points_mean_grad_enqueue(emu->emu_struct_array[c], points);
-	for (int c = 0; c < nr; c++) {
-		emulate_points_mean_grad_collect(emu->emu_struct_array[c], np, mc, gc);
-		for (int q = 0; q < np; q++) {
-			mp[(size_t)q * nr + c] = mc[q];
-			memcpy(gp + ((size_t)q * nr + c) * d, gc + (size_t)q * d, sizeof(double) * (size_t)d);
-		}
+	const size_t np = points->size1, nr = (size_t)emu->nr, d = points->size2;
+	double *mp = doubles(np * nr), *mc = doubles(np), *gp = doubles(np * nr * d), *gc = doubles(np * d);
+	for (size_t c = 0; c < nr; c++) emulate_points_mean_grad_enqueue(emu->emu_struct_array[c], points);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_mean_grad_collect(emu->emu_struct_array[c], (int)np, mc, gc);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(gp, gc, np, nr, c, d);
 	}
-	if (pca_space) {
-		if (mean_out) memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
-		memcpy(grad_out, gp, sizeof(double) * (size_t)np * nr * d);
-	} else {
-		for (int q = 0; q < np; q++)
-			for (int i = 0; i < nt; i++) {
-				double ms = 0.0;
-				double *go = grad_out + ((size_t)q * nt + i) * d;
-				for (int j = 0; j < d; j++) go[j] = 0.0;
-				for (int c = 0; c < nr; c++) {
-					const double f = gsl_matrix_get(m->pca_evecs_r, i, c) * sqrt(gsl_vector_get(m->pca_evals_r, c));
-					ms += f * mp[(size_t)q * nr + c];
-					for (int j = 0; j < d; j++) go[j] += f * gp[((size_t)q * nr + c) * d + j];
-				}
-				if (mean_out) mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
-			}
-	}
+	if (mean_out) deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
+	deliver(emu, pca_space, 0, 0, np, d, gp, grad_out);
 	free(mp); free(mc); free(gp); free(gc);
 }
 
 /* means, variances and the gradients of both: every component's variance-gradient batch is started before the first is
- * collected (its mean-gradient sweep, when asked for, runs at its collect); observable space by the reference's two rules
- * (multivar_support.c:118-137): factor evecs sqrt(evals) on the mean and its gradient, evecs^2 evals on the variance and its */
+ * collected (its mean-gradient sweep, when asked for, runs at its collect); in observable space the mean and its gradient
+ * take the rule's mean factor, the variance and its gradient the squared one */
 void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *var_out,
                                double *grad_mean_out, double *grad_var_out)
 {
-	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt, d = (int)points->size2;
-	const multi_modelstruct *m = emu->model;
+	const size_t np = points->size1, nr = (size_t)emu->nr, d = points->size2;
 	if (!mean_out && !var_out && !grad_mean_out && !grad_var_out) gpemu_host_fatal("emulate_points_multi_grad: every output is NULL\n");
 	if (!var_out && !grad_var_out) {                     /* no variance asked for: the mean-gradient sweeps alone */
-		double *g = grad_mean_out ? grad_mean_out : (double *)malloc(sizeof(double) * (size_t)np * (pca_space ? nr : nt) * d);
+		double *g = grad_mean_out ? grad_mean_out : doubles(np * (size_t)(pca_space ? emu->nr : emu->nt) * d);
 		emulate_points_multi_mean_grad(emu, points, pca_space, mean_out, g);
 		if (!grad_mean_out) free(g);
 		return;
 	}
-	const size_t ns = (size_t)np * nr, ng = ns * d;
-	double *mp = (double *)malloc(sizeof(double) * ns), *vp = (double *)malloc(sizeof(double) * ns);
-	double *gm = (double *)malloc(sizeof(double) * ng), *gv = (double *)malloc(sizeof(double) * ng);
-	double *mc = (double *)malloc(sizeof(double) * (size_t)np), *vc = (double *)malloc(sizeof(double) * (size_t)np);
-	double *gmc = (double *)malloc(sizeof(double) * (size_t)np * d), *gvc = (double *)malloc(sizeof(double) * (size_t)np * d);
-	for (int c = 0; c < nr; c++) emulate_points_grad_enqueue(emu->emu_struct_array[c], points);
-	for (int c = 0; c < nr; c++) {
-		emulate_points_grad_collect(emu->emu_struct_array[c], np, mc, vc, grad_mean_out ? gmc : NULL, gvc);
-		for (int q = 0; q < np; q++) {
-			mp[(size_t)q * nr + c] = mc[q];
-			vp[(size_t)q * nr + c] = vc[q];
-			if (grad_mean_out) memcpy(gm + ((size_t)q * nr + c) * d, gmc + (size_t)q * d, sizeof(double) * (size_t)d);
-			memcpy(gv + ((size_t)q * nr + c) * d, gvc + (size_t)q * d, sizeof(double) * (size_t)d);
-		}
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *gm = doubles(np * nr * d), *gv = doubles(np * nr * d);
+	double *mc = doubles(np), *vc = doubles(np), *gmc = doubles(np * d), *gvc = doubles(np * d);
+	for (size_t c = 0; c < nr; c++) emulate_points_grad_enqueue(emu->emu_struct_array[c], points);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_grad_collect(emu->emu_struct_array[c], (int)np, mc, vc, grad_mean_out ? gmc : NULL, gvc);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
+		if (grad_mean_out) place_component(gm, gmc, np, nr, c, d);
+		place_component(gv, gvc, np, nr, c, d);
 	}
-	if (pca_space) {
-		if (mean_out) memcpy(mean_out, mp, sizeof(double) * ns);
-		if (var_out) memcpy(var_out, vp, sizeof(double) * ns);
-		if (grad_mean_out) memcpy(grad_mean_out, gm, sizeof(double) * ng);
-		if (grad_var_out) memcpy(grad_var_out, gv, sizeof(double) * ng);
-	} else {
-		for (int q = 0; q < np; q++)
-			for (int i = 0; i < nt; i++) {
-				double ms = 0.0, vs = 0.0;
-				double *gmo = grad_mean_out ? grad_mean_out + ((size_t)q * nt + i) * d : NULL;
-				double *gvo = grad_var_out ? grad_var_out + ((size_t)q * nt + i) * d : NULL;
-				for (int j = 0; j < d; j++) { if (gmo) gmo[j] = 0.0; if (gvo) gvo[j] = 0.0; }
-				for (int c = 0; c < nr; c++) {
-					const double u = gsl_matrix_get(m->pca_evecs_r, i, c), lam = gsl_vector_get(m->pca_evals_r, c);
-					const double f = u * sqrt(lam), f2 = pow(u, 2.0) * lam;
-					ms += f * mp[(size_t)q * nr + c];
-					vs += f2 * vp[(size_t)q * nr + c];
-					for (int j = 0; j < d; j++) {
-						if (gmo) gmo[j] += f * gm[((size_t)q * nr + c) * d + j];
-						if (gvo) gvo[j] += f2 * gv[((size_t)q * nr + c) * d + j];
-					}
-				}
-				if (mean_out) mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
-				if (var_out) var_out[(size_t)q * nt + i] = vs;
-			}
-	}
+	if (mean_out) deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
+	if (var_out) deliver(emu, pca_space, 1, 0, np, 1, vp, var_out);
+	if (grad_mean_out) deliver(emu, pca_space, 0, 0, np, d, gm, grad_mean_out);
+	if (grad_var_out) deliver(emu, pca_space, 1, 0, np, d, gv, grad_var_out);
 	free(mp); free(vp); free(gm); free(gv); free(mc); free(vc); free(gmc); free(gvc);
 }
 
 /* the joint posterior covariance between the query points, per output (libemu.h): every component's gpemu_predict_cov_dev is
- * enqueued on its own stream before the first is collected; observable space by the variance half of the reference's rule
- * (multivar_support.c:118-157) on every element, the mean by its mean half */
+ * enqueued on its own stream before the first is collected.  The component matrices land component-major, [c][np x np]: in PCA
+ * space that is the output; in observable space it is ONE row of width np x np for the squared rule, every element alike */
 void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *cov_out)
 {
-	const int np = (int)points->size1, nr = emu->nr, nt = emu->nt;
-	const multi_modelstruct *m = emu->model;
-	const size_t mm = (size_t)np * np;
+	const size_t np = points->size1, nr = (size_t)emu->nr, mm = np * np;
 	if (!cov_out) gpemu_host_fatal("emulate_points_multi_cov: cov_out is NULL\n");
-	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *mc = (double *)malloc(sizeof(double) * (size_t)np);
-	double *cp = pca_space ? cov_out : (double *)malloc(sizeof(double) * mm * nr);
-	void **dev = (void **)malloc(sizeof(void *) * (size_t)nr);
-	for (int c = 0; c < nr; c++) emulate_points_cov_enqueue(emu->emu_struct_array[c], points, &dev[c]);
-	for (int c = 0; c < nr; c++) {
-		emulate_points_cov_collect(emu->emu_struct_array[c], dev[c], np, mc, cp + mm * c);
-		for (int q = 0; q < np; q++) mp[(size_t)q * nr + c] = mc[q];
+	double *mp = doubles(np * nr), *mc = doubles(np);
+	double *cp = pca_space ? cov_out : doubles(mm * nr);
+	void **dev = (void **)malloc(sizeof(void *) * nr);
+	for (size_t c = 0; c < nr; c++) emulate_points_cov_enqueue(emu->emu_struct_array[c], points, &dev[c]);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_cov_collect(emu->emu_struct_array[c], dev[c], (int)np, mc, cp + mm * c);
+		place_component(mp, mc, np, nr, c, 1);
 	}
-	if (pca_space) {
-		if (mean_out) memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
-	} else {
-		for (int i = 0; i < nt; i++) {
-			double *co = cov_out + mm * i;
-			for (size_t e = 0; e < mm; e++) co[e] = 0.0;
-			for (int c = 0; c < nr; c++) {
-				const double f2 = pow(gsl_matrix_get(m->pca_evecs_r, i, c), 2.0) * gsl_vector_get(m->pca_evals_r, c);
-				const double *cc = cp + mm * c;
-				for (size_t e = 0; e < mm; e++) co[e] += f2 * cc[e];
-			}
-		}
-		if (mean_out)
-			for (int q = 0; q < np; q++)
-				for (int i = 0; i < nt; i++) {
-					double ms = 0.0;
-					for (int c = 0; c < nr; c++)
-						ms += gsl_matrix_get(m->pca_evecs_r, i, c) * sqrt(gsl_vector_get(m->pca_evals_r, c)) * mp[(size_t)q * nr + c];
-					mean_out[(size_t)q * nt + i] = gsl_vector_get(m->training_mean, i) + ms;
-				}
+	if (!pca_space) {
+		gpemu_host_backproject(emu->model, 1, 0, 1, mm, cp, cov_out);
 		free(cp);
 	}
+	if (mean_out) deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
 	free(mp); free(mc); free(dev);
 }
 
@@ -663,32 +602,27 @@ void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_s
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
 {
-	const int np = emu->nmodel_points, nr = emu->nr;
-	double *mp = (double *)malloc(sizeof(double) * (size_t)np * nr), *vp = (double *)malloc(sizeof(double) * (size_t)np * nr);
-	double *mc = (double *)malloc(sizeof(double) * (size_t)np), *vc = (double *)malloc(sizeof(double) * (size_t)np);
-	void **dev = (void **)malloc(sizeof(void *) * (size_t)nr);
-	for (int c = 0; c < nr; c++) emulate_loo_enqueue(emu->emu_struct_array[c], &dev[c]);
-	for (int c = 0; c < nr; c++) {
+	const size_t np = (size_t)emu->nmodel_points, nr = (size_t)emu->nr;
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *mc = doubles(np), *vc = doubles(np);
+	void **dev = (void **)malloc(sizeof(void *) * nr);
+	for (size_t c = 0; c < nr; c++) emulate_loo_enqueue(emu->emu_struct_array[c], &dev[c]);
+	for (size_t c = 0; c < nr; c++) {
 		emulate_loo_collect(emu->emu_struct_array[c], dev[c], mc, vc);
-		for (int q = 0; q < np; q++) { mp[(size_t)q * nr + c] = mc[q]; vp[(size_t)q * nr + c] = vc[q]; }
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
 	}
-	if (pca_space) {
-		memcpy(mean_out, mp, sizeof(double) * (size_t)np * nr);
-		memcpy(var_out, vp, sizeof(double) * (size_t)np * nr);
-	} else {
-		backproject(emu, np, mp, vp, mean_out, var_out);
-	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
+	deliver(emu, pca_space, 1, 0, np, 1, vp, var_out);
 	free(mp); free(vp); free(mc); free(vc); free(dev);
 }
 
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
-	gsl_matrix view;
 	const int n = pca_space ? emu->nr : emu->nt;
 	double *q = (double *)malloc(sizeof(double) * the_point->size);
 	double *mo = (double *)malloc(sizeof(double) * (size_t)n), *vo = (double *)malloc(sizeof(double) * (size_t)n);
 	for (size_t i = 0; i < the_point->size; i++) q[i] = gsl_vector_get(the_point, i);
-	view.size1 = 1; view.size2 = the_point->size; view.tda = the_point->size; view.data = q; view.block = NULL; view.owner = 0;
+	gsl_matrix view = gpemu_matrix_view(q, 1, the_point->size);
 	emulate_points_multi(emu, &view, pca_space, mo, vo);
 	for (int i = 0; i < n; i++) { gsl_vector_set(the_mean, i, mo[i]); gsl_vector_set(the_variance, i, vo[i]); }
 	free(q); free(mo); free(vo);
