@@ -303,6 +303,53 @@ int gpemu_predict_cov(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host 
 int gpemu_predict_cov_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *mean_dev /* may be NULL */,
                           double *cov_dev /* M*M */);
 
+/* ---- hold-out validation and joint draws at the query points of one call ----
+ * S = Sigma + diag(noise), Sigma the joint covariance gpemu_predict_cov returns for the same queries (noise = NULL: none),
+ * is built and factored on the device, S = L_S L_S^T (lower Cholesky factor, the factorisation of the likelihood), and never
+ * leaves it.  With nobs rows of observations at the query points, yobs[a*M + p] (0 <= nobs <= 64):
+ *   werr[a*M + .] = L_S^-1 (yobs_a - mean)     the decorrelated ("Cholesky") errors: independent N(0, 1) under the model
+ *   maha[a]       = |werr_a|^2                  the squared Mahalanobis distance (yobs_a - mean)^T S^-1 (yobs_a - mean)
+ *   logdet        = 2 sum_p log (L_S)_pp        log det S
+ *   logpdf[a]     = -1/2 (maha[a] + logdet + M log 2 pi)     the joint log predictive density of row a
+ *   var[p]        = S_pp as factored: gpemu_predict_batch's variance to rounding, plus noise_p
+ * mean as gpemu_predict_cov returns it.  Every output may be NULL; yobs is NULL iff nobs = 0.
+ * A successful call leaves {M, L_S, mean} resident in the context: gpemu_predict_joint_draw then returns, for ndraw rows of
+ * standard normals z[s*M + .] supplied by the caller (any ndraw >= 1, blocks of 1024 internally),
+ *   out[s*M + .] = mean + L_S z_s              a joint draw from N(mean, S)
+ * so a draw with z = werr_a returns yobs_a.  The factor stays until the next factor call, gpemu_predict_joint_release,
+ * gpemu_set_model, gpemu_set_training, gpemu_set_mode with other flags or gpemu_predict_setup[_batch]; it takes
+ * 8 (M' + 64) M' bytes, M' = M rounded up to 64 (2.2 GB at M = 16384), which gpemu_predict_joint_release gives back.
+ * Cost: gpemu_predict_cov's sweep and product (M N^2 + M^2 N flops, no mirror) plus M^3 / 3 for the factorisation of ONE
+ * matrix; a block of draws is one triangular product of ndraw M^2 flops.  Few queries take the same kernels on one 64-row tile.
+ * Failure: S is not positive definite to working precision -- coinciding query points without noise, or a negative
+ * Sigma_pp + noise_p (the sign of noise is NOT checked: the device-pointer entry could not, so neither does): the host entry
+ * returns GPEMU_ERR_NOT_PD with *info = the 1-based row of the failed pivot, mean and var valid, werr, maha, logdet and
+ * logpdf NaN, and no factor is left (a draw then returns GPEMU_ERR_STATE).  *info = 0 otherwise.
+ * Errors: GPEMU_ERR_ARG, before anything is allocated or launched, for a NULL ctx, xq or info, npoints outside 1 .. 16384, nobs
+ * outside 0 .. 64, yobs NULL with nobs > 0, a NULL z or out, ndraw < 1; GPEMU_ERR_STATE without a prediction set-up, for a
+ * draw without a resident factor, and from the two host-buffer entries while a host-buffer prediction batch is pending, as
+ * for gpemu_predict_cov (the factor entry stages the queries through the same buffers; the batch stays collectable).
+ * Two identical calls return the same bits; the host and _dev entries and a context set up by gpemu_predict_setup_batch return
+ * the same bits; no atomics beyond the factorisation's info word.  The factor entry uses the batch buffers of
+ * gpemu_predict_batch as gpemu_predict_cov does and leaves nothing the other prediction entries read. */
+int gpemu_predict_joint_factor(gpemu_ctx *ctx, int npoints, const double *xq /* M*d host */, const double *noise /* M or NULL */,
+                               int nobs, const double *yobs /* nobs*M rows, NULL iff nobs == 0 */,
+                               double *mean /* M, may be NULL */, double *var /* M, may be NULL: the diagonal of S as factored */,
+                               double *werr /* nobs*M, may be NULL */, double *maha /* nobs, may be NULL */,
+                               double *logdet /* may be NULL */, double *logpdf /* nobs, may be NULL */, int *info);
+/* device pointers: only enqueues on the context's stream (the first call sizes the buffers).  stat_dev (may be NULL): 1 + nobs
+ * doubles, logdet then maha[0 .. nobs).  info_dev (required): one int, a value >= 0x7f7f7f7f for "no failed pivot", otherwise the
+ * 1-based row; it is the caller's to read -- this entry cannot know about a failed pivot and marks the factor resident either
+ * way.  A draw from a factor whose pivot failed returns unspecified numbers, reading inside the context's buffers only. */
+int gpemu_predict_joint_factor_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, const double *noise_dev /* may be NULL */,
+                                   int nobs, const double *yobs_dev, double *mean_dev /* may be NULL */, double *var_dev /* may be NULL */,
+                                   double *werr_dev /* may be NULL */, double *stat_dev /* 1 + nobs, may be NULL */, int *info_dev);
+int gpemu_predict_joint_draw(gpemu_ctx *ctx, int ndraw, const double *z /* ndraw*M host */, double *out /* ndraw*M host */);
+/* device pointers: only enqueues on the context's stream.  out_dev may be z_dev itself (each element is read before it is written). */
+int gpemu_predict_joint_draw_dev(gpemu_ctx *ctx, int ndraw, const double *z_dev, double *out_dev);
+/* drops the resident factor and frees every buffer of the joint entries (waits for the context's stream) */
+int gpemu_predict_joint_release(gpemu_ctx *ctx);
+
 /* ---- leave-one-out validation of a trained emulator -----------------
  * mean[i], var[i] for every training point i: what removing point i, alloc_emulator_struct on the other N - 1 points at
  * the same thetas and emulate_point at x_i return (GLS beta re-estimated, variance with the regression term and kappa
@@ -365,6 +412,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_MEAN_GRAD 9 /* the two launches of the mean-gradient sweep: flops = M*N*(3 d + 2 + 2 (d + 1)), bytes = 8*M*(2 d + 1) */
 #define GPEMU_PROF_VAR_GRAD 10 /* the fused sweep of the variance-gradient entry and its finish: flops = M*N*(3 d + 1 + 2 (d + 1)), bytes = 8*M*(N + 2 d); its two products report under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_COV     11  /* the prior and mirror launches of gpemu_predict_cov[_dev]: bytes = 8*M*M (the lower triangle written once, mirrored once); its symmetric product reports under GPEMU_PROF_GEMM */
+#define GPEMU_PROF_JOINT   12  /* the staging and clean launches of gpemu_predict_joint_factor[_dev] (bytes = 8*(64 M' + 2 M) and 4*M'*M', M' = M rounded up to 64) and the staging launch of every block of gpemu_predict_joint_draw[_dev] (bytes = 8*ndraw*(M' + 2 M)); the sweep, the products and the factorisation report under GPEMU_PROF_FILL / _COV / _GEMM / _LEAF / _POTRF */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

@@ -20,6 +20,7 @@ PROF_MEAN = 8
 PROF_MEAN_GRAD = 9
 PROF_VAR_GRAD = 10
 PROF_COV = 11
+PROF_JOINT = 12
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -112,6 +113,12 @@ SYMBOLS = {
     "gpemu_predict_var_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_predict_cov": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "gpemu_predict_cov_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_joint_factor": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpemu_predict_joint_factor_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_joint_draw": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "gpemu_predict_joint_draw_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gpemu_predict_joint_release": (C.c_int, [C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -522,6 +529,43 @@ class Context:
 
     def predict_cov_dev(self, M, xq_dev, mean_dev, cov_dev):
         self._chk(self.L.gpemu_predict_cov_dev(self.h, M, xq_dev, mean_dev, cov_dev))
+
+    # hold-out validation and joint draws at the query points of one call: S = Sigma + diag(noise) factored on
+    # the device, the factor kept resident for predict_joint_draw
+    def predict_joint_factor(self, Xq, noise=None, yobs=None):
+        """-> dict(mean[M], var[M], werr[nobs, M], maha[nobs], logdet, logpdf[nobs], info, status); status is OK or ERR_NOT_PD
+        (then info is the 1-based row of the failed pivot, mean and var are valid and the rest is NaN)"""
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        noise = None if noise is None else _a(noise).reshape(M)
+        yobs = None if yobs is None else _a(yobs).reshape(-1, M)
+        nobs = 0 if yobs is None else yobs.shape[0]
+        mean, var = np.empty(M), np.empty(M)
+        werr, maha, logpdf = np.empty((nobs, M)), np.empty(nobs), np.empty(nobs)
+        logdet, info = C.c_double(np.nan), C.c_int(-1)
+        rc = self.L.gpemu_predict_joint_factor(self.h, M, _p(Xq), None if noise is None else _p(noise), nobs,
+                                               _p(yobs) if nobs else None, _p(mean), _p(var), _p(werr), _p(maha), C.byref(logdet),
+                                               _p(logpdf), C.byref(info))
+        self._chk(rc, allow=(ERR_NOT_PD,))
+        return dict(mean=mean, var=var, werr=werr, maha=maha, logdet=logdet.value, logpdf=logpdf, info=info.value, status=rc)
+
+    def predict_joint_factor_dev(self, M, xq_dev, noise_dev, nobs, yobs_dev, mean_dev, var_dev, werr_dev, stat_dev, info_dev):
+        self._chk(self.L.gpemu_predict_joint_factor_dev(self.h, M, xq_dev, noise_dev, nobs, yobs_dev, mean_dev, var_dev, werr_dev,
+                                                        stat_dev, info_dev))
+
+    def predict_joint_draw(self, z):
+        """z: ndraw rows of M standard normals -> out[ndraw, M] = mean + L_S z, from the factor the last predict_joint_factor left"""
+        z = _a(z)
+        z = z.reshape(1, -1) if z.ndim == 1 else z
+        out = np.empty_like(z)
+        self._chk(self.L.gpemu_predict_joint_draw(self.h, z.shape[0], _p(z), _p(out)))
+        return out
+
+    def predict_joint_draw_dev(self, ndraw, z_dev, out_dev):
+        self._chk(self.L.gpemu_predict_joint_draw_dev(self.h, ndraw, z_dev, out_dev))
+
+    def predict_joint_release(self):
+        self._chk(self.L.gpemu_predict_joint_release(self.h))
 
     # -- memory / sync / profiling ------------------------------------------
     def dev_alloc(self, nbytes):

@@ -34,7 +34,8 @@ static int fail(gpemu_ctx *ctx, int code, const char *msg)
 }
 
 // the prediction state and the explicit inverse no longer belong to what the workspace, the model or the mode now say
-static void invalidate_prediction(gpemu_ctx *ctx) { ctx->pred_ready = false; ctx->cinv_ready = false; ctx->linvT_ready = false; }
+// (nor does a resident joint factor, gpemu_predict_joint_factor: its buffers stay, its content is no longer offered)
+static void invalidate_prediction(gpemu_ctx *ctx) { ctx->pred_ready = false; ctx->cinv_ready = false; ctx->linvT_ready = false; ctx->joint_M = 0; }
 
 // ---------------------------------------------------------------------------
 // profiling helpers
@@ -264,8 +265,9 @@ static void free_model(gpemu_ctx *ctx)
 	for (auto *b : {&ctx->dX, &ctx->dXg, &ctx->dMid, &ctx->dY, &ctx->dRrows, &ctx->dT, &ctx->dGramPart, &ctx->dLinvAug, &ctx->dBetaQ,
 	                &ctx->dKq, &ctx->dV, &ctx->dXq, &ctx->dMean, &ctx->dS, &ctx->dGradPart, &ctx->dAlpha,
 	                &ctx->dLooPart, &ctx->dLoo, &ctx->dMeanPart, &ctx->dMGradPart, &ctx->dMGrad, &ctx->dLinvAugT, &ctx->dVGradPart, &ctx->dCovR,
-	                &ctx->dCov})
+	                &ctx->dCov, &ctx->dJoint, &ctx->dJointMean, &ctx->dJointPart, &ctx->dJointZ, &ctx->dJointIO})
 		b->reset();
+	ctx->dJointInfo.reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -1636,11 +1638,10 @@ extern "C" int gpemu_predict_var_grad(gpemu_ctx *ctx, int M, const double *xq, d
 // moves C by single elements, so an odd M needs no padded scratch (its A and B rows are rows of dV, whose leading dimension
 // Np + Rp is a multiple of 64).  Uses dKq, dV and its own dCovR; everything only enqueued on the context's stream.
 // ---------------------------------------------------------------------------
-extern "C" int gpemu_predict_cov_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *cov_dev)
+// the part gpemu_predict_cov_dev and gpemu_predict_joint_factor_dev share: the lower 64 x 64 tiles of Sigma into S (M x M, leading
+// dimension lds >= M), everything but the mirror.  The arguments have been checked.
+static int predict_cov_lower(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *cov_dev, long lds)
 {
-	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq_dev || !cov_dev) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const int Np = ctx->Np, Rp = ctx->Rp, d = ctx->d;
 	const int mbp = round_up(M, 64);
 	int rc = ensure_pred_batch(ctx, mbp);
@@ -1657,19 +1658,29 @@ extern "C" int gpemu_predict_cov_dev(gpemu_ctx *ctx, int M, const double *xq_dev
 	HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, ldv, M, Np, ctx->nreg, ctx->order, d, xq_dev, ctx->dBetaQ, ctx->kappa,
 	                                  mean_dev ? mean_dev : spare, spare + mbp, 1, (long)mbp * ldv));
 	HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, M, Np, Rp, ctx->nreg, d, xq_dev, ctx->dBetaQ, rkeep));
-	if (prof_on(ctx, GPEMU_PROF_COV)) { ctx->prof.tag.push_back("predict_cov_prior"); ctx->prof.tag.push_back("predict_cov_mirror"); }
+	if (prof_on(ctx, GPEMU_PROF_COV)) ctx->prof.tag.push_back("predict_cov_prior");
 	{
 		// flops: per element of the lower triangle the squared distance (3 d) and the regression sum (2 nreg); bytes: the lower
-		// triangle written once here, mirrored once below
+		// triangle written once here (and mirrored once by gpemu_predict_cov_dev)
 		ProfScope ps(ctx, GPEMU_PROF_COV, 0.5 * M * (double)M * (3.0 * d + 2.0 * ctx->nreg), 4.0 * M * (double)M);
-		HIPCHK(ctx, launch_predict_cov_prior(ctx->stream, cov_dev, M, xq_dev, M, d, p, rkeep, Rp, ctx->dV, ldv, Np, ctx->nreg));
+		HIPCHK(ctx, launch_predict_cov_prior(ctx->stream, cov_dev, lds, xq_dev, M, d, p, rkeep, Rp, ctx->dV, ldv, Np, ctx->nreg));
 	}
 	GemmArgs g{};
-	g.C = cov_dev; g.ldc = M;
+	g.C = cov_dev; g.ldc = lds;
 	g.A = ctx->dV; g.lda = ldv;
 	g.B = ctx->dV; g.ldb = ldv;
 	g.m = M; g.n = M; g.k0 = 0; g.k1 = Np; g.alpha = -1.0; g.beta = 1; g.tri = 1;
 	HIPCHK(ctx, gemm(ctx, g));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_cov_dev(gpemu_ctx *ctx, int M, const double *xq_dev, double *mean_dev, double *cov_dev)
+{
+	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq_dev || !cov_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (const int rc = predict_cov_lower(ctx, M, xq_dev, mean_dev, cov_dev, M)) return rc;
+	if (prof_on(ctx, GPEMU_PROF_COV)) ctx->prof.tag.push_back("predict_cov_mirror");
 	{
 		ProfScope ps(ctx, GPEMU_PROF_COV, 0.0, 4.0 * M * (double)M);
 		HIPCHK(ctx, launch_predict_cov_mirror(ctx->stream, cov_dev, M, M));
@@ -1699,6 +1710,192 @@ extern "C" int gpemu_predict_cov(gpemu_ctx *ctx, int M, const double *xq, double
 	HIPCHK(ctx, hipMemcpyAsync(cov, ctx->dCov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	if (mean) memcpy(mean, hm, (size_t)M * sizeof(double));
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// hold-out validation and joint draws at the M query points of one call (gpemu.h): S = Sigma + diag(noise) is
+// built in the factorisation's layout -- the lower tiles of predict_cov_lower straight into the tall matrix dJoint,
+// (Mp + 64) x Mp with ld = Mp = M rounded up to 64; noise, identity pad and the rows yobs_a - mean in one staging pass --,
+// factored in place by potrf_all through a view (plain launches: a single matrix of a size that changes from call to call),
+// the solved rows turned into Mahalanobis distances and 2 sum log L_ii by the likelihood's Gram and finish kernels, and the
+// factor cleaned into a plain lower triangle that stays resident for gpemu_predict_joint_draw.  Everything only enqueued on
+// the context's stream; no atomics but the factorisation's info word.
+// ---------------------------------------------------------------------------
+constexpr int JOINT_DRAW_BLOCK = 1024;   // draws staged and multiplied at a time (8 * 1024 * Mp bytes of padded normals)
+
+extern "C" int gpemu_predict_joint_factor_dev(gpemu_ctx *ctx, int M, const double *xq_dev, const double *noise_dev, int nobs,
+                                              const double *yobs_dev, double *mean_dev, double *var_dev, double *werr_dev, double *stat_dev,
+                                              int *info_dev)
+{
+	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq_dev || !info_dev || nobs < 0 || nobs > JOINT_RHS || (nobs > 0 && !yobs_dev))
+		return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	ctx->joint_M = 0;                    // the resident factor, if any, is about to be overwritten
+	const int Mp = round_up(M, LEAF), Rp = JOINT_RHS;
+	const size_t tall = ((size_t)Mp + Rp) * Mp;
+	int rc = grow(ctx, ctx->dJoint, tall, false, "out of device memory for the joint factor (8 (M' + 64) M' bytes, M' = M rounded up to 64)");
+	if (!rc) rc = grow(ctx, ctx->dJointMean, (size_t)Mp);
+	if (!rc) rc = grow(ctx, ctx->dJointPart, (size_t)(Mp / LEAF + 1) * Rp * Rp + 2);
+	if (rc) return rc;
+	double *T = ctx->dJoint, *mu = ctx->dJointMean;
+	double *part = ctx->dJointPart, *res = part + (size_t)(Mp / LEAF) * Rp * Rp;
+	if ((rc = predict_cov_lower(ctx, M, xq_dev, mu, T, Mp))) return rc;
+	if (prof_on(ctx, GPEMU_PROF_JOINT)) { ctx->prof.tag.push_back("joint_stage"); ctx->prof.tag.push_back("joint_clean"); }
+	{
+		// bytes: the 64 right-hand-side rows and the diagonal (the pad is at most 63 rows more)
+		ProfScope ps(ctx, GPEMU_PROF_JOINT, 0.0, 8.0 * ((double)Rp * Mp + 2.0 * M));
+		HIPCHK(ctx, launch_joint_stage(ctx->stream, T, Mp, M, noise_dev, mu, yobs_dev, nobs, var_dev));
+	}
+	HIPCHK(ctx, hipMemsetAsync(info_dev, 0x7f, sizeof(int), ctx->stream));     // INFO_NONE
+	HIPCHK(ctx, trace_clear(ctx));
+	{
+		ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)Mp * Mp * Mp / 3.0, 0.0);
+		HIPCHK(ctx, potrf_all(ctx, Tall{T, info_dev, Mp, Rp, 1, (long)tall}, 0));
+	}
+	if (stat_dev) {
+		// G = Z Z^T of the solved rows Z_a = L_S^-1 (yobs_a - mean) and 2 sum_{p < M} log L_pp; stat = logdet, G_00, G_11, ...
+		HIPCHK(ctx, launch_gram_partials(ctx->stream, T + (size_t)Mp * Mp, Mp, Mp, nobs, Rp, part));
+		HIPCHK(ctx, launch_finish(ctx->stream, part, Mp / LEAF, Rp, nobs, T, Mp, M, res));
+		HIPCHK(ctx, hipMemcpyAsync(stat_dev, res + (size_t)Rp * Rp, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+		if (nobs > 0)
+			HIPCHK(ctx, hipMemcpy2DAsync(stat_dev + 1, sizeof(double), res, ((size_t)Rp + 1) * sizeof(double), sizeof(double), (size_t)nobs,
+			                             hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	if (werr_dev && nobs > 0)
+		HIPCHK(ctx, hipMemcpy2DAsync(werr_dev, (size_t)M * sizeof(double), T + (size_t)Mp * Mp, (size_t)Mp * sizeof(double),
+		                             (size_t)M * sizeof(double), (size_t)nobs, hipMemcpyDeviceToDevice, ctx->stream));
+	if (mean_dev) HIPCHK(ctx, hipMemcpyAsync(mean_dev, mu, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+	{
+		ProfScope ps(ctx, GPEMU_PROF_JOINT, 0.0, 4.0 * (double)Mp * Mp);
+		HIPCHK(ctx, launch_joint_clean(ctx->stream, T, Mp, Mp));
+	}
+	ctx->joint_M = M;
+	return GPEMU_OK;
+}
+
+// the device copies of a host call's arguments: one buffer, pieces at 16-byte multiples
+struct JointIO { double *noise, *yobs, *var, *werr, *stat; };
+static int joint_io(gpemu_ctx *ctx, int M, int nobs, JointIO *io)
+{
+	const size_t m2 = ((size_t)M + 1) & ~(size_t)1, ym = ((size_t)nobs * M + 1) & ~(size_t)1;
+	if (const int rc = grow(ctx, ctx->dJointIO, 2 * m2 + 2 * ym + 2 + JOINT_RHS)) return rc;
+	double *b = ctx->dJointIO;
+	*io = JointIO{b, b + m2, b + m2 + ym, b + 2 * m2 + ym, b + 2 * m2 + 2 * ym};
+	return GPEMU_OK;
+}
+
+// host buffers: the queries through the staging of the other host-buffer entries (hence not while one of their batches is
+// pending), the other arguments through dJointIO.  The sign of noise is not looked at (the device-pointer entry cannot):
+// a negative total on the diagonal shows up as a failed pivot.
+extern "C" int gpemu_predict_joint_factor(gpemu_ctx *ctx, int M, const double *xq, const double *noise, int nobs, const double *yobs,
+                                          double *mean, double *var, double *werr, double *maha, double *logdet, double *logpdf, int *info)
+{
+	if (!ctx || M < 1 || M > PRED_BATCH_MAX || !xq || !info || nobs < 0 || nobs > JOINT_RHS || (nobs > 0 && !yobs))
+		return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->pred_pending.kind != PRED_NONE) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d;
+	JointIO io;
+	int rc = ensure_pred_stage(ctx, M);
+	if (!rc) rc = joint_io(ctx, M, nobs, &io);
+	if (!rc) rc = grow(ctx, ctx->dJointInfo, 1);
+	if (rc) return rc;
+	double *hx = ctx->hStage;
+	memcpy(hx, xq, (size_t)M * d * sizeof(double));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dXq, hx, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (noise) HIPCHK(ctx, hipMemcpyAsync(io.noise, noise, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (nobs) HIPCHK(ctx, hipMemcpyAsync(io.yobs, yobs, (size_t)nobs * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	rc = gpemu_predict_joint_factor_dev(ctx, M, ctx->dXq, noise ? io.noise : nullptr, nobs, nobs ? io.yobs : nullptr, nullptr, io.var,
+	                                    io.werr, io.stat, ctx->dJointInfo);
+	if (rc) return rc;
+	int word = 0;
+	std::vector<double> stat((size_t)1 + nobs);
+	HIPCHK(ctx, hipMemcpyAsync(&word, ctx->dJointInfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(stat.data(), io.stat, stat.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (mean) HIPCHK(ctx, hipMemcpyAsync(mean, ctx->dJointMean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (var) HIPCHK(ctx, hipMemcpyAsync(var, io.var, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (werr && nobs) HIPCHK(ctx, hipMemcpyAsync(werr, io.werr, (size_t)nobs * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	const int bad = pivot_info(word);
+	*info = bad;
+	if (bad) {
+		// mean and var were written before the factorisation began; everything behind it is undefined, and no factor is left
+		ctx->joint_M = 0;
+		if (werr) for (size_t i = 0; i < (size_t)nobs * M; i++) werr[i] = NAN;
+		for (int a = 0; a < nobs; a++) { if (maha) maha[a] = NAN; if (logpdf) logpdf[a] = NAN; }
+		if (logdet) *logdet = NAN;
+		return fail(ctx, GPEMU_ERR_NOT_PD, "Sigma + diag(noise) is not positive definite");
+	}
+	if (logdet) *logdet = stat[0];
+	for (int a = 0; a < nobs; a++) {
+		if (maha) maha[a] = stat[1 + a];
+		if (logpdf) logpdf[a] = -0.5 * (stat[1 + a] + stat[0] + M * 1.8378770664093454835606594728112);   // log 2 pi
+	}
+	return GPEMU_OK;
+}
+
+// out[s] = mean + L_S z[s]: per block of draws the staging pass and ONE product on the factorisation's GEMM, C = out (ldc = M),
+// A = the padded normals, B = the resident factor, whose zeros above the diagonal let a tile stop at its last column (kend_mode)
+extern "C" int gpemu_predict_joint_draw_dev(gpemu_ctx *ctx, int ndraw, const double *z_dev, double *out_dev)
+{
+	if (!ctx || ndraw < 1 || !z_dev || !out_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready || ctx->joint_M < 1) return fail(ctx, GPEMU_ERR_STATE, "no resident joint factor: call gpemu_predict_joint_factor first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int M = ctx->joint_M, Mp = round_up(M, LEAF);
+	if (const int rc = grow(ctx, ctx->dJointZ, (size_t)std::min(ndraw, JOINT_DRAW_BLOCK) * Mp)) return rc;
+	for (int s0 = 0; s0 < ndraw; s0 += JOINT_DRAW_BLOCK) {
+		const int nd = std::min(JOINT_DRAW_BLOCK, ndraw - s0);
+		double *out = out_dev + (size_t)s0 * M;
+		{
+			if (prof_on(ctx, GPEMU_PROF_JOINT)) ctx->prof.tag.push_back("joint_draw_stage");
+			ProfScope ps(ctx, GPEMU_PROF_JOINT, 0.0, 8.0 * nd * ((double)Mp + 2.0 * M));
+			HIPCHK(ctx, launch_joint_draw_stage(ctx->stream, ctx->dJointZ, Mp, z_dev + (size_t)s0 * M, M, nd, out, ctx->dJointMean));
+		}
+		GemmArgs g{};
+		g.C = out; g.ldc = M;
+		g.A = ctx->dJointZ; g.lda = Mp;
+		g.B = ctx->dJoint; g.ldb = Mp;
+		g.m = nd; g.n = M; g.k0 = 0; g.k1 = Mp; g.alpha = 1.0; g.beta = 1; g.kend_mode = 1;
+		HIPCHK(ctx, gemm(ctx, g));
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_predict_joint_draw(gpemu_ctx *ctx, int ndraw, const double *z, double *out)
+{
+	if (!ctx || ndraw < 1 || !z || !out) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready || ctx->joint_M < 1) return fail(ctx, GPEMU_ERR_STATE, "no resident joint factor: call gpemu_predict_joint_factor first");
+	// (one rule for the host-buffer entries of the family, although the draws stage through a buffer of their own)
+	if (ctx->pred_pending.kind != PRED_NONE) return fail(ctx, GPEMU_ERR_STATE, "a prediction batch is enqueued: collect it first");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int M = ctx->joint_M;
+	const size_t blk = (size_t)std::min(ndraw, JOINT_DRAW_BLOCK) * M;
+	// (dJointIO: a factor call's copies have been read by the time it returned)
+	if (const int rc = grow(ctx, ctx->dJointIO, 2 * blk)) return rc;
+	double *dz = ctx->dJointIO, *dout = dz + blk;
+	for (int s0 = 0; s0 < ndraw; s0 += JOINT_DRAW_BLOCK) {
+		const int nd = std::min(JOINT_DRAW_BLOCK, ndraw - s0);
+		const size_t n = (size_t)nd * M;
+		HIPCHK(ctx, hipMemcpyAsync(dz, z + (size_t)s0 * M, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		if (const int rc = gpemu_predict_joint_draw_dev(ctx, nd, dz, dout)) return rc;
+		HIPCHK(ctx, hipMemcpyAsync(out + (size_t)s0 * M, dout, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// the resident factor and every buffer of the joint entries go back to the device (2.2 GB at M = 16384)
+extern "C" int gpemu_predict_joint_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->joint_M = 0;
+	for (auto *b : {&ctx->dJoint, &ctx->dJointMean, &ctx->dJointPart, &ctx->dJointZ, &ctx->dJointIO}) b->reset();
+	ctx->dJointInfo.reset();
 	return GPEMU_OK;
 }
 

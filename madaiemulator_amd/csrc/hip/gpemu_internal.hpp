@@ -17,6 +17,7 @@ constexpr int LEAF = 64;          // diagonal block / padding granule
 constexpr int GEMM_BM = 128;
 constexpr int GEMM_BN = 128;
 constexpr int GEMM_BK = 16;
+constexpr int JOINT_RHS = 64;     // right-hand-side rows of the joint factor's tall matrix: the most observation rows of a call
 
 inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
 
@@ -269,6 +270,15 @@ struct gpemu_ctx {
 	// then two rows of M' for a mean the caller did not ask for and the variance nobody reads; dCov: the M x M result of the
 	// host-buffer entry before it is copied out.  The entry also uses dKq and dV, as gpemu_predict_batch does.
 	gpemu::DevBuf<double> dCovR, dCov;
+	// hold-out validation and joint draws (gpemu_predict_joint_factor / _draw).  dJoint: the tall matrix
+	// [S ; 64 right-hand-side rows], (Mp + 64) x Mp with Mp = joint_M rounded up to 64 -- after a factor call the plain lower
+	// factor L_S, zeros above the diagonal; dJointMean: the means of its queries (Mp); joint_M > 0: both are resident and belong
+	// to the prediction state (cleared with pred_ready).  dJointPart: the Gram partials of the solved rows, then the finished
+	// Gram matrix and the log determinant; dJointZ: the zero-padded normals of a block of draws; dJointIO / dJointInfo: the
+	// host entries' device copies of noise, yobs, var, werr, the statistics, z and out, and their info word.
+	int joint_M = 0;
+	gpemu::DevBuf<double> dJoint, dJointMean, dJointPart, dJointZ, dJointIO;
+	gpemu::DevBuf<int> dJointInfo;
 	bool cinv_ready = false;
 	bool fact_in_T = false;      // the factorisation (with inverse rows) behind the prediction state sits in THIS context's workspace, element 0
 	                             // (false after gpemu_predict_setup_batch for every context but the first: their factorisations ran in the first one's)
@@ -353,6 +363,14 @@ hipError_t launch_predict_qr(hipStream_t s, double *V, long ldv, int M, int Np, 
 hipError_t launch_predict_cov_prior(hipStream_t s, double *S, long lds, const double *Xq, int M, int d, const CovParams &p,
                                     const double *R, long ldr, const double *V, long ldv, int Np, int nreg);
 hipError_t launch_predict_cov_mirror(hipStream_t s, double *S, long lds, int M);
+// hold-out validation and joint draws (gpemu_predict_joint_factor / _draw) on the tall matrix T = [S ; 64
+// right-hand-side rows], (Mp + 64) x Mp, Mp = M rounded up to 64: noise on the diagonal (var = the diagonal as factored), the
+// identity pad and the rows yobs_a - mean in one pass; everything above the diagonal of the factored rows zeroed; the normals
+// of nd <= 65535 draws zero-padded to Mp columns and their out rows pre-filled with the mean
+hipError_t launch_joint_stage(hipStream_t s, double *T, long ld, int M, const double *noise, const double *mean, const double *yobs,
+                              int nobs, double *var);
+hipError_t launch_joint_clean(hipStream_t s, double *T, long ld, int Mp);
+hipError_t launch_joint_draw_stage(hipStream_t s, double *Zp, long ldz, const double *z, int M, int nd, double *out, const double *mean);
 hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const double *src, long lds, int rows, int cols);
 hipError_t launch_predict_var_grad(hipStream_t s, double *gpart, long pstride, const double *Xq, int M, const double *X, const double *Xc,
                                    const double *mid, const double *At, long lda, int N, int Np, int d, const CovParams &p, bool gram);

@@ -1566,6 +1566,91 @@ hipError_t launch_predict_cov_mirror(hipStream_t s, double *S, long lds_, int M)
 	return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Hold-out validation and joint draws at query points (gpemu_predict_joint_factor / _draw): the tall matrix
+// T = [S ; right-hand-side rows] the factorisation works on, (Mp + 64) x Mp with Mp = M rounded up to 64 and row stride ld.
+// The sweep of the joint covariance has left the lower tiles of Sigma in rows and columns [0, M).
+// joint_stage_kernel, one pass, blockIdx.y names the row it writes:
+//   y < 64            right-hand-side row a = y: yobs_a - mean in columns < M for a < nobs, zero otherwise
+//   y = 64            the diagonal: S_pp = Sigma_pp + noise_p, also written to var
+//   y = 65 .. 128     row Mp - 64 + (y - 65) of the last tile row: the identity pad -- a row >= M becomes a row of the identity
+//                     (all Mp columns: every lower tile of the row), a row < M gets zeros in columns M .. Mp
+// Tiles above the diagonal are not touched: the factorisation reads lower tiles only.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void joint_stage_kernel(double *T, long ld, int M, int Mp, const double *noise, const double *mean,
+                                                          const double *yobs, int nobs, double *var)
+{
+	const int c = blockIdx.x * 256 + threadIdx.x;
+	if (c >= Mp) return;
+	const int y = blockIdx.y;
+	if (y < JOINT_RHS) {
+		T[(long)(Mp + y) * ld + c] = (y < nobs && c < M) ? yobs[(long)y * M + c] - mean[c] : 0.0;
+	} else if (y == JOINT_RHS) {
+		if (c >= M) return;
+		double *dg = T + (long)c * ld + c;
+		const double s = noise ? *dg + noise[c] : *dg;
+		*dg = s;
+		if (var) var[c] = s;
+	} else {
+		const int r = Mp - FT + (y - JOINT_RHS - 1);
+		if (r >= M) T[(long)r * ld + c] = (r == c) ? 1.0 : 0.0;
+		else if (c >= M) T[(long)r * ld + c] = 0.0;
+	}
+}
+
+// After the factorisation the part above the diagonal of rows [0, Mp) holds the diagonal blocks' inverses and tiles nobody
+// wrote: zero it, so that T is a plain lower-triangular factor whose rows the product of the draws may cut at the diagonal
+// (B[j][k] = 0 for k > j).  One workgroup per 64 x 64 tile on or above the diagonal.
+__global__ __launch_bounds__(256) void joint_clean_kernel(double *T, long ld, int Mp)
+{
+	const int tc = blockIdx.x, tr = blockIdx.y;
+	if (tc < tr) return;
+	const int col = tc * FT + (threadIdx.x & 63), rsub = threadIdx.x >> 6;
+#pragma unroll
+	for (int t = 0; t < 16; t++) {
+		const int row = tr * FT + rsub + 4 * t;
+		if (col > row && col < Mp && row < Mp) T[(long)row * ld + col] = 0.0;
+	}
+}
+
+// Draws: row s of Zp (nd x ldz, ldz >= Mp) = the normals z_s in columns < M, zero up to Mp; row s of out (nd x M) = mean, onto
+// which the product adds L_S z_s.  An element of z is read before the same element of out is written.
+__global__ __launch_bounds__(256) void joint_draw_stage_kernel(double *Zp, long ldz, const double *z, int M, int Mp, double *out,
+                                                               const double *mean)
+{
+	const int c = blockIdx.x * 256 + threadIdx.x;
+	if (c >= Mp) return;
+	const long s = blockIdx.y;
+	const double v = c < M ? z[s * M + c] : 0.0;
+	Zp[s * ldz + c] = v;
+	if (c < M) out[s * M + c] = mean[c];
+}
+
+hipError_t launch_joint_stage(hipStream_t s, double *T, long ld, int M, const double *noise, const double *mean, const double *yobs,
+                              int nobs, double *var)
+{
+	const int Mp = (M + FT - 1) / FT * FT;
+	if (M < 1 || ld < Mp || nobs < 0 || nobs > JOINT_RHS || (nobs && !yobs) || !mean) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(joint_stage_kernel, dim3((Mp + 255) / 256, 2 * JOINT_RHS + 1), dim3(256), 0, s, T, ld, M, Mp, noise, mean, yobs,
+	                   nobs, var);
+	return hipGetLastError();
+}
+
+hipError_t launch_joint_clean(hipStream_t s, double *T, long ld, int Mp)
+{
+	if (Mp < FT || Mp % FT || ld < Mp) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(joint_clean_kernel, dim3(Mp / FT, Mp / FT), dim3(256), 0, s, T, ld, Mp);
+	return hipGetLastError();
+}
+
+hipError_t launch_joint_draw_stage(hipStream_t s, double *Zp, long ldz, const double *z, int M, int nd, double *out, const double *mean)
+{
+	const int Mp = (M + FT - 1) / FT * FT;
+	if (M < 1 || nd < 1 || nd > 65535 || ldz < Mp) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(joint_draw_stage_kernel, dim3((Mp + 255) / 256, nd), dim3(256), 0, s, Zp, ldz, z, M, Mp, out, mean);
+	return hipGetLastError();
+}
+
 // transpose_kernel on a rows x cols block (multiples of 64): dst[j][i] = src[i][j]
 hipError_t launch_transpose_rect(hipStream_t s, double *dst, long ldd, const double *src, long lds_, int rows, int cols)
 {

@@ -124,6 +124,63 @@ void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &
 	for (int i = 0; i < number_outputs; i++) Covariances[i].assign(c.begin() + (size_t)i * np * np, c.begin() + (size_t)(i + 1) * np * np);
 }
 
+double emulator::ValidateHoldout(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<double> > &Observations,
+                                 std::vector<std::vector<double> > &Means, std::vector<std::vector<double> > &Variances,
+                                 std::vector<std::vector<double> > &WhitenedErrors, std::vector<double> &Mahalanobis,
+                                 std::vector<double> &LogDeterminant, std::vector<double> &LogDensity)
+{
+	const size_t np = xpoints.size(), nr = (size_t)the_model->nr;
+	if (Observations.size() != np) {
+		std::cerr << "Error::ValidateHoldout called with " << Observations.size() << " observations for " << np << " points" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	std::vector<double> flat = flatten("ValidateHoldout", xpoints, number_params);
+	std::vector<double> y = flatten("ValidateHoldout (Observations)", Observations, the_model->nt);
+	std::vector<double> m(np * nr), v(np * nr), w(np * nr);
+	Mahalanobis.assign(nr, 0.0);
+	LogDeterminant.assign(nr, 0.0);
+	LogDensity.assign(nr, 0.0);
+	double sum = 0.0;
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
+	emulate_points_multi_holdout(the_emulator, &view, y.data(), NULL, m.data(), v.data(), w.data(), Mahalanobis.data(), LogDeterminant.data(),
+	                             LogDensity.data(), &sum);
+	Means.assign(np, std::vector<double>(nr));
+	Variances.assign(np, std::vector<double>(nr));
+	WhitenedErrors.assign(np, std::vector<double>(nr));
+	for (size_t q = 0; q < np; q++)
+		for (size_t c = 0; c < nr; c++) {
+			Means[q][c] = m[q * nr + c];
+			Variances[q][c] = v[q * nr + c];
+			WhitenedErrors[q][c] = w[q * nr + c];
+		}
+	return sum;
+}
+
+void emulator::DrawEmulator(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<std::vector<double> > > &Normals,
+                            std::vector<std::vector<std::vector<double> > > &Draws)
+{
+	const size_t np = xpoints.size(), nr = (size_t)the_model->nr, no = (size_t)number_outputs;
+	const size_t nd = Normals.empty() ? 0 : Normals[0].size();
+	if (Normals.size() != nr || nd < 1) {
+		std::cerr << "Error::DrawEmulator called without normals for each of the " << nr << " PCA components" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	std::vector<double> flat = flatten("DrawEmulator", xpoints, number_params);
+	std::vector<double> z(nr * nd * np), out(nd * np * no);
+	for (size_t c = 0; c < nr; c++) {
+		if (Normals[c].size() != nd) { wrong_dimensions("DrawEmulator (Normals)"); gpemu_host_exit(EXIT_FAILURE); }
+		std::vector<double> zc = flatten("DrawEmulator (Normals)", Normals[c], (int)np);
+		for (size_t i = 0; i < nd * np; i++) z[c * nd * np + i] = zc[i];
+	}
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
+	emulate_points_multi_holdout(the_emulator, &view, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+	emulate_points_multi_draw(the_emulator, outputPCAValues ? 1 : 0, (int)np, (int)nd, z.data(), out.data());
+	Draws.assign(nd, std::vector<std::vector<double> >(np, std::vector<double>(no)));
+	for (size_t s = 0; s < nd; s++)
+		for (size_t q = 0; q < np; q++)
+			for (size_t i = 0; i < no; i++) Draws[s][q][i] = out[(s * np + q) * no + i];
+}
+
 void emulator::QueryEmulator(const std::vector<double> &xpoint, std::vector<double> &Means, std::vector<double> &Errors)
 {
 	if ((int)xpoint.size() != number_params) {

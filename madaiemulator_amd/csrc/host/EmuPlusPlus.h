@@ -41,6 +41,21 @@ public:
 	// rounding.  Covariances between different outputs are not modelled (libemu.h: emulate_points_multi_cov).
 	void QueryEmulatorCovariance(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Means,
 	                             std::vector<std::vector<double> > &Covariances);
+	// validation on a held-out campaign (libemu.h: emulate_points_multi_holdout): Observations[q] holds the nt observed outputs
+	// at xpoints[q], in observable space whatever PcaOnly says; they are projected onto the nr PCA components, and every
+	// component c answers in PCA space -- the diagnostics do not exist in observable space, where the covariance is singular
+	// whenever nr < nt.  Means[q][c], Variances[q][c], WhitenedErrors[q][c] (decorrelated errors, independent N(0, 1) under the
+	// model); Mahalanobis[c], LogDeterminant[c], LogDensity[c] per component.  Returns the sum of LogDensity: the joint log
+	// predictive density of the projected observations.  The factors stay resident for DrawEmulator.
+	double ValidateHoldout(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<double> > &Observations,
+	                       std::vector<std::vector<double> > &Means, std::vector<std::vector<double> > &Variances,
+	                       std::vector<std::vector<double> > &WhitenedErrors, std::vector<double> &Mahalanobis,
+	                       std::vector<double> &LogDeterminant, std::vector<double> &LogDensity);
+	// joint draws at xpoints from the emulator's posterior, Normals[c][s] the xpoints.size() standard normals of PCA component c
+	// for draw s (the caller's generator): Draws[s][q] has number_outputs entries, in observable space unless PcaOnly.  Factors
+	// the joint covariance at xpoints first (no noise); coinciding points end in the layer's fatal exit.
+	void DrawEmulator(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<std::vector<double> > > &Normals,
+	                  std::vector<std::vector<std::vector<double> > > &Draws);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -1063,6 +1063,75 @@ void emulate_points_cov_collect(emulator_struct *e, void *dev, int npoints, doub
 	check(en, rc, "emulate_points_cov");
 }
 
+/* hold-out validation at the query points (gpemu_predict_joint_factor in gpemu.h) with ONE row of observations (yobs NULL:
+ * none -- the call then only factors, for emulate_points_draw): every output may be NULL.  A matrix that is not positive
+ * definite ends in gpemu_host_fatal like every other device error. */
+#define HOLDOUT_LOG_2PI 1.8378770664093454835606594728112
+void emulate_points_holdout(emulator_struct *e, gsl_matrix *points, const double *yobs, const double *noise, double *mean, double *var,
+                            double *werr, double *maha, double *logdet, double *logpdf)
+{
+	struct entry *en = entry_of(e, "emulate_points_holdout");
+	double *q = pack_matrix(points);
+	int info = 0;
+	int rc = gpemu_predict_joint_factor(en->ctx, (int)points->size1, q, noise, yobs ? 1 : 0, yobs, mean, var, werr, maha, logdet, logpdf,
+	                                    &info);
+	free(q);
+	if (rc == GPEMU_ERR_NOT_PD) gpemu_host_fatal("emulate_points_holdout: Sigma + diag(noise) is not positive definite (pivot %d)\n", info);
+	check(en, rc, "emulate_points_holdout");
+}
+
+/* its two halves, like emulate_points_cov_enqueue / _collect: everything goes up, gpemu_predict_joint_factor_dev is enqueued on
+ * the component's own stream and the results wait in a device buffer -- queries, noise, observations, mean, var, werr, the two
+ * statistics (logdet, maha) and the info word, np doubles apart where they are vectors --; collect downloads them, which
+ * waits for that stream only, finishes logpdf as the device library does, and releases the buffer.  The factor stays resident
+ * in the component's context for emulate_points_draw. */
+void emulate_points_holdout_enqueue(emulator_struct *e, gsl_matrix *points, const double *yobs, const double *noise, void **dev_out)
+{
+	struct entry *en = entry_of(e, "emulate_points_holdout");
+	const size_t np = points->size1, d = points->size2;
+	double *q = pack_matrix(points);
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(en->ctx, (np * d + 5 * np + 4) * sizeof(double), &dev);
+	double *x = (double *)dev, *nz = x + np * d, *yo = nz + np, *mu = yo + np, *va = mu + np, *we = va + np, *st = we + np;
+	if (!rc) rc = gpemu_dev_upload(en->ctx, x, q, np * d * sizeof(double));
+	free(q);
+	if (!rc && noise) rc = gpemu_dev_upload(en->ctx, nz, noise, np * sizeof(double));
+	if (!rc && yobs) rc = gpemu_dev_upload(en->ctx, yo, yobs, np * sizeof(double));
+	if (!rc) rc = gpemu_predict_joint_factor_dev(en->ctx, (int)np, x, noise ? nz : NULL, yobs ? 1 : 0, yobs ? yo : NULL, mu, va, we, st,
+	                                             (int *)(st + 2));
+	check(en, rc, "emulate_points_holdout");
+	*dev_out = dev;
+}
+
+void emulate_points_holdout_collect(emulator_struct *e, void *dev, int npoints, int nobs, double *mean, double *var, double *werr,
+                                    double *maha, double *logdet, double *logpdf)
+{
+	struct entry *en = entry_of(e, "emulate_points_holdout");
+	const size_t np = (size_t)npoints, d = (size_t)en->d;
+	const double *mu = (const double *)dev + np * d + 2 * np, *va = mu + np, *we = va + np, *st = we + np;
+	double stat[2] = {0.0, 0.0};
+	int info = 0;
+	int rc = gpemu_dev_download(en->ctx, &info, st + 2, sizeof(int));
+	if (!rc) rc = gpemu_dev_download(en->ctx, stat, st, sizeof stat);
+	if (!rc && mean) rc = gpemu_dev_download(en->ctx, mean, mu, np * sizeof(double));
+	if (!rc && var) rc = gpemu_dev_download(en->ctx, var, va, np * sizeof(double));
+	if (!rc && werr && nobs) rc = gpemu_dev_download(en->ctx, werr, we, np * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	check(en, rc, "emulate_points_holdout");
+	if (info < 0x7f7f7f7f) gpemu_host_fatal("emulate_points_holdout: Sigma + diag(noise) is not positive definite (pivot %d)\n", info);
+	if (logdet) *logdet = stat[0];
+	if (nobs && maha) *maha = stat[1];
+	if (nobs && logpdf) *logpdf = -0.5 * (stat[1] + stat[0] + npoints * HOLDOUT_LOG_2PI);
+}
+
+/* joint draws from the factor the last emulate_points_holdout[_enqueue] on e left: out[s] = mean + L_S z[s], ndraw rows of
+ * npoints */
+void emulate_points_draw(emulator_struct *e, int ndraw, const double *z, double *out)
+{
+	struct entry *en = entry_of(e, "emulate_points_draw");
+	check(en, gpemu_predict_joint_draw(en->ctx, ndraw, z, out), "emulate_points_draw");
+}
+
 /* leave-one-out at every training point (gpemu_loo) */
 void emulate_loo(emulator_struct *e, double *mean, double *variance)
 {

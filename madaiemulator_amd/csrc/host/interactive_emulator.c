@@ -6,6 +6,7 @@
  *   interactive_emulator interactive_mode MODEL_SNAPSHOT_FILE [OPTIONS]
  *   interactive_emulator print_thetas MODEL_SNAPSHOT_FILE
  *   interactive_emulator validate MODEL_SNAPSHOT_FILE [--pca_output] [--quiet]     (not in the reference)
+ *   interactive_emulator validate MODEL_SNAPSHOT_FILE --holdout=FILE [--quiet]     (not in the reference)
  *
  * Kept quirks: --covariance_fn is atoi'd and compared with POWEREXPCOVFN=1 /
  * MATERN32=2 / MATERN52=3 (0 and 1 both mean power-exponential); --pca_variance falls through
@@ -30,7 +31,7 @@
 struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
-	char *run_mode, *inputfile, *statefile;
+	char *run_mode, *inputfile, *statefile, *holdoutfile;
 };
 
 static const char useage[] =
@@ -42,6 +43,10 @@ static const char useage[] =
 	"  interactive_emulator print_thetas MODEL_SNAPSHOT_FILE\n"
 	"or\n"
 	"  interactive_emulator validate MODEL_SNAPSHOT_FILE [--pca_output] [--quiet]  (leave-one-out mean and variance per training point)\n"
+	"or\n"
+	"  interactive_emulator validate MODEL_SNAPSHOT_FILE --holdout=FILE [--quiet]  (validation on a held-out campaign: FILE in the\n"
+	"      INPUT_MODEL_FILE format; per point and PCA component mean, variance and decorrelated error, per component the\n"
+	"      Mahalanobis distance and the joint log predictive density)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -173,6 +178,8 @@ static int interactive_mode(struct cmdLineOpts *o)
 	return rc == 0 ? 0 : EXIT_FAILURE;
 }
 
+static int validate_holdout(struct cmdLineOpts *o);      /* validate --holdout=FILE, below */
+
 /* Leave-one-out validation of a trained snapshot (not in the reference, which leaves validation to a held-out campaign):
  * one line per training point in design order, "mean_0 variance_0 mean_1 variance_1 ..." -- what the emulator trained on
  * the other N - 1 points at the same thetas answers at that point (emulate_loo_multi) -- and one summary line per output
@@ -180,6 +187,7 @@ static int interactive_mode(struct cmdLineOpts *o)
  * space the PCA truncation shows, and the mean of residual^2 / variance, near 1 for a calibrated emulator. */
 static int validate(struct cmdLineOpts *o)
 {
+	if (o->holdoutfile) return validate_holdout(o);
 	FILE *fp = fopen(o->statefile, "r");
 	if (!fp) return perr("Error opening file");
 	gpemu_host_warm_start();
@@ -217,6 +225,68 @@ static int validate(struct cmdLineOpts *o)
 			fprintf(stderr, "# loo output %d: rmse %.17g mean_standardised_sq %.17g\n", j, sqrt(ss / N), sz / N);
 		}
 	free(mean); free(var);
+	free_multi_emulator(emu);
+	return 0;
+}
+
+/* Validation of a trained snapshot on a held-out campaign (--holdout=FILE, FILE in the INPUT_MODEL_FILE format: "nt d N", the
+ * N hold-out design points, their N x nt observed outputs).  The observations are projected onto the snapshot's PCA components
+ * and every component is judged with the joint covariance between the hold-out points (emulate_points_multi_holdout), in PCA
+ * space -- the only space these diagnostics exist in.  stdout: one line per hold-out point, "mean_0 variance_0 werr_0 mean_1
+ * ..." over the components, werr the decorrelated error (independent N(0, 1) under the model; the per-point residual^2 /
+ * variance of the leave-one-out mode ignores the correlations between the points).  stderr, per component: the squared
+ * Mahalanobis distance (chi^2 with M degrees of freedom under the model), the joint log predictive density and the root
+ * mean square of (projected observation - mean); then their totals. */
+static int validate_holdout(struct cmdLineOpts *o)
+{
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	gsl_matrix *xh = NULL, *yh = NULL;
+	if (!open_model_file(o->holdoutfile, &xh, &yh)) return perr("Hold-out file read failed.");
+	const int d = model->nparams, nt = model->nt, nr = model->nr;
+	if ((int)xh->size2 != d || (int)yh->size2 != nt) {
+		fprintf(stderr, "the hold-out file has %d parameters and %d outputs, the snapshot %d and %d\n", (int)xh->size2, (int)yh->size2, d, nt);
+		return EXIT_FAILURE;
+	}
+	const size_t M = xh->size1;
+	multi_emulator *emu = alloc_multi_emulator(model);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "%d\n", d);
+		for (int i = 0; i < d; i++) fprintf(out, "%s%d\n", "param_", i);
+		fprintf(out, "%d\n", 3 * nr);
+		for (int i = 0; i < nr; i++) fprintf(out, "%s_%d\n%s_%d\n%s_%d\n", "mean", i, "variance", i, "werr", i);
+	}
+	double *Y = (double *)malloc(sizeof(double) * M * (size_t)nt), *z = (double *)malloc(sizeof(double) * M * (size_t)nr);
+	double *mean = (double *)malloc(sizeof(double) * M * (size_t)nr), *var = (double *)malloc(sizeof(double) * M * (size_t)nr);
+	double *werr = (double *)malloc(sizeof(double) * M * (size_t)nr), *stat = (double *)malloc(sizeof(double) * 3 * (size_t)nr);
+	double *maha = stat, *logdet = stat + nr, *logpdf = stat + 2 * nr, total = 0.0;
+	for (size_t p = 0; p < M; p++) for (int t = 0; t < nt; t++) Y[p * nt + t] = gsl_matrix_get(yh, p, t);
+	emulate_points_multi_holdout(emu, xh, Y, NULL, mean, var, werr, maha, logdet, logpdf, &total);
+	for (size_t p = 0; p < M; p++) {
+		for (int c = 0; c < nr; c++)
+			fprintf(out, "%s%.17g %.17g %.17g", c ? " " : "", mean[p * nr + c], var[p * nr + c], werr[p * nr + c]);
+		fprintf(out, "\n");
+	}
+	fflush(out);
+	if (!o->quietFlag) {
+		double dsum = 0.0;
+		gpemu_host_project_observations(model, M, Y, z);
+		for (int c = 0; c < nr; c++) {
+			double ss = 0.0;
+			for (size_t p = 0; p < M; p++) { const double r = z[(size_t)c * M + p] - mean[p * nr + c]; ss += r * r; }
+			fprintf(stderr, "# holdout component %d: points %d mahalanobis %.17g log_density %.17g rmse %.17g\n", c, (int)M, maha[c], logpdf[c],
+			        sqrt(ss / (double)M));
+			dsum += maha[c];
+		}
+		fprintf(stderr, "# holdout total: components %d points %d mahalanobis %.17g log_density %.17g\n", nr, (int)M, dsum, total);
+	}
+	free(Y); free(z); free(mean); free(var); free(werr); free(stat);
+	gsl_matrix_free(xh); gsl_matrix_free(yh);
 	free_multi_emulator(emu);
 	return 0;
 }
@@ -266,6 +336,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"exact_gradient", no_argument, NULL, 1001},          {"matern_fixed", no_argument, NULL, 1002},
 		/* the reference's compile-time BINARY_INTERACTIVE_MODE (interactive_emulator.c:119,392-396,418-438) as a run-time flag */
 		{"binary", no_argument, NULL, 1003},
+		/* validate on a held-out campaign instead of leave-one-out */
+		{"holdout", required_argument, NULL, 1004},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -288,6 +360,7 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1001: gpemu_host_set_modes(gpemu_host_modes() | 1 /* GPEMU_MODE_EXACT_GRAD */); break;
 		case 1002: gpemu_host_set_modes(gpemu_host_modes() | 2 /* GPEMU_MODE_MATERN_LOG */); break;
 		case 1003: o->binaryFlag = 1; break;
+		case 1004: o->holdoutfile = optarg; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;

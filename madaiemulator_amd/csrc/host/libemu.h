@@ -270,6 +270,21 @@ void emulate_points_cov(emulator_struct *e, gsl_matrix *points, double *mean, do
 /* emulate_points_cov in two halves, like emulate_loo_enqueue / _collect: *dev_out is the device buffer the results wait in */
 void emulate_points_cov_enqueue(emulator_struct *e, gsl_matrix *points, void **dev_out);
 void emulate_points_cov_collect(emulator_struct *e, void *dev, int npoints, double *mean, double *cov);
+/* extension: validation on a held-out campaign and joint draws (gpemu_predict_joint_factor / _draw in gpemu.h).  With
+ * S = Sigma + diag(noise) (Sigma as emulate_points_cov returns it, noise npoints variances or NULL) factored on the device,
+ * S = L L^T, and yobs one observation per row of points (npoints values, or NULL: factor only, for emulate_points_draw):
+ *   werr = L^-1 (yobs - mean) (npoints decorrelated errors), *maha = |werr|^2, *logdet = log det S,
+ *   *logpdf = -1/2 (maha + logdet + npoints log 2 pi), var = diag S; every output may be NULL.
+ * emulate_points_draw returns out[s] = mean + L z[s] for ndraw rows of npoints standard normals, from the factor the last
+ * emulate_points_holdout[_enqueue] on e left (kept until e is freed or the next hold-out call on it).  At most 16384 points.
+ * Errors, a matrix that is not positive definite among them (coinciding points without noise), end in gpemu_host_fatal. */
+void emulate_points_holdout(emulator_struct *e, gsl_matrix *points, const double *yobs, const double *noise, double *mean, double *var,
+                            double *werr, double *maha, double *logdet, double *logpdf);
+/* in two halves, like emulate_points_cov_enqueue / _collect; nobs = 1 when yobs was given to the enqueue, else 0 */
+void emulate_points_holdout_enqueue(emulator_struct *e, gsl_matrix *points, const double *yobs, const double *noise, void **dev_out);
+void emulate_points_holdout_collect(emulator_struct *e, void *dev, int npoints, int nobs, double *mean, double *var, double *werr,
+                                    double *maha, double *logdet, double *logpdf);
+void emulate_points_draw(emulator_struct *e, int ndraw, const double *z, double *out);
 /* extension: leave-one-out validation (gpemu_loo in gpemu.h).  mean[i], variance[i] for each of the N training points: what
  * alloc_emulator_struct on the other N - 1 points at the same thetas and emulate_point at x_i return, without refitting */
 void emulate_loo(emulator_struct *e, double *mean, double *variance);
@@ -315,6 +330,22 @@ void emulate_points_multi_grad(multi_emulator *emu, gsl_matrix *points, int pca_
  * the first is waited for.  Covariances BETWEEN outputs are not modelled here, as they are not in the reference: its PCA
  * components are independent emulators and its rule keeps only each output's own variance. */
 void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_space, double *mean_out, double *cov_out);
+/* extension: validation of a multi-output emulator on a held-out campaign.  Y (npoints x nt, observable space; NULL: factor
+ * only) is projected into PCA space exactly as gen_pca_decomp builds pca_zmatrix, (Y - training_mean) evecs / sqrt(evals), and
+ * every component c is validated on its own column by emulate_points_holdout (all components are started before the first is
+ * collected).  noise_pca (nr x npoints, may be NULL): observation variances per component, in PCA space.  Outputs, any may be
+ * NULL: mean_out, var_out, werr_out npoints x nr (the layout of emulate_points_multi in PCA space); maha_out, logdet_out,
+ * logpdf_out nr values; *logpdf_sum their sum, the joint log density of the projected observations -- the components are
+ * independent emulators.  These diagnostics exist in PCA space ONLY: in observable space the covariance of the nt outputs at a
+ * point, sum_c F_tc F_uc Sigma_c, has rank nr and is singular whenever nr < nt, so it has no Cholesky factor, no Mahalanobis
+ * distance and no density. */
+void emulate_points_multi_holdout(multi_emulator *emu, gsl_matrix *points, const double *Y, const double *noise_pca, double *mean_out,
+                                  double *var_out, double *werr_out, double *maha_out, double *logdet_out, double *logpdf_out,
+                                  double *logpdf_sum);
+/* joint draws at the npoints points of the last emulate_points_multi_holdout: z is nr x ndraw x npoints standard normals (component
+ * c draws with z[c] from its own factor), out is ndraw x npoints x nr in PCA space or ndraw x npoints x nt in observable space:
+ * training_mean + evecs diag(sqrt(evals)) draw_pca through gpemu_host_backproject (not squared, mean added) */
+void emulate_points_multi_draw(multi_emulator *emu, int pca_space, int npoints, int ndraw, const double *z, double *out);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);
@@ -385,6 +416,10 @@ void gpemu_host_release(void *params_or_emulator); /* drop the device context ca
  * width, both row-major and distinct.  The sum runs over c in index order from 0.0; the training mean is added last. */
 void gpemu_host_backproject(const multi_modelstruct *m, int squared, int add_mean, size_t nrows, size_t width,
                             const double *in, double *out);
+/* the observable -> PCA projection of emulate_points_multi_holdout, host arithmetic only (multi.c): Y is np x nt, z comes back
+ * component-major, z[c * np + p] = (sum_t (Y[p][t] - training_mean[t]) evecs[t][c]) * (1 / sqrt(evals[c])), the sum over t in
+ * index order from 0.0 -- the arithmetic gen_pca_decomp builds pca_zmatrix with */
+void gpemu_host_project_observations(const multi_modelstruct *m, size_t np, const double *Y, double *z);
 /* lock-step group: n restart threads (one struct estimate_thetas_params each, same model) share one device context;
  * their concurrent evalFnMulti / gradFnMulti / evalFnGradMulti / estimateSigmaFull calls are gathered into device
  * batches.  A member's thread calls gpemu_host_group_leave(params) when it will make no further calls. */

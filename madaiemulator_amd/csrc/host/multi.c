@@ -598,6 +598,68 @@ void emulate_points_multi_cov(multi_emulator *emu, gsl_matrix *points, int pca_s
 	free(mp); free(mc); free(dev);
 }
 
+/* Validation on a held-out campaign (libemu.h).  The observations Y (np x nt, observable space) go to PCA space by the
+ * arithmetic gen_pca_decomp builds pca_zmatrix with -- z[c][p] = (sum_t (Y[p][t] - training_mean[t]) evecs[t][c]) * (1 / sqrt(evals[c])),
+ * t in index order from 0.0 --, component-major, one row of np per component; then every component's factor call is enqueued
+ * on its own stream before the first is collected.  The components are independent emulators, so the joint log density of
+ * the projected observations is the sum of theirs. */
+void gpemu_host_project_observations(const multi_modelstruct *m, size_t np, const double *Y, double *z)
+{
+	const size_t nt = (size_t)m->nt, nr = (size_t)m->nr;
+	for (size_t p = 0; p < np; p++)
+		for (size_t c = 0; c < nr; c++) {
+			double s = 0.0;
+			for (size_t t = 0; t < nt; t++) s += (Y[p * nt + t] - gsl_vector_get(m->training_mean, t)) * gsl_matrix_get(m->pca_evecs_r, t, c);
+			z[c * np + p] = s * (1.0 / sqrt(gsl_vector_get(m->pca_evals_r, c)));
+		}
+}
+
+void emulate_points_multi_holdout(multi_emulator *emu, gsl_matrix *points, const double *Y, const double *noise_pca, double *mean_out,
+                                  double *var_out, double *werr_out, double *maha_out, double *logdet_out, double *logpdf_out,
+                                  double *logpdf_sum)
+{
+	const size_t np = points->size1, nr = (size_t)emu->nr;
+	const int nobs = Y ? 1 : 0;
+	double *z = Y ? doubles(nr * np) : NULL;
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *wp = doubles(np * nr), *mc = doubles(np), *vc = doubles(np), *wc = doubles(np);
+	void **dev = (void **)malloc(sizeof(void *) * nr);
+	if (Y) gpemu_host_project_observations(emu->model, np, Y, z);
+	for (size_t c = 0; c < nr; c++)
+		emulate_points_holdout_enqueue(emu->emu_struct_array[c], points, Y ? z + c * np : NULL, noise_pca ? noise_pca + c * np : NULL, &dev[c]);
+	double sum = 0.0;
+	for (size_t c = 0; c < nr; c++) {
+		double maha = 0.0, logdet = 0.0, logpdf = 0.0;
+		emulate_points_holdout_collect(emu->emu_struct_array[c], dev[c], (int)np, nobs, mc, vc, wc, &maha, &logdet, &logpdf);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
+		if (nobs) place_component(wp, wc, np, nr, c, 1);
+		if (maha_out && nobs) maha_out[c] = maha;
+		if (logdet_out) logdet_out[c] = logdet;
+		if (logpdf_out && nobs) logpdf_out[c] = logpdf;
+		sum += logpdf;
+	}
+	if (mean_out) memcpy(mean_out, mp, sizeof(double) * np * nr);
+	if (var_out) memcpy(var_out, vp, sizeof(double) * np * nr);
+	if (werr_out && nobs) memcpy(werr_out, wp, sizeof(double) * np * nr);
+	if (logpdf_sum && nobs) *logpdf_sum = sum;
+	free(z); free(mp); free(vp); free(wp); free(mc); free(vc); free(wc); free(dev);
+}
+
+/* joint draws at the points of the last emulate_points_multi_holdout: component c draws from its own resident factor with its
+ * own normals z[c] (ndraw x np); the results land [s][p][c], which is the PCA-space output, and go to observable space through
+ * the mean half of the rule, training mean added */
+void emulate_points_multi_draw(multi_emulator *emu, int pca_space, int npoints, int ndraw, const double *z, double *out)
+{
+	const size_t np = (size_t)npoints, nd = (size_t)ndraw, nr = (size_t)emu->nr;
+	double *dp = doubles(nd * np * nr), *dc = doubles(nd * np);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_points_draw(emu->emu_struct_array[c], ndraw, z + c * nd * np, dc);
+		place_component(dp, dc, nd * np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 0, 1, nd * np, 1, dp, out);
+	free(dp); free(dc);
+}
+
 /* leave-one-out at every training point: the components are independent contexts, so all are started before the first is
  * waited for, as above; component results are N x nr in design order, then the same back-projection */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out)
