@@ -366,6 +366,51 @@ int gpemu_loo(gpemu_ctx *ctx, double *mean /* N host */, double *var /* N host *
 /* the same with result buffers in HBM (device pointers): only enqueues on the context's stream, no host sync */
 int gpemu_loo_dev(gpemu_ctx *ctx, double *mean_dev, double *var_dev);
 
+/* ---- K-fold / leave-group-out validation of a trained emulator -----------------
+ * group[i] in 0 .. ngroups-1 names the group training point i is left out with, -1: never left out.  For every group B (b
+ * points, taken in ascending design index): what removing ALL of B, alloc_emulator_struct on the other N - b points at the
+ * same thetas and gpemu_predict_cov at x_B return -- GLS beta re-estimated, the variance with the regression term, kappa
+ * with the nugget, as gpemu_loo stands for with one point -- from the state gpemu_predict_setup[_batch] left in HBM, by the
+ * block form of gpemu_loo's closed form.  With P = C^-1 - W Q W^T and gamma = P y:
+ *   (P_BB)_ij = sum_k (L^-1)_ki (L^-1)_kj - w_i^T Q w_j        P_BB = R R^T (lower Cholesky, the likelihood's factorisation)
+ *   cov_B     = P_BB^-1           mean_B = y_B - cov_B gamma_B          var_i = (cov_B)_ii = sum_k (R^-1)_ki^2
+ *   werr_B    = R^-1 gamma_B = R^T (y_B - mean_B)      the decorrelated errors of the group: independent N(0, 1) under the model
+ *   maha[g]   = |werr_B|^2 = (y_B - mean_B)^T cov_B^-1 (y_B - mean_B)
+ *   logdet[g] = log det cov_B = -2 sum_i log R_ii       logpdf[g] = -1/2 (maha[g] + logdet[g] + b log 2 pi)
+ * With b = 1 this is gpemu_loo.  werr whitens with the UPPER factor R^-T of cov_B (cov_B = R^-T R^-1): werr_i depends on the
+ * errors of the group's members k >= i.  gpemu_predict_joint_factor's werr uses the lower factor of its S, so for the same
+ * points the two are different vectors of the same norm.
+ * mean, var, werr: N each, in design order, NaN where group[i] = -1; maha, logdet, logpdf, info: ngroups each.
+ * The clamp remark of gpemu_loo holds unchanged: the closed form reads C, which is not clamped; a refit's k-vector is.
+ * How it runs: chunks of at most GPEMU_MAX_BATCH groups, every group of the CALL padded to bp = the largest group rounded up
+ * to 64; per chunk of nbc groups a gather of the members' columns of L^-1, one batched product, a staging pass, ONE lock-step
+ * factorisation with inverse rows of the nbc matrices, and a finishing pass, all on the context's stream.  Memory per chunk:
+ * 8 nbc bp (Np + 2 bp + 64) bytes (Np = N rounded up to 64) plus 8 nbc (bp / 64 + 2) bytes of partial sums and the index
+ * tables (4 (2 N + 2 ngroups) bytes, device and pinned); nbc = the most groups, at most 64 and at least one, that keep the
+ * formula within 2 GiB (fixed, so the chunking depends on the call alone).  gpemu_lgo_release gives the buffers back (waits
+ * for the stream); gpemu_set_model and the end of the context free them too.
+ * A group whose P_BB is not positive definite to working precision: info[g] = the 1-based position of the failed pivot within
+ * the group (0 otherwise), NaN in all its outputs; the other groups stay valid, and the host entry returns GPEMU_ERR_NOT_PD.
+ * Errors: GPEMU_ERR_ARG for a NULL ctx, group, mean, var or info and for ngroups < 1, whatever the context's state;
+ * GPEMU_ERR_STATE without a valid prediction set-up; then GPEMU_ERR_ARG, before anything is allocated or launched, for
+ * ngroups > N, a label outside -1 .. ngroups-1, a label without members, a largest group b_max with N - b_max <= nreg (no
+ * degrees of freedom left: gpemu_loo's rule), bp > 16384.
+ * Two identical calls return the same bits; the host and _dev entries and a context set up by gpemu_predict_setup_batch return
+ * the same bits.  A group's bits may depend on the other groups of the call (the common padded size does).  No atomics beyond
+ * the factorisation's info words, no workgroup waits for another.  The entry works in buffers of its own: it leaves nothing
+ * another entry reads, a pending host-buffer prediction batch stays collectable, gpemu_get_cinverse keeps working. */
+int gpemu_lgo(gpemu_ctx *ctx, int ngroups, const int *group /* N host */, double *mean /* N */, double *var /* N */,
+              double *werr /* N, may be NULL */, double *maha /* ngroups, may be NULL */, double *logdet /* ngroups, may be NULL */,
+              double *logpdf /* ngroups, may be NULL */, int *info /* ngroups */);
+/* result buffers in HBM (device pointers), group still a HOST array (sizes and chunking are decided on the host): only
+ * enqueues on the context's stream.  stat_dev: maha[0 .. ngroups), then logdet[0 .. ngroups), then logpdf[0 .. ngroups);
+ * info_dev[g]: 0 or the 1-based position, already decoded.  The index tables go up through a pinned buffer of the context:
+ * a call first waits (on the host) until the previous call's upload out of that buffer has executed -- not for its kernels. */
+int gpemu_lgo_dev(gpemu_ctx *ctx, int ngroups, const int *group /* N HOST */, double *mean_dev, double *var_dev,
+                  double *werr_dev /* may be NULL */, double *stat_dev /* 3*ngroups, may be NULL */, int *info_dev /* ngroups */);
+/* frees every buffer of the two entries above (waits for the context's stream) */
+int gpemu_lgo_release(gpemu_ctx *ctx);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */
@@ -413,6 +458,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_VAR_GRAD 10 /* the fused sweep of the variance-gradient entry and its finish: flops = M*N*(3 d + 1 + 2 (d + 1)), bytes = 8*M*(N + 2 d); its two products report under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_COV     11  /* the prior and mirror launches of gpemu_predict_cov[_dev]: bytes = 8*M*M (the lower triangle written once, mirrored once); its symmetric product reports under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_JOINT   12  /* the staging and clean launches of gpemu_predict_joint_factor[_dev] (bytes = 8*(64 M' + 2 M) and 4*M'*M', M' = M rounded up to 64) and the staging launch of every block of gpemu_predict_joint_draw[_dev] (bytes = 8*ndraw*(M' + 2 M)); the sweep, the products and the factorisation report under GPEMU_PROF_FILL / _COV / _GEMM / _LEAF / _POTRF */
+#define GPEMU_PROF_LGO     13  /* the three launches per chunk of gpemu_lgo[_dev], nbc groups padded to bp: gather (bytes = 8 nbc bp Np: the rows of Z written; it reads at most the lower tiles of L^-1 besides), staging (bytes = 8 nbc bp (2 bp + 64): the lower tiles read and written, right-hand-side and identity rows written), finish (bytes = 8 nbc bp (bp / 2 + 4)); the product and the factorisation report under GPEMU_PROF_GEMM / _LEAF / _POTRF */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

@@ -21,6 +21,7 @@ PROF_MEAN_GRAD = 9
 PROF_VAR_GRAD = 10
 PROF_COV = 11
 PROF_JOINT = 12
+PROF_LGO = 13
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -121,6 +122,9 @@ SYMBOLS = {
     "gpemu_predict_joint_release": (C.c_int, [C.c_void_p]),
     "gpemu_loo": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_loo_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_lgo": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpemu_lgo_dev": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_lgo_release": (C.c_int, [C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -406,6 +410,42 @@ class Context:
 
     def loo_dev(self, mean_dev, var_dev):
         self._chk(self.L.gpemu_loo_dev(self.h, mean_dev, var_dev))
+
+    # K-fold / leave-group-out validation from the resident prediction state: every group left out as a
+    # whole, its joint prediction and predictive density in closed form, all groups of a call in lock-step batches
+    @staticmethod
+    def _lgo_labels(group, ngroups):
+        group = np.ascontiguousarray(group, dtype=np.int32).ravel()
+        if ngroups is None:
+            ngroups = int(group.max()) + 1 if group.size else 0
+        return group, int(ngroups)
+
+    def lgo(self, group, ngroups=None):
+        """group[i] in 0 .. ngroups-1 or -1 (never left out), N labels; ngroups defaults to the largest label + 1
+        -> dict(mean[N], var[N], werr[N] (design order, NaN for label -1), maha[ngroups], logdet[ngroups], logpdf[ngroups],
+        info[ngroups], status); status is OK or ERR_NOT_PD (then info[g] != 0 names the group and the pivot, and that group's
+        outputs are NaN)"""
+        group, ngroups = self._lgo_labels(group, ngroups)
+        if group.size != self.N:
+            raise GpemuError(ERR_ARG, "lgo: one label per training point")
+        ng = max(ngroups, 1)
+        mean, var, werr = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        maha, logdet, logpdf = np.empty(ng), np.empty(ng), np.empty(ng)
+        info = np.zeros(ng, dtype=np.int32)
+        rc = self.L.gpemu_lgo(self.h, ngroups, group.ctypes.data_as(_ip), _p(mean), _p(var), _p(werr), _p(maha), _p(logdet),
+                              _p(logpdf), info.ctypes.data_as(_ip))
+        self._chk(rc, allow=(ERR_NOT_PD,))
+        return dict(mean=mean, var=var, werr=werr, maha=maha, logdet=logdet, logpdf=logpdf, info=info, status=rc)
+
+    def lgo_dev(self, group, ngroups, mean_dev, var_dev, werr_dev, stat_dev, info_dev):
+        """group: HOST labels; the rest device pointers (werr_dev, stat_dev may be None); stat_dev: maha, logdet, logpdf, ngroups each"""
+        group, ngroups = self._lgo_labels(group, ngroups)
+        if group.size != self.N:
+            raise GpemuError(ERR_ARG, "lgo_dev: one label per training point")
+        self._chk(self.L.gpemu_lgo_dev(self.h, ngroups, group.ctypes.data_as(_ip), mean_dev, var_dev, werr_dev, stat_dev, info_dev))
+
+    def lgo_release(self):
+        self._chk(self.L.gpemu_lgo_release(self.h))
 
     def chol_inverse(self, A):
         A = _a(A).copy()

@@ -268,6 +268,9 @@ static void free_model(gpemu_ctx *ctx)
 	                &ctx->dCov, &ctx->dJoint, &ctx->dJointMean, &ctx->dJointPart, &ctx->dJointZ, &ctx->dJointIO})
 		b->reset();
 	ctx->dJointInfo.reset();
+	for (auto *b : {&ctx->dLgoZ, &ctx->dLgoT, &ctx->dLgoPart, &ctx->dLgoOut}) b->reset();
+	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
+	ctx->hLgoTab.reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -283,6 +286,7 @@ gpemu_ctx::~gpemu_ctx()
 	free_model(this);
 	for (auto e : prof.ev) hipEventDestroy(e);
 	for (auto e : pring.ev) if (e) hipEventDestroy(e);
+	if (lgo_ev) hipEventDestroy(lgo_ev);
 	for (auto &s : ring) if (s.ev) hipEventDestroy(s.ev);
 	if (stream) hipStreamDestroy(stream);
 }
@@ -1942,6 +1946,169 @@ extern "C" int gpemu_loo(gpemu_ctx *ctx, double *mean, double *var)
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	memcpy(mean, ctx->hLoo, N * sizeof(double));
 	memcpy(var, ctx->hLoo + N, N * sizeof(double));
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// K-fold / leave-group-out validation (gpemu.h): for every group B the joint leave-B-out prediction from the
+// resident L^-1, gamma, W^T and Q.  Per chunk of groups: gather the members' columns of L^-1 as rows Z_g, (C^-1)_BB = Z_g Z_g^T
+// (one batched product into the tall layout), staging (minus W_B Q W_B^T, pad, gamma_B, identity rows), ONE lock-step
+// factorisation with inverse rows through a view of dLgoT, |w|^2 and sum log R_ii by the likelihood's Gram and finish kernels
+// (one right-hand side, Rp = 1), the finishing pass.  Plain launches (the shape changes from call to call), everything on the
+// context's stream, only buffers of its own.
+// ---------------------------------------------------------------------------
+constexpr double LGO_BUDGET = 2147483648.0;   // bytes of 8 nbc bp (Np + 2 bp + 64) a chunk may take: fixed, so the chunking depends on the call alone
+constexpr int LGO_BP_MAX = 16384;
+
+struct LgoPlan {
+	int bp = 0, nbc = 0;
+	std::vector<int> count;
+};
+
+// the model-dependent argument checks, nothing allocated or launched; the padded size and the chunk size
+static int lgo_plan(gpemu_ctx *ctx, int ngroups, const int *group, LgoPlan *pl)
+{
+	const int N = ctx->N;
+	if (ngroups > N) return fail(ctx, GPEMU_ERR_ARG, "leave-group-out: more groups than training points");
+	pl->count.assign((size_t)ngroups, 0);
+	for (int i = 0; i < N; i++) {
+		if (group[i] < -1 || group[i] >= ngroups) return fail(ctx, GPEMU_ERR_ARG, "leave-group-out: a label outside -1 .. ngroups-1");
+		if (group[i] >= 0) pl->count[group[i]]++;
+	}
+	int bmax = 0;
+	for (int g = 0; g < ngroups; g++) {
+		if (!pl->count[g]) return fail(ctx, GPEMU_ERR_ARG, "leave-group-out: a label without members");
+		bmax = std::max(bmax, pl->count[g]);
+	}
+	if (N - bmax <= ctx->nreg) return fail(ctx, GPEMU_ERR_ARG, "leave-group-out needs N - (largest group) > nregression_fns");
+	if (round_up(bmax, LEAF) > LGO_BP_MAX) return fail(ctx, GPEMU_ERR_ARG, "leave-group-out: a group of more than 16384 points");
+	pl->bp = round_up(bmax, LEAF);
+	const double per = 8.0 * pl->bp * ((double)ctx->Np + 2.0 * pl->bp + LEAF);
+	pl->nbc = std::max(1, std::min(std::min(ngroups, GPEMU_MAX_BATCH), (int)(LGO_BUDGET / per)));
+	return GPEMU_OK;
+}
+
+static int lgo_run(gpemu_ctx *ctx, const LgoPlan &pl, int ngroups, const int *group, double *mean_dev, double *var_dev, double *werr_dev,
+                   double *stat_dev, int *info_dev)
+{
+	const int N = ctx->N, Np = ctx->Np, bp = pl.bp, nbc_max = pl.nbc;
+	const size_t tstride = ((size_t)2 * bp + LEAF) * bp, ntab = 2 * (size_t)N + 2 * (size_t)ngroups;
+	const char *oom = "out of device memory for leave-group-out (8 nbc bp (Np + 2 bp + 64) bytes per chunk of nbc groups padded to bp)";
+	int rc = grow(ctx, ctx->dLgoZ, (size_t)nbc_max * bp * Np, false, oom);
+	if (!rc) rc = grow(ctx, ctx->dLgoT, (size_t)nbc_max * tstride, false, oom);
+	if (!rc) rc = grow(ctx, ctx->dLgoPart, (size_t)nbc_max * (bp / LEAF + 2));
+	if (!rc) rc = grow(ctx, ctx->dLgoInfo, (size_t)nbc_max);
+	if (!rc) rc = grow(ctx, ctx->dLgoTab, ntab);
+	if (!rc) rc = grow(ctx, ctx->hLgoTab, ntab);
+	if (rc) return rc;
+	if (!ctx->lgo_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lgo_ev, hipEventDisableTiming));
+	HIPCHK(ctx, hipEventSynchronize(ctx->lgo_ev));        // the previous call's upload has left the pinned tables (a never-recorded event is complete)
+	// tables: colrow[N], members[N] (group after group, ascending design index), moff[ngroups], bsize[ngroups]
+	int *colrow = ctx->hLgoTab, *members = colrow + N, *moff = members + N, *bsize = moff + ngroups;
+	for (int g = 0, o = 0; g < ngroups; g++) { moff[g] = o; o += pl.count[g]; bsize[g] = 0; }
+	for (int i = 0; i < N; i++) {
+		const int g = group[i];
+		colrow[i] = -1;
+		if (g < 0) continue;
+		colrow[i] = g * bp + bsize[g];
+		members[moff[g] + bsize[g]++] = i;
+	}
+	for (int i = moff[ngroups - 1] + bsize[ngroups - 1]; i < N; i++) members[i] = 0;   // (behind the last member: uploaded, never read)
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dLgoTab, ctx->hLgoTab, ntab * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipEventRecord(ctx->lgo_ev, ctx->stream));
+	const int *d_colrow = ctx->dLgoTab, *d_members = d_colrow + N, *d_moff = d_members + N, *d_bsize = d_moff + ngroups;
+	// NaN (all bits set) for the points that are never left out; every member's element is overwritten below
+	HIPCHK(ctx, hipMemsetAsync(mean_dev, 0xff, (size_t)N * sizeof(double), ctx->stream));
+	HIPCHK(ctx, hipMemsetAsync(var_dev, 0xff, (size_t)N * sizeof(double), ctx->stream));
+	if (werr_dev) HIPCHK(ctx, hipMemsetAsync(werr_dev, 0xff, (size_t)N * sizeof(double), ctx->stream));
+	double *Z = ctx->dLgoZ, *T = ctx->dLgoT, *part = ctx->dLgoPart;
+	for (int g0 = 0; g0 < ngroups; g0 += nbc_max) {
+		const int nbc = std::min(nbc_max, ngroups - g0);
+		double *res = part + (size_t)nbc * (bp / LEAF);
+		if (prof_on(ctx, GPEMU_PROF_LGO)) for (const char *t : {"lgo_gather", "lgo_stage", "lgo_finish"}) ctx->prof.tag.push_back(t);
+		{
+			ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (double)Np);
+			HIPCHK(ctx, launch_lgo_gather(ctx->stream, ctx->dLinvAug, Np, N, Np, d_colrow, d_bsize, g0, nbc, bp, Z));
+		}
+		GemmArgs g{};
+		g.C = T; g.ldc = bp;
+		g.A = Z; g.lda = Np;
+		g.B = Z; g.ldb = Np;
+		g.m = bp; g.n = bp; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+		g.tri = 1; g.diag_off = 0;
+		g.nbatch = nbc; g.bsC = (long)tstride; g.bsA = g.bsB = (long)bp * Np;
+		HIPCHK(ctx, gemm(ctx, g));
+		{
+			ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (2.0 * bp + LEAF));
+			HIPCHK(ctx, launch_lgo_stage(ctx->stream, T, (long)tstride, g0, nbc, bp, d_members, d_moff, d_bsize, ctx->dLinvAug, Np, Np,
+			                             ctx->nreg, ctx->dBetaQ));
+		}
+		HIPCHK(ctx, hipMemsetAsync(ctx->dLgoInfo, 0x7f, (size_t)nbc * sizeof(int), ctx->stream));     // INFO_NONE
+		HIPCHK(ctx, trace_clear(ctx));
+		{
+			ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)nbc * bp * bp * bp / 3.0, 0.0);
+			HIPCHK(ctx, potrf_all(ctx, Tall{T, ctx->dLgoInfo, bp, LEAF, nbc, (long)tstride}, 1));
+		}
+		// |w|^2 of the solved right-hand-side row and 2 sum log R_ii (the pad's pivots are 1) per group
+		HIPCHK(ctx, launch_gram_partials(ctx->stream, T + (size_t)bp * bp, bp, bp, 1, 1, part, nbc, (long)tstride));
+		HIPCHK(ctx, launch_finish(ctx->stream, part, bp / LEAF, 1, 1, T, bp, bp, res, nbc, (long)tstride, 2));
+		{
+			ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (bp / 2.0 + 4.0));
+			HIPCHK(ctx, launch_lgo_finish(ctx->stream, T, (long)tstride, nbc, bp, d_members, d_moff, d_bsize, ctx->dLgoInfo, res, ctx->dY,
+			                              g0, ngroups, mean_dev, var_dev, werr_dev, stat_dev, info_dev));
+		}
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_lgo_dev(gpemu_ctx *ctx, int ngroups, const int *group, double *mean_dev, double *var_dev, double *werr_dev,
+                             double *stat_dev, int *info_dev)
+{
+	if (!ctx || ngroups < 1 || !group || !mean_dev || !var_dev || !info_dev) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	LgoPlan pl;
+	if (const int rc = lgo_plan(ctx, ngroups, group, &pl)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	return lgo_run(ctx, pl, ngroups, group, mean_dev, var_dev, werr_dev, stat_dev, info_dev);
+}
+
+extern "C" int gpemu_lgo(gpemu_ctx *ctx, int ngroups, const int *group, double *mean, double *var, double *werr, double *maha,
+                         double *logdet, double *logpdf, int *info)
+{
+	if (!ctx || ngroups < 1 || !group || !mean || !var || !info) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	LgoPlan pl;
+	if (const int rc0 = lgo_plan(ctx, ngroups, group, &pl)) return rc0;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t N = (size_t)ctx->N, G = (size_t)ngroups;
+	int rc = grow(ctx, ctx->dLgoOut, 3 * N + 3 * G);
+	if (!rc) rc = grow(ctx, ctx->dLgoInfoOut, G);
+	if (rc) return rc;
+	double *o = ctx->dLgoOut, *st = o + 3 * N;
+	rc = lgo_run(ctx, pl, ngroups, group, o, o + N, o + 2 * N, st, ctx->dLgoInfoOut);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(mean, o, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(var, o + N, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (werr) HIPCHK(ctx, hipMemcpyAsync(werr, o + 2 * N, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (maha) HIPCHK(ctx, hipMemcpyAsync(maha, st, G * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (logdet) HIPCHK(ctx, hipMemcpyAsync(logdet, st + G, G * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (logpdf) HIPCHK(ctx, hipMemcpyAsync(logpdf, st + 2 * G, G * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(info, ctx->dLgoInfoOut, G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (size_t g = 0; g < G; g++)
+		if (info[g]) return fail(ctx, GPEMU_ERR_NOT_PD, "leave-group-out: P_BB of a group is not positive definite");
+	return GPEMU_OK;
+}
+
+// every buffer of the leave-group-out entries goes back to the device
+extern "C" int gpemu_lgo_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (auto *b : {&ctx->dLgoZ, &ctx->dLgoT, &ctx->dLgoPart, &ctx->dLgoOut}) b->reset();
+	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
+	ctx->hLgoTab.reset();
 	return GPEMU_OK;
 }
 

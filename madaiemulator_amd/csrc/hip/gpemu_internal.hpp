@@ -285,6 +285,15 @@ struct gpemu_ctx {
 	// leave-one-out (gpemu_loo): partial column sums; means then variances (N each) on the device and in pinned memory
 	gpemu::DevBuf<double> dLooPart, dLoo;
 	gpemu::PinnedBuf<double> hLoo;
+	// leave-group-out (gpemu_lgo), per chunk of nbc groups padded to bp: dLgoZ the gathered columns of L^-1 as
+	// rows (nbc x bp x Np), dLgoT the tall matrices [P_BB ; 64 right-hand-side rows ; identity rows] (nbc x (2 bp + 64) x bp),
+	// dLgoPart the partial sums of |w|^2 then {maha, 2 sum log R_ii} per group, dLgoInfo the factorisation's info words;
+	// dLgoTab / hLgoTab the index tables of a call (device / pinned; lgo_ev: recorded behind the upload); dLgoOut / dLgoInfoOut
+	// the host entry's results before they are copied out
+	gpemu::DevBuf<double> dLgoZ, dLgoT, dLgoPart, dLgoOut;
+	gpemu::DevBuf<int> dLgoTab, dLgoInfo, dLgoInfoOut;
+	gpemu::PinnedBuf<int> hLgoTab;
+	hipEvent_t lgo_ev = nullptr;
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
 
@@ -419,5 +428,20 @@ size_t loo_scratch_elems(int N, int Np);
 hipError_t launch_loo_colsq(hipStream_t s, const double *LinvAug, long ld, int N, int Np, double *part);
 hipError_t launch_loo_finish(hipStream_t s, const double *part, const double *LinvAug, long ld, int N, int Np, int nreg,
                              const double *betaQ, const double *y, double *mean, double *var);
+// leave-group-out (gpemu_lgo) on nbc groups padded to bp, the groups g0 .. g0 + nbc - 1 of a call.  Tables:
+// colrow[i] = g * bp + position of design point i in its group g (-1: in none), members = the design indices group after group,
+// moff[g] / bsize[g] = where group g starts in members / how many it has.
+// gather: column i of L^-1 (rows [0, N) of LinvAug, k >= i only) -> row colrow[i] - g0 * bp of Z (nbc * bp rows of Np), zeros elsewhere
+hipError_t launch_lgo_gather(hipStream_t s, const double *LinvAug, long ld, int N, int Np, const int *colrow, const int *bsize,
+                             int g0, int nbc, int bp, double *Z);
+// staging of the tall matrices T (nbc x (2 bp + 64) x bp, the lower 64 x 64 tiles holding (C^-1)_BB): minus w_i^T Q w_j, identity
+// pad, gamma_B as right-hand-side row 0, identity rows
+hipError_t launch_lgo_stage(hipStream_t s, double *T, long tstride, int g0, int nbc, int bp, const int *members, const int *moff,
+                            const int *bsize, const double *LinvAug, long ld, int Np, int nreg, const double *betaQ);
+// finish after the factorisation: var, mean, werr scattered to design order, maha / logdet / logpdf and the decoded info word
+// per group.  res: {|w|^2, 2 sum log R_ii} per group of the chunk, info: the chunk's info words
+hipError_t launch_lgo_finish(hipStream_t s, const double *T, long tstride, int nbc, int bp, const int *members, const int *moff,
+                             const int *bsize, const int *info, const double *res, const double *y, int g0, int ngroups,
+                             double *mean, double *var, double *werr, double *stat, int *info_out);
 
 } // namespace gpemu

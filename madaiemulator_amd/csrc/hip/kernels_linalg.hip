@@ -1774,4 +1774,251 @@ hipError_t launch_loo_finish(hipStream_t s, const double *part, const double *Li
 	return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Leave-group-out validation (gpemu_lgo): the block form of the closed form above.  Per chunk of nbc groups,
+// all padded to bp rows (a multiple of 64):
+//   lgo_gather_kernel   Z_g[position of i][k] = (L^-1)_ki for k >= i, 0 elsewhere               (then (C^-1)_BB = Z_g Z_g^T, one batched product)
+//   lgo_stage_kernel    T_g = [(C^-1)_BB - W_B Q W_B^T, identity pad ; gamma_B, 63 zero rows ; I]  (then the lock-step factorisation)
+//   lgo_finish_kernel   var_i = sum_k U_ik^2, mean_i = y_i - sum_k U_ik w_k over the inverse rows U = R^-T and the solved row w
+//
+// lgo_gather_kernel, grid (Np / 64, Np / 64 + nbc * bp / 64).  Workgroup (kt, ct < Np / 64) owns the 64 x 64 tile of L^-1 at
+// rows 64 kt, columns 64 ct: the tile comes in as whole 512-byte row pieces (16 bytes per lane, eight loads in flight), goes
+// through LDS (row stride 65), and every column of it that belongs to a group of the chunk leaves as one 512-byte piece of a
+// row of Z.  What L^-1 holds above its diagonal (exact zeros inside the diagonal tiles only, unspecified further out: the
+// trap of loo_colsq_kernel) is never written: tiles above the diagonal (kt < ct) are not read at all and give zeros, the
+// diagonal tile is masked element by element; rows k >= N (the identity pad) give zeros.  A tile none of whose columns is
+// in the chunk returns before it loads.  Workgroup (kt, Np / 64 + g * bp / 64 + rt) zeroes the pad rows (position >= b_g)
+// among the 64 rows rt of group g.  Every element of Z is written exactly once per launch.
+// 256 threads, 33 KB of LDS, no scratch.
+// ---------------------------------------------------------------------------
+constexpr int LGO_LDP = 65;
+
+__global__ __launch_bounds__(256) void lgo_gather_kernel(const double *Linv, long ld, int N, int Np, const int *colrow, const int *bsize,
+                                                         int g0, int nbc, int bp, double *Z)
+{
+	__shared__ double tile[64 * LGO_LDP];
+	__shared__ int zrow[64];
+	__shared__ int anyrow;
+	const int tid = threadIdx.x, sub = tid >> 5, l = tid & 31;
+	const int kt = blockIdx.x, k0 = kt * 64, nct = Np / 64;
+	const double2 zero = make_double2(0.0, 0.0);
+	if ((int)blockIdx.y >= nct) {
+		const int q = (int)blockIdx.y - nct, rtiles = bp / 64;
+		const int g = q / rtiles, rt = q % rtiles;
+		const int b = bsize[g0 + g];
+		if (rt * 64 + 64 <= b) return;
+#pragma unroll
+		for (int p = 0; p < 8; p++) {
+			const int pos = rt * 64 + p * 8 + sub;
+			if (pos >= b) *reinterpret_cast<double2 *>(Z + ((long)g * bp + pos) * Np + k0 + 2 * l) = zero;
+		}
+		return;
+	}
+	const int ct = blockIdx.y, c0 = ct * 64;
+	if (tid < 64) {
+		const int c = c0 + tid;
+		int r = (c < N) ? colrow[c] : -1;
+		if (r >= 0) r -= g0 * bp;
+		if (r < 0 || r >= nbc * bp) r = -1;
+		zrow[tid] = r;
+		const unsigned long long m = __ballot(r >= 0);
+		if (tid == 0) anyrow = (m != 0ull);
+	}
+	__syncthreads();
+	if (!anyrow) return;
+	const bool lower = kt >= ct;
+	if (lower) {
+		double2 v[8];
+#pragma unroll
+		for (int p = 0; p < 8; p++) {
+			const int k = k0 + p * 8 + sub;
+			v[p] = zero;
+			if (k < N) v[p] = *reinterpret_cast<const double2 *>(Linv + (long)k * ld + c0 + 2 * l);
+		}
+#pragma unroll
+		for (int p = 0; p < 8; p++) {
+			tile[(p * 8 + sub) * LGO_LDP + 2 * l] = v[p].x;
+			tile[(p * 8 + sub) * LGO_LDP + 2 * l + 1] = v[p].y;
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int p = 0; p < 8; p++) {
+		const int c = p * 8 + sub;
+		const int r = zrow[c];
+		if (r < 0) continue;
+		const int i = c0 + c, k = k0 + 2 * l;
+		double2 o = zero;
+		if (lower) {
+			const double x = tile[(2 * l) * LGO_LDP + c], y = tile[(2 * l + 1) * LGO_LDP + c];
+			o.x = (k >= i) ? x : 0.0;
+			o.y = (k + 1 >= i) ? y : 0.0;
+		}
+		*reinterpret_cast<double2 *>(Z + (long)r * Np + k) = o;
+	}
+}
+
+hipError_t launch_lgo_gather(hipStream_t s, const double *LinvAug, long ld, int N, int Np, const int *colrow, const int *bsize,
+                             int g0, int nbc, int bp, double *Z)
+{
+	if (nbc < 1 || bp < 64 || bp % 64 || Np % 64 || N > Np || (ld & 1)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(lgo_gather_kernel, dim3(Np / 64, Np / 64 + nbc * (bp / 64)), dim3(256), 0, s, LinvAug, ld, N, Np, colrow, bsize,
+	                   g0, nbc, bp, Z);
+	return hipGetLastError();
+}
+
+// lgo_stage_kernel, grid (bp / 64, 2 bp / 64 + 1, nbc): one 64 x 64 tile of a group's tall matrix per workgroup, every access a
+// 16-byte piece of a row.  Tile rows below bp / 64 are the matrix: tiles above the diagonal are left alone (nobody reads
+// them); in the others element (r, c) of two members becomes (C^-1)_rc - w_r^T (Q w_c) -- the W^T rows of LinvAug and Q in
+// sixteen regression functions at a time through LDS, (Q w_c) summed over b = 0, 1, .., the outer sum over a = 0, 1, ..: one
+// fixed order --, and 1 on / 0 off the diagonal where r or c is a pad position.  Tile row bp / 64: right-hand-side row 0 =
+// gamma at the members (0 at the pad), rows 1 .. 63 zero.  The tile rows behind: the identity.
+// 256 threads, 16.5 KB of LDS, 16 accumulators per thread, no scratch.
+__global__ __launch_bounds__(256) void lgo_stage_kernel(double *T, long tstride, int g0, int bp, const int *members, const int *moff,
+                                                        const int *bsize, const double *LinvAug, long ld, int Np, int nreg,
+                                                        const double *betaQ)
+{
+	__shared__ double wr[16 * 64], qw[16 * 64];
+	__shared__ int ir[64], ic[64];
+	const int g = blockIdx.z, tc = blockIdx.x, tr = blockIdx.y, nt = bp / 64;
+	const int tid = threadIdx.x, sub = tid >> 5, l = tid & 31;
+	T += (long)g * tstride;
+	const int b = bsize[g0 + g];
+	const int *mem = members + moff[g0 + g];
+	const int c = tc * 64 + 2 * l;
+	if (tr >= nt) {
+		const double *gamma = LinvAug + (long)Np * ld;
+		const int rbase = (tr - nt) * 64;
+#pragma unroll
+		for (int p = 0; p < 8; p++) {
+			const int rr = rbase + p * 8 + sub;
+			double2 v = make_double2(0.0, 0.0);
+			if (rr == 0) {
+				if (c < b) v.x = gamma[mem[c]];
+				if (c + 1 < b) v.y = gamma[mem[c + 1]];
+			} else if (rr >= 64) {
+				v.x = (rr - 64 == c) ? 1.0 : 0.0;
+				v.y = (rr - 64 == c + 1) ? 1.0 : 0.0;
+			}
+			*reinterpret_cast<double2 *>(T + ((long)bp + rr) * bp + c) = v;
+		}
+		return;
+	}
+	if (tc > tr) return;
+	if (tid < 64) ir[tid] = (tr * 64 + tid < b) ? mem[tr * 64 + tid] : -1;
+	else if (tid < 128) ic[tid - 64] = (tc * 64 + tid - 64 < b) ? mem[tc * 64 + tid - 64] : -1;
+	__syncthreads();
+	const double *Wt = LinvAug + (long)(Np + 1) * ld;
+	const double *Q = betaQ + nreg;
+	double acc0[8], acc1[8];
+#pragma unroll
+	for (int p = 0; p < 8; p++) { acc0[p] = 0.0; acc1[p] = 0.0; }
+	for (int a0 = 0; a0 < nreg; a0 += 16) {
+		const int na = min(16, nreg - a0);
+		for (int e = tid; e < na * 64; e += 256) {
+			const int a = e >> 6, j = e & 63;
+			const int i_r = ir[j], i_c = ic[j];
+			wr[a * 64 + j] = (i_r >= 0) ? Wt[(long)(a0 + a) * ld + i_r] : 0.0;
+			double t = 0.0;
+			if (i_c >= 0)
+				for (int bb = 0; bb < nreg; bb++) t = fma(Q[(a0 + a) * nreg + bb], Wt[(long)bb * ld + i_c], t);
+			qw[a * 64 + j] = t;
+		}
+		__syncthreads();
+		for (int a = 0; a < na; a++) {
+			const double q0 = qw[a * 64 + 2 * l], q1 = qw[a * 64 + 2 * l + 1];
+#pragma unroll
+			for (int p = 0; p < 8; p++) {
+				const double w = wr[a * 64 + p * 8 + sub];
+				acc0[p] = fma(w, q0, acc0[p]);
+				acc1[p] = fma(w, q1, acc1[p]);
+			}
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int p = 0; p < 8; p++) {
+		const int r = tr * 64 + p * 8 + sub;
+		double2 *at = reinterpret_cast<double2 *>(T + (long)r * bp + c);
+		const double2 v = *at;
+		double2 o;
+		o.x = (r < b && c < b) ? v.x - acc0[p] : (r == c ? 1.0 : 0.0);
+		o.y = (r < b && c + 1 < b) ? v.y - acc1[p] : (r == c + 1 ? 1.0 : 0.0);
+		*at = o;
+	}
+}
+
+hipError_t launch_lgo_stage(hipStream_t s, double *T, long tstride, int g0, int nbc, int bp, const int *members, const int *moff,
+                            const int *bsize, const double *LinvAug, long ld, int Np, int nreg, const double *betaQ)
+{
+	if (nbc < 1 || nbc > 65535 || bp < 64 || bp % 64 || (tstride & 1)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(lgo_stage_kernel, dim3(bp / 64, 2 * (bp / 64) + 1, nbc), dim3(256), 0, s, T, tstride, g0, bp, members, moff, bsize,
+	                   LinvAug, ld, Np, nreg, betaQ);
+	return hipGetLastError();
+}
+
+// lgo_finish_kernel, grid (bp / 64, nbc): 64 members of a group per workgroup, a wave per member at a time (sixteen members per
+// wave).  The wave walks row i of U = R^-T from the 128-column piece that holds the diagonal to column b_g, 16 bytes per
+// lane, beside the solved right-hand-side row w; what U holds left of its diagonal is masked like L^-1's upper part.  Each
+// lane adds its own columns in order, the 64 lane sums are added by a butterfly: one fixed order.  Lane 0 scatters var, mean
+// and werr to the member's design index.  Thread 0 of a group's first workgroup writes maha, logdet, logpdf and the decoded
+// info word.  A group whose pivot failed gets NaN everywhere and its pivot's position.  No LDS, no scratch.
+__global__ __launch_bounds__(256) void lgo_finish_kernel(const double *T, long tstride, int bp, const int *members, const int *moff,
+                                                         const int *bsize, const int *info, const double *res, const double *y, int g0,
+                                                         int ngroups, double *mean, double *var, double *werr, double *stat,
+                                                         int *info_out)
+{
+	const int g = blockIdx.y, rt = blockIdx.x, G = g0 + g;
+	const int b = bsize[G];
+	if (rt * 64 >= b) return;
+	const int *mem = members + moff[G];
+	const double *Tg = T + (long)g * tstride;
+	const double *w = Tg + (long)bp * bp;
+	const double *U = Tg + ((long)bp + 64) * bp;
+	const int word = info[g];
+	const bool bad = word < 0x7f7f7f7f;                    // (INFO_NONE: what the factorisation's memset leaves for "no failed pivot")
+	const double nan = __longlong_as_double(0x7ff8000000000000ll);
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	for (int q = 0; q < 16; q++) {
+		const int pos = rt * 64 + wave * 16 + q;
+		if (pos >= b) break;
+		double sv = 0.0, se = 0.0;
+		for (int k = (pos & ~127) + 2 * lane; k < b; k += 128) {
+			const double2 u = *reinterpret_cast<const double2 *>(U + (long)pos * bp + k);
+			const double2 ww = *reinterpret_cast<const double2 *>(w + k);
+			if (k >= pos) { sv = fma(u.x, u.x, sv); se = fma(u.x, ww.x, se); }
+			if (k + 1 >= pos && k + 1 < b) { sv = fma(u.y, u.y, sv); se = fma(u.y, ww.y, se); }
+		}
+		for (int off = 32; off > 0; off >>= 1) {
+			sv += __shfl_xor(sv, off);
+			se += __shfl_xor(se, off);
+		}
+		if (lane == 0) {
+			const int i = mem[pos];
+			mean[i] = bad ? nan : y[i] - se;
+			var[i] = bad ? nan : sv;
+			if (werr) werr[i] = bad ? nan : w[pos];
+		}
+	}
+	if (rt == 0 && threadIdx.x == 0) {
+		const double maha = res[2 * g], logdet = -res[2 * g + 1];
+		if (stat) {
+			stat[G] = bad ? nan : maha;
+			stat[ngroups + G] = bad ? nan : logdet;
+			stat[2 * (long)ngroups + G] = bad ? nan : -0.5 * (maha + logdet + b * 1.8378770664093454835606594728112);   // log 2 pi
+		}
+		info_out[G] = bad ? word : 0;
+	}
+}
+
+hipError_t launch_lgo_finish(hipStream_t s, const double *T, long tstride, int nbc, int bp, const int *members, const int *moff,
+                             const int *bsize, const int *info, const double *res, const double *y, int g0, int ngroups,
+                             double *mean, double *var, double *werr, double *stat, int *info_out)
+{
+	if (nbc < 1 || nbc > 65535 || bp < 64 || bp % 64 || (tstride & 1)) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(lgo_finish_kernel, dim3(bp / 64, nbc), dim3(256), 0, s, T, tstride, bp, members, moff, bsize, info, res, y, g0,
+	                   ngroups, mean, var, werr, stat, info_out);
+	return hipGetLastError();
+}
+
 } // namespace gpemu

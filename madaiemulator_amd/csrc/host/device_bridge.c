@@ -1162,6 +1162,61 @@ void emulate_loo_collect(emulator_struct *e, void *dev, double *mean, double *va
 	check(en, rc, "emulate_loo");
 }
 
+/* K-fold / leave-group-out validation (gpemu_lgo in gpemu.h): group[i] in 0 .. ngroups-1 or -1.  mean, variance (required)
+ * and werr: N each in design order, NaN where group[i] = -1; maha, logpdf: ngroups each; werr, maha, logpdf may be NULL.  A
+ * group whose matrix is not positive definite ends in gpemu_host_fatal like every other device error. */
+static void lgo_not_pd(const int *info, int ngroups)
+{
+	for (int g = 0; g < ngroups; g++)
+		if (info[g]) gpemu_host_fatal("emulate_lgo: P_BB of group %d is not positive definite (pivot %d)\n", g, info[g]);
+}
+
+void emulate_lgo(emulator_struct *e, int ngroups, const int *group, double *mean, double *variance, double *werr, double *maha,
+                 double *logpdf)
+{
+	struct entry *en = entry_of(e, "emulate_lgo");
+	int *info = (int *)calloc((size_t)(ngroups > 0 ? ngroups : 1), sizeof(int));
+	const int rc = gpemu_lgo(en->ctx, ngroups, group, mean, variance, werr, maha, NULL, logpdf, info);
+	if (rc == GPEMU_ERR_NOT_PD) lgo_not_pd(info, ngroups);
+	free(info);
+	check(en, rc, "emulate_lgo");
+}
+
+/* its two halves, like emulate_loo_enqueue / _collect: gpemu_lgo_dev is enqueued on the component's own stream and the results
+ * wait in a device buffer -- mean, variance, werr (N each), maha, logdet, logpdf (ngroups each), then the info words --;
+ * collect downloads them, which waits for that stream only, and releases the buffer */
+void emulate_lgo_enqueue(emulator_struct *e, int ngroups, const int *group, void **dev_out)
+{
+	struct entry *en = entry_of(e, "emulate_lgo");
+	const size_t n = (size_t)e->nmodel_points, g = (size_t)(ngroups > 0 ? ngroups : 0);
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(en->ctx, (3 * n + 3 * g) * sizeof(double) + (g + 1) * sizeof(int), &dev);
+	double *o = (double *)dev;
+	if (!rc) rc = gpemu_lgo_dev(en->ctx, ngroups, group, o, o + n, o + 2 * n, o + 3 * n, (int *)(o + 3 * n + 3 * g));
+	if (rc && dev) (void)gpemu_dev_free(en->ctx, dev);
+	check(en, rc, "emulate_lgo");
+	*dev_out = dev;
+}
+
+void emulate_lgo_collect(emulator_struct *e, void *dev, int ngroups, double *mean, double *variance, double *werr, double *maha,
+                         double *logpdf)
+{
+	struct entry *en = entry_of(e, "emulate_lgo");
+	const size_t n = (size_t)e->nmodel_points, g = (size_t)ngroups;
+	const double *o = (const double *)dev, *st = o + 3 * n;
+	int *info = (int *)calloc(g, sizeof(int));
+	int rc = gpemu_dev_download(en->ctx, info, st + 3 * g, g * sizeof(int));
+	if (!rc) rc = gpemu_dev_download(en->ctx, mean, o, n * sizeof(double));
+	if (!rc) rc = gpemu_dev_download(en->ctx, variance, o + n, n * sizeof(double));
+	if (!rc && werr) rc = gpemu_dev_download(en->ctx, werr, o + 2 * n, n * sizeof(double));
+	if (!rc && maha) rc = gpemu_dev_download(en->ctx, maha, st, g * sizeof(double));
+	if (!rc && logpdf) rc = gpemu_dev_download(en->ctx, logpdf, st + 2 * g, g * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	if (!rc) lgo_not_pd(info, ngroups);
+	free(info);
+	check(en, rc, "emulate_lgo");
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

@@ -7,6 +7,7 @@
  *   interactive_emulator print_thetas MODEL_SNAPSHOT_FILE
  *   interactive_emulator validate MODEL_SNAPSHOT_FILE [--pca_output] [--quiet]     (not in the reference)
  *   interactive_emulator validate MODEL_SNAPSHOT_FILE --holdout=FILE [--quiet]     (not in the reference)
+ *   interactive_emulator validate MODEL_SNAPSHOT_FILE --folds=K | --groups=FILE [--pca_output] [--quiet]     (not in the reference)
  *
  * Kept quirks: --covariance_fn is atoi'd and compared with POWEREXPCOVFN=1 /
  * MATERN32=2 / MATERN52=3 (0 and 1 both mean power-exponential); --pca_variance falls through
@@ -31,7 +32,8 @@
 struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
-	char *run_mode, *inputfile, *statefile, *holdoutfile;
+	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile;
+	int folds, foldsGiven;
 };
 
 static const char useage[] =
@@ -47,6 +49,14 @@ static const char useage[] =
 	"  interactive_emulator validate MODEL_SNAPSHOT_FILE --holdout=FILE [--quiet]  (validation on a held-out campaign: FILE in the\n"
 	"      INPUT_MODEL_FILE format; per point and PCA component mean, variance and decorrelated error, per component the\n"
 	"      Mahalanobis distance and the joint log predictive density)\n"
+	"or\n"
+	"  interactive_emulator validate MODEL_SNAPSHOT_FILE --folds=K [--pca_output] [--quiet]  (K-fold cross-validation: training point i\n"
+	"      is left out with fold i mod K, 2 <= K <= number of training points; mean and variance per training point from the\n"
+	"      emulator on the other folds, per PCA component the Mahalanobis distance and joint log predictive density of the folds)\n"
+	"or\n"
+	"  interactive_emulator validate MODEL_SNAPSHOT_FILE --groups=FILE [--pca_output] [--quiet]  (leave-group-out: FILE holds one\n"
+	"      integer per training point, the group it is left out with, 0 .. number of groups - 1, or -1 for never)\n"
+	"  --holdout, --folds and --groups exclude each other.\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -179,6 +189,7 @@ static int interactive_mode(struct cmdLineOpts *o)
 }
 
 static int validate_holdout(struct cmdLineOpts *o);      /* validate --holdout=FILE, below */
+static int validate_lgo(struct cmdLineOpts *o);          /* validate --folds=K / --groups=FILE, below */
 
 /* Leave-one-out validation of a trained snapshot (not in the reference, which leaves validation to a held-out campaign):
  * one line per training point in design order, "mean_0 variance_0 mean_1 variance_1 ..." -- what the emulator trained on
@@ -188,6 +199,7 @@ static int validate_holdout(struct cmdLineOpts *o);      /* validate --holdout=F
 static int validate(struct cmdLineOpts *o)
 {
 	if (o->holdoutfile) return validate_holdout(o);
+	if (o->foldsGiven || o->groupsfile) return validate_lgo(o);
 	FILE *fp = fopen(o->statefile, "r");
 	if (!fp) return perr("Error opening file");
 	gpemu_host_warm_start();
@@ -291,6 +303,86 @@ static int validate_holdout(struct cmdLineOpts *o)
 	return 0;
 }
 
+/* K-fold (--folds=K: training point i in fold i mod K) and leave-group-out (--groups=FILE: one integer label per training
+ * point, -1 = never left out) validation of a trained snapshot: every group is left out as a whole and predicted jointly by
+ * the emulator on the other points at the same thetas (emulate_lgo_multi), so that replicated or clustered runs cannot carry
+ * each other as they do in the leave-one-out mode.  stdout as in the leave-one-out mode (NaN for label -1).  stderr, per
+ * output: rmse and mean residual^2 / variance over the points that were left out; per PCA component: the squared Mahalanobis
+ * distances of the groups (chi^2 with dof = the number of left-out points under the model) and their joint log predictive
+ * densities, both summed over the groups. */
+static int validate_lgo(struct cmdLineOpts *o)
+{
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	const int d = model->nparams, nt = model->nt, nr = model->nr, N = model->nmodel_points;
+	const int nout = o->pcaOutputFlag ? nr : nt;
+	int *group = (int *)malloc(sizeof(int) * (size_t)N), ngroups = 0, left = 0;
+	if (o->groupsfile) {
+		FILE *gf = fopen(o->groupsfile, "r");
+		if (!gf) return perr("Error opening the groups file");
+		for (int i = 0; i < N; i++) {
+			if (fscanf(gf, "%d", &group[i]) != 1 || group[i] < -1) {
+				fprintf(stderr, "the groups file needs %d integers >= -1, one per training point\n", N);
+				return EXIT_FAILURE;
+			}
+			if (group[i] + 1 > ngroups) ngroups = group[i] + 1;
+		}
+		fclose(gf);
+		if (ngroups < 1) return perr("the groups file leaves no point out");
+	} else {
+		if (o->folds < 2 || o->folds > N) {
+			fprintf(stderr, "--folds=K needs 2 <= K <= %d training points\n", N);
+			return EXIT_FAILURE;
+		}
+		ngroups = o->folds;
+		for (int i = 0; i < N; i++) group[i] = i % ngroups;
+	}
+	for (int i = 0; i < N; i++) left += group[i] >= 0;
+	multi_emulator *emu = alloc_multi_emulator(model);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "%d\n", d);
+		for (int i = 0; i < d; i++) fprintf(out, "%s%d\n", "param_", i);
+		fprintf(out, "%d\n", 2 * nt);
+		for (int i = 0; i < nt; i++) fprintf(out, "%s_%d\n%s_%d\n", "mean", i, "variance", i);
+	}
+	double *mean = (double *)malloc(sizeof(double) * (size_t)N * nout), *var = (double *)malloc(sizeof(double) * (size_t)N * nout);
+	double *maha = (double *)malloc(sizeof(double) * (size_t)nr * ngroups), *logpdf = (double *)malloc(sizeof(double) * (size_t)nr * ngroups);
+	emulate_lgo_multi(emu, o->pcaOutputFlag, ngroups, group, mean, var, maha, logpdf);
+	for (int i = 0; i < N; i++) {
+		for (int j = 0; j < nout; j++)
+			fprintf(out, "%s%.17g %.17g", j ? " " : "", mean[(size_t)i * nout + j], var[(size_t)i * nout + j]);
+		fprintf(out, "\n");
+	}
+	fflush(out);
+	if (!o->quietFlag) {
+		for (int j = 0; j < nout; j++) {
+			double ss = 0.0, sz = 0.0;
+			for (int i = 0; i < N; i++) {
+				if (group[i] < 0) continue;
+				const double given = o->pcaOutputFlag ? gsl_vector_get(model->pca_model_array[j]->training_vector, i)
+				                                      : gsl_matrix_get(model->training_matrix, i, j);
+				const double r = given - mean[(size_t)i * nout + j];
+				ss += r * r;
+				sz += r * r / var[(size_t)i * nout + j];
+			}
+			fprintf(stderr, "# lgo output %d: rmse %.17g mean_standardised_sq %.17g\n", j, sqrt(ss / left), sz / left);
+		}
+		for (int c = 0; c < nr; c++) {
+			double ms = 0.0, ls = 0.0;
+			for (int g = 0; g < ngroups; g++) { ms += maha[(size_t)c * ngroups + g]; ls += logpdf[(size_t)c * ngroups + g]; }
+			fprintf(stderr, "# lgo component %d: maha %.17g dof %d logpdf %.17g\n", c, ms, left, ls);
+		}
+	}
+	free(mean); free(var); free(maha); free(logpdf); free(group);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static int print_thetas(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -338,6 +430,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"binary", no_argument, NULL, 1003},
 		/* validate on a held-out campaign instead of leave-one-out */
 		{"holdout", required_argument, NULL, 1004},
+		/* ... or by K folds / by groups read from a file, every group left out as a whole */
+		{"folds", required_argument, NULL, 1005},             {"groups", required_argument, NULL, 1006},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -361,12 +455,15 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1002: gpemu_host_set_modes(gpemu_host_modes() | 2 /* GPEMU_MODE_MATERN_LOG */); break;
 		case 1003: o->binaryFlag = 1; break;
 		case 1004: o->holdoutfile = optarg; break;
+		case 1005: o->folds = atoi(optarg); o->foldsGiven = 1; break;
+		case 1006: o->groupsfile = optarg; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
 		}
 	}
 	if (optind >= argc) exit(perr(useage));
+	if ((o->holdoutfile != NULL) + o->foldsGiven + (o->groupsfile != NULL) > 1) exit(perr(useage));
 	o->run_mode = argv[optind];
 	if (!strcmp(o->run_mode, "estimate_thetas")) {
 		if (optind + 2 >= argc) exit(perr(useage));

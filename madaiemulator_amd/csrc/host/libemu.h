@@ -291,6 +291,18 @@ void emulate_loo(emulator_struct *e, double *mean, double *variance);
 /* emulate_loo in two halves, like emulate_points_enqueue / _collect: *dev_out is the device buffer the results wait in */
 void emulate_loo_enqueue(emulator_struct *e, void **dev_out);
 void emulate_loo_collect(emulator_struct *e, void *dev, double *mean, double *variance);
+/* extension: K-fold / leave-group-out validation (gpemu_lgo in gpemu.h).  group[i] in 0 .. ngroups-1 names the group training
+ * point i is left out with (-1: never left out).  For every group: what alloc_emulator_struct on the other points at the same
+ * thetas predicts JOINTLY at the group's points, without refitting.  mean, variance (required), werr (the group's decorrelated
+ * errors; may be NULL): N each in design order, NaN for label -1; maha (squared Mahalanobis distance of the group's errors),
+ * logpdf (their joint log predictive density): ngroups each, may be NULL.  A group whose matrix is not positive definite
+ * ends in gpemu_host_fatal. */
+void emulate_lgo(emulator_struct *e, int ngroups, const int *group, double *mean, double *variance, double *werr, double *maha,
+                 double *logpdf);
+/* emulate_lgo in two halves, like emulate_loo_enqueue / _collect: *dev_out is the device buffer the results wait in */
+void emulate_lgo_enqueue(emulator_struct *e, int ngroups, const int *group, void **dev_out);
+void emulate_lgo_collect(emulator_struct *e, void *dev, int ngroups, double *mean, double *variance, double *werr, double *maha,
+                         double *logpdf);
 
 /* ---- multi_modelstruct.h / multivar_support.h ---------------------------------- */
 multi_modelstruct *alloc_multimodelstruct(gsl_matrix *xmodel_in, gsl_matrix *training_matrix_in, int cov_fn_index,
@@ -349,6 +361,11 @@ void emulate_points_multi_draw(multi_emulator *emu, int pca_space, int npoints, 
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);
+/* extension: K-fold / leave-group-out validation of a multi-output emulator, the same groups for every component (all components
+ * are started before the first is waited for).  mean_out, var_out as emulate_loo_multi lays them out (NaN rows for label -1);
+ * maha_out, logpdf_out (may be NULL): nr x ngroups, component-major, in PCA space only, as for the hold-out mode */
+void emulate_lgo_multi(multi_emulator *emu, int pca_space, int ngroups, const int *group, double *mean_out, double *var_out,
+                       double *maha_out, double *logpdf_out);
 
 /* ---- libRbind/rbind.h: the batched likelihood entry point, R-free (rbind.c:626-724) ---------------- */
 void callEvalLhoodList(double *xmodel_in, int *nparams_in, double *pointList_in, int *nevalPoints_in,

@@ -678,6 +678,26 @@ void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, dou
 	free(mp); free(vp); free(mc); free(vc); free(dev);
 }
 
+/* K-fold / leave-group-out validation, the same groups for every component: started and collected as above; the per-group
+ * diagnostics stay in PCA space, component-major */
+void emulate_lgo_multi(multi_emulator *emu, int pca_space, int ngroups, const int *group, double *mean_out, double *var_out,
+                       double *maha_out, double *logpdf_out)
+{
+	const size_t np = (size_t)emu->nmodel_points, nr = (size_t)emu->nr, ng = (size_t)(ngroups > 0 ? ngroups : 0);
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *mc = doubles(np), *vc = doubles(np);
+	void **dev = (void **)malloc(sizeof(void *) * nr);
+	for (size_t c = 0; c < nr; c++) emulate_lgo_enqueue(emu->emu_struct_array[c], ngroups, group, &dev[c]);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_lgo_collect(emu->emu_struct_array[c], dev[c], ngroups, mc, vc, NULL, maha_out ? maha_out + c * ng : NULL,
+		                    logpdf_out ? logpdf_out + c * ng : NULL);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, mean_out);
+	deliver(emu, pca_space, 1, 0, np, 1, vp, var_out);
+	free(mp); free(vp); free(mc); free(vc); free(dev);
+}
+
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
 	const int n = pca_space ? emu->nr : emu->nt;
