@@ -503,6 +503,25 @@ typedef struct gpemu_gemm_launch_args {
 	int fa, fa_c0;
 } gpemu_gemm_launch_args;
 int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_gemm_launch_args *args, int *info_out);
+/* ONE trailing update of the factorisation, made exactly as production makes it, on tall matrices inside one host buffer
+ * (the arena): matrix b at element offset off + b*stride is ld rows of ld columns (the matrix proper), rp right-hand-side
+ * rows under them and, with inv, identity rows under those.  With P = rows c0+k .. of columns c0 .. c0+k-1 (the factored
+ * panel), rows c0+k .. ld+rp-1 (inv: and c0+k more) of columns c0+k .. c0+k+ncols-1 become C - P P^T on and below the
+ * diagonal of the matrix proper (tiles that meet it are computed whole or in part) and in every right-hand-side and identity
+ * row.  rhs_live: how many of the rp right-hand-side rows can be non-zero (the others must be +0), 0 = unknown.  ride: the
+ * GPEMU_RHS_RIDE switch for this call; the context's other switches apply as they are.  Where the update runs on 64x64 tiles
+ * the factor-ahead rules of the context apply (info_out as gpemu_test_gemm_launch, max(nbatch, 1) words, may be NULL).
+ * The whole arena is uploaded, and downloaded after the update.  GPEMU_ERR_ARG, before anything runs: a NULL pointer; k no
+ * positive multiple of 16; c0 < 0, ncols < 1 or c0 + k + ncols > ld; rhs_live outside 0 .. rp; inv or ride not 0/1; nbatch
+ * outside 0 .. GPEMU_MAX_BATCH; an odd off, ld, stride or c0; matrices of a batch that overlap; or a footprint -- rows
+ * c0+k .. ld+rp(+c0+k)-1 of columns c0 .. c0+k+ncols-1 of every matrix -- that leaves [0, arena_len). */
+typedef struct gpemu_update_launch_args {
+	long off, ld, stride;
+	int c0, k, ncols;
+	int rp, inv;
+	int rhs_live, nbatch, ride;
+} gpemu_update_launch_args;
+int gpemu_test_update_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_update_launch_args *args, int *info_out);
 /* ONE call of the Cholesky leaf launchers (the 64-column kernels of every factorisation) on a matrix inside one host
  * buffer (the arena), element offset off, row stride ld; nbatch > 1: that many matrices, bstride elements apart.
  *   GPEMU_LEAF_FACTOR        the 64x64 block at (c0, c0) leaves as its Cholesky factor: the lower triangle is L, the upper

@@ -37,6 +37,12 @@ class GemmLaunchArgs(C.Structure):
                                         "kend_off", "nbatch", "ksplit", "force_cfg", "fa", "fa_c0")])
 
 
+class UpdateLaunchArgs(C.Structure):
+    """gpemu_update_launch_args of include/gpemu.h"""
+    _fields_ = ([(f, C.c_long) for f in ("off", "ld", "stride")] +
+                [(f, C.c_int) for f in ("c0", "k", "ncols", "rp", "inv", "rhs_live", "nbatch", "ride")])
+
+
 class LeafLaunchArgs(C.Structure):
     """gpemu_leaf_launch_args of include/gpemu.h"""
     _fields_ = ([(f, C.c_long) for f in ("off", "ld", "bstride")] +
@@ -143,6 +149,7 @@ SYMBOLS = {
     "gpemu_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     "gpemu_test_gemm_nt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp]),
     "gpemu_test_gemm_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(GemmLaunchArgs), _ip]),
+    "gpemu_test_update_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(UpdateLaunchArgs), _ip]),
     "gpemu_test_leaf_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(LeafLaunchArgs), _ip]),
     "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
     "gpemu_test_fill_launch": (C.c_int, [C.c_void_p, C.POINTER(FillLaunchArgs)]),
@@ -652,6 +659,16 @@ class Context:
         a = GemmLaunchArgs(**{k: float(v) if k == "alpha" else int(v) for k, v in args.items()})
         info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
         self._chk(self.L.gpemu_test_gemm_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
+        return out, info
+
+    def test_update_launch(self, arena, **args):
+        """one trailing update of the factorisation, as production makes it, on tall matrices inside `arena`
+        (gpemu_test_update_launch; args: the fields of UpdateLaunchArgs, default ride = 1) -> (the arena after the update, info
+        word per matrix).  GpemuError(ERR_ARG) for a refused call."""
+        out = _a(arena).ravel().copy()
+        a = UpdateLaunchArgs(**{k: int(v) for k, v in dict(dict(ride=1), **args).items()})
+        info = np.zeros(max(a.nbatch, 1), dtype=np.int32)
+        self._chk(self.L.gpemu_test_update_launch(self.h, _p(out), out.size, C.byref(a), info.ctypes.data_as(_ip)))
         return out, info
 
     def test_leaf_launch(self, arena, **args):

@@ -184,6 +184,7 @@ static Sched read_environment()
 	v = geti("GPEMU_NB_TOP", 0);
 	sc.nb_top = v >= LEAF ? (v / LEAF) * LEAF : 0;
 	sc.split_rhs_rows = geti("GPEMU_SPLIT_RHS_ROWS", 1) != 0;
+	sc.rhs_ride = geti("GPEMU_RHS_RIDE", 1) != 0;
 	v = geti("GPEMU_PANEL_ROWS", 1);
 	sc.panel_rows = v >= 0 && v <= 2 ? v : 1;
 	v = geti("GPEMU_PANEL_SPLIT", 1);
@@ -518,12 +519,14 @@ static int make_cov_params_batch(gpemu_ctx *ctx, int nb, const double *thetas, i
 // The matrices come as a view (Tall); stream, schedule switches, profiling and trace are the context's.
 // ---------------------------------------------------------------------------
 // (the context's own workspace as it stands: after staging, which sets nb and the stride, and never kept across calls)
-static Tall tall_of(gpemu_ctx *ctx) { return Tall{ctx->dT, ctx->dInfo, ctx->Np, ctx->Rp, ctx->nb, (long)ctx->T_stride}; }
+static Tall tall_of(gpemu_ctx *ctx) { return Tall{ctx->dT, ctx->dInfo, ctx->Np, ctx->Rp, ctx->nb, (long)ctx->T_stride, ctx->nrhs}; }
 
 // *fa_done: set when the update ran with the factor-ahead tile, i.e. the 64x64 diagonal block at c0+k is already
 // factored when the update has finished and the next leaf must not factor it again
 // row_cut > 0 (without inverse rows): the update stops at that row -- the rows from there on are panel_rows_kernel's
-static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, int ncols, int inv, bool *fa_done, int row_cut = 0)
+// ride: 1 / 0 = riders on / off for this call, -1 = the context's GPEMU_RHS_RIDE (what production passes)
+static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, int ncols, int inv, bool *fa_done, int row_cut = 0,
+                                  int ride = -1)
 {
 	// C[rows >= r0, cols r0 .. r0+ncols) -= P P^T with P = the factored panel columns [c0, c0+k) and r0 = c0 + k
 	const long ld = t.Np;
@@ -553,15 +556,26 @@ static hipError_t trailing_update(gpemu_ctx *ctx, const Tall &t, int c0, int k, 
 		// at the first update of a batch at N = 8192).  Three launches instead: the matrix rows (triangular part, full 128-row
 		// tiles), the right-hand-side rows on 64x64 tiles, the identity rows (gradient / inverse only).  Same k-ordered chain
 		// per element whatever the tile shape: the bits do not change.
+		// Riders (GPEMU_RHS_RIDE): when at most 16 of the right-hand-side rows can be non-zero, the idle waves of the matrix
+		// rows' diagonal tiles take them (gemm_nt_kernel, RIDE) and the second launch is dropped: it read the whole panel a
+		// second time for 64 rows of which 48 and more are 0 - 0 b.  Rows 16 .. Rp-1 are then not touched: +0 before and after
+		// for finite operands.  (A panel with Inf or NaN in it -- after a failed pivot -- made them NaN in the old launch and
+		// leaves them +0 here; nothing reads them, the Gram and finish kernels take nrhs rows, and the info word reports the pivot.)
 		GemmArgs a = g;
 		a.m = c_rows;
+		if ((ride < 0 ? ctx->sched.rhs_ride : ride) && t.rhs_live > 0 && t.rhs_live <= 16 && t.Rp >= 16 && ncols % GEMM_BM == 0) {
+			a.ride_C = g.C + (long)c_rows * ld; a.ride_A = g.A + (long)c_rows * ld; a.ride_rows = 16;
+			if (!gemm_ride_ok(a)) { a.ride_C = nullptr; a.ride_A = nullptr; a.ride_rows = 0; }
+		}
 		hipError_t e = gemm(ctx, a);
 		if (e != hipSuccess) return e;
-		GemmArgs b = g;
-		b.C = g.C + (long)c_rows * ld; b.A = g.A + (long)c_rows * ld;
-		b.m = t.Rp; b.tri = 0; b.force_cfg = 2;
-		e = gemm(ctx, b);
-		if (e != hipSuccess) return e;
+		if (!a.ride_rows) {
+			GemmArgs b = g;
+			b.C = g.C + (long)c_rows * ld; b.A = g.A + (long)c_rows * ld;
+			b.m = t.Rp; b.tri = 0; b.force_cfg = 2;
+			e = gemm(ctx, b);
+			if (e != hipSuccess) return e;
+		}
 		const int i_rows = g.m - c_rows - t.Rp;
 		if (i_rows > 0) {
 			GemmArgs c = g;
@@ -1756,7 +1770,7 @@ extern "C" int gpemu_predict_joint_factor_dev(gpemu_ctx *ctx, int M, const doubl
 	HIPCHK(ctx, trace_clear(ctx));
 	{
 		ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)Mp * Mp * Mp / 3.0, 0.0);
-		HIPCHK(ctx, potrf_all(ctx, Tall{T, info_dev, Mp, Rp, 1, (long)tall}, 0));
+		HIPCHK(ctx, potrf_all(ctx, Tall{T, info_dev, Mp, Rp, 1, (long)tall, 0}, 0));
 	}
 	if (stat_dev) {
 		// G = Z Z^T of the solved rows Z_a = L_S^-1 (yobs_a - mean) and 2 sum_{p < M} log L_pp; stat = logdet, G_00, G_11, ...
@@ -2047,7 +2061,7 @@ static int lgo_run(gpemu_ctx *ctx, const LgoPlan &pl, int ngroups, const int *gr
 		HIPCHK(ctx, trace_clear(ctx));
 		{
 			ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)nbc * bp * bp * bp / 3.0, 0.0);
-			HIPCHK(ctx, potrf_all(ctx, Tall{T, ctx->dLgoInfo, bp, LEAF, nbc, (long)tstride}, 1));
+			HIPCHK(ctx, potrf_all(ctx, Tall{T, ctx->dLgoInfo, bp, LEAF, nbc, (long)tstride, 0}, 1));
 		}
 		// |w|^2 of the solved right-hand-side row and 2 sum log R_ii (the pad's pivots are 1) per group
 		HIPCHK(ctx, launch_gram_partials(ctx->stream, T + (size_t)bp * bp, bp, bp, 1, 1, part, nbc, (long)tstride));
@@ -2755,6 +2769,53 @@ extern "C" int gpemu_test_gemm_launch(gpemu_ctx *ctx, double *arena, long arena_
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	if (info_out)
 		for (int b = 0; b < std::max(p->nbatch, 1); b++) info_out[b] = pivot_info(inf[(size_t)b]);
+	return GPEMU_OK;
+}
+
+// One trailing_update() call -- the routine every factorisation calls, unchanged, with its split into matrix rows,
+// right-hand-side rows (a launch of their own, or riders in the first) and identity rows -- on tall matrices inside ONE host
+// buffer, the arena: uploads the whole arena, runs the update with the context's Sched (`ride` passed to trailing_update in place of GPEMU_RHS_RIDE
+// for this call), downloads the whole arena.  The tall matrix is what Tall describes: ld matrix rows of ld columns, rp
+// right-hand-side rows under them, and with inv the identity rows under those, of which the update takes c0+k.
+// Footprint per matrix, checked against [0, arena_len) first: rows c0+k .. ld+rp(+c0+k)-1 of columns c0 .. c0+k+ncols-1.
+// The kernels move 16-byte pieces of rows: off, ld, stride and c0 must be even, k a multiple of 16.
+extern "C" int gpemu_test_update_launch(gpemu_ctx *ctx, double *arena, long arena_len, const gpemu_update_launch_args *p, int *info_out)
+{
+	if (!ctx || !arena || !p) return GPEMU_ERR_ARG;
+	constexpr long DIM_MAX = 1L << 20, LEN_MAX = 1L << 32, STRIDE_MAX = 1L << 32;   // no product below leaves 63 bits
+	if (arena_len < 1 || arena_len > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "update_launch: arena length");
+	if (p->ld < 1 || p->ld > DIM_MAX || p->rp < 0 || p->rp > DIM_MAX || (p->inv != 0 && p->inv != 1) || (p->ride != 0 && p->ride != 1))
+		return fail(ctx, GPEMU_ERR_ARG, "update_launch: ld, rp, inv, ride");
+	if (p->c0 < 0 || p->k < GEMM_BK || (p->k % GEMM_BK) != 0 || p->ncols < 1 || (long)p->c0 + p->k + p->ncols > p->ld)
+		return fail(ctx, GPEMU_ERR_ARG, "update_launch: c0 >= 0, k a multiple of 16, ncols >= 1, c0 + k + ncols <= ld");
+	if (p->rhs_live < 0 || p->rhs_live > p->rp) return fail(ctx, GPEMU_ERR_ARG, "update_launch: rhs_live is 0 .. rp");
+	if (p->nbatch < 0 || p->nbatch > GPEMU_MAX_BATCH || p->stride < 0 || p->stride > STRIDE_MAX)
+		return fail(ctx, GPEMU_ERR_ARG, "update_launch: nbatch, stride");
+	if (p->off < 0 || ((p->off | p->ld | p->stride | p->c0) & 1)) return fail(ctx, GPEMU_ERR_ARG, "update_launch: off, ld, stride and c0 must be even");
+	const int nb = std::max(p->nbatch, 1);
+	const long r0 = (long)p->c0 + p->k, row_end = p->ld + p->rp + (p->inv ? r0 : 0);
+	const long last = p->off + (long)(nb - 1) * p->stride + (row_end - 1) * p->ld + r0 + p->ncols - 1;
+	if (last >= arena_len) return fail(ctx, GPEMU_ERR_ARG, "update_launch: the update would address memory outside the arena");
+	if (nb > 1 && p->stride < (row_end - 1) * p->ld + r0 + p->ncols)
+		return fail(ctx, GPEMU_ERR_ARG, "update_launch: the matrices of the batch overlap");
+
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dArena;
+	DevBuf<int> dInfo;
+	HIPCHK(ctx, dArena.grow((size_t)arena_len));
+	HIPCHK(ctx, dInfo.grow((size_t)nb));
+	std::vector<int> inf((size_t)nb, INFO_NONE);
+	HIPCHK(ctx, hipMemcpyAsync(dArena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dInfo, inf.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+	const Tall t{dArena + p->off, dInfo, (int)p->ld, p->rp, nb, (long)p->stride, p->rhs_live};
+	bool fa_done = false;
+	HIPCHK(ctx, trailing_update(ctx, t, p->c0, p->k, p->ncols, p->inv, &fa_done, 0, p->ride));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(arena, dArena, (size_t)arena_len * 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(inf.data(), dInfo, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (info_out)
+		for (int b = 0; b < nb; b++) info_out[b] = pivot_info(inf[(size_t)b]);
 	return GPEMU_OK;
 }
 

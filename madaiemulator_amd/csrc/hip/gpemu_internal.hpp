@@ -75,10 +75,16 @@ struct GemmArgs {
 	int no_neg_modifier; // 1: alpha = -1 by negating the accumulators on the way in and out, as rounds 1-3 did (A/B switch)
 	int row_table;       // 1: the square product with row-start skipping (C^-1 = U U^T) gives whole tile rows to an XCD (build_row_table)
 	int stagger_ticks;   // > 0: of the launch's first round, the workgroup in the odd slot of its CU starts this many 10 ns ticks late (kernel comment)
+	// riders (128x128 tiles of a triangular update, C - A B^T): the two idle waves of every diagonal tile update the
+	// ride_rows x 128 block of right-hand-side rows over their tile column from the B image in LDS (kernel comment)
+	double *ride_C;      // row 0 of the right-hand-side block, at column 0 of the update (ldc, bsC as C)
+	const double *ride_A; // the same rows at column 0 of the panel (lda, bsA as A)
+	int ride_rows;       // 16 or 0
 };
 
 // what a lock-step factorisation works on: nb tall matrices, stride elements apart, and their info words (a view, no owner)
-struct Tall { double *T; int *info; int Np, Rp, nb; long stride; };
+// rhs_live: how many of the Rp right-hand-side rows can be non-zero (the rest are +0 and stay +0); 0: the view cannot say
+struct Tall { double *T; int *info; int Np, Rp, nb; long stride; int rhs_live; };
 
 // Schedule switches of ONE context: read from the environment once, when the context is created (INTEGRATION.md lists
 // the variables), and constant for its lifetime.  Two contexts of a process may differ; nothing process-wide is written
@@ -94,6 +100,7 @@ struct Sched {
 	int idle_waves = 1;          // GPEMU_IDLE_WAVES: waves wholly above the diagonal of a diagonal tile issue no matrix instructions
 	int nb_top = 0;              // GPEMU_NB_TOP: outer panel width; 0 = automatic (512 for one matrix, 2048 / 1024 for a batch)
 	int split_rhs_rows = 1;      // GPEMU_SPLIT_RHS_ROWS: big-tile updates take the 64 right-hand-side rows in a launch of their own
+	int rhs_ride = 1;            // GPEMU_RHS_RIDE: in those updates the live right-hand-side rows (at most 16) ride in the idle waves of the diagonal tiles instead
 	int neg_modifier = 1;        // GPEMU_NEG_MODIFIER: C - A B^T through the NEG bit of the fp64 matrix instruction
 	int grad_gram = 1;           // GPEMU_GRAD_GRAM: the exact gradient's tile distances from the matrix unit (grad_exact_gram_kernel)
 	int leaf_staged = -1;        // GPEMU_LEAF_STAGED: the leaf solve moves whole 512-byte row pieces through an LDS strip (1), element-wise (0), automatic by launch size (-1)
@@ -418,6 +425,7 @@ hipError_t launch_panel_rows(hipStream_t s, double *T, long ld, int cg, int r_fa
                              long bstride);
 bool gemm_factor_ahead_ok(const GemmArgs &a);
 bool gemm_uses_big_tiles(const GemmArgs &a);
+bool gemm_ride_ok(const GemmArgs &a);
 hipError_t launch_gram_partials(hipStream_t s, const double *Z, long ld, int Np, int nrhs, int Rp, double *part,
                                 int nbatch = 1, long zstride = 0);
 hipError_t launch_finish(hipStream_t s, const double *part, int nparts, int Rp, int nrhs, const double *T, long ld,

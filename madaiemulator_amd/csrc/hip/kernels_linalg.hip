@@ -80,7 +80,131 @@ __device__ __forceinline__ void diag_inverse_ahead(double *A, int blk, int lane,
 // k-ordered chain whatever the tile shape: 128x128 and 64x64 tiles give the same bits.
 // (The register-staged loops of rounds 1-2, their L2-prefetch variant and the 128x64 / 256x128 / 128x256 shapes measured
 // slower -- profiles/r02_gemm_*.txt -- and left the tree in round 3; `git log` has them.)
-template <int BM, int BN, int MINW, int WGM, int WGN, int FA = 0, int NEG = 0>
+// The LDS image of an operand chunk, in one place for its two users, gemm_nt_kernel and gemm_ride_wave (the layout itself is
+// described in the kernel's k-loop): the size of one buffer, the LDS-DMA piece of one wave-instruction, and the swizzle f(R)
+// of the 16-byte slots of image row R, r16 = R mod 16.
+constexpr int gemm_image_bytes(int bm, int bn) { return (bm + bn) * GEMM_BK * 8; }
+constexpr int GEMM_PIECE_BYTES = 1024;                  // 8 rows x 128 B
+__device__ __forceinline__ int gemm_image_swz(int r16) { return (r16 >> 1) ^ (((r16 + 4) >> 3) & 1); }
+
+// A rider wave of a diagonal 128x128 tile (gemm_nt_kernel, RIDE, below): wave uw = 1 or 3 of the tile's eight.  It moves
+// its share of the operand chunks and meets the barriers exactly as every wave of the tile does -- the image, the pieces
+// and the swizzle are the kernel's (8 waves, two A and two B pieces each, the tile is whole: no row clamps) -- and between
+// them updates rows 0-15 of the right-hand-side block over 64 columns of the tile.  A function of its own, entered before
+// the kernel holds any accumulator: inside the kernel's k-loop everything the tile's own waves hold counted as live
+// across the rider's loop, and the compiler spilled 88 registers.
+template <int NEG>
+__device__ __forceinline__ void gemm_ride_wave(const GemmArgs &g, double *smem, int t, int kb, int ke, int uw, int lane)
+{
+	constexpr int BM = 128, NW = 8, BUFB = gemm_image_bytes(BM, BM);
+	char *lds = reinterpret_cast<char *>(smem);
+	const int prow = 8 * uw + (lane >> 3);
+	const int prow16 = prow & 15;
+	const int pseg = (lane & 7) ^ gemm_image_swz(prow16);
+	const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.A + (long)t * BM * g.lda), 0, -1, 0x00020000);
+	const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.B + (long)t * BM * g.ldb), 0, -1, 0x00020000);
+	unsigned vo[4];
+#pragma unroll
+	for (int p = 0; p < 2; p++) {
+		vo[p] = (unsigned)((long)(8 * NW * p + prow) * g.lda * 8 + 16 * pseg);
+		vo[2 + p] = (unsigned)((long)(8 * NW * p + prow) * g.ldb * 8 + 16 * pseg);
+	}
+	typedef __attribute__((address_space(3))) void *lds_ptr_t;
+#define RIDE_DMA(buf, kk)                                                                                         \
+	do {                                                                                                          \
+		char *d = lds + (buf) * BUFB + uw * GEMM_PIECE_BYTES;                                                      \
+		__builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)d, 16, vo[0], (kk) * 8, 0, 0);                   \
+		__builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(d + GEMM_PIECE_BYTES * NW), 16, vo[1], (kk) * 8, 0, 0);     \
+		__builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(d + 2 * GEMM_PIECE_BYTES * NW), 16, vo[2], (kk) * 8, 0, 0); \
+		__builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(d + 3 * GEMM_PIECE_BYTES * NW), 16, vo[3], (kk) * 8, 0, 0); \
+	} while (0)
+	// lane (q, gq): row q of the right-hand-side block and of each 16-row group of B, segment 4 t + gq of a chunk
+	const int q = lane & 15, gq = lane >> 4;
+	const int fsw = gemm_image_swz(q);
+	const int half = uw >> 1;                               // wave 1: the tile's columns 0-63, wave 3: 64-127
+	const int fb0 = (BM + half * 64 + q) * 128 + 16 * (gq ^ fsw);
+	double *rc = g.ride_C + (long)blockIdx.y * g.bsC + (long)gq * g.ldc + t * BM + half * 64 + q;
+	const double *ra = g.ride_A + (long)blockIdx.y * g.bsA + (long)q * g.lda + 2 * gq;
+	d4_t acc[4];
+#pragma unroll
+	for (int r = 0; r < 4; r++)
+#pragma unroll
+		for (int j = 0; j < 4; j++) acc[j][r] = rc[(long)(4 * r) * g.ldc + 16 * j];
+#define RIDE_FRAGS(FB_, buf, t_)                                                                                  \
+	do {                                                                                                          \
+		const char *pb = lds + (buf) * BUFB + (fb0 ^ (64 * (t_)));                                                 \
+		_Pragma("unroll") for (int j = 0; j < 4; j++) FB_[j] = *reinterpret_cast<const d2_t *>(pb + j * 2048);     \
+	} while (0)
+#define RIDE_BLOCK(A_, FB_)                                                                                       \
+	do {                                                                                                          \
+		_Pragma("unroll") for (int h = 0; h < 2; h++)                                                              \
+			_Pragma("unroll") for (int j = 0; j < 4; j++)                                                          \
+				acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(A_[h], FB_[j][h], acc[j], 0, 0, NEG);                \
+	} while (0)
+	// the A fragments of a chunk: what a lane would read from the LDS image of an A operand, from global memory
+#define RIDE_LOAD(kk)                                                                                             \
+	do {                                                                                                          \
+		nx = *reinterpret_cast<const d2_t *>(ra + (kk));                                                           \
+		ny = *reinterpret_cast<const d2_t *>(ra + (kk) + 8);                                                       \
+	} while (0)
+	d2_t xa, ya, nx, ny, xb[4], yb[4];
+	// BARRIERS: one behind the first chunk and one per chunk, between its two blocks -- the kernel body's, one for one (a
+	// barrier more or less in either of the two loops hangs the tile)
+	RIDE_DMA(0, kb);
+	RIDE_LOAD(kb);
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	__syncthreads();
+	xa = nx; ya = ny;
+	if (kb + GEMM_BK < ke) {
+		RIDE_DMA(1, kb + GEMM_BK);
+		RIDE_LOAD(kb + GEMM_BK);
+	}
+	RIDE_FRAGS(xb, 0, 0);
+	int cur = 0;
+	for (int k = kb; k < ke; k += GEMM_BK) {
+		RIDE_FRAGS(yb, cur, 1);
+		__builtin_amdgcn_sched_barrier(0);
+		RIDE_BLOCK(xa, xb);
+		__builtin_amdgcn_sched_barrier(0);
+		// the barriers of the tile's k-loop, one for one; the A fragments of chunk k+1 have landed with its image
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__syncthreads();
+		xa = nx;                                            // (the x block is through with the old one; the y block is not)
+		const d2_t cy = ny;
+		__builtin_amdgcn_sched_barrier(0);
+		if (k + 2 * GEMM_BK < ke) {
+			RIDE_DMA(cur, k + 2 * GEMM_BK);
+			RIDE_LOAD(k + 2 * GEMM_BK);
+		}
+		if (k + GEMM_BK < ke) RIDE_FRAGS(xb, cur ^ 1, 0);
+		__builtin_amdgcn_sched_barrier(0);
+		RIDE_BLOCK(ya, yb);
+		__builtin_amdgcn_sched_barrier(0);
+		ya = cy;
+		cur ^= 1;
+	}
+#undef RIDE_DMA
+#undef RIDE_FRAGS
+#undef RIDE_BLOCK
+#undef RIDE_LOAD
+#pragma unroll
+	for (int r = 0; r < 4; r++)
+#pragma unroll
+		for (int j = 0; j < 4; j++) rc[(long)(4 * r) * g.ldc + 16 * j] = acc[j][r];
+}
+
+// RIDE = 1 (riders, 128x128 tiles of a triangular update C - A B^T): the right-hand-side rows under the matrix rows need
+// C_r[16 x n] -= R[16 x K] B^T over the same columns and the same panel B.  The B image of a diagonal tile (tm == tn) holds
+// exactly the panel rows of its tile column, the diagonal tiles cover every column once, and two of their eight waves are
+// idle (above): wave 1 takes columns 0-63 of the tile and wave 3 columns 64-127 for ride_rows = 16 right-hand-side rows.  A
+// rider keeps one row of four accumulators, started from ride_C; its A fragments (row q of ride_A, doubles k+8t+2g, +1:
+// what a lane reads from the LDS image of an A operand) come straight from global memory in 16-byte loads, requested one
+// chunk ahead beside the wave's LDS-DMA, so that the wait in front of the barrier covers them; its B fragments are the
+// image's.  Per chunk the x block and then the y block of 2 x 4 matrix instructions: per accumulator the k-ordered chain
+// the 64x64 tiles run for these rows, so the launch of their own that they had is dropped with the bits unchanged -- no
+// second pass over the panel, no tile slot, a quarter of that launch's matrix instructions (it carried 64 rows, 48 of
+// them zero), on the two SIMDs of the tile that carry one live wave instead of two.
+template <int BM, int BN, int MINW, int WGM, int WGN, int FA = 0, int NEG = 0, int RIDE = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs g)
 {
 	constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -139,6 +263,18 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs 
 		// prediction sweep: 0.70 against 1.01 M predictions/s, round 4)
 	}
 	if (g.tri && tn * BN > tm * BM + BM - 1 + g.diag_off) return;
+	if constexpr (RIDE != 0) {
+		static_assert(!RIDE || (BM == 128 && BN == 128 && WGM == 4 && WGN == 2 && NEG == 1 && FA == 0), "riders live in the idle waves of the 128x128 tile of C - A B^T");
+		// launch_gemm has checked (gemm_ride_ok): triangular, diag_off 0, idle waves on, n a multiple of 128, m >= n, the whole
+		// k-range for every tile -- every diagonal tile is whole, and its waves 1 and 3 are the idle ones of the comment
+		// further down.  (through readfirstlane, as `idle` there: a branch the compiler knows to be wave-uniform; and ahead of
+		// everything the tile's own waves keep in registers: placed behind the trace stamp, the kernel spilled it)
+		const int rw = threadIdx.x >> 6;
+		if (__builtin_amdgcn_readfirstlane((int)(g.ride_rows && tm == tn && (rw == 1 || rw == 3))) != 0) {
+			gemm_ride_wave<NEG>(g, smem, tn, g.k0, g.k1, __builtin_amdgcn_readfirstlane(rw), threadIdx.x & 63);
+			return;
+		}
+	}
 	const TraceT0 tr0 = trace_begin(g.trace);
 	// (prologue and epilogue at wave priority 3, the k-loop at 0: the prologue shrinks from 13.3 to 7.8 us -- its instructions
 	// wait for issue slots behind the neighbours' 64-cycle matrix instructions -- and the launch gets 1-4 % SLOWER: those
@@ -262,14 +398,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs 
 		// slots: (4t+g) ^ f(q) for the outer rows and (4t+g) ^ 1 ^ f(q) for the middle ones are 8 different values because
 		// f(q) ^ (4 <= q <= 11) = q >> 1.  (The first form of the swizzle, (R & 7) ^ ((R >> 3) & 1), assumed contiguous
 		// 16-lane groups: SQ_LDS_BANK_CONFLICT = half of SQ_LDS_IDX_ACTIVE.)
-		constexpr int BUFB = (BM + BN) * GEMM_BK * 8;
+		constexpr int BUFB = gemm_image_bytes(BM, BN);
 		char *lds = reinterpret_cast<char *>(smem);
 		// DMA pieces: wave w moves rows 8 NW p + 8 w .. + 7 of the image for p = 0 .. NPA+NPB-1 (the first NPA: A rows),
 		// lane l -> row + (l >> 3), slot l & 7 (8 NW is a multiple of 16: row mod 16, hence f, does not depend on p)
 		const int uw = __builtin_amdgcn_readfirstlane(wave);
 		const int prow = 8 * uw + (lane >> 3);
 		const int prow16 = prow & 15;
-		const int pseg = (lane & 7) ^ ((prow16 >> 1) ^ (((prow16 + 4) >> 3) & 1));
+		const int pseg = (lane & 7) ^ gemm_image_swz(prow16);
 		int ra0 = tm * BM; if (ra0 > g.m - 1) ra0 = g.m - 1;
 		int rb0 = tn * BN; if (rb0 > g.n - 1) rb0 = g.n - 1;
 		const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g.A + (long)ra0 * g.lda), 0, -1, 0x00020000);
@@ -286,10 +422,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs 
 			vo[NPA + p] = (unsigned)((long)(br - rb0) * g.ldb * 8 + 16 * pseg);
 		}
 		typedef __attribute__((address_space(3))) void *lds_ptr_t;
-#define GEMM_DMA1(rs, d, p, kk) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)((d) + 1024 * NW * (p)), 16, vo[p], (kk) * 8, 0, 0)
+#define GEMM_DMA1(rs, d, p, kk) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)((d) + GEMM_PIECE_BYTES * NW * (p)), 16, vo[p], (kk) * 8, 0, 0)
 #define GEMM_DMA(buf, kk)                                                                                         \
 		do {                                                                                                      \
-			char *d = lds + (buf) * BUFB + uw * 1024;                                                              \
+			char *d = lds + (buf) * BUFB + uw * GEMM_PIECE_BYTES;                                                  \
 			GEMM_DMA1(rsA, d, 0, kk);                                                                              \
 			if constexpr (NPA > 1) GEMM_DMA1(rsA, d, 1, kk);                                                       \
 			if constexpr (NPA > 2) GEMM_DMA1(rsA, d, 2, kk);                                                       \
@@ -301,7 +437,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs 
 		} while (0)
 		// fragment addresses: lane (q, gq) reads row q of its 16-row group, logical segment 4 t + gq
 		const int q = lane & 15, gq = lane >> 4;
-		const int fsw = (q >> 1) ^ (((q + 4) >> 3) & 1);
+		const int fsw = gemm_image_swz(q);
 		const int fa0 = (wm * WM + q) * 128 + 16 * (gq ^ fsw);
 		const int fb0 = (BM + wn * WN + q) * 128 + 16 * (gq ^ fsw);
 #define GEMM_FRAGS(FA_, FB_, buf, t)                                                                              \
@@ -321,6 +457,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_nt_kernel(GemmArgs 
 		d2_t xa[TM], xb[TN], ya[TM], yb[TN];
 		// (every wave's buffer_load ... lds must have landed before the barrier that hands the chunk to the other waves: the
 		// compiler places this wait itself today; it is spelled out so that correctness does not hang on that)
+		// BARRIERS: this one behind chunk 0 and the one per chunk in the loop below are mirrored, one for one, in gemm_ride_wave
+		// (the rider waves of a diagonal tile never come here); so are the image, the pieces and the swizzle, through
+		// gemm_image_bytes, GEMM_PIECE_BYTES and gemm_image_swz.  Change the two together.
 		// (chunk 1 requested together with chunk 0, waiting for chunk 0 alone -- vmcnt(NPA + NPB) -- was measured: the 13-14 us
 		// of a tile's prologue did not move, round 4)
 		GEMM_DMA(0, kb);
@@ -649,6 +788,14 @@ bool gemm_factor_ahead_ok(const GemmArgs &a)
 	       !a.kend_mode && a.ksplit <= 1 && choose_gemm_cfg(a) == 2;
 }
 
+// would launch_gemm run this update with riders (ride_C, ride_A, ride_rows set)?  (the caller then drops the launch the
+// right-hand-side rows had)  Every column needs its diagonal 128x128 tile, whole, with its two idle waves.
+bool gemm_ride_ok(const GemmArgs &a)
+{
+	return a.ride_rows == 16 && a.ride_C && a.ride_A && a.tri && a.diag_off == 0 && a.m >= a.n && a.n % 128 == 0 && a.beta == 1 &&
+	       a.alpha == -1.0 && !a.no_neg_modifier && !a.keep_idle_waves && !a.kstart_mode && !a.kend_mode && a.ksplit <= 1 &&
+	       a.k1 > a.k0 && choose_gemm_cfg(a) == 8;
+}
 
 // ---------------------------------------------------------------------------
 // Tile order.  Workgroups are dealt round-robin to the 8 XCDs (ids b and b+8 share an XCD and its 4 MB L2).  In the
@@ -795,6 +942,12 @@ hipError_t launch_gemm(hipStream_t s, const GemmArgs &a_in)
 	if ((long)T * nbatch < 1024 || a.ksplit > 1) a.stagger_ticks = 0;
 	// C - A B^T on top of C (every update of the factorisation): the instantiations whose matrix instruction negates A
 	const bool neg = a.beta && a.alpha == -1.0 && !a.no_neg_modifier;
+	if (a.ride_rows) {
+		// riders: the caller drops the right-hand-side rows' own launch, so a launch that cannot carry them is an error
+		if (!gemm_ride_ok(a)) return hipErrorInvalidValue;
+		hipLaunchKernelGGL((gemm_nt_kernel<128, 128, 4, 4, 2, 0, 1, 1>), dim3(T, nbatch), dim3(512), 0, s, a);
+		return hipGetLastError();
+	}
 	if (neg) {
 		if (cfg == 8) hipLaunchKernelGGL((gemm_nt_kernel<128, 128, 4, 4, 2, 0, 1>), dim3(T, nbatch), dim3(512), 0, s, a);
 		else if (a.fa) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 4, 2, 2, 1, 1>), dim3(T, nbatch), dim3(256), 0, s, a);
