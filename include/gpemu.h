@@ -651,6 +651,61 @@ typedef struct gpemu_fill_launch_args {
 	int M, Rp, guard;
 } gpemu_fill_launch_args;
 int gpemu_test_fill_launch(gpemu_ctx *ctx, const gpemu_fill_launch_args *args);
+/* ONE call of a launcher that reads the device-resident factor of gpemu_predict_setup -- the launchers the one-query and
+ * few-query prediction products, gpemu_loo and gpemu_lgo call, unchanged -- on operands of the caller's.  What these kernels
+ * share: above its diagonal L^-1 holds exact zeros only inside the diagonal 16 x 16 blocks and nothing specified further out
+ * (U = R^-T of leave-group-out likewise left of its diagonal), so none of that may reach an output.  LinvAug (lin, row
+ * stride ld): rows [0, Np) = L^-1, row Np = gamma, rows Np+1 .. Np+nreg = W^T; betaq = beta (nreg) then Q (nreg x nreg).
+ *   GPEMU_RES_SKINNY, GPEMU_RES_GEMV   Vp[s][q][n] = sum over k in slice s = [s klen, min((s+1) klen, K)), k < ke(n), of
+ *                         Kq[q][k] L[n][k], ke(n) = (n & ~15) + 16 for n < ntri and K otherwise.  kq: 16 rows of stride ldk (the
+ *                         one-query kernel reads row 0), lin: ntot rows of stride ld, vp: nslice x vrows x ldv.  The skinny
+ *                         kernel writes rows 0 .. 15, the one-query kernel row 0, columns [0, ntot) of every slice.
+ *   GPEMU_RES_LOO_COLSQ   part[c][j] = sum of (L^-1)_rj^2 over rows r of the 64-row chunk c with j <= r < N, for every column
+ *                         j < Np of every launched (512-column strip, chunk) pair: chunk >= 8 * strip.  part: ceil(N/64) x Np.
+ *   GPEMU_RES_LOO_FINISH  P_ii = sum_c part[c][i] - w_i^T Q w_i over the launched chunks, var_i = 1 / P_ii, mean_i = y_i -
+ *                         gamma_i / P_ii for i < N.
+ *   GPEMU_RES_LGO_GATHER  z (nbc x bp x Np): row colrow[i] - g0 bp, where inside the chunk, = column i of L^-1 from row i to
+ *                         row N-1, zero elsewhere; the pad rows of every group zero.  Every element is written.
+ *   GPEMU_RES_LGO_STAGE   the staging of nbc tall matrices t ((2 bp + 64) x bp each, tstride apart) whose lower 64 x 64 tiles
+ *                         hold (C^-1)_BB: minus w_r^T Q w_c between members, identity at the pad, row bp = gamma at the
+ *                         members, rows bp+1 .. bp+63 zero, then the identity rows.  Tiles above the diagonal are not touched.
+ *   GPEMU_RES_LGO_FINISH  from factored tall matrices (row bp = the solved row w, rows bp+64 .. = U), info (nbc words as the
+ *                         factorisation leaves them) and res ({|w|^2, 2 sum log R_ii} per group): var, mean, werr at the
+ *                         members' design indices, stat (maha, logdet, logpdf: 3 x ngroups) and info_out (ngroups) at
+ *                         g0 .. g0+nbc-1.  werr and stat may be NULL.
+ *   GPEMU_RES_LGO_TAIL    everything gpemu_lgo runs per chunk behind the staging launch, on staged matrices t of the
+ *                         caller's: the lock-step factorisation with inverse rows, |w|^2 and the log-determinant, the
+ *                         finishing pass.  Outputs as GPEMU_RES_LGO_FINISH; returns what gpemu_lgo returns: GPEMU_ERR_NOT_PD
+ *                         if info_out of a group of the chunk is not 0 (that group's outputs are NaN, the others valid).
+ * Tables as gpemu_lgo builds them: colrow (N), members (nmembers), moff and bsize (ngroups).  Lengths the shape fixes: betaq
+ * nreg + nreg^2, y N, res 2 nbc, info nbc, stat 3 ngroups, info_out ngroups; mean, var and werr hold out_len >= N each
+ * (elements from N on are not written).
+ * Every region the op takes is uploaded whole and downloaded whole after the launch, so the caller's prefill shows what was
+ * written.  The device buffers are the call's own; no model is needed; the context's prediction state, factorisation
+ * workspace and result ring are not touched.
+ * GPEMU_ERR_ARG, before anything runs: a NULL pointer among the op's regions and tables; op outside its values; K or klen no
+ * multiple of 16, ntot no multiple of 64, ntri no multiple of 16 or beyond ntot or K, nslice * klen < K, vrows < 16, ldv <
+ * ntot; ld or ldk below K or no multiple of 4 (products), ld odd or below Np (the other ops that take lin); N outside
+ * 1 .. Np or Np no multiple of 64 (the same ops; N < 1 for the others); nreg outside 1 .. 63 (the ops that take betaq); bp no multiple of 64, nbc outside 1 .. GPEMU_MAX_BATCH, g0 + nbc > ngroups; an odd tstride
+ * or one below (2 bp + 64) bp; a group size outside 1 .. bp, members outside 0 .. N-1 or beyond nmembers, a colrow entry
+ * outside -1 .. ngroups bp - 1; or a footprint beyond the given length of a region. */
+#define GPEMU_RES_SKINNY 0
+#define GPEMU_RES_GEMV 1
+#define GPEMU_RES_LOO_COLSQ 2
+#define GPEMU_RES_LOO_FINISH 3
+#define GPEMU_RES_LGO_GATHER 4
+#define GPEMU_RES_LGO_STAGE 5
+#define GPEMU_RES_LGO_FINISH 6
+#define GPEMU_RES_LGO_TAIL 7
+typedef struct gpemu_resident_launch_args {
+	double *lin, *kq, *vp, *part, *betaq, *y, *z, *t, *res, *mean, *var, *werr, *stat;
+	const int *colrow, *members, *moff, *bsize, *info;
+	int *info_out;
+	long lin_len, ld, kq_len, ldk, vp_len, ldv, part_len, z_len, t_len, tstride, out_len;
+	int op, K, ntri, ntot, nslice, klen, vrows;
+	int N, Np, nreg, g0, nbc, bp, ngroups, nmembers;
+} gpemu_resident_launch_args;
+int gpemu_test_resident_launch(gpemu_ctx *ctx, const gpemu_resident_launch_args *args);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

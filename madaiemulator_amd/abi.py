@@ -68,6 +68,19 @@ class FillLaunchArgs(C.Structure):
 FILL_STAGE, FILL_KVEC, FILL_FULL = 0, 1, 2
 
 
+class ResidentLaunchArgs(C.Structure):
+    """gpemu_resident_launch_args of include/gpemu.h"""
+    _fields_ = ([(f, _dp) for f in ("lin", "kq", "vp", "part", "betaq", "y", "z", "t", "res", "mean", "var", "werr", "stat")] +
+                [(f, _ip) for f in ("colrow", "members", "moff", "bsize", "info", "info_out")] +
+                [(f, C.c_long) for f in ("lin_len", "ld", "kq_len", "ldk", "vp_len", "ldv", "part_len", "z_len", "t_len", "tstride", "out_len")] +
+                [(f, C.c_int) for f in ("op", "K", "ntri", "ntot", "nslice", "klen", "vrows",
+                                        "N", "Np", "nreg", "g0", "nbc", "bp", "ngroups", "nmembers")])
+
+
+RES_SKINNY, RES_GEMV, RES_LOO_COLSQ, RES_LOO_FINISH, RES_LGO_GATHER, RES_LGO_STAGE, RES_LGO_FINISH, RES_LGO_TAIL = range(8)
+_RES_LEN = dict(lin="lin_len", kq="kq_len", vp="vp_len", part="part_len", z="z_len", t="t_len", mean="out_len")
+
+
 # every symbol include/gpemu.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gpemu_ctx_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -153,6 +166,7 @@ SYMBOLS = {
     "gpemu_test_leaf_launch": (C.c_int, [C.c_void_p, _dp, C.c_long, C.POINTER(LeafLaunchArgs), _ip]),
     "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
     "gpemu_test_fill_launch": (C.c_int, [C.c_void_p, C.POINTER(FillLaunchArgs)]),
+    "gpemu_test_resident_launch": (C.c_int, [C.c_void_p, C.POINTER(ResidentLaunchArgs)]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
     "gpemu_test_potrf": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
@@ -730,6 +744,33 @@ class Context:
             e.region = res
             raise
         return res, form_out, norm2
+
+    def test_resident_launch(self, op, allow=(), **args):
+        """one call of a launcher that reads the resident factor (gpemu_test_resident_launch).  args: the fields of
+        ResidentLaunchArgs; an array (float64 regions, int32 tables) is copied, passed with its length where the struct has
+        one, and comes back as the entry left it -> (dict of the regions after the launch, status).  GpemuError for a status
+        that is neither OK nor in `allow` (ERR_ARG for a refused launch, ERR_NOT_PD from RES_LGO_TAIL)."""
+        ptrs = {f for f, t in ResidentLaunchArgs._fields_ if t in (_dp, _ip)}
+        dbl = {f for f, t in ResidentLaunchArgs._fields_ if t is _dp}
+        kw, out = dict(op=int(op)), {}
+        for k, v in args.items():
+            if k not in ptrs:
+                kw[k] = int(v)
+            elif v is not None:
+                a = np.array(v, dtype=np.float64 if k in dbl else np.int32, order="C").ravel()
+                out[k] = a
+                kw[k] = a.ctypes.data_as(_dp if k in dbl else _ip)
+                if k in _RES_LEN and _RES_LEN[k] not in args:
+                    kw[_RES_LEN[k]] = a.size
+        # the lengths the entry takes from the shape: what it would read from or write to a shorter host array is refused here
+        g = lambda k: kw.get(k, 0)
+        fixed = dict(betaq=g("nreg") + g("nreg") ** 2, y=g("N"), res=2 * g("nbc"), info=g("nbc"), stat=3 * g("ngroups"), info_out=g("ngroups"),
+                     colrow=g("N"), members=g("nmembers"), moff=g("ngroups"), bsize=g("ngroups"), var=g("out_len"), werr=g("out_len"))
+        for k, n in fixed.items():
+            if k in out and out[k].size < n:
+                raise ValueError(f"{k} holds {out[k].size} values, the entry takes {n}")
+        rc = self._chk(self.L.gpemu_test_resident_launch(self.h, C.byref(ResidentLaunchArgs(**kw))), allow=allow)
+        return out, rc
 
     def trace_dump(self, path):
         self._chk(self.L.gpemu_trace_dump(self.h, str(path).encode()))

@@ -2002,6 +2002,40 @@ static int lgo_plan(gpemu_ctx *ctx, int ngroups, const int *group, LgoPlan *pl)
 	return GPEMU_OK;
 }
 
+// What follows the staging launch for one chunk of nbc staged tall matrices T (tstride apart, padded to bp): the info words to
+// INFO_NONE, ONE lock-step factorisation with inverse rows, |w|^2 and sum log R_ii by the likelihood's Gram and finish kernels
+// (one right-hand side, Rp = 1), the finishing pass.  info: nbc words, part: nbc * (bp / 64 + 2) doubles.  lgo_run calls it per
+// chunk on the context's buffers, gpemu_test_resident_launch (GPEMU_RES_LGO_TAIL) on buffers of its own.
+static int lgo_chunk_tail(gpemu_ctx *ctx, double *T, long tstride, int nbc, int bp, int *info, double *part, const int *d_members,
+                          const int *d_moff, const int *d_bsize, const double *dY, int g0, int ngroups, double *mean_dev, double *var_dev,
+                          double *werr_dev, double *stat_dev, int *info_dev)
+{
+	double *res = part + (size_t)nbc * (bp / LEAF);
+	HIPCHK(ctx, hipMemsetAsync(info, 0x7f, (size_t)nbc * sizeof(int), ctx->stream));     // INFO_NONE
+	HIPCHK(ctx, trace_clear(ctx));
+	{
+		ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)nbc * bp * bp * bp / 3.0, 0.0);
+		HIPCHK(ctx, potrf_all(ctx, Tall{T, info, bp, LEAF, nbc, tstride, 0}, 1));
+	}
+	// |w|^2 of the solved right-hand-side row and 2 sum log R_ii (the pad's pivots are 1) per group
+	HIPCHK(ctx, launch_gram_partials(ctx->stream, T + (size_t)bp * bp, bp, bp, 1, 1, part, nbc, tstride));
+	HIPCHK(ctx, launch_finish(ctx->stream, part, bp / LEAF, 1, 1, T, bp, bp, res, nbc, tstride, 2));
+	{
+		ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (bp / 2.0 + 4.0));
+		HIPCHK(ctx, launch_lgo_finish(ctx->stream, T, tstride, nbc, bp, d_members, d_moff, d_bsize, info, res, dY, g0, ngroups, mean_dev,
+		                              var_dev, werr_dev, stat_dev, info_dev));
+	}
+	return GPEMU_OK;
+}
+
+// the status of a leave-group-out call from the decoded info words of its groups
+static int lgo_status(gpemu_ctx *ctx, int ngroups, const int *info)
+{
+	for (int g = 0; g < ngroups; g++)
+		if (info[g]) return fail(ctx, GPEMU_ERR_NOT_PD, "leave-group-out: P_BB of a group is not positive definite");
+	return GPEMU_OK;
+}
+
 static int lgo_run(gpemu_ctx *ctx, const LgoPlan &pl, int ngroups, const int *group, double *mean_dev, double *var_dev, double *werr_dev,
                    double *stat_dev, int *info_dev)
 {
@@ -2038,7 +2072,6 @@ static int lgo_run(gpemu_ctx *ctx, const LgoPlan &pl, int ngroups, const int *gr
 	double *Z = ctx->dLgoZ, *T = ctx->dLgoT, *part = ctx->dLgoPart;
 	for (int g0 = 0; g0 < ngroups; g0 += nbc_max) {
 		const int nbc = std::min(nbc_max, ngroups - g0);
-		double *res = part + (size_t)nbc * (bp / LEAF);
 		if (prof_on(ctx, GPEMU_PROF_LGO)) for (const char *t : {"lgo_gather", "lgo_stage", "lgo_finish"}) ctx->prof.tag.push_back(t);
 		{
 			ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (double)Np);
@@ -2057,20 +2090,9 @@ static int lgo_run(gpemu_ctx *ctx, const LgoPlan &pl, int ngroups, const int *gr
 			HIPCHK(ctx, launch_lgo_stage(ctx->stream, T, (long)tstride, g0, nbc, bp, d_members, d_moff, d_bsize, ctx->dLinvAug, Np, Np,
 			                             ctx->nreg, ctx->dBetaQ));
 		}
-		HIPCHK(ctx, hipMemsetAsync(ctx->dLgoInfo, 0x7f, (size_t)nbc * sizeof(int), ctx->stream));     // INFO_NONE
-		HIPCHK(ctx, trace_clear(ctx));
-		{
-			ProfScope ps(ctx, GPEMU_PROF_POTRF, (double)nbc * bp * bp * bp / 3.0, 0.0);
-			HIPCHK(ctx, potrf_all(ctx, Tall{T, ctx->dLgoInfo, bp, LEAF, nbc, (long)tstride, 0}, 1));
-		}
-		// |w|^2 of the solved right-hand-side row and 2 sum log R_ii (the pad's pivots are 1) per group
-		HIPCHK(ctx, launch_gram_partials(ctx->stream, T + (size_t)bp * bp, bp, bp, 1, 1, part, nbc, (long)tstride));
-		HIPCHK(ctx, launch_finish(ctx->stream, part, bp / LEAF, 1, 1, T, bp, bp, res, nbc, (long)tstride, 2));
-		{
-			ProfScope ps(ctx, GPEMU_PROF_LGO, 0.0, 8.0 * nbc * bp * (bp / 2.0 + 4.0));
-			HIPCHK(ctx, launch_lgo_finish(ctx->stream, T, (long)tstride, nbc, bp, d_members, d_moff, d_bsize, ctx->dLgoInfo, res, ctx->dY,
-			                              g0, ngroups, mean_dev, var_dev, werr_dev, stat_dev, info_dev));
-		}
+		if (const int rc2 = lgo_chunk_tail(ctx, T, (long)tstride, nbc, bp, ctx->dLgoInfo, part, d_members, d_moff, d_bsize, ctx->dY, g0, ngroups,
+		                                   mean_dev, var_dev, werr_dev, stat_dev, info_dev))
+			return rc2;
 	}
 	return GPEMU_OK;
 }
@@ -2109,9 +2131,7 @@ extern "C" int gpemu_lgo(gpemu_ctx *ctx, int ngroups, const int *group, double *
 	if (logpdf) HIPCHK(ctx, hipMemcpyAsync(logpdf, st + 2 * G, G * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(info, ctx->dLgoInfoOut, G * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	for (size_t g = 0; g < G; g++)
-		if (info[g]) return fail(ctx, GPEMU_ERR_NOT_PD, "leave-group-out: P_BB of a group is not positive definite");
-	return GPEMU_OK;
+	return lgo_status(ctx, ngroups, info);
 }
 
 // every buffer of the leave-group-out entries goes back to the device
@@ -3086,6 +3106,162 @@ extern "C" int gpemu_test_fill_launch(gpemu_ctx *ctx, const gpemu_fill_launch_ar
 	HIPCHK(ctx, hipMemcpyAsync(p->out, dOut, (size_t)footprint * 8, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
+}
+
+// ONE call of a launcher that reads the device-resident factor -- the launchers the prediction products, gpemu_loo and
+// gpemu_lgo call, unchanged -- on operands of the caller's, in device buffers of the call's own: every region the op takes is
+// uploaded whole, the launch runs, every region is downloaded whole, so the caller's prefill shows what was read and what
+// was written.  GPEMU_RES_LGO_TAIL runs lgo_chunk_tail (what lgo_run runs per chunk behind the staging launch) on the
+// caller's staged matrices and returns what lgo_status makes of the info words, as gpemu_lgo does.
+// What a launch may address is computed here first, from the kernels' grids and loops (kernels_linalg.hip), and anything
+// beyond the given lengths is refused; the tables' entries are checked too, since the kernels index with them.
+// No model is needed.  Of the context: the stream, and for the tail the schedule switches, the trace and the GEMM tile-table
+// cache that every factorisation uses; prediction state, factorisation workspace and result ring are not touched.
+extern "C" int gpemu_test_resident_launch(gpemu_ctx *ctx, const gpemu_resident_launch_args *p)
+{
+	if (!ctx || !p) return GPEMU_ERR_ARG;
+	if (p->op < GPEMU_RES_SKINNY || p->op > GPEMU_RES_LGO_TAIL) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: op");
+	constexpr long DIM_MAX = 1L << 16, LEN_MAX = 1L << 30;             // no product below leaves 63 bits
+	const int op = p->op;
+	const bool prod = op == GPEMU_RES_SKINNY || op == GPEMU_RES_GEMV, colsq = op == GPEMU_RES_LOO_COLSQ, loofin = op == GPEMU_RES_LOO_FINISH;
+	const bool gather = op == GPEMU_RES_LGO_GATHER, stage = op == GPEMU_RES_LGO_STAGE, fin = op == GPEMU_RES_LGO_FINISH;
+	const bool tail = op == GPEMU_RES_LGO_TAIL, lgo = gather || stage || fin || tail;
+	// the double regions: host pointer, given length (uploaded and downloaded whole), the launch's footprint
+	enum { R_LIN, R_KQ, R_VP, R_PART, R_BETAQ, R_Y, R_Z, R_T, R_RES, R_MEAN, R_VAR, R_WERR, R_STAT, R_COUNT };
+	double *host[R_COUNT] = {};
+	long len[R_COUNT] = {}, need[R_COUNT] = {};
+	auto take = [&](int r, double *h, long given, long footprint) { host[r] = h; len[r] = given; need[r] = footprint; };
+	const long N = p->N, Np = p->Np, ld = p->ld, nreg = p->nreg, bp = p->bp, nbc = p->nbc, g0 = p->g0, ngroups = p->ngroups;
+	if (!prod) {
+		const bool aug = !fin && !tail;                                 // the ops that read LinvAug: Np, ld (and nreg) are theirs
+		if (N < 1 || N > DIM_MAX) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: N");
+		if (aug && (N > Np || Np > DIM_MAX || Np % LEAF)) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: 1 <= N <= Np, Np a multiple of 64");
+		if ((loofin || stage) && (nreg < 1 || nreg > 63)) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: nreg outside 1 .. 63");
+		if (aug && (ld < Np || ld > DIM_MAX || (ld & 1))) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: ld must be even and >= Np");
+	}
+	if (lgo) {
+		if (bp < LEAF || bp > 4096 || bp % LEAF || nbc < 1 || nbc > GPEMU_MAX_BATCH || g0 < 0 || ngroups > DIM_MAX || g0 + nbc > ngroups)
+			return fail(ctx, GPEMU_ERR_ARG, "resident_launch: bp a multiple of 64 up to 4096, 1 <= nbc <= GPEMU_MAX_BATCH, 0 <= g0, g0 + nbc <= ngroups");
+		if (!p->bsize || (gather ? !p->colrow : (!p->members || !p->moff))) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: NULL table");
+		if (!gather && (p->nmembers < 1 || p->nmembers > DIM_MAX)) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: nmembers");
+		for (long g = 0; g < ngroups; g++) {
+			const long b = p->bsize[g];
+			if (b < 1 || b > bp) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: a group size outside 1 .. bp");
+			if (gather) continue;
+			const long o = p->moff[g];
+			if (o < 0 || o + b > p->nmembers) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: a group's members leave the table");
+			for (long j = o; j < o + b; j++)
+				if (p->members[j] < 0 || p->members[j] >= N) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: a member outside 0 .. N-1");
+		}
+		if (gather)
+			for (long i = 0; i < N; i++)
+				if (p->colrow[i] < -1 || p->colrow[i] >= ngroups * bp) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: a colrow entry outside -1 .. ngroups * bp - 1");
+	}
+	const long tmat = (2 * bp + LEAF) * bp, nmem = gather ? 0 : p->nmembers;
+	if (stage || fin || tail) {
+		if ((p->tstride & 1) || p->tstride < tmat || p->tstride > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: tstride must be even and >= (2 bp + 64) bp");
+		take(R_T, p->t, p->t_len, (nbc - 1) * p->tstride + tmat);
+	}
+	if (prod) {
+		const long K = p->K, ntot = p->ntot, ntri = p->ntri, nslice = p->nslice, klen = p->klen;
+		if (K < 16 || K > DIM_MAX || K % 16 || ntot < LEAF || ntot > DIM_MAX || ntot % LEAF) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: K a multiple of 16, ntot a multiple of 64");
+		if (ntri < 0 || ntri > ntot || ntri > K || ntri % 16) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: ntri a multiple of 16, at most ntot and K");
+		if (nslice < 1 || nslice > 4096 || klen < 16 || klen > DIM_MAX || klen % 16) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: klen must be a multiple of 16");
+		if (nslice * klen < K) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: the slices do not cover K");
+		if (ld < K || ld > DIM_MAX || (ld & 3) || p->ldk < K || p->ldk > DIM_MAX || (p->ldk & 3))
+			return fail(ctx, GPEMU_ERR_ARG, "resident_launch: ld and ldk must be multiples of 4 and >= K (32-byte row pieces)");
+		if (p->ldv < ntot || p->ldv > DIM_MAX || p->vrows < 16 || p->vrows > DIM_MAX) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: ldv >= ntot, vrows >= 16");
+		take(R_LIN, p->lin, p->lin_len, (ntot - 1) * ld + K);
+		take(R_KQ, p->kq, p->kq_len, 15 * p->ldk + K);
+		take(R_VP, p->vp, p->vp_len, nslice * p->vrows * p->ldv);
+	} else if (colsq) {
+		take(R_LIN, p->lin, p->lin_len, (N - 1) * ld + Np);
+		take(R_PART, p->part, p->part_len, (long)loo_scratch_elems((int)N, (int)Np));
+	} else if (loofin) {
+		take(R_PART, p->part, p->part_len, (long)loo_scratch_elems((int)N, (int)Np));
+		take(R_LIN, p->lin, p->lin_len, (Np + nreg) * ld + Np);
+		take(R_BETAQ, p->betaq, nreg + nreg * nreg, nreg + nreg * nreg);
+		take(R_Y, p->y, N, N);
+		take(R_MEAN, p->mean, p->out_len, N);
+		take(R_VAR, p->var, p->out_len, N);
+	} else if (gather) {
+		take(R_LIN, p->lin, p->lin_len, (N - 1) * ld + Np);
+		take(R_Z, p->z, p->z_len, nbc * bp * Np);
+	} else if (stage) {
+		take(R_LIN, p->lin, p->lin_len, (Np + nreg) * ld + N);
+		take(R_BETAQ, p->betaq, nreg + nreg * nreg, nreg + nreg * nreg);
+	} else {
+		if (fin) take(R_RES, p->res, 2 * nbc, 2 * nbc);
+		take(R_Y, p->y, N, N);
+		take(R_MEAN, p->mean, p->out_len, N);
+		take(R_VAR, p->var, p->out_len, N);
+		if (p->werr) take(R_WERR, p->werr, p->out_len, N);
+		if (p->stat) take(R_STAT, p->stat, 3 * ngroups, 3 * ngroups);
+		if (!p->info_out || (fin && !p->info)) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: NULL pointer");
+	}
+	for (int r = 0; r < R_COUNT; r++) {
+		if (!need[r]) continue;
+		if (!host[r]) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: NULL pointer");
+		if (len[r] < need[r] || len[r] > LEN_MAX) return fail(ctx, GPEMU_ERR_ARG, "resident_launch: the launch would address memory beyond a region's length");
+	}
+
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	DevBuf<double> dev[R_COUNT], dPart;
+	DevBuf<int> dTab, dInfo, dInfoOut;
+	// every allocation first; from the first copy on nothing returns before the stream has been waited for
+	for (int r = 0; r < R_COUNT; r++)
+		if (need[r]) HIPCHK(ctx, dev[r].grow((size_t)len[r]));
+	const size_t ntab = lgo ? (size_t)N + (size_t)nmem + 2 * (size_t)ngroups : 0;
+	std::vector<int> tab(ntab, 0), inf(lgo ? (size_t)nbc : 1, INFO_NONE);
+	const int *d_colrow = nullptr, *d_members = nullptr, *d_moff = nullptr, *d_bsize = nullptr;
+	if (lgo) {
+		int *h = tab.data();
+		if (gather) memcpy(h, p->colrow, (size_t)N * sizeof(int));
+		else { memcpy(h + N, p->members, (size_t)nmem * sizeof(int)); memcpy(h + N + nmem, p->moff, (size_t)ngroups * sizeof(int)); }
+		memcpy(h + N + nmem + ngroups, p->bsize, (size_t)ngroups * sizeof(int));
+		HIPCHK(ctx, dTab.grow(ntab));
+		d_colrow = dTab; d_members = d_colrow + N; d_moff = d_members + nmem; d_bsize = d_moff + ngroups;
+		if (fin || tail) {
+			HIPCHK(ctx, dInfo.grow((size_t)nbc));
+			HIPCHK(ctx, dInfoOut.grow((size_t)ngroups));
+			if (fin) memcpy(inf.data(), p->info, (size_t)nbc * sizeof(int));
+		}
+		if (tail) HIPCHK(ctx, dPart.grow((size_t)nbc * (size_t)(bp / LEAF + 2)));
+	}
+	hipError_t e = hipSuccess;
+	int rc = GPEMU_OK;
+	for (int r = 0; r < R_COUNT && e == hipSuccess; r++)
+		if (need[r]) e = hipMemcpyAsync(dev[r], host[r], (size_t)len[r] * 8, hipMemcpyHostToDevice, ctx->stream);
+	if (lgo && e == hipSuccess) e = hipMemcpyAsync(dTab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+	if ((fin || tail) && e == hipSuccess) e = hipMemcpyAsync(dInfo, inf.data(), (size_t)nbc * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+	if ((fin || tail) && e == hipSuccess) e = hipMemcpyAsync(dInfoOut, p->info_out, (size_t)ngroups * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) {
+		hipStream_t s = ctx->stream;
+		if (op == GPEMU_RES_SKINNY)
+			e = launch_skinny_nt(s, dev[R_KQ], p->ldk, dev[R_LIN], ld, dev[R_VP], p->ldv, (long)p->vrows * p->ldv, 1, p->ntot, p->K, p->ntri, p->nslice, p->klen);
+		else if (op == GPEMU_RES_GEMV)
+			e = launch_gemv_tri(s, dev[R_KQ], p->ldk, dev[R_LIN], ld, dev[R_VP], p->ldv, (long)p->vrows * p->ldv, 1, p->ntot, p->K, p->ntri, p->nslice, p->klen);
+		else if (colsq) e = launch_loo_colsq(s, dev[R_LIN], ld, (int)N, (int)Np, dev[R_PART]);
+		else if (loofin) e = launch_loo_finish(s, dev[R_PART], dev[R_LIN], ld, (int)N, (int)Np, (int)nreg, dev[R_BETAQ], dev[R_Y], dev[R_MEAN], dev[R_VAR]);
+		else if (gather) e = launch_lgo_gather(s, dev[R_LIN], ld, (int)N, (int)Np, d_colrow, d_bsize, (int)g0, (int)nbc, (int)bp, dev[R_Z]);
+		else if (stage)
+			e = launch_lgo_stage(s, dev[R_T], p->tstride, (int)g0, (int)nbc, (int)bp, d_members, d_moff, d_bsize, dev[R_LIN], ld, (int)Np, (int)nreg, dev[R_BETAQ]);
+		else if (fin)
+			e = launch_lgo_finish(s, dev[R_T], p->tstride, (int)nbc, (int)bp, d_members, d_moff, d_bsize, dInfo, dev[R_RES], dev[R_Y], (int)g0, (int)ngroups,
+			                      dev[R_MEAN], dev[R_VAR], need[R_WERR] ? (double *)dev[R_WERR] : nullptr, need[R_STAT] ? (double *)dev[R_STAT] : nullptr, dInfoOut);
+		else
+			rc = lgo_chunk_tail(ctx, dev[R_T], p->tstride, (int)nbc, (int)bp, dInfo, dPart, d_members, d_moff, d_bsize, dev[R_Y], (int)g0, (int)ngroups,
+			                    dev[R_MEAN], dev[R_VAR], need[R_WERR] ? (double *)dev[R_WERR] : nullptr, need[R_STAT] ? (double *)dev[R_STAT] : nullptr, dInfoOut);
+	}
+	const hipError_t es = hipStreamSynchronize(ctx->stream);
+	if (rc) return rc;
+	HIPCHK(ctx, e);
+	HIPCHK(ctx, es);
+	for (int r = 0; r < R_COUNT; r++)
+		if (need[r]) HIPCHK(ctx, hipMemcpyAsync(host[r], dev[r], (size_t)len[r] * 8, hipMemcpyDeviceToHost, ctx->stream));
+	if (fin || tail) HIPCHK(ctx, hipMemcpyAsync(p->info_out, dInfoOut, (size_t)ngroups * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return tail ? lgo_status(ctx, (int)nbc, p->info_out + g0) : GPEMU_OK;
 }
 
 // the GEMM tile order of a launch with tiles_m x tiles_n tiles (tri: lower triangle only) and super-blocks of side sb:
