@@ -411,6 +411,51 @@ int gpemu_lgo_dev(gpemu_ctx *ctx, int ngroups, const int *group /* N HOST */, do
 /* frees every buffer of the two entries above (waits for the context's stream) */
 int gpemu_lgo_release(gpemu_ctx *ctx);
 
+/* ---- main effects and Sobol indices of the posterior mean, in closed form -----------------
+ * Stands in for the reference's sensitivity analysis in R (src/libSA/sa-fns.R: the Oakley-O'Hagan integrals of a
+ * squared-exponential emulator with a (1, x) regression).  One difference in the measure: the reference integrates against a
+ * GAUSSIAN input measure, this integrates over a BOX -- independent uniform inputs on [lo_l, hi_l], the caller's box, which
+ * may be narrower than the design or leave design points outside.  This is the plug-in analysis of the posterior mean; the
+ * emulator-uncertainty terms of Oakley-O'Hagan are not computed.
+ * The function analysed is the one gpemu_predict_mean evaluates, for the power-exponential covariance, without the k-vector
+ * clamp:   m(x) = beta_0 + sum_l q_l(x_l) + A sum_i gamma_i prod_l k_l(x_il, x_l),   q_l(x) = sum_{p=1..order} beta_{p,l} x^p,
+ * k_l(a, x) = exp(-s_l (x - a)^2 / 2), s_l = exp(-2 theta_{2+l}), A the amplitude of the k-vector.  The nugget rule acts on a
+ * set of measure zero and drops out; the clamp does not (the remark at gpemu_loo): the closed form integrates the unclamped
+ * kernel, the two functions differ by at most sum_i |gamma_i| 1e-10.
+ * The kernel is a product of one-dimensional Gaussians and the regression basis is additive in the coordinates, so every
+ * conditional expectation m_u = E[m | x_u] factorises into one-dimensional integrals with an erf closed form.  For two
+ * contexts a and b on the SAME design (lengths s and t, weights gamma and gamma', amplitudes A and A'; b may be a):
+ *   e0[0], e0[1]   E[m^a], E[m^b]
+ *   cov_all        Cov(m^a, m^b)                                with b = a: V, the total variance
+ *   cov_first[j]   Cov(m^a_{j}, m^b_{j})                        with b = a: V_j, the first-order variance of coordinate j
+ *   cov_rest[j]    Cov(m^a_{-j}, m^b_{-j})  (all but j known)   with b = a: V - cov_rest[j] = VT_j, the total-effect variance
+ * The cross case is what a multi-output emulator needs: its PCA components are not independent under the input measure.
+ * gpemu_sens_main returns E0 and the main-effect curves main[j*ngrid + g] = E[m | x_j = grid[j*ngrid + g]].
+ * How it runs, three launches on a's stream: the per-point integrals of both contexts (five N x d tables each: I, J^1, J^2, J^3
+ * and the leave-one-out products of I); the full N x N square of pair terms in 64 x 64 tiles, 2 d + 1 partial sums per tile
+ * (2 N^2 d erf evaluations: bound by vector fp64); the finish, which adds the partials in a fixed order and assembles the
+ * polynomial parts, E0 removed from the constant term before any second moment is formed.  An erf difference whose arguments
+ * have one sign is taken as an erfc difference, and leave-one-out products come from prefix and suffix products, never from
+ * a division.  d <= 16 keeps its per-coordinate values in registers; a larger d (any up to GPEMU_MAX_PARAMS) takes the same
+ * loop rolled, with them in private memory: slower.  Memory: 8 (10 N d + ceil(N / 64)^2 (2 d + 1)) bytes.
+ * No atomics, no workgroup waits for another.  Two identical calls return the same bits, and so do the host and _dev entries
+ * and a context set up by gpemu_predict_setup_batch.  The _dev entry only enqueues (lo and hi are HOST arrays: they travel as
+ * kernel arguments); with b != a it orders a's stream behind b's pending work, and b's stream behind the call, with events:
+ * no host synchronisation.  The entries work in buffers of their own, in a: they leave nothing another entry reads, a pending
+ * prediction batch stays collectable; gpemu_sens_release gives the buffers back (waits for the stream), gpemu_set_model and
+ * the end of the context free them too.
+ * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL pointer and ngrid < 1, whatever the state;
+ * GPEMU_ERR_STATE without a prediction set-up on either context; then GPEMU_ERR_ARG for a Matern model (the closed form
+ * exists for the power-exponential covariance only), contexts on different devices, contexts whose designs differ in N, d
+ * or any coordinate (the host copies are compared) or whose regression orders differ, a non-finite bound or hi_l <= lo_l. */
+int gpemu_sens_cov(gpemu_ctx *a, gpemu_ctx *b /* may be a */, const double *lo, const double *hi /* d each, host */,
+                   double *e0 /* 2: E0 of a, of b */, double *cov_all, double *cov_first /* d */, double *cov_rest /* d */);
+int gpemu_sens_cov_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi /* HOST */,
+                       double *out_dev /* 3 + 2 d: e0a, e0b, cov_all, first[d], rest[d] */);
+int gpemu_sens_main(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid /* d*ngrid host: row j = values of x_j */,
+                    double *e0, double *main /* d*ngrid: E[m | x_j = grid[j][g]] */);
+int gpemu_sens_release(gpemu_ctx *ctx);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */
@@ -459,6 +504,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_COV     11  /* the prior and mirror launches of gpemu_predict_cov[_dev]: bytes = 8*M*M (the lower triangle written once, mirrored once); its symmetric product reports under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_JOINT   12  /* the staging and clean launches of gpemu_predict_joint_factor[_dev] (bytes = 8*(64 M' + 2 M) and 4*M'*M', M' = M rounded up to 64) and the staging launch of every block of gpemu_predict_joint_draw[_dev] (bytes = 8*ndraw*(M' + 2 M)); the sweep, the products and the factorisation report under GPEMU_PROF_FILL / _COV / _GEMM / _LEAF / _POTRF */
 #define GPEMU_PROF_LGO     13  /* the three launches per chunk of gpemu_lgo[_dev], nbc groups padded to bp: gather (bytes = 8 nbc bp Np: the rows of Z written; it reads at most the lower tiles of L^-1 besides), staging (bytes = 8 nbc bp (2 bp + 64): the lower tiles read and written, right-hand-side and identity rows written), finish (bytes = 8 nbc bp (bp / 2 + 4)); the product and the factorisation report under GPEMU_PROF_GEMM / _LEAF / _POTRF */
+#define GPEMU_PROF_SENS    14  /* the three launches of gpemu_sens_cov[_dev] -- prep (flops = 88 N d: both contexts, two erf and two exp per point and coordinate counted as one flop each; bytes = 8 (10 N d + N d): the tables written, the design read), sweep (flops = N^2 (19 d + 2): per pair and coordinate one exp and two erf or erfc counted as one flop each among 16 others, then the 2 d + 1 sums; bytes = 8 T: the T = ceil(N / 64)^2 (2 d + 1) partial sums written), finish (flops = T, bytes = 8 T) -- and the two of gpemu_sens_main: prep, curves (flops = 6 N d ngrid, bytes = 16 d ngrid) */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 
@@ -706,6 +752,10 @@ typedef struct gpemu_resident_launch_args {
 	int N, Np, nreg, g0, nbc, bp, ngroups, nmembers;
 } gpemu_resident_launch_args;
 int gpemu_test_resident_launch(gpemu_ctx *ctx, const gpemu_resident_launch_args *args);
+/* beta (nreg) and gamma = C^-1 (y - H beta) (N), bit for bit as the prediction state holds them in HBM.  For tests whose bar is
+ * a few ulp (the closed-form sensitivity entries): their reference must start from these two vectors, since another
+ * factorisation's gamma differs from the device's by far more than that.  GPEMU_ERR_STATE without a prediction set-up. */
+int gpemu_test_pred_state(gpemu_ctx *ctx, double *beta, double *gamma);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

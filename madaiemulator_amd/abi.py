@@ -22,6 +22,7 @@ PROF_VAR_GRAD = 10
 PROF_COV = 11
 PROF_JOINT = 12
 PROF_LGO = 13
+PROF_SENS = 14
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -144,6 +145,10 @@ SYMBOLS = {
     "gpemu_lgo": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "gpemu_lgo_dev": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_lgo_release": (C.c_int, [C.c_void_p]),
+    "gpemu_sens_cov": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpemu_sens_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
+    "gpemu_sens_main": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp]),
+    "gpemu_sens_release": (C.c_int, [C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -167,6 +172,7 @@ SYMBOLS = {
     "gpemu_test_grad_sums": (C.c_int, [C.c_void_p, C.POINTER(GradSumsArgs)]),
     "gpemu_test_fill_launch": (C.c_int, [C.c_void_p, C.POINTER(FillLaunchArgs)]),
     "gpemu_test_resident_launch": (C.c_int, [C.c_void_p, C.POINTER(ResidentLaunchArgs)]),
+    "gpemu_test_pred_state": (C.c_int, [C.c_void_p, _dp, _dp]),
     "gpemu_test_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _dp, _dp]),
     "gpemu_test_potrf": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
@@ -467,6 +473,42 @@ class Context:
 
     def lgo_release(self):
         self._chk(self.L.gpemu_lgo_release(self.h))
+
+    # main effects and Sobol indices of the posterior mean in closed form: uniform inputs on the box [lo, hi]
+    def sens_cov(self, lo, hi, other=None):
+        """-> dict(e0[2], cov_all, cov_first[d], cov_rest[d]) of this context and `other` (default: itself) on one design"""
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_cov: one bound pair per coordinate")
+        b = self if other is None else other
+        e0, ca, cf, cr = np.empty(2), np.empty(1), np.empty(self.d), np.empty(self.d)
+        self._chk(self.L.gpemu_sens_cov(self.h, b.h, _p(lo), _p(hi), _p(e0), _p(ca), _p(cf), _p(cr)))
+        return dict(e0=e0, cov_all=ca[0], cov_first=cf, cov_rest=cr)
+
+    def sens_cov_dev(self, lo, hi, out_dev, other=None):
+        """lo, hi: HOST bounds; out_dev: 3 + 2 d doubles on the device (e0a, e0b, cov_all, first[d], rest[d])"""
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_cov_dev: one bound pair per coordinate")
+        self._chk(self.L.gpemu_sens_cov_dev(self.h, (self if other is None else other).h, _p(lo), _p(hi), out_dev))
+
+    def sens_main(self, lo, hi, grid):
+        """grid[j][g]: values of x_j (d rows) -> (e0, main[d, G]) with main[j][g] = E[m | x_j = grid[j][g]]"""
+        lo, hi, grid = _a(lo).ravel(), _a(hi).ravel(), _a(grid).reshape(self.d, -1)
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_main: one bound pair per coordinate")
+        e0, main = np.empty(1), np.empty(grid.shape)
+        self._chk(self.L.gpemu_sens_main(self.h, _p(lo), _p(hi), grid.shape[1], _p(grid), _p(e0), _p(main)))
+        return e0[0], main
+
+    def sens_release(self):
+        self._chk(self.L.gpemu_sens_release(self.h))
+
+    def pred_state(self):
+        """-> (beta[nreg], gamma[N]) bit for bit as the prediction state holds them (parity tests)"""
+        beta, gamma = np.empty(self.nreg), np.empty(self.N)
+        self._chk(self.L.gpemu_test_pred_state(self.h, _p(beta), _p(gamma)))
+        return beta, gamma
 
     def chol_inverse(self, A):
         A = _a(A).copy()

@@ -272,6 +272,7 @@ static void free_model(gpemu_ctx *ctx)
 	for (auto *b : {&ctx->dLgoZ, &ctx->dLgoT, &ctx->dLgoPart, &ctx->dLgoOut}) b->reset();
 	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
 	ctx->hLgoTab.reset();
+	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid}) b->reset();
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -288,6 +289,8 @@ gpemu_ctx::~gpemu_ctx()
 	for (auto e : prof.ev) hipEventDestroy(e);
 	for (auto e : pring.ev) if (e) hipEventDestroy(e);
 	if (lgo_ev) hipEventDestroy(lgo_ev);
+	if (sens_ev) hipEventDestroy(sens_ev);
+	if (sens_ev2) hipEventDestroy(sens_ev2);
 	for (auto &s : ring) if (s.ev) hipEventDestroy(s.ev);
 	if (stream) hipStreamDestroy(stream);
 }
@@ -2143,6 +2146,159 @@ extern "C" int gpemu_lgo_release(gpemu_ctx *ctx)
 	for (auto *b : {&ctx->dLgoZ, &ctx->dLgoT, &ctx->dLgoPart, &ctx->dLgoOut}) b->reset();
 	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
 	ctx->hLgoTab.reset();
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// main effects and Sobol indices of the posterior mean in closed form (gpemu.h): three launches on a's
+// stream -- the per-point integrals of both contexts, the N x N sweep of pair terms into per-tile partials, the finish.
+// Reads dX, dBetaQ and the gamma row of dLinvAug of both contexts; everything it writes is its own (dSens*), all in a.
+// ---------------------------------------------------------------------------
+// every check of a call, nothing allocated or launched; fills the box with both contexts' squared inverse lengths
+static int sens_check(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, SensBox *bx)
+{
+	if (!a->pred_ready || !b->pred_ready) return fail(a, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (a->kind != GPEMU_POWEREXP || b->kind != GPEMU_POWEREXP)
+		return fail(a, GPEMU_ERR_ARG, "sensitivity: the closed form exists for the power-exponential covariance only (a Matern kernel is no product over the coordinates)");
+	if (a->device != b->device) return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts are on different devices");
+	if (a->N != b->N || a->d != b->d || (a != b && a->hX != b->hX))
+		return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts hold different designs");
+	if (a->order != b->order) return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts differ in their regression order");
+	const int d = a->d;
+	for (int l = 0; l < d; l++)
+		if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > lo[l]) || !std::isfinite(hi[l] - lo[l]))
+			return fail(a, GPEMU_ERR_ARG, "sensitivity: every bound must be finite, with hi > lo");
+	memset(bx, 0, sizeof *bx);
+	bx->d = d;
+	for (int l = 0; l < d; l++) {
+		bx->s[l] = 2.0 * a->pred_cov.w[l] * a->pred_cov.w[l];      // w = sqrt(1/2) e^-theta: s = e^(-2 theta)
+		bx->t[l] = 2.0 * b->pred_cov.w[l] * b->pred_cov.w[l];
+		bx->lo[l] = lo[l];
+		bx->hi[l] = hi[l];
+	}
+	return GPEMU_OK;
+}
+
+// a's stream behind b's pending work, without the host waiting
+static int sens_order_streams(gpemu_ctx *a, gpemu_ctx *b)
+{
+	if (a == b) return GPEMU_OK;
+	if (!a->sens_ev) HIPCHK(a, hipEventCreateWithFlags(&a->sens_ev, hipEventDisableTiming));
+	if (!a->sens_ev2) HIPCHK(a, hipEventCreateWithFlags(&a->sens_ev2, hipEventDisableTiming));
+	HIPCHK(a, hipEventRecord(a->sens_ev, b->stream));
+	HIPCHK(a, hipStreamWaitEvent(a->stream, a->sens_ev, 0));
+	return GPEMU_OK;
+}
+
+static int sens_prep(gpemu_ctx *a, const SensBox &bx)
+{
+	const int N = a->N, d = a->d;
+	int rc = grow(a, a->dSensPrep, sens_prep_elems(N, d));
+	if (!rc) rc = grow(a, a->dSensCst, (size_t)SENS_CST * GPEMU_MAX_PARAMS);
+	if (rc) return rc;
+	// per point and coordinate of either context two erf and two exp with some forty flops around them; the tables out
+	ProfScope ps(a, GPEMU_PROF_SENS, 2.0 * N * d * 44.0, 8.0 * ((double)sens_prep_elems(N, d) + (double)N * d));
+	HIPCHK(a, launch_sens_prep(a->stream, a->dX, N, bx, a->dSensPrep, a->dSensCst));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_cov_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, double *out_dev)
+{
+	if (!a || !b || !lo || !hi || !out_dev) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(a, b, lo, hi, &bx)) return rc;
+	HIPCHK(a, hipSetDevice(a->device));
+	const int N = a->N, d = a->d, Np = a->Np;
+	if (const int rc = grow(a, a->dSensPart, sens_part_elems(N, d))) return rc;
+	if (const int rc = sens_order_streams(a, b)) return rc;
+	if (prof_on(a, GPEMU_PROF_SENS)) for (const char *t : {"sens_prep", "sens_sweep", "sens_finish"}) a->prof.tag.push_back(t);
+	if (const int rc = sens_prep(a, bx)) return rc;
+	const double *gamA = a->dLinvAug + (size_t)Np * Np, *gamB = b->dLinvAug + (size_t)Np * Np;
+	{
+		// per pair and coordinate: one exp and two erf / erfc (counted as one flop each) among 16 flops, then 2 (2 d + 1) for the sums
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (19.0 * d + 2.0), 8.0 * (double)sens_part_elems(N, d));
+		HIPCHK(a, launch_sens_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPrep, a->dSensCst, a->dSensPart));
+	}
+	{
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)sens_part_elems(N, d), 8.0 * (double)sens_part_elems(N, d));
+		HIPCHK(a, launch_sens_finish(a->stream, a->dSensPart, N, d, a->order, gamA, a->dBetaQ, a->pred_cov.amp, gamB, b->dBetaQ,
+		                             b->pred_cov.amp, a->dSensPrep, a->dSensCst, out_dev));
+	}
+	if (a != b) {
+		// b's later work (a new set-up would rewrite its gamma) runs behind this call
+		HIPCHK(a, hipEventRecord(a->sens_ev2, a->stream));
+		HIPCHK(a, hipStreamWaitEvent(b->stream, a->sens_ev2, 0));
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_cov(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, double *e0, double *cov_all,
+                              double *cov_first, double *cov_rest)
+{
+	if (!a || !b || !lo || !hi || !e0 || !cov_all || !cov_first || !cov_rest) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(a, b, lo, hi, &bx)) return rc;
+	HIPCHK(a, hipSetDevice(a->device));
+	const size_t d = (size_t)a->d;
+	if (const int rc = grow(a, a->dSensOut, 3 + 2 * (size_t)GPEMU_MAX_PARAMS)) return rc;
+	if (const int rc = gpemu_sens_cov_dev(a, b, lo, hi, a->dSensOut)) return rc;
+	std::vector<double> o(3 + 2 * d);
+	HIPCHK(a, hipMemcpyAsync(o.data(), a->dSensOut, o.size() * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+	HIPCHK(a, hipStreamSynchronize(a->stream));
+	e0[0] = o[0];
+	e0[1] = o[1];
+	*cov_all = o[2];
+	memcpy(cov_first, o.data() + 3, d * sizeof(double));
+	memcpy(cov_rest, o.data() + 3 + d, d * sizeof(double));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_main(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main)
+{
+	if (!ctx || !lo || !hi || !grid || !e0 || !main || ngrid < 1) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np;
+	const size_t ng = (size_t)d * ngrid;
+	int rc = grow(ctx, ctx->dSensGrid, 2 * ng);
+	if (!rc) rc = grow(ctx, ctx->dSensOut, 3 + 2 * (size_t)GPEMU_MAX_PARAMS);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dSensGrid, grid, ng * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (prof_on(ctx, GPEMU_PROF_SENS)) for (const char *t : {"sens_prep", "sens_main"}) ctx->prof.tag.push_back(t);
+	if ((rc = sens_prep(ctx, bx))) return rc;
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS, (double)ng * N * 6.0, 8.0 * 2.0 * (double)ng);
+		HIPCHK(ctx, launch_sens_main(ctx->stream, ctx->dX, N, d, ctx->order, ctx->dLinvAug + (size_t)Np * Np, ctx->dBetaQ, ctx->pred_cov.amp,
+		                             ctx->dSensPrep, ctx->dSensCst, ctx->dSensGrid, ngrid, ctx->dSensOut, ctx->dSensGrid + ng));
+	}
+	HIPCHK(ctx, hipMemcpyAsync(main, ctx->dSensGrid + ng, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(e0, ctx->dSensOut, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// every buffer of the sensitivity entries goes back to the device
+extern "C" int gpemu_sens_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid}) b->reset();
+	return GPEMU_OK;
+}
+
+// beta and gamma = C^-1 (y - H beta) exactly as the prediction state holds them (parity tests: a reference that is to be
+// met to rounding must start from the same two vectors, not from another factorisation's)
+extern "C" int gpemu_test_pred_state(gpemu_ctx *ctx, double *beta, double *gamma)
+{
+	if (!ctx || !beta || !gamma) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipMemcpyAsync(beta, ctx->dBetaQ, (size_t)ctx->nreg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(gamma, ctx->dLinvAug + (size_t)ctx->Np * ctx->Np, (size_t)ctx->N * sizeof(double), hipMemcpyDeviceToHost,
+	                           ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 

@@ -41,6 +41,16 @@ struct CovParams {
 	double w[GPEMU_MAX_PARAMS];
 };
 
+// The box and the two contexts' squared inverse lengths s_l = exp(-2 theta_{2+l}) of a sensitivity call, handed to its
+// prep kernel by value (kernels_sens.hip); SENS_CST: rows of the per-coordinate constants that kernel leaves for the sweep
+struct SensBox {
+	int d;
+	int pad_;
+	double s[GPEMU_MAX_PARAMS], t[GPEMU_MAX_PARAMS];
+	double lo[GPEMU_MAX_PARAMS], hi[GPEMU_MAX_PARAMS];
+};
+constexpr int SENS_CST = 7;
+
 // C[m x n] = beta*C + alpha * A[m x K] * B[n x K]^T over k in [k0,k1)
 struct GemmArgs {
 	double *C;
@@ -301,6 +311,12 @@ struct gpemu_ctx {
 	gpemu::DevBuf<int> dLgoTab, dLgoInfo, dLgoInfoOut;
 	gpemu::PinnedBuf<int> hLgoTab;
 	hipEvent_t lgo_ev = nullptr;
+	// sensitivity entries (gpemu_sens_cov / gpemu_sens_main): dSensPrep the per-point tables of both contexts
+	// (2 x 5 x d x N), dSensCst the sweep's per-coordinate constants, dSensPart the tiles' partial sums, dSensOut the 3 + 2 d
+	// results of the host entry (and E0 of the main-effect entry), dSensGrid that entry's grid, then its curves; sens_ev: this
+	// context's stream behind the other context's pending work, sens_ev2: the other's stream behind this call
+	gpemu::DevBuf<double> dSensPrep, dSensCst, dSensPart, dSensOut, dSensGrid;
+	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
 
@@ -451,5 +467,19 @@ hipError_t launch_lgo_stage(hipStream_t s, double *T, long tstride, int g0, int 
 hipError_t launch_lgo_finish(hipStream_t s, const double *T, long tstride, int nbc, int bp, const int *members, const int *moff,
                              const int *bsize, const int *info, const double *res, const double *y, int g0, int ngroups,
                              double *mean, double *var, double *werr, double *stat, int *info_out);
+
+// ---- kernels_sens.hip: closed-form sensitivity analysis of the posterior mean
+// prep: sens_prep_elems doubles, table q (I, J^1, J^2, J^3, Pex) of context c at ((c * 5 + q) * d + l) * N + i; cst: SENS_CST
+// rows of GPEMU_MAX_PARAMS; part: sens_part_elems doubles, 2 d + 1 sums per 64 x 64 tile; out: e0a, e0b, cov_all, first[d], rest[d]
+size_t sens_prep_elems(int N, int d);
+size_t sens_part_elems(int N, int d);
+hipError_t launch_sens_prep(hipStream_t s, const double *X, int N, const SensBox &bx, double *prep, double *cst);
+hipError_t launch_sens_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *prep,
+                             const double *cst, double *part);
+hipError_t launch_sens_finish(hipStream_t s, const double *part, int N, int d, int order, const double *gamA, const double *betaA,
+                              double ampA, const double *gamB, const double *betaB, double ampB, const double *prep, const double *cst,
+                              double *out);
+hipError_t launch_sens_main(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
+                            const double *prep, const double *cst, const double *grid, int ngrid, double *e0, double *out);
 
 } // namespace gpemu

@@ -124,6 +124,53 @@ void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &
 	for (int i = 0; i < number_outputs; i++) Covariances[i].assign(c.begin() + (size_t)i * np * np, c.begin() + (size_t)(i + 1) * np * np);
 }
 
+// the box of the two sensitivity methods, checked to have number_params entries on either side
+static void check_box(const char *method, const std::vector<double> &lo, const std::vector<double> &hi, int number_params)
+{
+	if ((int)lo.size() != number_params || (int)hi.size() != number_params) {
+		std::cerr << "Error::" << method << " called with a box that has not one bound pair per parameter" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+}
+
+void emulator::QueryEmulatorSensitivity(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<double> &Means,
+                                        std::vector<double> &Variances, std::vector<std::vector<double> > &FirstOrder,
+                                        std::vector<std::vector<double> > &Total)
+{
+	check_box("QueryEmulatorSensitivity", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params;
+	std::vector<double> f(no * d), t(no * d);
+	Means.assign(no, 0.0);
+	Variances.assign(no, 0.0);
+	emulate_sensitivity_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), Means.data(), Variances.data(), f.data(), t.data());
+	FirstOrder.assign(no, std::vector<double>(d));
+	Total.assign(no, std::vector<double>(d));
+	for (size_t i = 0; i < no; i++)
+		for (size_t j = 0; j < d; j++) {
+			const double V = Variances[i];
+			FirstOrder[i][j] = V != 0.0 ? f[i * d + j] / V : NAN;
+			Total[i][j] = V != 0.0 ? t[i * d + j] / V : NAN;
+		}
+}
+
+void emulator::QueryEmulatorMainEffects(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
+                                        std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves)
+{
+	check_box("QueryEmulatorMainEffects", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params, G = grid.empty() ? 0 : grid[0].size();
+	if (grid.size() != d || G < 1) {
+		std::cerr << "Error::QueryEmulatorMainEffects called with a grid that has not one non-empty row per parameter" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	std::vector<double> g = flatten("QueryEmulatorMainEffects", grid, (int)G), m(d * G * no);
+	Means.assign(no, 0.0);
+	emulate_main_effects_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), (int)G, g.data(), Means.data(), m.data());
+	Curves.assign(no, std::vector<std::vector<double> >(d, std::vector<double>(G)));
+	for (size_t i = 0; i < no; i++)
+		for (size_t j = 0; j < d; j++)
+			for (size_t k = 0; k < G; k++) Curves[i][j][k] = m[(j * G + k) * no + i];
+}
+
 double emulator::ValidateHoldout(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<double> > &Observations,
                                  std::vector<std::vector<double> > &Means, std::vector<std::vector<double> > &Variances,
                                  std::vector<std::vector<double> > &WhitenedErrors, std::vector<double> &Mahalanobis,

@@ -56,6 +56,17 @@ public:
 	// the joint covariance at xpoints first (no noise); coinciding points end in the layer's fatal exit.
 	void DrawEmulator(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<std::vector<double> > > &Normals,
 	                  std::vector<std::vector<std::vector<double> > > &Draws);
+	// sensitivity analysis of the posterior mean over the box [lo, hi] (number_params entries each; independent uniform inputs),
+	// in closed form, power-exponential covariance only (libemu.h: emulate_sensitivity_multi).  Per output t: Means[t] = E0,
+	// Variances[t] = V, FirstOrder[t][j] = V_j / V and Total[t][j] = VT_j / V, the first-order and total-effect Sobol indices of
+	// parameter j (NaN where V = 0).  In observable space the cross-covariances between the PCA components are included.
+	void QueryEmulatorSensitivity(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<double> &Means,
+	                              std::vector<double> &Variances, std::vector<std::vector<double> > &FirstOrder,
+	                              std::vector<std::vector<double> > &Total);
+	// main-effect curves: grid[j] holds the values of parameter j (number_params rows of equal length G);
+	// Curves[t][j][g] = E[output t | x_j = grid[j][g]], Means[t] = E0
+	void QueryEmulatorMainEffects(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
+	                              std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

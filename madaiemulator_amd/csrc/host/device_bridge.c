@@ -1217,6 +1217,60 @@ void emulate_lgo_collect(emulator_struct *e, void *dev, int ngroups, double *mea
 	check(en, rc, "emulate_lgo");
 }
 
+/* main effects and Sobol indices of the posterior mean in closed form over the box [lo, hi] (gpemu_sens_cov / gpemu_sens_main in
+ * gpemu.h): the variance V, the first-order parts V_j and the total-effect parts VT_j = V - Var(E[m | x_-j]) */
+void emulate_sensitivity(emulator_struct *e, const double *lo, const double *hi, double *e0, double *var, double *first, double *total)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity");
+	const size_t d = (size_t)en->d;
+	double both[2], *rest = (double *)malloc(sizeof(double) * (d ? d : 1));
+	const int rc = gpemu_sens_cov(en->ctx, en->ctx, lo, hi, both, var, first, rest);
+	if (!rc) {
+		*e0 = both[0];
+		for (size_t j = 0; j < d; j++) total[j] = *var - rest[j];
+	}
+	free(rest);
+	check(en, rc, "emulate_sensitivity");
+}
+
+void emulate_main_effects(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main)
+{
+	struct entry *en = entry_of(e, "emulate_main_effects");
+	check(en, gpemu_sens_main(en->ctx, lo, hi, ngrid, grid, e0, main), "emulate_main_effects");
+}
+
+/* the covariances in two halves, for one emulator or two on one design: gpemu_sens_cov_dev is enqueued on a's stream (which it
+ * orders behind b's pending work itself) and the 3 + 2 d results wait in a device buffer; collect downloads them, which waits
+ * for a's stream only, and releases the buffer */
+void emulate_sensitivity_enqueue(emulator_struct *a, emulator_struct *b, const double *lo, const double *hi, void **dev_out)
+{
+	struct entry *ea = entry_of(a, "emulate_sensitivity"), *eb = b ? entry_of(b, "emulate_sensitivity") : ea;
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(ea->ctx, (3 + 2 * (size_t)ea->d) * sizeof(double), &dev);
+	if (!rc) rc = gpemu_sens_cov_dev(ea->ctx, eb->ctx, lo, hi, (double *)dev);
+	if (rc && dev) (void)gpemu_dev_free(ea->ctx, dev);
+	check(ea, rc, "emulate_sensitivity");
+	*dev_out = dev;
+}
+
+void emulate_sensitivity_collect(emulator_struct *a, void *dev, double *e0, double *cov_all, double *cov_first, double *cov_rest)
+{
+	struct entry *en = entry_of(a, "emulate_sensitivity");
+	const size_t d = (size_t)en->d;
+	double *o = (double *)malloc(sizeof(double) * (3 + 2 * d));
+	int rc = gpemu_dev_download(en->ctx, o, dev, (3 + 2 * d) * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	if (!rc) {
+		e0[0] = o[0];
+		e0[1] = o[1];
+		*cov_all = o[2];
+		memcpy(cov_first, o + 3, sizeof(double) * d);
+		memcpy(cov_rest, o + 3 + d, sizeof(double) * d);
+	}
+	free(o);
+	check(en, rc, "emulate_sensitivity");
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

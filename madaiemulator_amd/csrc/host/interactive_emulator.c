@@ -32,8 +32,8 @@
 struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
-	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile;
-	int folds, foldsGiven;
+	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile;
+	int folds, foldsGiven, grid;
 };
 
 static const char useage[] =
@@ -57,6 +57,12 @@ static const char useage[] =
 	"  interactive_emulator validate MODEL_SNAPSHOT_FILE --groups=FILE [--pca_output] [--quiet]  (leave-group-out: FILE holds one\n"
 	"      integer per training point, the group it is left out with, 0 .. number of groups - 1, or -1 for never)\n"
 	"  --holdout, --folds and --groups exclude each other.\n"
+	"or\n"
+	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--pca_output] [--quiet]  (main effects and Sobol\n"
+	"      indices of the posterior mean, in closed form, for independent uniform inputs on a box: FILE holds one line \"lo hi\" per\n"
+	"      parameter, default the range of the design.  Per output one line: variance, the first-order indices, the total\n"
+	"      indices (NaN where the variance is 0); with --grid=G then, per output and parameter, the main-effect curve on G equally\n"
+	"      spaced values, followed by the mean.  Power-exponential covariance only)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -383,6 +389,83 @@ static int validate_lgo(struct cmdLineOpts *o)
 	return 0;
 }
 
+/* Sensitivity analysis of a trained snapshot (the reference's counterpart is the R code of src/libSA; here in closed form over a
+ * box, emulate_sensitivity_multi): which parameter an output depends on, and how strongly.  stdout, per output, one line
+ * "variance S_0 .. S_{d-1} T_0 .. T_{d-1}" -- S_j = V_j / V the first-order and T_j = VT_j / V the total-effect index, NaN where
+ * V = 0 --; with --grid=G then, per output, d lines of G values each, E[output | x_j = lo_j + g (hi_j - lo_j) / (G - 1)] (G = 1:
+ * the centre of the box), followed by a line holding E0. */
+static int sensitivity(struct cmdLineOpts *o)
+{
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	const int d = model->nparams, nt = model->nt, N = model->nmodel_points, G = o->grid;
+	const int nout = o->pcaOutputFlag ? model->nr : nt;
+	if (model->cov_fn_index > 1) return perr("sensitivity: the closed form exists for the power-exponential covariance only");
+	if (G < 0) return perr("--grid=G needs G >= 1");
+	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
+	if (o->boxfile) {
+		FILE *bf = fopen(o->boxfile, "r");
+		if (!bf) return perr("Error opening the box file");
+		for (int j = 0; j < d; j++)
+			if (fscanf(bf, "%lf %lf", &lo[j], &hi[j]) != 2 || !(hi[j] > lo[j])) {
+				fprintf(stderr, "the box file needs %d lines \"lo hi\" with lo < hi, one per parameter\n", d);
+				return EXIT_FAILURE;
+			}
+		fclose(bf);
+	} else {
+		for (int j = 0; j < d; j++) {
+			lo[j] = hi[j] = gsl_matrix_get(model->xmodel, 0, j);
+			for (int i = 1; i < N; i++) {
+				const double x = gsl_matrix_get(model->xmodel, i, j);
+				if (x < lo[j]) lo[j] = x;
+				if (x > hi[j]) hi[j] = x;
+			}
+			if (!(hi[j] > lo[j])) {
+				fprintf(stderr, "parameter %d does not vary over the design: give a box with --box=FILE\n", j);
+				return EXIT_FAILURE;
+			}
+		}
+	}
+	multi_emulator *emu = alloc_multi_emulator(model);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "%d\n", d);
+		for (int j = 0; j < d; j++) fprintf(out, "%s%d %.17g %.17g\n", "param_", j, lo[j], hi[j]);
+		fprintf(out, "%d\n", nout);
+	}
+	double *e0 = (double *)malloc(sizeof(double) * (size_t)nout), *var = (double *)malloc(sizeof(double) * (size_t)nout);
+	double *first = (double *)malloc(sizeof(double) * (size_t)nout * d), *total = (double *)malloc(sizeof(double) * (size_t)nout * d);
+	emulate_sensitivity_multi(emu, o->pcaOutputFlag, lo, hi, e0, var, first, total);
+	for (int t = 0; t < nout; t++) {
+		fprintf(out, "%.17g", var[t]);
+		for (int j = 0; j < d; j++) fprintf(out, " %.17g", var[t] != 0.0 ? first[(size_t)t * d + j] / var[t] : NAN);
+		for (int j = 0; j < d; j++) fprintf(out, " %.17g", var[t] != 0.0 ? total[(size_t)t * d + j] / var[t] : NAN);
+		fprintf(out, "\n");
+	}
+	if (G > 0) {
+		double *grid = (double *)malloc(sizeof(double) * (size_t)d * G), *mainv = (double *)malloc(sizeof(double) * (size_t)d * G * nout);
+		for (int j = 0; j < d; j++)
+			for (int g = 0; g < G; g++) grid[(size_t)j * G + g] = G > 1 ? lo[j] + g * (hi[j] - lo[j]) / (G - 1) : 0.5 * (lo[j] + hi[j]);
+		emulate_main_effects_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv);
+		for (int t = 0; t < nout; t++) {
+			for (int j = 0; j < d; j++) {
+				for (int g = 0; g < G; g++) fprintf(out, "%s%.17g", g ? " " : "", mainv[((size_t)j * G + g) * nout + t]);
+				fprintf(out, "\n");
+			}
+			fprintf(out, "%.17g\n", e0[t]);
+		}
+		free(grid); free(mainv);
+	}
+	fflush(out);
+	free(lo); free(hi); free(e0); free(var); free(first); free(total);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static int print_thetas(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -432,6 +515,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"holdout", required_argument, NULL, 1004},
 		/* ... or by K folds / by groups read from a file, every group left out as a whole */
 		{"folds", required_argument, NULL, 1005},             {"groups", required_argument, NULL, 1006},
+		/* sensitivity: the box of the input measure, the number of main-effect values per parameter */
+		{"box", required_argument, NULL, 1007},               {"grid", required_argument, NULL, 1008},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -457,6 +542,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1004: o->holdoutfile = optarg; break;
 		case 1005: o->folds = atoi(optarg); o->foldsGiven = 1; break;
 		case 1006: o->groupsfile = optarg; break;
+		case 1007: o->boxfile = optarg; break;
+		case 1008: o->grid = atoi(optarg); if (o->grid < 1) o->grid = -1; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
@@ -487,6 +574,7 @@ int main(int argc, char **argv)
 	else if (!strcmp(o->run_mode, "interactive_mode")) rc = interactive_mode(o);
 	else if (!strcmp(o->run_mode, "print_thetas")) rc = print_thetas(o);
 	else if (!strcmp(o->run_mode, "validate")) rc = validate(o);
+	else if (!strcmp(o->run_mode, "sensitivity")) rc = sensitivity(o);
 	else { free(o); return perr(useage); }
 	free(o);
 	return rc;

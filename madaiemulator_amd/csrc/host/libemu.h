@@ -303,6 +303,19 @@ void emulate_lgo(emulator_struct *e, int ngroups, const int *group, double *mean
 void emulate_lgo_enqueue(emulator_struct *e, int ngroups, const int *group, void **dev_out);
 void emulate_lgo_collect(emulator_struct *e, void *dev, int ngroups, double *mean, double *variance, double *werr, double *maha,
                          double *logpdf);
+/* extension: main effects and Sobol indices of the posterior mean in closed form (gpemu_sens_cov / gpemu_sens_main in gpemu.h;
+ * the reference's counterpart is the R code of src/libSA/sa-fns.R, which integrates against a Gaussian input measure -- this
+ * integrates over the box [lo_l, hi_l], independent uniform inputs).  Power-exponential covariance only.  lo, hi: nparams each.
+ * emulate_sensitivity: *e0 = E[m], *var = V = Var(m), first[j] = V_j = Var(E[m | x_j]), total[j] = VT_j = V - Var(E[m | x_-j])
+ * (nparams each; the indices are first[j] / V and total[j] / V).  emulate_main_effects: *e0 and main[j * ngrid + g] =
+ * E[m | x_j = grid[j * ngrid + g]], row j of grid holding the values of x_j.  A Matern model, a bad box: gpemu_host_fatal. */
+void emulate_sensitivity(emulator_struct *e, const double *lo, const double *hi, double *e0, double *var, double *first, double *total);
+void emulate_main_effects(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main);
+/* the covariances behind emulate_sensitivity in two halves, for one emulator (b = a or NULL) or for two on the same design:
+ * gpemu_sens_cov_dev is enqueued on a's stream, *dev_out is the device buffer the results wait in; collect returns e0[2] (E0 of
+ * a, of b), *cov_all = Cov(m^a, m^b), cov_first[j] = Cov(E[m^a | x_j], E[m^b | x_j]), cov_rest[j] = Cov(E[m^a | x_-j], E[m^b | x_-j]) */
+void emulate_sensitivity_enqueue(emulator_struct *a, emulator_struct *b, const double *lo, const double *hi, void **dev_out);
+void emulate_sensitivity_collect(emulator_struct *a, void *dev, double *e0, double *cov_all, double *cov_first, double *cov_rest);
 
 /* ---- multi_modelstruct.h / multivar_support.h ---------------------------------- */
 multi_modelstruct *alloc_multimodelstruct(gsl_matrix *xmodel_in, gsl_matrix *training_matrix_in, int cov_fn_index,
@@ -366,6 +379,20 @@ void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, dou
  * maha_out, logpdf_out (may be NULL): nr x ngroups, component-major, in PCA space only, as for the hold-out mode */
 void emulate_lgo_multi(multi_emulator *emu, int pca_space, int ngroups, const int *group, double *mean_out, double *var_out,
                        double *maha_out, double *logpdf_out);
+/* extension: sensitivity analysis of a multi-output emulator over the box [lo, hi].  Outputs per output (nr in PCA space, nt in
+ * observable space): e0_out, var_out one value each; first_out, total_out nparams values each, output-major.  In PCA space the
+ * components are analysed one by one.  In observable space y_t = training_mean[t] + sum_c B_tc m_c with B_tc = evecs[t][c]
+ * sqrt(evals[c]), and the components are NOT independent under the input measure (they are functions of the same x), so
+ *   Var_u(y_t) = sum_{c,c'} B_tc B_tc' cov_u(c, c'):
+ * all nr (nr + 1) / 2 pairs of components are analysed (two device contexts each), every pair started before the first is
+ * collected, and contracted on the host.  The squared rule of gpemu_host_backproject (sum_c B_tc^2 var_c) is for the emulator's
+ * posterior uncertainty, where the components ARE independent; here it would drop every cross term. */
+void emulate_sensitivity_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *e0_out, double *var_out,
+                               double *first_out, double *total_out);
+/* main-effect curves of every output: main_out is (nparams x ngrid) x (nr or nt), element ((j * ngrid + g) * nout + t); e0_out
+ * nr or nt values.  Observable space by the mean half of the rule (linear in the components), training mean added. */
+void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
+                                double *e0_out, double *main_out);
 
 /* ---- libRbind/rbind.h: the batched likelihood entry point, R-free (rbind.c:626-724) ---------------- */
 void callEvalLhoodList(double *xmodel_in, int *nparams_in, double *pointList_in, int *nevalPoints_in,

@@ -698,6 +698,84 @@ void emulate_lgo_multi(multi_emulator *emu, int pca_space, int ngroups, const in
 	free(mp); free(vp); free(mc); free(vc); free(dev);
 }
 
+/* Sensitivity analysis of every output over the box [lo, hi] (libemu.h).  PCA space: component c against itself, nr calls.
+ * Observable space: y_t = training_mean[t] + sum_c B_tc m_c, B_tc = evecs[t][c] sqrt(evals[c]).  The components are functions of
+ * the SAME inputs, so under the input measure they are correlated and every conditional variance is the full quadratic form
+ *   Var_u(y_t) = sum_{c,c'} B_tc B_tc' cov_u(c, c')
+ * over all pairs: nr (nr + 1) / 2 device calls on two contexts each (cov_u is symmetric in the pair), all enqueued before the
+ * first is collected.  gpemu_host_backproject's squared rule, sum_c B_tc^2 var_c, is NOT used here: it is right for the
+ * emulator's posterior variance, where the components are independent random functions, and would drop every cross term of
+ * this one, where they are fixed functions of a random input. */
+void emulate_sensitivity_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *e0_out, double *var_out,
+                               double *first_out, double *total_out)
+{
+	const size_t nr = (size_t)emu->nr, nt = (size_t)emu->nt, d = (size_t)emu->nparams;
+	const size_t npair = pca_space ? nr : nr * (nr + 1) / 2, w = 1 + 2 * d;
+	void **dev = (void **)malloc(sizeof(void *) * npair);
+	double *cv = doubles(npair * w), *e0 = doubles(nr), both[2];
+	size_t k = 0;
+	for (size_t c = 0; c < nr; c++)
+		for (size_t c2 = c; c2 < (pca_space ? c + 1 : nr); c2++)
+			emulate_sensitivity_enqueue(emu->emu_struct_array[c], emu->emu_struct_array[c2], lo, hi, &dev[k++]);
+	k = 0;
+	for (size_t c = 0; c < nr; c++)
+		for (size_t c2 = c; c2 < (pca_space ? c + 1 : nr); c2++, k++) {
+			/* row k: cov_all, cov_first[d], cov_rest[d] of the pair */
+			emulate_sensitivity_collect(emu->emu_struct_array[c], dev[k], both, cv + k * w, cv + k * w + 1, cv + k * w + 1 + d);
+			if (c2 == c) e0[c] = both[0];
+		}
+	if (pca_space) {
+		for (size_t c = 0; c < nr; c++) {
+			e0_out[c] = e0[c];
+			var_out[c] = cv[c * w];
+			for (size_t j = 0; j < d; j++) {
+				first_out[c * d + j] = cv[c * w + 1 + j];
+				total_out[c * d + j] = cv[c * w] - cv[c * w + 1 + d + j];
+			}
+		}
+	} else {
+		double *acc = doubles(w);
+		for (size_t t = 0; t < nt; t++) {
+			for (size_t i = 0; i < w; i++) acc[i] = 0.0;
+			double m = 0.0;
+			k = 0;
+			for (size_t c = 0; c < nr; c++) {
+				const double bc = gsl_matrix_get(emu->model->pca_evecs_r, t, c) * sqrt(gsl_vector_get(emu->model->pca_evals_r, c));
+				m += bc * e0[c];
+				for (size_t c2 = c; c2 < nr; c2++, k++) {
+					const double b2 = gsl_matrix_get(emu->model->pca_evecs_r, t, c2) * sqrt(gsl_vector_get(emu->model->pca_evals_r, c2));
+					const double f = (c2 == c ? 1.0 : 2.0) * bc * b2;
+					for (size_t i = 0; i < w; i++) acc[i] += f * cv[k * w + i];
+				}
+			}
+			e0_out[t] = gsl_vector_get(emu->model->training_mean, t) + m;
+			var_out[t] = acc[0];
+			for (size_t j = 0; j < d; j++) {
+				first_out[t * d + j] = acc[1 + j];
+				total_out[t * d + j] = acc[0] - acc[1 + d + j];
+			}
+		}
+		free(acc);
+	}
+	free(dev); free(cv); free(e0);
+}
+
+/* main-effect curves of every output: the components one after the other (gpemu_sens_main waits for its result), then the mean
+ * half of the rule -- a conditional mean is linear in the components -- with the training mean added */
+void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
+                                double *e0_out, double *main_out)
+{
+	const size_t nr = (size_t)emu->nr, np = (size_t)emu->nparams * (size_t)(ngrid > 0 ? ngrid : 0);
+	double *mp = doubles(np * nr), *mc = doubles(np), *ep = doubles(nr);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_main_effects(emu->emu_struct_array[c], lo, hi, ngrid, grid, &ep[c], mc);
+		place_component(mp, mc, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, main_out);
+	deliver(emu, pca_space, 0, 1, 1, 1, ep, e0_out);
+	free(mp); free(mc); free(ep);
+}
+
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
 	const int n = pca_space ? emu->nr : emu->nt;
