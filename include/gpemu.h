@@ -416,7 +416,7 @@ int gpemu_lgo_release(gpemu_ctx *ctx);
  * squared-exponential emulator with a (1, x) regression).  One difference in the measure: the reference integrates against a
  * GAUSSIAN input measure, this integrates over a BOX -- independent uniform inputs on [lo_l, hi_l], the caller's box, which
  * may be narrower than the design or leave design points outside.  This is the plug-in analysis of the posterior mean; the
- * emulator-uncertainty terms of Oakley-O'Hagan are not computed.
+ * emulator-uncertainty terms of Oakley-O'Hagan are gpemu_sens_post's and gpemu_sens_main_var's, below.
  * The function analysed is the one gpemu_predict_mean evaluates, for the power-exponential covariance, without the k-vector
  * clamp:   m(x) = beta_0 + sum_l q_l(x_l) + A sum_i gamma_i prod_l k_l(x_il, x_l),   q_l(x) = sum_{p=1..order} beta_{p,l} x^p,
  * k_l(a, x) = exp(-s_l (x - a)^2 / 2), s_l = exp(-2 theta_{2+l}), A the amplitude of the k-vector.  The nugget rule acts on a
@@ -455,6 +455,44 @@ int gpemu_sens_cov_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const doubl
 int gpemu_sens_main(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid /* d*ngrid host: row j = values of x_j */,
                     double *e0, double *main /* d*ngrid: E[m | x_j = grid[j][g]] */);
 int gpemu_sens_release(gpemu_ctx *ctx);
+
+/* ---- emulator uncertainty of the main effects and Sobol indices, in closed form -----------------
+ * The entries above analyse the posterior MEAN.  These add what the emulator does not know: the terms the reference's
+ * src/libSA/trivial-test-2.R evaluates per point of a main-effect curve and plots as a confidence band.  f is the posterior
+ * process with mean m and covariance (no k-vector clamp, and no nugget anywhere: it is jitter, not part of the function)
+ *   c*(x, x') = c(x, x') - k(x)^T C^-1 k(x') + r(x)^T Q r(x'),   r(x) = h(x) - W^T k(x),  W = C^-1 H,  Q = (H^T C^-1 H)^-1.
+ * For a set u of coordinates, S_u = E_{x_u} Var*[E[f | x_u]]: c* integrated over the box with the coordinates of u shared
+ * between x and x' and the others independent.  gpemu_sens_post returns
+ *   s_none       S for u empty: Var*[E0], the posterior variance of the overall mean
+ *   s_all        S for u = all: the box average of the posterior variance of f (the IMSE of the design); the box average of
+ *                gpemu_predict_batch's variance minus the nugget, up to the clamp
+ *   s_first[j]   S for u = {j}          s_rest[j]   S for u = all but j
+ * with s_none <= s_first[j], s_rest[j] <= s_all (Jensen).  With V, V_j = cov_first[j], VT_j = V - cov_rest[j] of
+ * gpemu_sens_cov(ctx, ctx), the posterior expectations of the variances of f itself are
+ *   E*[V] = V + s_all - s_none,   E*[V_j] = V_j + s_first[j] - s_none,   E*[VT_j] = VT_j + s_all - s_rest[j].
+ * One context: the PCA components of a multi-output emulator are independent a posteriori, there is no cross case.
+ * gpemu_sens_main_var returns, per grid value, var[j*ngrid + g] = Var*[E[f | x_j = grid[j*ngrid + g]]], the curve itself
+ * (main, as gpemu_sens_main's to rounding) and var_e0 = Var*[E0] (s_none to rounding).
+ * How gpemu_sens_post runs, on the context's stream: the per-point tables of gpemu_sens_cov; the corner C^-1 = U U^T that
+ * gpemu_get_cinverse caches (built once per set-up; 2 N^3 / 3 flops the first time, read only); a launch that writes G = W Q
+ * and P = C^-1 - G W^T on the lower 64 x 64 tiles; the pair sweep of gpemu_sens_cov over the LOWER tiles, every pair term
+ * weighted by its element of P in place of gamma_i gamma_i', 2 d + 2 partial sums per tile; the finish.  Memory: 8 (N'^2 +
+ * N nreg + T') bytes besides the tables and the corner, N' = N rounded up to 64, T' = ceil(N/64) (ceil(N/64) + 1) / 2 (2 d + 2).
+ * gpemu_sens_main_var: the tables, d ngrid + 1 rows T_i = A k_j(x_ij, x) Pex_j(i) into the prediction's k-vector buffer, the
+ * prediction's product with [L^-1; gamma; W^T] (K never split), a finish with T for the k-vector and E[h | x_j = x] for h.
+ * It uses the prediction batch buffers in stream order, as gpemu_predict_cov_dev does; a pending prediction batch stays
+ * collectable.  No atomics, no workgroup waits for another; two calls return the same bits, so do the host and _dev entries and
+ * a context set up by gpemu_predict_setup_batch (a later component of such a batch factors alone first, as for
+ * gpemu_get_cinverse).  gpemu_sens_release frees these entries' buffers too.
+ * Errors as for gpemu_sens_cov, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL pointer (main and var_e0
+ * may be NULL) and ngrid < 1; GPEMU_ERR_STATE without a prediction set-up; GPEMU_ERR_ARG for a Matern model, a non-finite
+ * bound or hi_l <= lo_l. */
+int gpemu_sens_post(gpemu_ctx *ctx, const double *lo, const double *hi /* d each, host */,
+                    double *s_none, double *s_all, double *s_first /* d */, double *s_rest /* d */);
+int gpemu_sens_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HOST */,
+                        double *out_dev /* 2 + 2 d: s_none, s_all, first[d], rest[d] */);
+int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid /* d*ngrid host */,
+                        double *main /* d*ngrid, may be NULL */, double *var /* d*ngrid */, double *var_e0 /* may be NULL */);
 
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
@@ -505,6 +543,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_JOINT   12  /* the staging and clean launches of gpemu_predict_joint_factor[_dev] (bytes = 8*(64 M' + 2 M) and 4*M'*M', M' = M rounded up to 64) and the staging launch of every block of gpemu_predict_joint_draw[_dev] (bytes = 8*ndraw*(M' + 2 M)); the sweep, the products and the factorisation report under GPEMU_PROF_FILL / _COV / _GEMM / _LEAF / _POTRF */
 #define GPEMU_PROF_LGO     13  /* the three launches per chunk of gpemu_lgo[_dev], nbc groups padded to bp: gather (bytes = 8 nbc bp Np: the rows of Z written; it reads at most the lower tiles of L^-1 besides), staging (bytes = 8 nbc bp (2 bp + 64): the lower tiles read and written, right-hand-side and identity rows written), finish (bytes = 8 nbc bp (bp / 2 + 4)); the product and the factorisation report under GPEMU_PROF_GEMM / _LEAF / _POTRF */
 #define GPEMU_PROF_SENS    14  /* the three launches of gpemu_sens_cov[_dev] -- prep (flops = 88 N d: both contexts, two erf and two exp per point and coordinate counted as one flop each; bytes = 8 (10 N d + N d): the tables written, the design read), sweep (flops = N^2 (19 d + 2): per pair and coordinate one exp and two erf or erfc counted as one flop each among 16 others, then the 2 d + 1 sums; bytes = 8 T: the T = ceil(N / 64)^2 (2 d + 1) partial sums written), finish (flops = T, bytes = 8 T) -- and the two of gpemu_sens_main: prep, curves (flops = 6 N d ngrid, bytes = 16 d ngrid) */
+#define GPEMU_PROF_SENS_POST 15 /* the four launches of gpemu_sens_post[_dev], L = n (n + 1) / 2 lower tiles with n = ceil(N / 64) -- prep (as GPEMU_PROF_SENS), pmat (flops = L (128 nreg^2 + 4096 (2 nreg + 1)): G for the tile's 64 rows, then a product of length nreg per pair; bytes = 8 * 8192 L: the corner's tile read, P's written), weighted sweep (flops = 4096 L (20 d + 3): the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; bytes = 8 (4096 L + T'), T' = L (2 d + 2): P read, the partial sums written), finish (flops = T' + (2 d + 2) nreg (2 nreg + 4 N), bytes = 8 (T' + (2 d + 2) 3 N nreg)) -- and of gpemu_sens_main_var: prep, then per block of mb rows tvec (flops = 6 mb N, bytes = 8 mb' Np, mb' = mb rounded up to 64) and band finish (flops = mb (2 Np + 2 nreg^2), bytes = 8 mb (Np + 64)); the corner and the band's product report under GPEMU_PROF_GEMM */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 
@@ -756,6 +795,9 @@ int gpemu_test_resident_launch(gpemu_ctx *ctx, const gpemu_resident_launch_args 
  * a few ulp (the closed-form sensitivity entries): their reference must start from these two vectors, since another
  * factorisation's gamma differs from the device's by far more than that.  GPEMU_ERR_STATE without a prediction set-up. */
 int gpemu_test_pred_state(gpemu_ctx *ctx, double *beta, double *gamma);
+/* the same for gpemu_sens_post: P = C^-1 - W Q W^T (N*N, both triangles), G = W Q (N*nreg) and Q (nreg*nreg), bit for bit what
+ * the last call's weighted sweep and finish multiplied by.  GPEMU_ERR_STATE before the first gpemu_sens_post of a model. */
+int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P /* N*N, both triangles */, double *G /* N*nreg */, double *Q /* nreg*nreg */);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

@@ -23,6 +23,7 @@ PROF_COV = 11
 PROF_JOINT = 12
 PROF_LGO = 13
 PROF_SENS = 14
+PROF_SENS_POST = 15
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 RESULT_RING = 4
 
@@ -149,6 +150,10 @@ SYMBOLS = {
     "gpemu_sens_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_main": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp]),
     "gpemu_sens_release": (C.c_int, [C.c_void_p]),
+    "gpemu_sens_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpemu_sens_post_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p]),
+    "gpemu_sens_main_var": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpemu_test_sens_post_state": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -503,6 +508,38 @@ class Context:
 
     def sens_release(self):
         self._chk(self.L.gpemu_sens_release(self.h))
+
+    # emulator uncertainty of the same quantities: S_u = E Var*[E[f | x_u]] of the posterior process f
+    def sens_post(self, lo, hi):
+        """-> dict(s_none, s_all, s_first[d], s_rest[d])"""
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_post: one bound pair per coordinate")
+        sn, sa, sf, sr = np.empty(1), np.empty(1), np.empty(self.d), np.empty(self.d)
+        self._chk(self.L.gpemu_sens_post(self.h, _p(lo), _p(hi), _p(sn), _p(sa), _p(sf), _p(sr)))
+        return dict(s_none=sn[0], s_all=sa[0], s_first=sf, s_rest=sr)
+
+    def sens_post_dev(self, lo, hi, out_dev):
+        """lo, hi: HOST bounds; out_dev: 2 + 2 d doubles on the device (s_none, s_all, first[d], rest[d])"""
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_post_dev: one bound pair per coordinate")
+        self._chk(self.L.gpemu_sens_post_dev(self.h, _p(lo), _p(hi), out_dev))
+
+    def sens_main_var(self, lo, hi, grid):
+        """grid[j][g]: values of x_j (d rows) -> (main[d, G], var[d, G], var_e0): the curves, Var*[E[f | x_j = grid[j][g]]], Var*[E0]"""
+        lo, hi, grid = _a(lo).ravel(), _a(hi).ravel(), _a(grid).reshape(self.d, -1)
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_main_var: one bound pair per coordinate")
+        main, var, ve0 = np.empty(grid.shape), np.empty(grid.shape), np.empty(1)
+        self._chk(self.L.gpemu_sens_main_var(self.h, _p(lo), _p(hi), grid.shape[1], _p(grid), _p(main), _p(var), _p(ve0)))
+        return main, var, ve0[0]
+
+    def sens_post_state(self):
+        """-> (P[N, N], G[N, nreg], Q[nreg, nreg]) bit for bit as the last sens_post read them (parity tests)"""
+        P, G, Q = np.empty((self.N, self.N)), np.empty((self.N, self.nreg)), np.empty((self.nreg, self.nreg))
+        self._chk(self.L.gpemu_test_sens_post_state(self.h, _p(P), _p(G), _p(Q)))
+        return P, G, Q
 
     def pred_state(self):
         """-> (beta[nreg], gamma[N]) bit for bit as the prediction state holds them (parity tests)"""

@@ -272,7 +272,10 @@ static void free_model(gpemu_ctx *ctx)
 	for (auto *b : {&ctx->dLgoZ, &ctx->dLgoT, &ctx->dLgoPart, &ctx->dLgoOut}) b->reset();
 	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
 	ctx->hLgoTab.reset();
-	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid}) b->reset();
+	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid, &ctx->dSensP, &ctx->dSensG,
+	                &ctx->dSensPostPart})
+		b->reset();
+	ctx->sens_post_N = 0;
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -2190,14 +2193,14 @@ static int sens_order_streams(gpemu_ctx *a, gpemu_ctx *b)
 	return GPEMU_OK;
 }
 
-static int sens_prep(gpemu_ctx *a, const SensBox &bx)
+static int sens_prep(gpemu_ctx *a, const SensBox &bx, int cls = GPEMU_PROF_SENS)
 {
 	const int N = a->N, d = a->d;
 	int rc = grow(a, a->dSensPrep, sens_prep_elems(N, d));
 	if (!rc) rc = grow(a, a->dSensCst, (size_t)SENS_CST * GPEMU_MAX_PARAMS);
 	if (rc) return rc;
 	// per point and coordinate of either context two erf and two exp with some forty flops around them; the tables out
-	ProfScope ps(a, GPEMU_PROF_SENS, 2.0 * N * d * 44.0, 8.0 * ((double)sens_prep_elems(N, d) + (double)N * d));
+	ProfScope ps(a, cls, 2.0 * N * d * 44.0, 8.0 * ((double)sens_prep_elems(N, d) + (double)N * d));
 	HIPCHK(a, launch_sens_prep(a->stream, a->dX, N, bx, a->dSensPrep, a->dSensCst));
 	return GPEMU_OK;
 }
@@ -2284,7 +2287,10 @@ extern "C" int gpemu_sens_release(gpemu_ctx *ctx)
 	if (!ctx) return GPEMU_ERR_ARG;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid}) b->reset();
+	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid, &ctx->dSensP, &ctx->dSensG,
+	                &ctx->dSensPostPart})
+		b->reset();
+	ctx->sens_post_N = 0;
 	return GPEMU_OK;
 }
 
@@ -2321,11 +2327,10 @@ static hipError_t build_corner(gpemu_ctx *ctx, const Tall &t, double *S, long ld
 	return gemm(ctx, g);
 }
 
-extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
+// the corner of a context with a prediction set-up, in dS (side and leading dimension S_dim), built once per set-up
+// (gpemu_get_cinverse and gpemu_sens_post)
+static int ensure_corner(gpemu_ctx *ctx)
 {
-	if (!ctx || !cinv_out) return GPEMU_ERR_ARG;
-	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
-	HIPCHK(ctx, hipSetDevice(ctx->device));
 	if (!ctx->cinv_ready && !ctx->fact_in_T) {
 		// set up by gpemu_predict_setup_batch as a later component: its factorisation ran in the first context's workspace
 		// (round 5: reading this context's own, never allocated workspace here was a GPU memory fault).  The explicit inverse is
@@ -2343,6 +2348,15 @@ extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
 		HIPCHK(ctx, build_corner(ctx, tall_of(ctx), ctx->dS, (long)dim));
 		ctx->cinv_ready = true;
 	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
+{
+	if (!ctx || !cinv_out) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (const int rc = ensure_corner(ctx)) return rc;
 	const int N = ctx->N, Rp = ctx->Rp;
 	const size_t dim = ctx->S_dim;
 	HIPCHK(ctx, hipMemcpy2DAsync(cinv_out, (size_t)N * sizeof(double), ctx->dS + (size_t)Rp * dim + Rp,
@@ -2354,6 +2368,132 @@ extern "C" int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out)
 		for (int j0 = i0; j0 < N; j0 += 64)
 			for (int i = i0; i < std::min(i0 + 64, N); i++)
 				for (int j = std::max(j0, i + 1); j < std::min(j0 + 64, N); j++) cinv_out[(size_t)i * N + j] = cinv_out[(size_t)j * N + i];
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// emulator uncertainty of the main effects and Sobol indices (gpemu.h).  gpemu_sens_post: prep, the corner
+// C^-1 = U U^T (built once per set-up, shared with gpemu_get_cinverse, read only), P and G from it, the weighted sweep over
+// the lower tiles, the finish.  Writes dSensPrep, dSensCst and its own dSensP, dSensG, dSensPostPart.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_sens_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi, double *out_dev)
+{
+	if (!ctx || !lo || !hi || !out_dev) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int N = ctx->N, d = ctx->d, nreg = ctx->nreg, Rp = ctx->Rp;
+	const size_t ldp = (size_t)round_up(N, 64), npart = sens_post_part_elems(N, d);
+	const double ntl = (double)(ldp / 64) * (double)(ldp / 64 + 1) / 2.0;           // lower tiles
+	int rc = grow(ctx, ctx->dSensPostPart, npart);
+	if (!rc) rc = grow(ctx, ctx->dSensP, ldp * ldp);
+	if (!rc) rc = grow(ctx, ctx->dSensG, (size_t)N * nreg);
+	if (rc) return rc;
+	if (prof_on(ctx, GPEMU_PROF_SENS_POST))
+		for (const char *t : {"sens_prep", "sens_pmat", "sens_sweep_weighted", "sens_post_finish"}) ctx->prof.tag.push_back(t);
+	if ((rc = sens_prep(ctx, bx, GPEMU_PROF_SENS_POST))) return rc;
+	if ((rc = ensure_corner(ctx))) return rc;
+	const double *Q = ctx->dBetaQ + nreg;
+	{
+		// per tile: G for its 64 rows (2 nreg^2 each), then 2 nreg + 1 per pair; the corner's tile read, P's written
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * (128.0 * nreg * nreg + 4096.0 * (2.0 * nreg + 1.0)), 8.0 * ntl * 8192.0);
+		HIPCHK(ctx, launch_sens_pmat(ctx->stream, ctx->dS, (long)ctx->S_dim, Rp, Q, N, nreg, ctx->dSensG, ctx->dSensP));
+	}
+	{
+		// the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; P read, the sums written
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (20.0 * d + 3.0), 8.0 * (ntl * 4096.0 + (double)npart));
+		HIPCHK(ctx, launch_sens_sweep_weighted(ctx->stream, ctx->dX, N, d, ctx->dSensPrep, ctx->dSensCst, ctx->dSensP, ctx->dSensPostPart));
+	}
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, (double)npart + (2.0 * d + 2.0) * nreg * (2.0 * nreg + 4.0 * N),
+		             8.0 * ((double)npart + (2.0 * d + 2.0) * 3.0 * N * nreg));
+		HIPCHK(ctx, launch_sens_post_finish(ctx->stream, ctx->dSensPostPart, N, d, ctx->order, nreg, ctx->pred_cov.amp, ctx->dSensPrep,
+		                                    ctx->dSensCst, ctx->dSensG, Q, out_dev));
+	}
+	ctx->sens_post_N = N;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_post(gpemu_ctx *ctx, const double *lo, const double *hi, double *s_none, double *s_all, double *s_first,
+                               double *s_rest)
+{
+	if (!ctx || !lo || !hi || !s_none || !s_all || !s_first || !s_rest) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t d = (size_t)ctx->d;
+	if (const int rc = grow(ctx, ctx->dSensOut, 3 + 2 * (size_t)GPEMU_MAX_PARAMS)) return rc;
+	if (const int rc = gpemu_sens_post_dev(ctx, lo, hi, ctx->dSensOut)) return rc;
+	std::vector<double> o(2 + 2 * d);
+	HIPCHK(ctx, hipMemcpyAsync(o.data(), ctx->dSensOut, o.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*s_none = o[0];
+	*s_all = o[1];
+	memcpy(s_first, o.data() + 2, d * sizeof(double));
+	memcpy(s_rest, o.data() + 2 + d, d * sizeof(double));
+	return GPEMU_OK;
+}
+
+// The confidence band of the main-effect curves: the prediction's variance formula with T for the k-vector.  Blocks of up to
+// PRED_BATCH_MAX of the d ngrid + 1 rows through dKq and dV in stream order, as gpemu_predict_cov_dev uses them; K is never
+// split (few rows take the same 64-row tiles, so a row's bits do not depend on ngrid).
+extern "C" int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid, double *main,
+                                   double *var, double *var_e0)
+{
+	if (!ctx || !lo || !hi || !grid || !var || ngrid < 1) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np, Rp = ctx->Rp;
+	const size_t ng = (size_t)d * ngrid, M = ng + 1;
+	const int cap = (int)std::min((size_t)PRED_BATCH_MAX, (M + 63) / 64 * 64);
+	int rc = grow(ctx, ctx->dSensGrid, ng + 2 * M);
+	if (!rc) rc = ensure_pred_batch(ctx, cap);
+	if (rc) return rc;
+	double *dgrid = ctx->dSensGrid, *dmain = dgrid + ng, *dvar = dmain + M;
+	HIPCHK(ctx, hipMemcpyAsync(dgrid, grid, ng * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (prof_on(ctx, GPEMU_PROF_SENS_POST)) ctx->prof.tag.push_back("sens_prep");
+	if ((rc = sens_prep(ctx, bx, GPEMU_PROF_SENS_POST))) return rc;
+	const long ldv = (long)Np + Rp;
+	for (size_t r0 = 0; r0 < M; r0 += cap) {
+		const int mb = (int)std::min((size_t)cap, M - r0), mbp = round_up(mb, 64);
+		if (prof_on(ctx, GPEMU_PROF_SENS_POST)) for (const char *t : {"sens_tvec", "sens_band_finish"}) ctx->prof.tag.push_back(t);
+		{
+			ProfScope ps(ctx, GPEMU_PROF_SENS_POST, 6.0 * mb * (double)N, 8.0 * (double)mbp * Np);
+			HIPCHK(ctx, launch_sens_tvec(ctx->stream, ctx->dX, N, Np, d, ctx->pred_cov.amp, ctx->dSensPrep, ctx->dSensCst, dgrid, ngrid,
+			                             (int)r0, mb, mbp, ctx->dKq));
+		}
+		HIPCHK(ctx, launch_aug_product(ctx, aug_product_args(ctx, mb)));
+		{
+			ProfScope ps(ctx, GPEMU_PROF_SENS_POST, (double)mb * (2.0 * Np + 2.0 * ctx->nreg * ctx->nreg), 8.0 * (double)mb * (double)ldv);
+			HIPCHK(ctx, launch_sens_band_finish(ctx->stream, ctx->dV, ldv, mb, (int)r0, Np, ctx->nreg, d, ngrid, ctx->dSensCst, dgrid,
+			                                    ctx->dBetaQ, ctx->pred_cov.amp, dmain, dvar));
+		}
+	}
+	if (main) HIPCHK(ctx, hipMemcpyAsync(main, dmain, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(var, dvar, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (var_e0) HIPCHK(ctx, hipMemcpyAsync(var_e0, dvar + ng, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// P (N x N, both triangles), G = W Q (N x nreg) and Q (nreg x nreg) exactly as the last gpemu_sens_post left and read them
+// (parity tests: the reference starts from the bits the weighted sweep and its finish multiply by)
+extern "C" int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P, double *G, double *Q)
+{
+	if (!ctx || !P || !G || !Q) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->sens_post_N != ctx->N || !ctx->dSensP) return fail(ctx, GPEMU_ERR_STATE, "gpemu_sens_post has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t N = (size_t)ctx->N, nreg = (size_t)ctx->nreg, ldp = (size_t)round_up(ctx->N, 64);
+	// row i' of the buffer holds P_ii' for every i of the tiles at and below its own: the upper triangle of the output
+	HIPCHK(ctx, hipMemcpy2DAsync(P, N * sizeof(double), ctx->dSensP, ldp * sizeof(double), N * sizeof(double), N, hipMemcpyDeviceToHost,
+	                             ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(G, ctx->dSensG, N * nreg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(Q, ctx->dBetaQ + nreg, nreg * nreg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	for (size_t i = 0; i < N; i++)
+		for (size_t j = i + 1; j < N; j++) P[j * N + i] = P[i * N + j];
 	return GPEMU_OK;
 }
 

@@ -316,6 +316,10 @@ struct gpemu_ctx {
 	// results of the host entry (and E0 of the main-effect entry), dSensGrid that entry's grid, then its curves; sens_ev: this
 	// context's stream behind the other context's pending work, sens_ev2: the other's stream behind this call
 	gpemu::DevBuf<double> dSensPrep, dSensCst, dSensPart, dSensOut, dSensGrid;
+	// gpemu_sens_post: dSensP the pair weights P = C^-1 - W Q W^T on the lower tiles (Np x Np), dSensG = W Q
+	// (N x nreg), dSensPostPart the weighted sweep's partial sums; sens_post_N: the N they were last written for (0: never)
+	gpemu::DevBuf<double> dSensP, dSensG, dSensPostPart;
+	int sens_post_N = 0;
 	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
@@ -481,5 +485,19 @@ hipError_t launch_sens_finish(hipStream_t s, const double *part, int N, int d, i
                               double *out);
 hipError_t launch_sens_main(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
                             const double *prep, const double *cst, const double *grid, int ngrid, double *e0, double *out);
+// emulator uncertainty.  S: the corner of gpemu_get_cinverse (leading dimension lds, C^-1 at (Rp, Rp), W in
+// columns 1 .. nreg); Pw: (N rounded up to 64)^2 doubles, Pw[i' * ldp + i] = P_ii' on the lower tiles; G: N x nreg; part:
+// sens_post_part_elems doubles, 2 d + 2 sums per lower tile; out: s_none, s_all, first[d], rest[d]
+size_t sens_post_part_elems(int N, int d);
+hipError_t launch_sens_pmat(hipStream_t s, const double *S, long lds, int Rp, const double *Q, int N, int nreg, double *G, double *Pw);
+hipError_t launch_sens_sweep_weighted(hipStream_t s, const double *X, int N, int d, const double *prep, const double *cst, const double *Pw,
+                                      double *part);
+hipError_t launch_sens_post_finish(hipStream_t s, const double *part, int N, int d, int order, int nreg, double amp, const double *prep,
+                                   const double *cst, const double *G, const double *Q, double *out);
+// the band: rows r0 .. r0 + mb of the d ngrid + 1 into Kq (mbp rows of Np); then the finish over V = Kq LinvAug^T
+hipError_t launch_sens_tvec(hipStream_t s, const double *X, int N, int Np, int d, double amp, const double *prep, const double *cst,
+                            const double *grid, int ngrid, int r0, int mb, int mbp, double *Kq);
+hipError_t launch_sens_band_finish(hipStream_t s, const double *V, long ldv, int mb, int r0, int Np, int nreg, int d, int ngrid,
+                                   const double *cst, const double *grid, const double *betaQ, double amp, double *main, double *var);
 
 } // namespace gpemu

@@ -171,6 +171,51 @@ void emulator::QueryEmulatorMainEffects(const std::vector<double> &lo, const std
 			for (size_t k = 0; k < G; k++) Curves[i][j][k] = m[(j * G + k) * no + i];
 }
 
+void emulator::QueryEmulatorSensitivityUncertainty(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<double> &MeanVariances,
+                                                   std::vector<double> &IntegratedVariances, std::vector<double> &ExpectedVariances,
+                                                   std::vector<std::vector<double> > &ExpectedFirstOrder,
+                                                   std::vector<std::vector<double> > &ExpectedTotal)
+{
+	check_box("QueryEmulatorSensitivityUncertainty", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params;
+	std::vector<double> f(no * d), t(no * d);
+	MeanVariances.assign(no, 0.0);
+	IntegratedVariances.assign(no, 0.0);
+	ExpectedVariances.assign(no, 0.0);
+	emulate_sensitivity_uncertainty_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), MeanVariances.data(),
+	                                      IntegratedVariances.data(), ExpectedVariances.data(), f.data(), t.data());
+	ExpectedFirstOrder.assign(no, std::vector<double>(d));
+	ExpectedTotal.assign(no, std::vector<double>(d));
+	for (size_t i = 0; i < no; i++)
+		for (size_t j = 0; j < d; j++) {
+			ExpectedFirstOrder[i][j] = f[i * d + j];
+			ExpectedTotal[i][j] = t[i * d + j];
+		}
+}
+
+void emulator::QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
+                                            std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,
+                                            std::vector<std::vector<std::vector<double> > > &Bands)
+{
+	check_box("QueryEmulatorMainEffectBands", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params, G = grid.empty() ? 0 : grid[0].size();
+	if (grid.size() != d || G < 1) {
+		std::cerr << "Error::QueryEmulatorMainEffectBands called with a grid that has not one non-empty row per parameter" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	std::vector<double> g = flatten("QueryEmulatorMainEffectBands", grid, (int)G), m(d * G * no), s(d * G * no);
+	Means.assign(no, 0.0);
+	emulate_main_effects_band_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), (int)G, g.data(), Means.data(), m.data(), s.data());
+	Curves.assign(no, std::vector<std::vector<double> >(d, std::vector<double>(G)));
+	Bands.assign(no, std::vector<std::vector<double> >(d, std::vector<double>(G)));
+	for (size_t i = 0; i < no; i++)
+		for (size_t j = 0; j < d; j++)
+			for (size_t k = 0; k < G; k++) {
+				Curves[i][j][k] = m[(j * G + k) * no + i];
+				Bands[i][j][k] = s[(j * G + k) * no + i];
+			}
+}
+
 double emulator::ValidateHoldout(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<double> > &Observations,
                                  std::vector<std::vector<double> > &Means, std::vector<std::vector<double> > &Variances,
                                  std::vector<std::vector<double> > &WhitenedErrors, std::vector<double> &Mahalanobis,

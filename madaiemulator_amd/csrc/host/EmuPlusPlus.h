@@ -67,6 +67,18 @@ public:
 	// Curves[t][j][g] = E[output t | x_j = grid[j][g]], Means[t] = E0
 	void QueryEmulatorMainEffects(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
 	                              std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves);
+	// the emulator's own uncertainty about that analysis (libemu.h: emulate_sensitivity_uncertainty_multi), in variance units, not
+	// divided by V.  Per output t: MeanVariances[t] = Var*[E0], IntegratedVariances[t] = the box average of the posterior variance,
+	// ExpectedVariances[t] = E*[V], ExpectedFirstOrder[t][j] = E*[V_j], ExpectedTotal[t][j] = E*[VT_j].  In observable space the
+	// uncertainty terms take the squared rule over the PCA components (independent a posteriori), the plug-in part its cross terms.
+	void QueryEmulatorSensitivityUncertainty(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<double> &MeanVariances,
+	                                         std::vector<double> &IntegratedVariances, std::vector<double> &ExpectedVariances,
+	                                         std::vector<std::vector<double> > &ExpectedFirstOrder,
+	                                         std::vector<std::vector<double> > &ExpectedTotal);
+	// QueryEmulatorMainEffects with Bands[t][j][g] = the posterior standard deviation of E[output t | x_j = grid[j][g]]
+	void QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
+	                                  std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,
+	                                  std::vector<std::vector<std::vector<double> > > &Bands);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -1271,6 +1271,52 @@ void emulate_sensitivity_collect(emulator_struct *a, void *dev, double *e0, doub
 	check(en, rc, "emulate_sensitivity");
 }
 
+/* the emulator-uncertainty terms of the same analysis (gpemu_sens_post / gpemu_sens_main_var in gpemu.h):
+ * s = S_none, S_all, S_first[d], S_rest[d] with S_u = E Var*[E[f | x_u]] of the posterior process f */
+void emulate_sensitivity_post(emulator_struct *e, const double *lo, const double *hi, double *s)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_post");
+	const size_t d = (size_t)en->d;
+	check(en, gpemu_sens_post(en->ctx, lo, hi, s, s + 1, s + 2, s + 2 + d), "emulate_sensitivity_post");
+}
+
+/* E*[V] = V + S_all - S_none, E*[V_j] = V_j + S_j - S_none, E*[VT_j] = VT_j + S_all - S_{-j}: one gpemu_sens_cov, one gpemu_sens_post */
+void emulate_sensitivity_uncertainty(emulator_struct *e, const double *lo, const double *hi, double *var_e0, double *imse, double *evar,
+                                     double *efirst, double *etotal)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_uncertainty");
+	const size_t d = (size_t)en->d;
+	double e0, var, *w = (double *)malloc(sizeof(double) * (4 * d + 2)), *first = w, *total = w + d, *s = w + 2 * d;
+	emulate_sensitivity(e, lo, hi, &e0, &var, first, total);
+	emulate_sensitivity_post(e, lo, hi, s);
+	*var_e0 = s[0];
+	*imse = s[1];
+	*evar = var + s[1] - s[0];
+	for (size_t j = 0; j < d; j++) {
+		efirst[j] = first[j] + s[2 + j] - s[0];
+		etotal[j] = total[j] + s[1] - s[2 + d + j];
+	}
+	free(w);
+}
+
+/* the curves of emulate_main_effects with var[j * ngrid + g] = Var*[E[f | x_j = grid[j * ngrid + g]]] and *var_e0 = Var*[E0] */
+void emulate_main_effects_var(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
+                              double *var, double *var_e0)
+{
+	struct entry *en = entry_of(e, "emulate_main_effects_band");
+	int rc = gpemu_sens_main(en->ctx, lo, hi, ngrid, grid, e0, main);
+	if (!rc) rc = gpemu_sens_main_var(en->ctx, lo, hi, ngrid, grid, NULL, var, var_e0);
+	check(en, rc, "emulate_main_effects_band");
+}
+
+void emulate_main_effects_band(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
+                               double *sd)
+{
+	emulate_main_effects_var(e, lo, hi, ngrid, grid, e0, main, sd, NULL);
+	const size_t n = (size_t)entry_of(e, "emulate_main_effects_band")->d * (size_t)(ngrid > 0 ? ngrid : 0);
+	for (size_t i = 0; i < n; i++) sd[i] = sqrt(sd[i] > 0.0 ? sd[i] : 0.0);
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

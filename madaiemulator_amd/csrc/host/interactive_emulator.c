@@ -33,7 +33,7 @@ struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
 	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile;
-	int folds, foldsGiven, grid;
+	int folds, foldsGiven, grid, uncertainty;
 };
 
 static const char useage[] =
@@ -58,11 +58,14 @@ static const char useage[] =
 	"      integer per training point, the group it is left out with, 0 .. number of groups - 1, or -1 for never)\n"
 	"  --holdout, --folds and --groups exclude each other.\n"
 	"or\n"
-	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--pca_output] [--quiet]  (main effects and Sobol\n"
+	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--uncertainty] [--pca_output] [--quiet]  (main effects and Sobol\n"
 	"      indices of the posterior mean, in closed form, for independent uniform inputs on a box: FILE holds one line \"lo hi\" per\n"
 	"      parameter, default the range of the design.  Per output one line: variance, the first-order indices, the total\n"
 	"      indices (NaN where the variance is 0); with --grid=G then, per output and parameter, the main-effect curve on G equally\n"
-	"      spaced values, followed by the mean.  Power-exponential covariance only)\n"
+	"      spaced values, followed by the mean.  --uncertainty adds the emulator's own uncertainty: after the index lines, per output\n"
+	"      one line with the posterior standard deviation of the mean, the box average of the posterior variance, the expected\n"
+	"      variance and the expected first-order and total indices; with --grid, under every curve a line with its posterior\n"
+	"      standard deviations.  Power-exponential covariance only)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -393,7 +396,12 @@ static int validate_lgo(struct cmdLineOpts *o)
  * box, emulate_sensitivity_multi): which parameter an output depends on, and how strongly.  stdout, per output, one line
  * "variance S_0 .. S_{d-1} T_0 .. T_{d-1}" -- S_j = V_j / V the first-order and T_j = VT_j / V the total-effect index, NaN where
  * V = 0 --; with --grid=G then, per output, d lines of G values each, E[output | x_j = lo_j + g (hi_j - lo_j) / (G - 1)] (G = 1:
- * the centre of the box), followed by a line holding E0. */
+ * the centre of the box), followed by a line holding E0.
+ * --uncertainty (emulate_sensitivity_uncertainty_multi, emulate_main_effects_band_multi): after those lines, per output, one line
+ * "sd(E0) IMSE E*[V] E*[V_0]/E*[V] .. E*[VT_0]/E*[V] .." -- the posterior standard deviation of the mean, the box average of the
+ * posterior variance, the expected variance of the emulated function and its expected first-order and total parts over it --;
+ * and with --grid=G every curve is followed by a line of G posterior standard deviations of its values.  Without the flag the
+ * output is what it was before the flag existed. */
 static int sensitivity(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -446,19 +454,37 @@ static int sensitivity(struct cmdLineOpts *o)
 		for (int j = 0; j < d; j++) fprintf(out, " %.17g", var[t] != 0.0 ? total[(size_t)t * d + j] / var[t] : NAN);
 		fprintf(out, "\n");
 	}
+	if (o->uncertainty) {
+		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
+		double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
+		emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
+		for (int t = 0; t < nout; t++) {
+			fprintf(out, "%.17g %.17g %.17g", sqrt(ve0[t] > 0.0 ? ve0[t] : 0.0), imse[t], evar[t]);
+			for (int j = 0; j < d; j++) fprintf(out, " %.17g", evar[t] != 0.0 ? ef[(size_t)t * d + j] / evar[t] : NAN);
+			for (int j = 0; j < d; j++) fprintf(out, " %.17g", evar[t] != 0.0 ? et[(size_t)t * d + j] / evar[t] : NAN);
+			fprintf(out, "\n");
+		}
+		free(ve0); free(ef);
+	}
 	if (G > 0) {
 		double *grid = (double *)malloc(sizeof(double) * (size_t)d * G), *mainv = (double *)malloc(sizeof(double) * (size_t)d * G * nout);
+		double *sdv = o->uncertainty ? (double *)malloc(sizeof(double) * (size_t)d * G * nout) : NULL;
 		for (int j = 0; j < d; j++)
 			for (int g = 0; g < G; g++) grid[(size_t)j * G + g] = G > 1 ? lo[j] + g * (hi[j] - lo[j]) / (G - 1) : 0.5 * (lo[j] + hi[j]);
-		emulate_main_effects_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv);
+		if (sdv) emulate_main_effects_band_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv, sdv);
+		else emulate_main_effects_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv);
 		for (int t = 0; t < nout; t++) {
 			for (int j = 0; j < d; j++) {
 				for (int g = 0; g < G; g++) fprintf(out, "%s%.17g", g ? " " : "", mainv[((size_t)j * G + g) * nout + t]);
 				fprintf(out, "\n");
+				if (sdv) {
+					for (int g = 0; g < G; g++) fprintf(out, "%s%.17g", g ? " " : "", sdv[((size_t)j * G + g) * nout + t]);
+					fprintf(out, "\n");
+				}
 			}
 			fprintf(out, "%.17g\n", e0[t]);
 		}
-		free(grid); free(mainv);
+		free(grid); free(mainv); free(sdv);
 	}
 	fflush(out);
 	free(lo); free(hi); free(e0); free(var); free(first); free(total);
@@ -517,6 +543,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"folds", required_argument, NULL, 1005},             {"groups", required_argument, NULL, 1006},
 		/* sensitivity: the box of the input measure, the number of main-effect values per parameter */
 		{"box", required_argument, NULL, 1007},               {"grid", required_argument, NULL, 1008},
+		/* ... and the emulator's own uncertainty about the indices and the curves */
+		{"uncertainty", no_argument, NULL, 1009},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -544,6 +572,7 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1006: o->groupsfile = optarg; break;
 		case 1007: o->boxfile = optarg; break;
 		case 1008: o->grid = atoi(optarg); if (o->grid < 1) o->grid = -1; break;
+		case 1009: o->uncertainty = 1; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;

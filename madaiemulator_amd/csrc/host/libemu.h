@@ -316,6 +316,22 @@ void emulate_main_effects(emulator_struct *e, const double *lo, const double *hi
  * a, of b), *cov_all = Cov(m^a, m^b), cov_first[j] = Cov(E[m^a | x_j], E[m^b | x_j]), cov_rest[j] = Cov(E[m^a | x_-j], E[m^b | x_-j]) */
 void emulate_sensitivity_enqueue(emulator_struct *a, emulator_struct *b, const double *lo, const double *hi, void **dev_out);
 void emulate_sensitivity_collect(emulator_struct *a, void *dev, double *e0, double *cov_all, double *cov_first, double *cov_rest);
+/* extension: the emulator's own uncertainty about those quantities (gpemu_sens_post / gpemu_sens_main_var in gpemu.h; the
+ * reference's counterpart is the confidence band of src/libSA/trivial-test-2.R).  f is the posterior process, m its mean, and
+ * S_u = E Var*[E[f | x_u]].  emulate_sensitivity_post: s = S_none, S_all, S_first[nparams], S_rest[nparams] as the device returns
+ * them.  emulate_sensitivity_uncertainty: *var_e0 = S_none = Var*[E0]; *imse = S_all, the box average of the posterior variance
+ * (no nugget); the posterior expectations of the variances of f itself, *evar = E*[V] = V + S_all - S_none, efirst[j] = E*[V_j] =
+ * V_j + S_j - S_none, etotal[j] = E*[VT_j] = VT_j + S_all - S_{-j}, from one gpemu_sens_cov and one gpemu_sens_post.  A small
+ * first[j] with a large efirst[j] - first[j] is an index the design does not resolve.  emulate_main_effects_band: the curves of
+ * emulate_main_effects with sd[j * ngrid + g] = sqrt(max(Var*[E[f | x_j = grid[j * ngrid + g]]], 0)); emulate_main_effects_var
+ * returns the variances themselves and *var_e0 (may be NULL). */
+void emulate_sensitivity_post(emulator_struct *e, const double *lo, const double *hi, double *s /* 2 + 2 nparams */);
+void emulate_sensitivity_uncertainty(emulator_struct *e, const double *lo, const double *hi, double *var_e0, double *imse, double *evar,
+                                     double *efirst, double *etotal);
+void emulate_main_effects_var(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
+                              double *var, double *var_e0);
+void emulate_main_effects_band(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
+                               double *sd);
 
 /* ---- multi_modelstruct.h / multivar_support.h ---------------------------------- */
 multi_modelstruct *alloc_multimodelstruct(gsl_matrix *xmodel_in, gsl_matrix *training_matrix_in, int cov_fn_index,
@@ -393,6 +409,17 @@ void emulate_sensitivity_multi(multi_emulator *emu, int pca_space, const double 
  * nr or nt values.  Observable space by the mean half of the rule (linear in the components), training mean added. */
 void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
                                 double *e0_out, double *main_out);
+/* the emulator-uncertainty terms per output: var_e0_out, imse_out, evar_out one value each, efirst_out, etotal_out nparams values
+ * each, output-major, as emulate_sensitivity_uncertainty defines them.  In observable space the two halves take OPPOSITE rules --
+ * the opposite of the trap described at emulate_sensitivity_multi.  The plug-in part (V, V_j, VT_j of the posterior mean) keeps its
+ * cross terms between components, which are functions of the same random input.  The S terms are posterior variances, and the PCA
+ * components are independent a posteriori, so they take the squared rule of gpemu_host_backproject: S_u(y_t) = sum_c B_tc^2 S_u^c,
+ * with no cross terms.  emulate_main_effects_band_multi: main_out as emulate_main_effects_multi, sd_out in the same layout, the
+ * square root of the squared rule applied to the components' variances. */
+void emulate_sensitivity_uncertainty_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *var_e0_out,
+                                           double *imse_out, double *evar_out, double *efirst_out, double *etotal_out);
+void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
+                                     double *e0_out, double *main_out, double *sd_out);
 
 /* ---- libRbind/rbind.h: the batched likelihood entry point, R-free (rbind.c:626-724) ---------------- */
 void callEvalLhoodList(double *xmodel_in, int *nparams_in, double *pointList_in, int *nevalPoints_in,

@@ -776,6 +776,49 @@ void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double
 	free(mp); free(mc); free(ep);
 }
 
+/* The emulator-uncertainty terms of every output (libemu.h).  The plug-in part comes from emulate_sensitivity_multi, cross terms
+ * and all.  The S terms of the components go through the SQUARED rule: they are posterior variances and the components are
+ * independent a posteriori, S_u(y_t) = sum_c B_tc^2 S_u^c. */
+void emulate_sensitivity_uncertainty_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *var_e0_out,
+                                           double *imse_out, double *evar_out, double *efirst_out, double *etotal_out)
+{
+	const size_t nr = (size_t)emu->nr, d = (size_t)emu->nparams, w = 2 + 2 * d, nout = pca_space ? nr : (size_t)emu->nt;
+	double *sc = doubles(nr * w), *so = doubles(nout * w), *e0 = doubles(nout), *var = doubles(nout);
+	emulate_sensitivity_multi(emu, pca_space, lo, hi, e0, var, efirst_out, etotal_out);
+	for (size_t c = 0; c < nr; c++) emulate_sensitivity_post(emu->emu_struct_array[c], lo, hi, sc + c * w);
+	deliver(emu, pca_space, 1, 0, 1, w, sc, so);
+	for (size_t t = 0; t < nout; t++) {
+		const double *s = so + t * w;
+		var_e0_out[t] = s[0];
+		imse_out[t] = s[1];
+		evar_out[t] = var[t] + s[1] - s[0];
+		for (size_t j = 0; j < d; j++) {
+			efirst_out[t * d + j] += s[2 + j] - s[0];
+			etotal_out[t * d + j] += s[1] - s[2 + d + j];
+		}
+	}
+	free(sc); free(so); free(e0); free(var);
+}
+
+/* the curves by the mean half of the rule, their posterior variances by the squared half, then the square root */
+void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
+                                     double *e0_out, double *main_out, double *sd_out)
+{
+	const size_t nr = (size_t)emu->nr, np = (size_t)emu->nparams * (size_t)(ngrid > 0 ? ngrid : 0);
+	const size_t nout = pca_space ? nr : (size_t)emu->nt;
+	double *mp = doubles(np * nr), *vp = doubles(np * nr), *mc = doubles(np), *vc = doubles(np), *ep = doubles(nr);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_main_effects_var(emu->emu_struct_array[c], lo, hi, ngrid, grid, &ep[c], mc, vc, NULL);
+		place_component(mp, mc, np, nr, c, 1);
+		place_component(vp, vc, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 0, 1, np, 1, mp, main_out);
+	deliver(emu, pca_space, 1, 0, np, 1, vp, sd_out);
+	deliver(emu, pca_space, 0, 1, 1, 1, ep, e0_out);
+	for (size_t i = 0; i < np * nout; i++) sd_out[i] = sqrt(sd_out[i] > 0.0 ? sd_out[i] : 0.0);
+	free(mp); free(vp); free(mc); free(vc); free(ep);
+}
+
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
 	const int n = pca_space ? emu->nr : emu->nt;
