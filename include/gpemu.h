@@ -494,6 +494,47 @@ int gpemu_sens_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HO
 int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid /* d*ngrid host */,
                         double *main /* d*ngrid, may be NULL */, double *var /* d*ngrid */, double *var_e0 /* may be NULL */);
 
+/* ---- second-order Sobol indices and interaction surfaces, in closed form -----------------
+ * VT_j - V_j > 0 says that parameter j interacts with something; these entries say with which parameter, and what the
+ * interaction looks like.  For u = {j, k} every conditional expectation still factorises into the one-dimensional integrals
+ * above.  Pairs j < k are numbered p(j, k) = j (2 d - j - 1) / 2 + (k - j - 1), npairs = d (d - 1) / 2.
+ * gpemu_sens_pairs returns cov_pair[p(j, k)] = Cov(E[m^a | x_j, x_k], E[m^b | x_j, x_k]) for two contexts on the same design
+ * (b may be a).  With b = a this is V_jk; the interaction variance is V_jk - V_j - V_k (V_j = cov_first[j] of gpemu_sens_cov)
+ * and the second-order index is that over V.  The cross case is what a multi-output emulator needs, as for gpemu_sens_cov.
+ * gpemu_sens_pairs_post returns s_pair[p(j, k)] = S_u of gpemu_sens_post for u = {j, k}, s_none <= s_first[j], s_first[k] <=
+ * s_pair <= s_all, and with it the posterior expectations
+ *   E*[V_jk] = V_jk + s_pair - s_none,
+ *   E*[V_jk - V_j - V_k] = V_jk - V_j - V_k + s_pair - s_first[j] - s_first[k] + s_none.
+ * gpemu_sens_joint returns, for one pair j != k and npts points (xj[g], xk[g]), E0, the two-way surface
+ * joint[g] = E[m | x_j = xj[g], x_k = xk[g]] and the interaction effect inter[g] = joint - main_j - main_k + E0.  The
+ * regression basis is additive, so the polynomial parts of inter cancel exactly; it is summed as
+ * A sum_i gamma_i [k_j k_k Pex2_jk - k_j Pex_j - k_k Pex_k + prod_l I_l](i), never as a difference of the large values.
+ * How they run: the per-point tables of gpemu_sens_cov; a launch that writes the leave-two-out products
+ * Pex2_jk(i) = prod_{l != j,k} I_l(i) of both contexts (prefix, running-middle and suffix products: O(d^2) per point, no
+ * division); the pair sweep, 64 x 64 tiles of point pairs times blocks of 8 x 8 coordinates -- one launch for the blocks on
+ * the diagonal (28 pairs, 8 one-dimensional integrals per pair of points), for d > 8 one more for the others (64 pairs, 16
+ * integrals) -- which leaves npairs partial sums per tile; the finish.  gpemu_sens_pairs_post weights every pair term by its
+ * element of P over the lower tiles, as gpemu_sens_post does (the same launch writes P and G).  gpemu_sens_joint: the tables,
+ * then one workgroup per point.  Any d from 2 to GPEMU_MAX_PARAMS takes the same kernels, all sums in registers.
+ * Memory, besides the tables of gpemu_sens_cov (and P, G and the corner for the post entry):
+ * 8 (2 N npairs + ceil(N / 64)^2 npairs + npairs) bytes; gpemu_sens_joint 8 (2 N npairs + 4 npts).
+ * No atomics, no workgroup waits for another, every sum has one order: two calls return the same bits, and so do the host and
+ * _dev entries and a context set up by gpemu_predict_setup_batch.  The _dev entries only enqueue; with b != a the streams are
+ * ordered by events as for gpemu_sens_cov_dev.  The buffers are the entries' own: a pending prediction batch stays
+ * collectable; gpemu_sens_release, gpemu_set_model and the end of the context free them.
+ * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL pointer (inter may be NULL), whatever the state;
+ * GPEMU_ERR_STATE without a prediction set-up on either context; then GPEMU_ERR_ARG for d < 2, a Matern model, contexts on
+ * different devices or with different designs or regression orders, a non-finite bound or hi_l <= lo_l, j == k or an index
+ * outside 0 .. d - 1, npts < 1. */
+int gpemu_sens_pairs(gpemu_ctx *a, gpemu_ctx *b /* may be a */, const double *lo, const double *hi /* d each, host */,
+                     double *cov_pair /* npairs */);
+int gpemu_sens_pairs_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi /* HOST */, double *out_dev /* npairs */);
+int gpemu_sens_pairs_post(gpemu_ctx *ctx, const double *lo, const double *hi /* d each, host */, double *s_pair /* npairs */);
+int gpemu_sens_pairs_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HOST */, double *out_dev /* npairs */);
+int gpemu_sens_joint(gpemu_ctx *ctx, const double *lo, const double *hi, int j, int k, int npts,
+                     const double *xj, const double *xk /* npts each, host */, double *e0, double *joint /* npts */,
+                     double *inter /* npts, may be NULL */);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */

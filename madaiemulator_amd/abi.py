@@ -154,6 +154,11 @@ SYMBOLS = {
     "gpemu_sens_post_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_main_var": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpemu_test_sens_post_state": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "gpemu_sens_pairs": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp]),
+    "gpemu_sens_pairs_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
+    "gpemu_sens_pairs_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "gpemu_sens_pairs_post_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p]),
+    "gpemu_sens_joint": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -540,6 +545,47 @@ class Context:
         P, G, Q = np.empty((self.N, self.N)), np.empty((self.N, self.nreg)), np.empty((self.nreg, self.nreg))
         self._chk(self.L.gpemu_test_sens_post_state(self.h, _p(P), _p(G), _p(Q)))
         return P, G, Q
+
+    # second order: pairs j < k at p = j (2 d - j - 1) / 2 + (k - j - 1)
+    def _box(self, what, lo, hi):
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        if lo.size != self.d or hi.size != self.d:
+            raise GpemuError(ERR_ARG, f"{what}: one bound pair per coordinate")
+        return lo, hi
+
+    def sens_pairs(self, lo, hi, other=None):
+        """-> cov_pair[d (d - 1) / 2] of this context and `other` (default: itself) on one design"""
+        lo, hi = self._box("sens_pairs", lo, hi)
+        out = np.empty(self.d * (self.d - 1) // 2)
+        self._chk(self.L.gpemu_sens_pairs(self.h, (self if other is None else other).h, _p(lo), _p(hi), _p(out)))
+        return out
+
+    def sens_pairs_dev(self, lo, hi, out_dev, other=None):
+        """lo, hi: HOST bounds; out_dev: d (d - 1) / 2 doubles on the device"""
+        lo, hi = self._box("sens_pairs_dev", lo, hi)
+        self._chk(self.L.gpemu_sens_pairs_dev(self.h, (self if other is None else other).h, _p(lo), _p(hi), out_dev))
+
+    def sens_pairs_post(self, lo, hi):
+        """-> s_pair[d (d - 1) / 2]"""
+        lo, hi = self._box("sens_pairs_post", lo, hi)
+        out = np.empty(self.d * (self.d - 1) // 2)
+        self._chk(self.L.gpemu_sens_pairs_post(self.h, _p(lo), _p(hi), _p(out)))
+        return out
+
+    def sens_pairs_post_dev(self, lo, hi, out_dev):
+        """lo, hi: HOST bounds; out_dev: d (d - 1) / 2 doubles on the device"""
+        lo, hi = self._box("sens_pairs_post_dev", lo, hi)
+        self._chk(self.L.gpemu_sens_pairs_post_dev(self.h, _p(lo), _p(hi), out_dev))
+
+    def sens_joint(self, lo, hi, j, k, xj, xk):
+        """-> (e0, joint[npts], inter[npts]) at the points (x_j, x_k) = (xj[g], xk[g])"""
+        lo, hi = self._box("sens_joint", lo, hi)
+        xj, xk = _a(xj).ravel(), _a(xk).ravel()
+        if xj.size != xk.size:
+            raise GpemuError(ERR_ARG, "sens_joint: one value of x_k per value of x_j")
+        e0, joint, inter = np.empty(1), np.empty(xj.size), np.empty(xj.size)
+        self._chk(self.L.gpemu_sens_joint(self.h, _p(lo), _p(hi), j, k, xj.size, _p(xj), _p(xk), _p(e0), _p(joint), _p(inter)))
+        return e0[0], joint, inter
 
     def pred_state(self):
         """-> (beta[nreg], gamma[N]) bit for bit as the prediction state holds them (parity tests)"""

@@ -273,7 +273,7 @@ static void free_model(gpemu_ctx *ctx)
 	for (auto *b : {&ctx->dLgoTab, &ctx->dLgoInfo, &ctx->dLgoInfoOut}) b->reset();
 	ctx->hLgoTab.reset();
 	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid, &ctx->dSensP, &ctx->dSensG,
-	                &ctx->dSensPostPart})
+	                &ctx->dSensPostPart, &ctx->dSensPex2, &ctx->dSensPairPart, &ctx->dSensPairOut})
 		b->reset();
 	ctx->sens_post_N = 0;
 	ctx->hStage.reset();
@@ -2288,7 +2288,7 @@ extern "C" int gpemu_sens_release(gpemu_ctx *ctx)
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	for (auto *b : {&ctx->dSensPrep, &ctx->dSensCst, &ctx->dSensPart, &ctx->dSensOut, &ctx->dSensGrid, &ctx->dSensP, &ctx->dSensG,
-	                &ctx->dSensPostPart})
+	                &ctx->dSensPostPart, &ctx->dSensPex2, &ctx->dSensPairPart, &ctx->dSensPairOut})
 		b->reset();
 	ctx->sens_post_N = 0;
 	return GPEMU_OK;
@@ -2494,6 +2494,167 @@ extern "C" int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P, double *G, 
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	for (size_t i = 0; i < N; i++)
 		for (size_t j = i + 1; j < N; j++) P[j * N + i] = P[i * N + j];
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// second order: pair covariances, their emulator uncertainty and the two-way surface (gpemu.h).  The tables
+// and constants of gpemu_sens_cov, then the leave-two-out products, the pair sweep and its finish; everything written is the
+// entries' own (dSensPrep, dSensCst, dSensPex2, dSensPairPart, dSensPairOut; the post entry also dSensP, dSensG).
+// ---------------------------------------------------------------------------
+static int sens_pair_check(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, SensBox *bx)
+{
+	if (const int rc = sens_check(a, b, lo, hi, bx)) return rc;
+	if (a->d < 2) return fail(a, GPEMU_ERR_ARG, "sensitivity: a pair needs two parameters");
+	return GPEMU_OK;
+}
+
+// the tables of both contexts and their leave-two-out products
+static int sens_pair_prep(gpemu_ctx *a, const SensBox &bx, int cls)
+{
+	const int N = a->N, d = a->d;
+	if (const int rc = sens_prep(a, bx, cls)) return rc;
+	// per point d (d - 1) / 2 values of two products each, once per context
+	ProfScope ps(a, cls, 2.0 * N * d * (d - 1.0), 8.0 * 3.0 * (double)sens_pex2_elems(N, d));
+	HIPCHK(a, launch_sens_pair_prep(a->stream, a->dSensPrep, N, d, a->dSensPex2));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_pairs_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, double *out_dev)
+{
+	if (!a || !b || !lo || !hi || !out_dev) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_pair_check(a, b, lo, hi, &bx)) return rc;
+	HIPCHK(a, hipSetDevice(a->device));
+	const int N = a->N, d = a->d, Np = a->Np;
+	const double npairs = d * (d - 1) / 2.0, nb = (d + 7) / 8, nii = 8.0 * nb + 8.0 * nb * (nb - 1.0);   // II values per pair of points
+	int rc = grow(a, a->dSensPex2, sens_pex2_elems(N, d));
+	if (!rc) rc = grow(a, a->dSensPairPart, sens_pair_part_elems(N, d));
+	if (rc) return rc;
+	if ((rc = sens_order_streams(a, b))) return rc;
+	if (prof_on(a, GPEMU_PROF_SENS))
+		for (const char *t : {"sens_prep", "sens_pair_prep", "sens_pair_sweep", "sens_pair_finish"}) a->prof.tag.push_back(t);
+	if ((rc = sens_pair_prep(a, bx, GPEMU_PROF_SENS))) return rc;
+	const double *gamA = a->dLinvAug + (size_t)Np * Np, *gamB = b->dLinvAug + (size_t)Np * Np;
+	{
+		// per pair of points: the II values of gpemu_sens_cov (19 flops each) for 8 coordinates per diagonal block and 16 per
+		// other block, then 3 flops per pair of coordinates (both launches under one scope when d > 8)
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (19.0 * nii + 3.0 * npairs), 8.0 * (double)sens_pair_part_elems(N, d));
+		HIPCHK(a, launch_sens_pair_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPex2, a->dSensCst, nullptr, a->dSensPairPart));
+	}
+	{
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)sens_pair_part_elems(N, d), 8.0 * (double)sens_pair_part_elems(N, d));
+		HIPCHK(a, launch_sens_pair_finish(a->stream, a->dSensPairPart, N, d, a->order, gamA, a->dBetaQ, a->pred_cov.amp, gamB, b->dBetaQ,
+		                                  b->pred_cov.amp, a->dSensPrep, a->dSensCst, out_dev));
+	}
+	if (a != b) {
+		// b's later work (a new set-up would rewrite its gamma) runs behind this call
+		HIPCHK(a, hipEventRecord(a->sens_ev2, a->stream));
+		HIPCHK(a, hipStreamWaitEvent(b->stream, a->sens_ev2, 0));
+	}
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_pairs(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double *hi, double *cov_pair)
+{
+	if (!a || !b || !lo || !hi || !cov_pair) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_pair_check(a, b, lo, hi, &bx)) return rc;
+	HIPCHK(a, hipSetDevice(a->device));
+	const size_t npairs = (size_t)a->d * (a->d - 1) / 2;
+	if (const int rc = grow(a, a->dSensPairOut, npairs)) return rc;
+	if (const int rc = gpemu_sens_pairs_dev(a, b, lo, hi, a->dSensPairOut)) return rc;
+	HIPCHK(a, hipMemcpyAsync(cov_pair, a->dSensPairOut, npairs * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+	HIPCHK(a, hipStreamSynchronize(a->stream));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_pairs_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi, double *out_dev)
+{
+	if (!ctx || !lo || !hi || !out_dev) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_pair_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int N = ctx->N, d = ctx->d, nreg = ctx->nreg, Rp = ctx->Rp;
+	const size_t ldp = (size_t)round_up(N, 64);
+	const double ntl = (double)(ldp / 64) * (double)(ldp / 64 + 1) / 2.0;           // lower tiles
+	const double npairs = d * (d - 1) / 2.0, nb = (d + 7) / 8, nii = 8.0 * nb + 8.0 * nb * (nb - 1.0);   // II values per pair of points
+	int rc = grow(ctx, ctx->dSensPex2, sens_pex2_elems(N, d));
+	if (!rc) rc = grow(ctx, ctx->dSensPairPart, sens_pair_part_elems(N, d));
+	if (!rc) rc = grow(ctx, ctx->dSensP, ldp * ldp);
+	if (!rc) rc = grow(ctx, ctx->dSensG, (size_t)N * nreg);
+	if (rc) return rc;
+	if (prof_on(ctx, GPEMU_PROF_SENS_POST))
+		for (const char *t : {"sens_prep", "sens_pair_prep", "sens_pmat", "sens_pair_sweep_weighted", "sens_pair_post_finish"})
+			ctx->prof.tag.push_back(t);
+	if ((rc = sens_pair_prep(ctx, bx, GPEMU_PROF_SENS_POST))) return rc;
+	if ((rc = ensure_corner(ctx))) return rc;
+	const double *Q = ctx->dBetaQ + nreg;
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * (128.0 * nreg * nreg + 4096.0 * (2.0 * nreg + 1.0)), 8.0 * ntl * 8192.0);
+		HIPCHK(ctx, launch_sens_pmat(ctx->stream, ctx->dS, (long)ctx->S_dim, Rp, Q, N, nreg, ctx->dSensG, ctx->dSensP));
+	}
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (20.0 * nii + 3.0 * npairs),
+		             8.0 * ntl * (4096.0 * nb * (nb + 1.0) / 2.0 + npairs));
+		HIPCHK(ctx, launch_sens_pair_sweep(ctx->stream, ctx->dX, N, d, nullptr, nullptr, ctx->dSensPex2, ctx->dSensCst, ctx->dSensP,
+		                                   ctx->dSensPairPart));
+	}
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * npairs + npairs * nreg * (2.0 * nreg + 4.0 * N),
+		             8.0 * (ntl * npairs + npairs * 3.0 * N * nreg));
+		HIPCHK(ctx, launch_sens_pair_post_finish(ctx->stream, ctx->dSensPairPart, N, d, nreg, ctx->pred_cov.amp, ctx->dSensPrep, ctx->dSensCst,
+		                                         ctx->dSensG, Q, out_dev));
+	}
+	ctx->sens_post_N = N;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_pairs_post(gpemu_ctx *ctx, const double *lo, const double *hi, double *s_pair)
+{
+	if (!ctx || !lo || !hi || !s_pair) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_pair_check(ctx, ctx, lo, hi, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t npairs = (size_t)ctx->d * (ctx->d - 1) / 2;
+	if (const int rc = grow(ctx, ctx->dSensPairOut, npairs)) return rc;
+	if (const int rc = gpemu_sens_pairs_post_dev(ctx, lo, hi, ctx->dSensPairOut)) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(s_pair, ctx->dSensPairOut, npairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_joint(gpemu_ctx *ctx, const double *lo, const double *hi, int j, int k, int npts, const double *xj,
+                                const double *xk, double *e0, double *joint, double *inter)
+{
+	if (!ctx || !lo || !hi || !xj || !xk || !e0 || !joint) return GPEMU_ERR_ARG;
+	SensBox bx;
+	if (const int rc = sens_pair_check(ctx, ctx, lo, hi, &bx)) return rc;
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np;
+	if (j == k || j < 0 || k < 0 || j >= d || k >= d) return fail(ctx, GPEMU_ERR_ARG, "sensitivity: a pair is two different parameters of 0 .. d - 1");
+	if (npts < 1) return fail(ctx, GPEMU_ERR_ARG, "sensitivity: npts < 1");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t ng = (size_t)npts;
+	int rc = grow(ctx, ctx->dSensGrid, 4 * ng);
+	if (!rc) rc = grow(ctx, ctx->dSensOut, 3 + 2 * (size_t)GPEMU_MAX_PARAMS);
+	if (!rc) rc = grow(ctx, ctx->dSensPex2, sens_pex2_elems(N, d));
+	if (rc) return rc;
+	// the smaller coordinate first: the tables are numbered by j < k
+	double *dxj = ctx->dSensGrid, *dxk = dxj + ng, *djoint = dxk + ng, *dinter = djoint + ng;
+	HIPCHK(ctx, hipMemcpyAsync(j < k ? dxj : dxk, xj, ng * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(j < k ? dxk : dxj, xk, ng * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (prof_on(ctx, GPEMU_PROF_SENS)) for (const char *t : {"sens_prep", "sens_pair_prep", "sens_joint"}) ctx->prof.tag.push_back(t);
+	if ((rc = sens_pair_prep(ctx, bx, GPEMU_PROF_SENS))) return rc;
+	{
+		ProfScope ps(ctx, GPEMU_PROF_SENS, (double)ng * N * 16.0, 8.0 * 4.0 * (double)ng);
+		HIPCHK(ctx, launch_sens_joint(ctx->stream, ctx->dX, N, d, ctx->order, ctx->dLinvAug + (size_t)Np * Np, ctx->dBetaQ, ctx->pred_cov.amp,
+		                              ctx->dSensPrep, ctx->dSensPex2, ctx->dSensCst, std::min(j, k), std::max(j, k), npts, dxj, dxk,
+		                              ctx->dSensOut, djoint, dinter));
+	}
+	HIPCHK(ctx, hipMemcpyAsync(joint, djoint, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (inter) HIPCHK(ctx, hipMemcpyAsync(inter, dinter, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(e0, ctx->dSensOut, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 

@@ -320,6 +320,9 @@ struct gpemu_ctx {
 	// (N x nreg), dSensPostPart the weighted sweep's partial sums; sens_post_N: the N they were last written for (0: never)
 	gpemu::DevBuf<double> dSensP, dSensG, dSensPostPart;
 	int sens_post_N = 0;
+	// second order: dSensPex2 the leave-two-out products of both contexts (2 x npairs x N), dSensPairPart the
+	// pair sweeps' partial sums (npairs per tile), dSensPairOut the npairs results of the host entries
+	gpemu::DevBuf<double> dSensPex2, dSensPairPart, dSensPairOut;
 	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
@@ -499,5 +502,22 @@ hipError_t launch_sens_tvec(hipStream_t s, const double *X, int N, int Np, int d
                             const double *grid, int ngrid, int r0, int mb, int mbp, double *Kq);
 hipError_t launch_sens_band_finish(hipStream_t s, const double *V, long ldv, int mb, int r0, int Np, int nreg, int d, int ngrid,
                                    const double *cst, const double *grid, const double *betaQ, double amp, double *main, double *var);
+// second order, npairs = d (d - 1) / 2, pair (j < k) at p = j (2 d - j - 1) / 2 + (k - j - 1).  pex2:
+// sens_pex2_elems doubles, Pex2_jk(i) of context c at (c * npairs + p) * N + i, from the I table of prep; part:
+// sens_pair_part_elems doubles, npairs sums per 64 x 64 tile (Pw given: per lower tile, weighted, context 0 alone); out: npairs
+size_t sens_pex2_elems(int N, int d);
+size_t sens_pair_part_elems(int N, int d);
+hipError_t launch_sens_pair_prep(hipStream_t s, const double *prep, int N, int d, double *pex2);
+hipError_t launch_sens_pair_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pex2,
+                                  const double *cst, const double *Pw, double *part);
+hipError_t launch_sens_pair_finish(hipStream_t s, const double *part, int N, int d, int order, const double *gamA, const double *betaA,
+                                   double ampA, const double *gamB, const double *betaB, double ampB, const double *prep, const double *cst,
+                                   double *out);
+hipError_t launch_sens_pair_post_finish(hipStream_t s, const double *part, int N, int d, int nreg, double amp, const double *prep,
+                                        const double *cst, const double *G, const double *Q, double *out);
+// the two-way surface of the pair j < k at npts points (xj[g], xk[g]): e0, joint[npts], inter[npts]
+hipError_t launch_sens_joint(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
+                             const double *prep, const double *pex2, const double *cst, int j, int k, int npts, const double *xj,
+                             const double *xk, double *e0, double *joint, double *inter);
 
 } // namespace gpemu

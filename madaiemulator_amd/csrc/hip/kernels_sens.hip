@@ -664,4 +664,358 @@ hipError_t launch_sens_main(hipStream_t s, const double *X, int N, int d, int or
 	return hipGetLastError();
 }
 
+// ===========================================================================
+// Second order (gpemu_sens_pairs / gpemu_sens_pairs_post / gpemu_sens_joint): u = {j, k}, j < k, numbered
+// p(j, k) = j (2 d - j - 1) / 2 + (k - j - 1).  The pair term is  II_j II_k Pex2_jk(i) Pex2'_jk(i'),  Pex2_jk = prod_{l != j,k} I_l.
+// New kernels beside the ones above, which they leave as they are; the per-point tables and cst are sens_prep_kernel's.
+// ===========================================================================
+constexpr int SENS_PB = 8;                                                        // coordinates of a block of the pair sweep
+
+__host__ __device__ __forceinline__ int sens_pair_index(int j, int k, int d) { return j * (2 * d - j - 1) / 2 + (k - j - 1); }
+
+// pair p -> (j, k)
+__device__ __forceinline__ void sens_pair_coords(int p, int d, int &j, int &k)
+{
+	j = 0;
+	while (p >= d - 1 - j) { p -= d - 1 - j; j++; }
+	k = j + 1 + p;
+}
+
+// ---------------------------------------------------------------------------
+// pair prep: workgroup (x, c, j) writes, for 256 design points of context c, Pex2_jk(i) for every k > j:
+// table c at pex2 + c * npairs * N, pair p at p * N + i.  prod_{l < j} I_l, then the suffix products on the way down and the
+// running middle products on the way up, in the table itself: O(d^2) products per point, no division (the factors underflow
+// to 0 for far points), no private array.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sens_pair_prep_kernel(const double *prep, int N, int d, double *pex2)
+{
+	const int c = blockIdx.y, j = blockIdx.z, i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= N) return;
+	const double *I = prep + (long)c * 5 * d * N + i;                             // I_l(i) at I[l * N]
+	double *out = pex2 + ((long)c * (d * (d - 1) / 2) + sens_pair_index(j, j + 1, d)) * N + i;   // pair (j, k) at out[(k - j - 1) * N]
+	double pre = 1.0;
+	for (int l = 0; l < j; l++) pre *= I[(long)l * N];
+	double suf = 1.0;
+	for (int k = d - 1; k > j; k--) {
+		out[(long)(k - j - 1) * N] = pre * suf;
+		suf *= I[(long)k * N];
+	}
+	double mid = 1.0;
+	for (int k = j + 1; k < d; k++) {
+		out[(long)(k - j - 1) * N] *= mid;
+		mid *= I[(long)k * N];
+	}
+}
+
+// ---------------------------------------------------------------------------
+// pair sweep: the N x N square of point pairs in 64 x 64 tiles (blockIdx.x, .y) as sens_sweep_kernel walks it, times the
+// blocks of SENS_PB x SENS_PB coordinates (Ja <= Kb) in blockIdx.z.  DIAG: Ja = Kb = z, the 28 pairs j < k of one block, 8 II
+// values per pair of points; otherwise z numbers the blocks Ja < Kb, 64 pairs, 16 II values.  A thread owns a row and the
+// columns wave + 4 k of every 16-column chunk, whose coordinates and weights gamma'_i' Pex2'_jk(i') go through LDS (slot
+// jj * 8 + kk of 64 per column, a diagonal block uses those with jj < kk); it keeps one sum per pair in registers (the loops
+// unroll completely: no private memory) and applies the row's own gamma_i Pex2_jk(i) once at the end.  Then the butterfly over
+// the lanes, the four waves in order, and part[tile * npairs + p(j, k)].  Coordinates >= d give II = 0 and weights 0 and are
+// never stored; rows and columns >= N are computed on zero coordinates with zero weights: finite values times 0.
+// WEIGHTED (gpemu_sens_pairs_post; one context): P_ii' from sens_pmat_kernel in place of gamma_i gamma'_i', one workgroup
+// per LOWER tile (blockIdx.x), sums counted twice off the diagonal.
+// ---------------------------------------------------------------------------
+template <bool DIAG, bool WEIGHTED>
+__global__ __launch_bounds__(256) void sens_pair_sweep_kernel(const double *X, int N, int d, const double *gamA, const double *gamB,
+                                                              const double *pex2A, const double *pex2B, const double *cst, double *part,
+                                                              const double *Pw)
+{
+	constexpr int B = SENS_PB, NC = DIAG ? B : 2 * B, NP = B * B;
+	__shared__ double cst_s[SENS_CST * 2 * B], xb_s[SENS_CHUNK * 2 * B], w_s[SENS_CHUNK * NP], red[4 * NP];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	int tr = blockIdx.y, tc = blockIdx.x;
+	if constexpr (WEIGHTED) sens_lower_tile(blockIdx.x, tr, tc);
+	int Ja = blockIdx.z, Kb = blockIdx.z;
+	if constexpr (!DIAG) {
+		sens_lower_tile(blockIdx.z, Kb, Ja);                                      // Ja <= Kb' < Kb' + 1
+		Kb += 1;
+	}
+	const int npairs = d * (d - 1) / 2;
+	// slot t of the NC coordinates: the block Ja first, then (off the diagonal) the block Kb
+	auto coord = [&](int t) { return (t < B ? Ja : Kb) * B + (t & (B - 1)); };
+	for (int e = tid; e < SENS_CST * NC; e += 256) {
+		const int r = e / NC, t = e % NC, l = coord(t);
+		cst_s[r * 2 * B + t] = l < d ? cst[r * GPEMU_MAX_PARAMS + l] : 0.0;
+	}
+	const int row = tr * 64 + lane;
+	const bool rowv = row < N;
+	[[maybe_unused]] const long ldp = (long)((N + 63) / 64) * 64;
+	double xr[NC], acc[NP];
+#pragma unroll
+	for (int t = 0; t < NC; t++) {
+		const int l = coord(t);
+		xr[t] = (rowv && l < d) ? X[(long)row * d + l] : 0.0;
+	}
+#pragma unroll
+	for (int e = 0; e < NP; e++) acc[e] = 0.0;
+	for (int ch = 0; ch < 64 / SENS_CHUNK; ch++) {
+		__syncthreads();
+		for (int e = tid; e < SENS_CHUNK * NC; e += 256) {
+			const int cc = e % SENS_CHUNK, t = e / SENS_CHUNK, l = coord(t);
+			const int col = tc * 64 + ch * SENS_CHUNK + cc;
+			xb_s[cc * 2 * B + t] = (col < N && l < d) ? X[(long)col * d + l] : 0.0;
+		}
+		for (int e = tid; e < SENS_CHUNK * NP; e += 256) {
+			const int cc = e % SENS_CHUNK, lp = e / SENS_CHUNK;
+			const int col = tc * 64 + ch * SENS_CHUNK + cc;
+			const int j = Ja * B + lp / B, k = Kb * B + lp % B;
+			double w = 0.0;
+			if (col < N && j < k && k < d) {
+				w = pex2B[(long)sens_pair_index(j, k, d) * N + col];
+				if constexpr (!WEIGHTED) w *= gamB[col];
+			}
+			w_s[cc * NP + lp] = w;
+		}
+		__syncthreads();
+		for (int k4 = 0; k4 < SENS_CHUNK / 4; k4++) {
+			const int cc = wave + 4 * k4;
+			const double *xc = xb_s + cc * 2 * B, *w = w_s + cc * NP;
+			double a[NC];
+#pragma unroll
+			for (int t = 0; t < NC; t++) {
+				a[t] = 0.0;
+				if (coord(t) >= d) continue;
+				const double dx = xr[t] - xc[t];
+				const double c = cst_s[1 * 2 * B + t] * xr[t] + cst_s[2 * 2 * B + t] * xc[t], al = cst_s[3 * 2 * B + t];
+				a[t] = exp(-0.5 * cst_s[0 * 2 * B + t] * dx * dx) * cst_s[4 * 2 * B + t] *
+				       erf_diff(al * (cst_s[5 * 2 * B + t] - c), al * (cst_s[6 * 2 * B + t] - c));
+			}
+			[[maybe_unused]] double pw = 1.0;
+			if constexpr (WEIGHTED) pw = Pw[(long)(tc * 64 + ch * SENS_CHUNK + cc) * ldp + row];
+#pragma unroll
+			for (int jj = 0; jj < B; jj++) {
+				const double aj = WEIGHTED ? pw * a[jj] : a[jj];
+#pragma unroll
+				for (int kk = DIAG ? jj + 1 : 0; kk < B; kk++)
+					acc[jj * B + kk] = fma(w[jj * B + kk], aj * a[DIAG ? kk : B + kk], acc[jj * B + kk]);
+			}
+		}
+	}
+	// the row's own factor, the 64 rows of the wave by a butterfly, the four waves in order
+	double gr;
+	if constexpr (WEIGHTED) gr = rowv ? 1.0 : 0.0;
+	else gr = rowv ? gamA[row] : 0.0;
+#pragma unroll
+	for (int jj = 0; jj < B; jj++) {
+#pragma unroll
+		for (int kk = DIAG ? jj + 1 : 0; kk < B; kk++) {
+			const int j = Ja * B + jj, k = Kb * B + kk;
+			if (k >= d) continue;                                                 // (j < k: the same for every thread of the workgroup)
+			double t = rowv ? gr * pex2A[(long)sens_pair_index(j, k, d) * N + row] * acc[jj * B + kk] : 0.0;
+			for (int m = 1; m < 64; m <<= 1) t += __shfl_xor(t, m);
+			if (lane == 0) red[wave * NP + jj * B + kk] = t;
+		}
+	}
+	__syncthreads();
+	if (tid < NP) {
+		const int j = Ja * B + tid / B, k = Kb * B + tid % B;
+		if (j < k && k < d) {
+			const double t = ((red[tid] + red[NP + tid]) + red[2 * NP + tid]) + red[3 * NP + tid];
+			const long p = sens_pair_index(j, k, d);
+			// (weighted) an off-diagonal tile stands for its mirror image too: P and the pair terms are symmetric
+			if constexpr (WEIGHTED) part[(long)blockIdx.x * npairs + p] = tr > tc ? 2.0 * t : t;
+			else part[((long)tr * gridDim.x + tc) * npairs + p] = t;
+		}
+	}
+}
+
+// D_l of sens_finish_kernel, by its instructions in its order
+__device__ double sens_dl(const SensSide &a, const SensSide &b, int order, int N, int d, int l, double lo, double hi, double Fa, double Fb,
+                          double *red)
+{
+	const double Eqa = sens_eq(a.beta, order, d, l, lo, hi), Eqb = sens_eq(b.beta, order, d, l, lo, hi);
+	double cq = 0.0;                                                              // Cov(q^a_l, q^b_l)
+	for (int p = 1; p <= order; p++)
+		for (int r = 1; r <= order; r++)
+			cq = fma(a.beta[1 + (p - 1) * d + l] * b.beta[1 + (r - 1) * d + l],
+			         sens_moment(lo, hi, p + r) - sens_moment(lo, hi, p) * sens_moment(lo, hi, r), cq);
+	const double Hab = sens_poly_kernel(a, b, order, N, d, l, red), Hba = sens_poly_kernel(b, a, order, N, d, l, red);
+	return cq + (Hab - Eqa * Fb) + (Hba - Eqb * Fa);
+}
+
+// ---------------------------------------------------------------------------
+// pair finish: workgroup p -> out[p] = cov_pair[p] = D_j + D_k + A A' KK_jk - F^a F^b  (the rule at sens_finish_kernel with
+// u = {j, k}: E0 has left the constant term before any second moment is formed); the tiles' sums in tile order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sens_pair_finish_kernel(const double *part, int ntiles, SensSide a, SensSide b, int N, int d,
+                                                               int order, const double *cst, double *out)
+{
+	__shared__ double red[256];
+	const int p = blockIdx.x, np = d * (d - 1) / 2;
+	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
+	int j, k;
+	sens_pair_coords(p, d, j, k);
+	double kk = 0.0;
+	for (int t = threadIdx.x; t < ntiles; t += 256) kk += part[(long)t * np + p];
+	kk = block_sum(kk, red);
+	const double Fa = sens_kernel_mean(a, N, d, red), Fb = sens_kernel_mean(b, N, d, red);
+	double sumD = 0.0;
+	if (order > 0) {
+		sumD += sens_dl(a, b, order, N, d, j, lo[j], hi[j], Fa, Fb, red);
+		sumD += sens_dl(a, b, order, N, d, k, lo[k], hi[k], Fa, Fb, red);
+	}
+	if (threadIdx.x == 0) out[p] = sumD + (a.A * b.A * kk - Fa * Fb);
+}
+
+// ---------------------------------------------------------------------------
+// pair post finish: workgroup p -> out[p] = S_u for u = {j, k}, by the rules at sens_post_finish_kernel (CC_u, Hm_u, HK_u;
+// two different coordinates of u are independent: E h_a E h_b), the weighted pair sweep's sums in tile order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sens_pair_post_finish_kernel(const double *part, int ntiles, const double *prep, const double *G,
+                                                                    const double *Q, double A, int N, int d, int nreg, const double *cst,
+                                                                    double *out)
+{
+	__shared__ double red[256], eh[GPEMU_MAX_PARAMS];
+	const int p = blockIdx.x, np = d * (d - 1) / 2, tid = threadIdx.x;
+	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
+	const long q = (long)d * N;
+	int j, k;
+	sens_pair_coords(p, d, j, k);
+	auto inu = [&](int l) { return l == j || l == k; };
+	if (tid < nreg) eh[tid] = sens_eh(tid, d, lo, hi);
+	double kk = 0.0;
+	for (int t = tid; t < ntiles; t += 256) kk += part[(long)t * np + p];
+	kk = block_sum(kk, red);                                                      // (its barriers publish eh)
+	double cc = A;
+	for (int l = 0; l < d; l++)
+		if (!inu(l)) cc *= sens_uu(2.0 * cst[l], hi[l] - lo[l]);                  // (s = t: row 0 of cst holds s / 2)
+	double hq = 0.0;
+	for (int e = tid; e < nreg * nreg; e += 256) {
+		const int a = e / nreg, b = e % nreg;
+		double hm = eh[a] * eh[b];
+		if (a > 0 && b > 0 && (a - 1) % d == (b - 1) % d && inu((a - 1) % d)) {
+			const int l = (a - 1) % d;
+			hm = sens_moment(lo[l], hi[l], (a - 1) / d + (b - 1) / d + 2);
+		}
+		hq = fma(Q[e], hm, hq);
+	}
+	hq = block_sum(hq, red);
+	double hk = 0.0;
+	for (int i = tid; i < N; i += 256) {
+		const double pi = prep[i] * prep[4 * q + i];
+		double g = 0.0;
+		for (int a = 0; a < nreg; a++) {
+			const int l = a ? (a - 1) % d : 0, o = a ? (a - 1) / d + 1 : 0;
+			const double t = (a && inu(l)) ? prep[o * q + (long)l * N + i] * prep[4 * q + (long)l * N + i] : eh[a] * pi;
+			g = fma(G[(long)i * nreg + a], t, g);
+		}
+		hk += g;
+	}
+	hk = block_sum(hk, red);
+	if (tid == 0) out[p] = ((cc - A * A * kk) + hq) - 2.0 * A * hk;
+}
+
+// ---------------------------------------------------------------------------
+// joint: workgroup g, in the shape of sens_main_kernel, for the pair (j, k) and the point (xj[g], xk[g]):
+//   joint[g] = beta_0 + q_j + q_k + sum_{l != j,k} E q_l + A sum_i gamma_i k_j k_k Pex2_jk(i),
+//   inter[g] = joint - main_j - main_k + E0 = A sum_i gamma_i [k_j k_k Pex2_jk - k_j Pex_j - k_k Pex_k + prod_l I_l](i)
+// -- the regression basis is additive, the polynomial parts cancel exactly and are never formed.  Workgroup 0 also writes E0.
+// pex2: the table of the pair, N values.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sens_joint_kernel(const double *X, SensSide a, const double *pex2, int N, int d, int order,
+                                                         const double *cst, int j, int k, const double *xj, const double *xk, double *e0,
+                                                         double *joint, double *inter)
+{
+	__shared__ double red[256];
+	const int g = blockIdx.x;
+	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
+	const double sj = 2.0 * cst[j], sk = 2.0 * cst[k];                            // (one context, s = t: row 0 holds s / 2)
+	const double x = xj[g], z = xk[g];
+	const long q = (long)d * N;
+	double vj = 0.0, vi = 0.0;
+	for (int i = threadIdx.x; i < N; i += 256) {
+		const double dx = x - X[(long)i * d + j], dz = z - X[(long)i * d + k];
+		const double kj = exp(-0.5 * sj * dx * dx), kz = exp(-0.5 * sk * dz * dz);
+		const double t = kj * kz * pex2[i];
+		vj = fma(a.gam[i], t, vj);
+		vi = fma(a.gam[i], ((t - kj * a.prep[4 * q + (long)j * N + i]) - kz * a.prep[4 * q + (long)k * N + i]) + a.prep[i] * a.prep[4 * q + i], vi);
+	}
+	const double kern = a.A * block_sum(vj, red), kint = a.A * block_sum(vi, red);
+	double S = a.beta[0], rest = a.beta[0];
+	for (int l = 0; l < d; l++) {
+		const double Eq = sens_eq(a.beta, order, d, l, lo[l], hi[l]);
+		S += Eq;
+		if (l != j && l != k) rest += Eq;
+	}
+	double qq = 0.0, xp = 1.0, zp = 1.0;
+	for (int p = 1; p <= order; p++) {
+		xp *= x;
+		zp *= z;
+		qq += a.beta[1 + (p - 1) * d + j] * xp + a.beta[1 + (p - 1) * d + k] * zp;
+	}
+	if (threadIdx.x == 0) {
+		joint[g] = rest + qq + kern;
+		inter[g] = kint;
+	}
+	if (g == 0) {
+		const double F = sens_kernel_mean(a, N, d, red);
+		if (threadIdx.x == 0) *e0 = S + F;
+	}
+}
+
+size_t sens_pex2_elems(int N, int d) { return (size_t)2 * (size_t)(d * (d - 1) / 2) * N; }
+size_t sens_pair_part_elems(int N, int d) { const size_t nt = (size_t)((N + 63) / 64); return nt * nt * (size_t)(d * (d - 1) / 2); }
+
+hipError_t launch_sens_pair_prep(hipStream_t s, const double *prep, int N, int d, double *pex2)
+{
+	if (N < 1 || d < 2 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(sens_pair_prep_kernel, dim3((N + 255) / 256, 2, d - 1), dim3(256), 0, s, prep, N, d, pex2);
+	return hipGetLastError();
+}
+
+// the diagonal coordinate blocks, then (d > SENS_PB) the blocks Ja < Kb; Pw = nullptr: unweighted over the full square of
+// tiles, else weighted over the lower tiles (gamA, gamB not read, pex2 of context 0 on both sides)
+hipError_t launch_sens_pair_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pex2,
+                                  const double *cst, const double *Pw, double *part)
+{
+	if (N < 1 || d < 2 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	const int nt = (N + 63) / 64, nb = (d + SENS_PB - 1) / SENS_PB, noff = nb * (nb - 1) / 2;
+	const double *pa = pex2, *pb = Pw ? pex2 : pex2 + sens_pex2_elems(N, d) / 2;
+	if (Pw) {
+		const int ntl = nt * (nt + 1) / 2;
+		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, true>), dim3(ntl, 1, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+		if (noff)
+			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, true>), dim3(ntl, 1, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+	} else {
+		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, false>), dim3(nt, nt, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+		if (noff)
+			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, false>), dim3(nt, nt, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_sens_pair_finish(hipStream_t s, const double *part, int N, int d, int order, const double *gamA, const double *betaA,
+                                   double ampA, const double *gamB, const double *betaB, double ampB, const double *prep, const double *cst,
+                                   double *out)
+{
+	const int nt = (N + 63) / 64;
+	const SensSide a{gamA, betaA, prep, ampA}, b{gamB, betaB, prep + (size_t)5 * d * N, ampB};
+	hipLaunchKernelGGL(sens_pair_finish_kernel, dim3(d * (d - 1) / 2), dim3(256), 0, s, part, nt * nt, a, b, N, d, order, cst, out);
+	return hipGetLastError();
+}
+
+hipError_t launch_sens_pair_post_finish(hipStream_t s, const double *part, int N, int d, int nreg, double amp, const double *prep,
+                                        const double *cst, const double *G, const double *Q, double *out)
+{
+	const int nt = (N + 63) / 64;
+	hipLaunchKernelGGL(sens_pair_post_finish_kernel, dim3(d * (d - 1) / 2), dim3(256), 0, s, part, nt * (nt + 1) / 2, prep, G, Q, amp, N, d,
+	                   nreg, cst, out);
+	return hipGetLastError();
+}
+
+hipError_t launch_sens_joint(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
+                             const double *prep, const double *pex2, const double *cst, int j, int k, int npts, const double *xj,
+                             const double *xk, double *e0, double *joint, double *inter)
+{
+	if (npts < 1 || N < 1 || d < 2 || d > GPEMU_MAX_PARAMS || j < 0 || k <= j || k >= d) return hipErrorInvalidValue;
+	const SensSide a{gam, beta, prep, amp};
+	hipLaunchKernelGGL(sens_joint_kernel, dim3(npts), dim3(256), 0, s, X, a, pex2 + (size_t)sens_pair_index(j, k, d) * N, N, d, order, cst, j, k,
+	                   xj, xk, e0, joint, inter);
+	return hipGetLastError();
+}
+
 } // namespace gpemu

@@ -216,6 +216,65 @@ void emulator::QueryEmulatorMainEffectBands(const std::vector<double> &lo, const
 			}
 }
 
+void emulator::QueryEmulatorInteractions(const std::vector<double> &lo, const std::vector<double> &hi,
+                                         std::vector<std::vector<double> > &PairVariances, std::vector<std::vector<double> > &SecondOrder)
+{
+	check_box("QueryEmulatorInteractions", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params, np = d * (d - 1) / 2;
+	std::vector<double> v(no * np), in(no * np), e0(no), var(no), f(no * d), t(no * d);
+	emulate_sensitivity_pairs_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), v.data(), in.data());
+	emulate_sensitivity_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), e0.data(), var.data(), f.data(), t.data());
+	PairVariances.assign(no, std::vector<double>(np));
+	SecondOrder.assign(no, std::vector<double>(np));
+	for (size_t i = 0; i < no; i++)
+		for (size_t p = 0; p < np; p++) {
+			PairVariances[i][p] = v[i * np + p];
+			SecondOrder[i][p] = var[i] != 0.0 ? in[i * np + p] / var[i] : NAN;
+		}
+}
+
+void emulator::QueryEmulatorInteractionUncertainty(const std::vector<double> &lo, const std::vector<double> &hi,
+                                                   std::vector<std::vector<double> > &ExpectedPairVariances,
+                                                   std::vector<std::vector<double> > &ExpectedInteractions)
+{
+	check_box("QueryEmulatorInteractionUncertainty", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, d = (size_t)number_params, np = d * (d - 1) / 2;
+	std::vector<double> v(no * np), in(no * np);
+	emulate_sensitivity_pairs_uncertainty_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), v.data(), in.data());
+	ExpectedPairVariances.assign(no, std::vector<double>(np));
+	ExpectedInteractions.assign(no, std::vector<double>(np));
+	for (size_t i = 0; i < no; i++)
+		for (size_t p = 0; p < np; p++) {
+			ExpectedPairVariances[i][p] = v[i * np + p];
+			ExpectedInteractions[i][p] = in[i * np + p];
+		}
+}
+
+void emulator::QueryEmulatorInteractionSurface(const std::vector<double> &lo, const std::vector<double> &hi, int j, int k,
+                                               const std::vector<double> &gj, const std::vector<double> &gk, std::vector<double> &Means,
+                                               std::vector<std::vector<std::vector<double> > > &Joint,
+                                               std::vector<std::vector<std::vector<double> > > &Interaction)
+{
+	check_box("QueryEmulatorInteractionSurface", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, G = gj.size();
+	if (G < 1 || gk.size() != G) {
+		std::cerr << "Error::QueryEmulatorInteractionSurface called with grids that are empty or differ in length" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	std::vector<double> jt(G * G * no), it(G * G * no);
+	Means.assign(no, 0.0);
+	emulate_interaction_surface_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), j, k, (int)G, gj.data(), gk.data(), Means.data(),
+	                                  jt.data(), it.data());
+	Joint.assign(no, std::vector<std::vector<double> >(G, std::vector<double>(G)));
+	Interaction.assign(no, std::vector<std::vector<double> >(G, std::vector<double>(G)));
+	for (size_t i = 0; i < no; i++)
+		for (size_t a = 0; a < G; a++)
+			for (size_t b = 0; b < G; b++) {
+				Joint[i][a][b] = jt[(a * G + b) * no + i];
+				Interaction[i][a][b] = it[(a * G + b) * no + i];
+			}
+}
+
 double emulator::ValidateHoldout(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<double> > &Observations,
                                  std::vector<std::vector<double> > &Means, std::vector<std::vector<double> > &Variances,
                                  std::vector<std::vector<double> > &WhitenedErrors, std::vector<double> &Mahalanobis,

@@ -79,6 +79,22 @@ public:
 	void QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
 	                                  std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,
 	                                  std::vector<std::vector<std::vector<double> > > &Bands);
+	// second order (libemu.h: emulate_sensitivity_pairs_multi): pairs j < k of parameters at p = j (2 number_params - j - 1) / 2 +
+	// (k - j - 1).  Per output t: PairVariances[t][p] = V_jk = Var(E[output | x_j, x_k]) and SecondOrder[t][p] =
+	// (V_jk - V_j - V_k) / V, the second-order Sobol index (NaN where V = 0).  number_params >= 2.
+	void QueryEmulatorInteractions(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<std::vector<double> > &PairVariances,
+	                               std::vector<std::vector<double> > &SecondOrder);
+	// the emulator's own uncertainty about them (emulate_sensitivity_pairs_uncertainty_multi), in variance units:
+	// ExpectedPairVariances[t][p] = E*[V_jk], ExpectedInteractions[t][p] = E*[V_jk - V_j - V_k]
+	void QueryEmulatorInteractionUncertainty(const std::vector<double> &lo, const std::vector<double> &hi,
+	                                         std::vector<std::vector<double> > &ExpectedPairVariances,
+	                                         std::vector<std::vector<double> > &ExpectedInteractions);
+	// the two-way surface of parameters j != k on the grid gj x gk (equal lengths G): Joint[t][a][b] = E[output t | x_j = gj[a],
+	// x_k = gk[b]], Interaction[t][a][b] = Joint - main effect of j - main effect of k + E0, Means[t] = E0
+	void QueryEmulatorInteractionSurface(const std::vector<double> &lo, const std::vector<double> &hi, int j, int k, const std::vector<double> &gj,
+	                                     const std::vector<double> &gk, std::vector<double> &Means,
+	                                     std::vector<std::vector<std::vector<double> > > &Joint,
+	                                     std::vector<std::vector<std::vector<double> > > &Interaction);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -1317,6 +1317,84 @@ void emulate_main_effects_band(emulator_struct *e, const double *lo, const doubl
 	for (size_t i = 0; i < n; i++) sd[i] = sqrt(sd[i] > 0.0 ? sd[i] : 0.0);
 }
 
+/* second order (gpemu_sens_pairs / gpemu_sens_pairs_post / gpemu_sens_joint in gpemu.h): pairs j < k at
+ * p = j (2 d - j - 1) / 2 + (k - j - 1).  vpair[p] = V_jk = Var(E[m | x_j, x_k]), inter[p] = V_jk - V_j - V_k */
+void emulate_sensitivity_pairs(emulator_struct *e, const double *lo, const double *hi, double *vpair, double *inter)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_pairs");
+	const size_t d = (size_t)en->d;
+	check(en, gpemu_sens_pairs(en->ctx, en->ctx, lo, hi, vpair), "emulate_sensitivity_pairs");
+	double e0, var, *first = (double *)malloc(sizeof(double) * 2 * (d ? d : 1)), *total = first + d;
+	emulate_sensitivity(e, lo, hi, &e0, &var, first, total);
+	for (size_t j = 0, p = 0; j < d; j++)
+		for (size_t k = j + 1; k < d; k++, p++) inter[p] = vpair[p] - first[j] - first[k];
+	free(first);
+}
+
+/* the pair covariances in two halves, for one emulator or two on one design, as emulate_sensitivity_enqueue / _collect */
+void emulate_sensitivity_pairs_enqueue(emulator_struct *a, emulator_struct *b, const double *lo, const double *hi, void **dev_out)
+{
+	struct entry *ea = entry_of(a, "emulate_sensitivity_pairs"), *eb = b ? entry_of(b, "emulate_sensitivity_pairs") : ea;
+	const size_t npairs = (size_t)ea->d * ((size_t)ea->d - 1) / 2;
+	void *dev = NULL;
+	int rc = gpemu_dev_alloc(ea->ctx, (npairs ? npairs : 1) * sizeof(double), &dev);
+	if (!rc) rc = gpemu_sens_pairs_dev(ea->ctx, eb->ctx, lo, hi, (double *)dev);
+	if (rc && dev) (void)gpemu_dev_free(ea->ctx, dev);
+	check(ea, rc, "emulate_sensitivity_pairs");
+	*dev_out = dev;
+}
+
+void emulate_sensitivity_pairs_collect(emulator_struct *a, void *dev, double *cov_pair)
+{
+	struct entry *en = entry_of(a, "emulate_sensitivity_pairs");
+	const size_t npairs = (size_t)en->d * ((size_t)en->d - 1) / 2;
+	int rc = gpemu_dev_download(en->ctx, cov_pair, dev, npairs * sizeof(double));
+	if (!rc) rc = gpemu_dev_free(en->ctx, dev);
+	check(en, rc, "emulate_sensitivity_pairs");
+}
+
+/* s_pair[p] = S_u of emulate_sensitivity_post for u = {j, k} */
+void emulate_sensitivity_pairs_post(emulator_struct *e, const double *lo, const double *hi, double *s_pair)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_pairs_post");
+	check(en, gpemu_sens_pairs_post(en->ctx, lo, hi, s_pair), "emulate_sensitivity_pairs_post");
+}
+
+/* E*[V_jk] = V_jk + S_jk - S_none,  E*[V_jk - V_j - V_k] = V_jk - V_j - V_k + S_jk - S_j - S_k + S_none */
+void emulate_sensitivity_pairs_uncertainty(emulator_struct *e, const double *lo, const double *hi, double *evpair, double *einter)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_pairs_uncertainty");
+	const size_t d = (size_t)en->d, npairs = d * (d ? d - 1 : 0) / 2;
+	double *s = (double *)malloc(sizeof(double) * (2 + 2 * d + (npairs ? npairs : 1))), *sp = s + 2 + 2 * d;
+	emulate_sensitivity_pairs(e, lo, hi, evpair, einter);
+	emulate_sensitivity_post(e, lo, hi, s);
+	emulate_sensitivity_pairs_post(e, lo, hi, sp);
+	for (size_t j = 0, p = 0; j < d; j++)
+		for (size_t k = j + 1; k < d; k++, p++) {
+			evpair[p] += sp[p] - s[0];
+			einter[p] += sp[p] - s[2 + j] - s[2 + k] + s[0];
+		}
+	free(s);
+}
+
+/* the two-way surface of the pair (j, k) on the grid gj x gk (ngrid values each): joint[a * ngrid + b] = E[m | x_j = gj[a], x_k = gk[b]],
+ * inter the interaction effect joint - main_j - main_k + E0 in the same layout (may be NULL) */
+void emulate_interaction_surface(emulator_struct *e, const double *lo, const double *hi, int j, int k, int ngrid, const double *gj,
+                                 const double *gk, double *e0, double *joint, double *inter)
+{
+	struct entry *en = entry_of(e, "emulate_interaction_surface");
+	const size_t g = (size_t)(ngrid > 0 ? ngrid : 0), n = g * g;
+	double *xj = (double *)malloc(sizeof(double) * 2 * (n ? n : 1)), *xk = xj + n;
+	for (size_t a = 0; gj && gk && a < g; a++)
+		for (size_t b = 0; b < g; b++) {
+			xj[a * g + b] = gj[a];
+			xk[a * g + b] = gk[b];
+		}
+	const int rc = gpemu_sens_joint(en->ctx, lo, hi, j, k, (int)n, gj ? xj : NULL, gk ? xk : NULL, e0, joint, inter);
+	free(xj);
+	check(en, rc, "emulate_interaction_surface");
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

@@ -33,7 +33,7 @@ struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
 	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile;
-	int folds, foldsGiven, grid, uncertainty;
+	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
 static const char useage[] =
@@ -58,14 +58,18 @@ static const char useage[] =
 	"      integer per training point, the group it is left out with, 0 .. number of groups - 1, or -1 for never)\n"
 	"  --holdout, --folds and --groups exclude each other.\n"
 	"or\n"
-	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--uncertainty] [--pca_output] [--quiet]  (main effects and Sobol\n"
+	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--uncertainty] [--pairs] [--surface=j,k] [--pca_output] [--quiet]  (main effects and Sobol\n"
 	"      indices of the posterior mean, in closed form, for independent uniform inputs on a box: FILE holds one line \"lo hi\" per\n"
 	"      parameter, default the range of the design.  Per output one line: variance, the first-order indices, the total\n"
 	"      indices (NaN where the variance is 0); with --grid=G then, per output and parameter, the main-effect curve on G equally\n"
 	"      spaced values, followed by the mean.  --uncertainty adds the emulator's own uncertainty: after the index lines, per output\n"
 	"      one line with the posterior standard deviation of the mean, the box average of the posterior variance, the expected\n"
 	"      variance and the expected first-order and total indices; with --grid, under every curve a line with its posterior\n"
-	"      standard deviations.  Power-exponential covariance only)\n"
+	"      standard deviations.  --pairs appends, per output, one line with the second-order indices (V_jk - V_j - V_k) / V of the\n"
+	"      pairs of parameters (0,1), (0,2), .., (d-2,d-1) (NaN where the variance is 0), and with --uncertainty then, per output, one\n"
+	"      line with the expected interaction variances over the expected variance.  --surface=j,k with --grid=G appends, per output,\n"
+	"      G lines of G values: the interaction effect of parameters j and k on the grid, row a at the a-th value of parameter j.\n"
+	"      Power-exponential covariance only)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -414,6 +418,9 @@ static int sensitivity(struct cmdLineOpts *o)
 	const int nout = o->pcaOutputFlag ? model->nr : nt;
 	if (model->cov_fn_index > 1) return perr("sensitivity: the closed form exists for the power-exponential covariance only");
 	if (G < 0) return perr("--grid=G needs G >= 1");
+	if ((o->pairs || o->surface) && d < 2) return perr("--pairs and --surface need a model with two parameters or more");
+	if (o->surface && (G < 1 || o->surfJ == o->surfK || o->surfJ < 0 || o->surfK < 0 || o->surfJ >= d || o->surfK >= d))
+		return perr("--surface=j,k needs two different parameters of 0 .. d - 1, and --grid=G");
 	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
 	if (o->boxfile) {
 		FILE *bf = fopen(o->boxfile, "r");
@@ -486,6 +493,45 @@ static int sensitivity(struct cmdLineOpts *o)
 		}
 		free(grid); free(mainv); free(sdv);
 	}
+	if (o->pairs) {
+		/* per output one line of the d (d - 1) / 2 second-order indices; with --uncertainty then one line of E*[V_jk - V_j - V_k] / E*[V] */
+		const size_t np = (size_t)d * (d - 1) / 2;
+		double *vp = (double *)malloc(sizeof(double) * 2 * (size_t)nout * np), *in = vp + (size_t)nout * np;
+		emulate_sensitivity_pairs_multi(emu, o->pcaOutputFlag, lo, hi, vp, in);
+		for (int t = 0; t < nout; t++) {
+			for (size_t p = 0; p < np; p++) fprintf(out, "%s%.17g", p ? " " : "", var[t] != 0.0 ? in[(size_t)t * np + p] / var[t] : NAN);
+			fprintf(out, "\n");
+		}
+		if (o->uncertainty) {
+			double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
+			double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
+			emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
+			emulate_sensitivity_pairs_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, vp, in);
+			for (int t = 0; t < nout; t++) {
+				for (size_t p = 0; p < np; p++) fprintf(out, "%s%.17g", p ? " " : "", evar[t] != 0.0 ? in[(size_t)t * np + p] / evar[t] : NAN);
+				fprintf(out, "\n");
+			}
+			free(ve0); free(ef);
+		}
+		free(vp);
+	}
+	if (o->surface) {
+		/* per output G lines of G values: the interaction effect of the pair on the grid of the curves */
+		double *gj = (double *)malloc(sizeof(double) * 2 * (size_t)G), *gk = gj + G;
+		double *jt = (double *)malloc(sizeof(double) * 2 * (size_t)G * G * nout), *it = jt + (size_t)G * G * nout;
+		const int sj = o->surfJ, sk = o->surfK;
+		for (int g = 0; g < G; g++) {
+			gj[g] = G > 1 ? lo[sj] + g * (hi[sj] - lo[sj]) / (G - 1) : 0.5 * (lo[sj] + hi[sj]);
+			gk[g] = G > 1 ? lo[sk] + g * (hi[sk] - lo[sk]) / (G - 1) : 0.5 * (lo[sk] + hi[sk]);
+		}
+		emulate_interaction_surface_multi(emu, o->pcaOutputFlag, lo, hi, sj, sk, G, gj, gk, e0, jt, it);
+		for (int t = 0; t < nout; t++)
+			for (int a = 0; a < G; a++) {
+				for (int b = 0; b < G; b++) fprintf(out, "%s%.17g", b ? " " : "", it[((size_t)a * G + b) * nout + t]);
+				fprintf(out, "\n");
+			}
+		free(gj); free(jt);
+	}
 	fflush(out);
 	free(lo); free(hi); free(e0); free(var); free(first); free(total);
 	free_multi_emulator(emu);
@@ -545,6 +591,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"box", required_argument, NULL, 1007},               {"grid", required_argument, NULL, 1008},
 		/* ... and the emulator's own uncertainty about the indices and the curves */
 		{"uncertainty", no_argument, NULL, 1009},
+		/* ... second order: the indices of all pairs of parameters, the interaction effect of one pair on the grid */
+		{"pairs", no_argument, NULL, 1010},                   {"surface", required_argument, NULL, 1011},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -573,6 +621,11 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1007: o->boxfile = optarg; break;
 		case 1008: o->grid = atoi(optarg); if (o->grid < 1) o->grid = -1; break;
 		case 1009: o->uncertainty = 1; break;
+		case 1010: o->pairs = 1; break;
+		case 1011:
+			o->surface = 1;
+			if (sscanf(optarg, "%d,%d", &o->surfJ, &o->surfK) != 2) o->surfJ = o->surfK = -1;
+			break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;

@@ -332,6 +332,24 @@ void emulate_main_effects_var(emulator_struct *e, const double *lo, const double
                               double *var, double *var_e0);
 void emulate_main_effects_band(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
                                double *sd);
+/* extension: second-order Sobol indices and interaction surfaces in closed form (gpemu_sens_pairs / gpemu_sens_pairs_post /
+ * gpemu_sens_joint in gpemu.h).  total[j] > first[j] says that parameter j interacts; these say with which parameter.  Pairs j < k
+ * are numbered p = j (2 nparams - j - 1) / 2 + (k - j - 1), npairs = nparams (nparams - 1) / 2; nparams >= 2.
+ * emulate_sensitivity_pairs: vpair[p] = V_jk = Var(E[m | x_j, x_k]) and inter[p] = V_jk - V_j - V_k, the interaction variance (the
+ * second-order index is inter[p] / V).  _enqueue / _collect: the covariances Cov(E[m^a | x_j, x_k], E[m^b | x_j, x_k]) in two halves
+ * for one emulator (b = a or NULL) or two on the same design, as emulate_sensitivity_enqueue / _collect.
+ * emulate_sensitivity_pairs_post: s_pair[p] = S_u for u = {j, k}.  emulate_sensitivity_pairs_uncertainty: the posterior expectations
+ * evpair[p] = E*[V_jk] = V_jk + S_jk - S_none and einter[p] = E*[V_jk - V_j - V_k] = inter[p] + S_jk - S_j - S_k + S_none.
+ * emulate_interaction_surface: for one pair j != k and ngrid values of each coordinate, *e0, joint[a * ngrid + b] =
+ * E[m | x_j = gj[a], x_k = gk[b]] and inter[a * ngrid + b] = joint - main_j - main_k + E0, the interaction effect (may be NULL),
+ * summed without ever forming the large values it is the difference of. */
+void emulate_sensitivity_pairs(emulator_struct *e, const double *lo, const double *hi, double *vpair, double *inter);
+void emulate_sensitivity_pairs_enqueue(emulator_struct *a, emulator_struct *b, const double *lo, const double *hi, void **dev_out);
+void emulate_sensitivity_pairs_collect(emulator_struct *a, void *dev, double *cov_pair);
+void emulate_sensitivity_pairs_post(emulator_struct *e, const double *lo, const double *hi, double *s_pair);
+void emulate_sensitivity_pairs_uncertainty(emulator_struct *e, const double *lo, const double *hi, double *evpair, double *einter);
+void emulate_interaction_surface(emulator_struct *e, const double *lo, const double *hi, int j, int k, int ngrid, const double *gj,
+                                 const double *gk, double *e0, double *joint, double *inter);
 
 /* ---- multi_modelstruct.h / multivar_support.h ---------------------------------- */
 multi_modelstruct *alloc_multimodelstruct(gsl_matrix *xmodel_in, gsl_matrix *training_matrix_in, int cov_fn_index,
@@ -420,6 +438,18 @@ void emulate_sensitivity_uncertainty_multi(multi_emulator *emu, int pca_space, c
                                            double *imse_out, double *evar_out, double *efirst_out, double *etotal_out);
 void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
                                      double *e0_out, double *main_out, double *sd_out);
+/* second order per output: vpair_out, inter_out, evpair_out, einter_out are npairs values each, output-major, as
+ * emulate_sensitivity_pairs / _uncertainty define them.  Observable space exactly as for emulate_sensitivity_multi /
+ * _uncertainty_multi: the plug-in half keeps all cross terms between components, sum_{c,c'} B_tc B_tc' cov_pair(c, c') (every pair
+ * of components started before the first is collected); the S half takes the squared rule.  The surface is linear in the
+ * components: joint_out and inter_out (may be NULL) are (ngrid x ngrid) x (nr or nt), element ((a * ngrid + b) * nout + t), the
+ * training mean added to joint_out and e0_out and not to inter_out. */
+void emulate_sensitivity_pairs_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *vpair_out,
+                                     double *inter_out);
+void emulate_sensitivity_pairs_uncertainty_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *evpair_out,
+                                                 double *einter_out);
+void emulate_interaction_surface_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int j, int k, int ngrid,
+                                       const double *gj, const double *gk, double *e0_out, double *joint_out, double *inter_out);
 
 /* ---- libRbind/rbind.h: the batched likelihood entry point, R-free (rbind.c:626-724) ---------------- */
 void callEvalLhoodList(double *xmodel_in, int *nparams_in, double *pointList_in, int *nevalPoints_in,

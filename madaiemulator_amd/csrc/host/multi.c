@@ -819,6 +819,93 @@ void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const d
 	free(mp); free(vp); free(mc); free(vc); free(ep);
 }
 
+/* Second order for every output (libemu.h): vpair_out[t * npairs + p] = V_jk of output t, inter_out the interaction variances
+ * V_jk - V_j - V_k.  As emulate_sensitivity_multi: in observable space the full quadratic form over all pairs of components,
+ *   V_jk(y_t) = sum_{c,c'} B_tc B_tc' cov_pair(c, c'),
+ * every pair of components started before the first is collected; V_j and V_k from emulate_sensitivity_multi. */
+void emulate_sensitivity_pairs_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *vpair_out,
+                                     double *inter_out)
+{
+	const size_t nr = (size_t)emu->nr, nt = (size_t)emu->nt, d = (size_t)emu->nparams, w = d * (d ? d - 1 : 0) / 2;
+	const size_t ncomp = pca_space ? nr : nr * (nr + 1) / 2, nout = pca_space ? nr : nt;
+	void **dev = (void **)malloc(sizeof(void *) * ncomp);
+	double *cv = doubles(ncomp * (w ? w : 1));
+	size_t k = 0;
+	for (size_t c = 0; c < nr; c++)
+		for (size_t c2 = c; c2 < (pca_space ? c + 1 : nr); c2++)
+			emulate_sensitivity_pairs_enqueue(emu->emu_struct_array[c], emu->emu_struct_array[c2], lo, hi, &dev[k++]);
+	k = 0;
+	for (size_t c = 0; c < nr; c++)
+		for (size_t c2 = c; c2 < (pca_space ? c + 1 : nr); c2++, k++)
+			emulate_sensitivity_pairs_collect(emu->emu_struct_array[c], dev[k], cv + k * w);
+	if (pca_space) memcpy(vpair_out, cv, sizeof(double) * nr * w);
+	else
+		for (size_t t = 0; t < nt; t++) {
+			double *acc = vpair_out + t * w;
+			for (size_t i = 0; i < w; i++) acc[i] = 0.0;
+			k = 0;
+			for (size_t c = 0; c < nr; c++) {
+				const double bc = gsl_matrix_get(emu->model->pca_evecs_r, t, c) * sqrt(gsl_vector_get(emu->model->pca_evals_r, c));
+				for (size_t c2 = c; c2 < nr; c2++, k++) {
+					const double b2 = gsl_matrix_get(emu->model->pca_evecs_r, t, c2) * sqrt(gsl_vector_get(emu->model->pca_evals_r, c2));
+					const double f = (c2 == c ? 1.0 : 2.0) * bc * b2;
+					for (size_t i = 0; i < w; i++) acc[i] += f * cv[k * w + i];
+				}
+			}
+		}
+	double *e0 = doubles(nout), *var = doubles(nout), *first = doubles(nout * d), *total = doubles(nout * d);
+	emulate_sensitivity_multi(emu, pca_space, lo, hi, e0, var, first, total);
+	for (size_t t = 0; t < nout; t++)
+		for (size_t j = 0, p = 0; j < d; j++)
+			for (size_t k2 = j + 1; k2 < d; k2++, p++) inter_out[t * w + p] = vpair_out[t * w + p] - first[t * d + j] - first[t * d + k2];
+	free(dev); free(cv); free(e0); free(var); free(first); free(total);
+}
+
+/* The posterior expectations E*[V_jk] and E*[V_jk - V_j - V_k] of every output (libemu.h): the plug-in half from
+ * emulate_sensitivity_pairs_multi, cross terms and all; the S terms of the components through the SQUARED rule, as in
+ * emulate_sensitivity_uncertainty_multi. */
+void emulate_sensitivity_pairs_uncertainty_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *evpair_out,
+                                                 double *einter_out)
+{
+	const size_t nr = (size_t)emu->nr, d = (size_t)emu->nparams, np = d * (d ? d - 1 : 0) / 2, w = 2 + 2 * d + np;
+	const size_t nout = pca_space ? nr : (size_t)emu->nt;
+	double *sc = doubles(nr * w), *so = doubles(nout * w);
+	emulate_sensitivity_pairs_multi(emu, pca_space, lo, hi, evpair_out, einter_out);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_sensitivity_post(emu->emu_struct_array[c], lo, hi, sc + c * w);
+		emulate_sensitivity_pairs_post(emu->emu_struct_array[c], lo, hi, sc + c * w + 2 + 2 * d);
+	}
+	deliver(emu, pca_space, 1, 0, 1, w, sc, so);
+	for (size_t t = 0; t < nout; t++) {
+		const double *s = so + t * w, *sp = s + 2 + 2 * d;
+		for (size_t j = 0, p = 0; j < d; j++)
+			for (size_t k = j + 1; k < d; k++, p++) {
+				evpair_out[t * np + p] += sp[p] - s[0];
+				einter_out[t * np + p] += sp[p] - s[2 + j] - s[2 + k] + s[0];
+			}
+	}
+	free(sc); free(so);
+}
+
+/* the two-way surface of every output on the grid gj x gk: joint_out and inter_out (may be NULL) are (ngrid x ngrid) x (nr or nt),
+ * element ((a * ngrid + b) * nout + t); a conditional mean is linear in the components -- the mean half of the rule, the
+ * training mean added to joint and to e0_out; the interaction effect has none */
+void emulate_interaction_surface_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int j, int k, int ngrid,
+                                       const double *gj, const double *gk, double *e0_out, double *joint_out, double *inter_out)
+{
+	const size_t nr = (size_t)emu->nr, g = (size_t)(ngrid > 0 ? ngrid : 0), np = g * g;
+	double *jp = doubles(np * nr), *ip = doubles(np * nr), *jc = doubles(np ? np : 1), *ic = doubles(np ? np : 1), *ep = doubles(nr);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_interaction_surface(emu->emu_struct_array[c], lo, hi, j, k, ngrid, gj, gk, &ep[c], jc, ic);
+		place_component(jp, jc, np, nr, c, 1);
+		place_component(ip, ic, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 0, 1, np, 1, jp, joint_out);
+	if (inter_out) deliver(emu, pca_space, 0, 0, np, 1, ip, inter_out);
+	deliver(emu, pca_space, 0, 1, 1, 1, ep, e0_out);
+	free(jp); free(ip); free(jc); free(ic); free(ep);
+}
+
 static void one_point(multi_emulator *emu, gsl_vector *the_point, gsl_vector *the_mean, gsl_vector *the_variance, int pca_space)
 {
 	const int n = pca_space ? emu->nr : emu->nt;
