@@ -413,9 +413,11 @@ int gpemu_lgo_release(gpemu_ctx *ctx);
 
 /* ---- main effects and Sobol indices of the posterior mean, in closed form -----------------
  * Stands in for the reference's sensitivity analysis in R (src/libSA/sa-fns.R: the Oakley-O'Hagan integrals of a
- * squared-exponential emulator with a (1, x) regression).  One difference in the measure: the reference integrates against a
- * GAUSSIAN input measure, this integrates over a BOX -- independent uniform inputs on [lo_l, hi_l], the caller's box, which
- * may be narrower than the design or leave design points outside.  This is the plug-in analysis of the posterior mean; the
+ * squared-exponential emulator with a (1, x) regression).  The input measure is independent per coordinate and, by default,
+ * a BOX -- uniform inputs on [lo_l, hi_l], the caller's box, which may be narrower than the design or leave design points
+ * outside.  The reference integrates against a GAUSSIAN input measure: gpemu_sens_set_measure (below, after gpemu_sens_joint)
+ * makes any coordinate Gaussian, and lo_l / hi_l then mean its mean and standard deviation in every entry of this family.
+ * This is the plug-in analysis of the posterior mean; the
  * emulator-uncertainty terms of Oakley-O'Hagan are gpemu_sens_post's and gpemu_sens_main_var's, below.
  * The function analysed is the one gpemu_predict_mean evaluates, for the power-exponential covariance, without the k-vector
  * clamp:   m(x) = beta_0 + sum_l q_l(x_l) + A sum_i gamma_i prod_l k_l(x_il, x_l),   q_l(x) = sum_{p=1..order} beta_{p,l} x^p,
@@ -535,6 +537,37 @@ int gpemu_sens_joint(gpemu_ctx *ctx, const double *lo, const double *hi, int j, 
                      const double *xj, const double *xk /* npts each, host */, double *e0, double *joint /* npts */,
                      double *inter /* npts, may be NULL */);
 
+/* ---- the input measure of the sensitivity entries -----------------
+ * A property of the context, one kind per coordinate, as gpemu_set_mode is a property: no entry's signature changes.  The
+ * stored kinds decide how EVERY gpemu_sens_* entry (host and _dev) reads lo_l and hi_l:
+ *   GPEMU_MEASURE_UNIFORM   x_l uniform on [lo_l, hi_l]   (the default; the only measure before there was a switch)
+ *   GPEMU_MEASURE_GAUSS     x_l ~ N(lo_l, hi_l^2): lo_l is the MEAN, hi_l the STANDARD DEVIATION
+ * The coordinates stay independent.  With mean mu, variance sg^2, lengths s (context a) and t (b), a = x_il, b = x_i'l,
+ * D1 = 1 + s sg^2, D2 = 1 + (s + t) sg^2, a Gaussian coordinate's one-dimensional integrals are Gaussians themselves:
+ *   I_l(i)     = D1^-1/2 exp(-(s / D1) (a - mu)^2 / 2)
+ *   J^1 = I c,  J^2 = I (c^2 + v),  J^3 = I (c^3 + 3 c v),   c = (s sg^2 a + mu) / D1,  v = sg^2 / D1
+ *   II_l(i,i') = D2^-1/2 exp(-[s t sg^2 (a - b)^2 + s (a - mu)^2 + t (b - mu)^2] / (2 D2))
+ *   E x^n      : m_0 = 1, m_1 = mu, m_n = mu m_{n-1} + (n - 1) sg^2 m_{n-2}   (n <= 6)
+ *   UU_l       = (1 + 2 s sg^2)^-1/2      (the prior double integral of gpemu_sens_post / _main_var / _pairs_post)
+ * one exp and no erf; the three terms of II's exponent are all <= 0: no cancellation, no erfc case.  Everything is written in
+ * sg^2, so very wide and very narrow measures stay finite.  Everything downstream of these five (the finishes, P, the band,
+ * the leave-two-out products, the surfaces) does not know the measure.  A grid or surface value on a Gaussian coordinate is
+ * any finite real.  The N x N sweeps have three instantiations per shape: all uniform (the code as it was, the same bits
+ * as before the switch existed), all Gaussian (no erf code at all), and mixed (a branch per coordinate, uniform over a wave).
+ * gpemu_sens_set_measure(ctx, kind): d values, or NULL for all uniform.  gpemu_set_model resets the kinds to all uniform (d
+ * may change); gpemu_set_training, gpemu_predict_setup[_batch] and gpemu_sens_release keep them.  Errors: GPEMU_ERR_ARG for a
+ * NULL ctx (for gpemu_sens_get_measure also a NULL kind) or a kind outside {0, 1} (nothing is stored then);
+ * GPEMU_ERR_STATE before a model is set.
+ * Argument checks of the sensitivity entries under a measure, still before anything is allocated or launched: a uniform
+ * coordinate keeps its check (finite bounds, hi_l > lo_l); a Gaussian coordinate needs a finite mean and a finite standard
+ * deviation > 0 -- hi_l <= lo_l is accepted there; in the two-context entries the kinds of a and b must agree, else
+ * GPEMU_ERR_ARG.
+ * Not built: correlated Gaussian inputs (a full covariance matrix), truncated Gaussians, Matern kernels. */
+#define GPEMU_MEASURE_UNIFORM 0   /* x_l uniform on [lo_l, hi_l]            (the default) */
+#define GPEMU_MEASURE_GAUSS   1   /* x_l ~ N(lo_l, hi_l^2): lo_l is the MEAN, hi_l the STANDARD DEVIATION */
+int gpemu_sens_set_measure(gpemu_ctx *ctx, const int *kind /* d values, or NULL: all uniform */);
+int gpemu_sens_get_measure(const gpemu_ctx *ctx, int *kind /* d */);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */
@@ -585,6 +618,10 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_LGO     13  /* the three launches per chunk of gpemu_lgo[_dev], nbc groups padded to bp: gather (bytes = 8 nbc bp Np: the rows of Z written; it reads at most the lower tiles of L^-1 besides), staging (bytes = 8 nbc bp (2 bp + 64): the lower tiles read and written, right-hand-side and identity rows written), finish (bytes = 8 nbc bp (bp / 2 + 4)); the product and the factorisation report under GPEMU_PROF_GEMM / _LEAF / _POTRF */
 #define GPEMU_PROF_SENS    14  /* the three launches of gpemu_sens_cov[_dev] -- prep (flops = 88 N d: both contexts, two erf and two exp per point and coordinate counted as one flop each; bytes = 8 (10 N d + N d): the tables written, the design read), sweep (flops = N^2 (19 d + 2): per pair and coordinate one exp and two erf or erfc counted as one flop each among 16 others, then the 2 d + 1 sums; bytes = 8 T: the T = ceil(N / 64)^2 (2 d + 1) partial sums written), finish (flops = T, bytes = 8 T) -- and the two of gpemu_sens_main: prep, curves (flops = 6 N d ngrid, bytes = 16 d ngrid) */
 #define GPEMU_PROF_SENS_POST 15 /* the four launches of gpemu_sens_post[_dev], L = n (n + 1) / 2 lower tiles with n = ceil(N / 64) -- prep (as GPEMU_PROF_SENS), pmat (flops = L (128 nreg^2 + 4096 (2 nreg + 1)): G for the tile's 64 rows, then a product of length nreg per pair; bytes = 8 * 8192 L: the corner's tile read, P's written), weighted sweep (flops = 4096 L (20 d + 3): the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; bytes = 8 (4096 L + T'), T' = L (2 d + 2): P read, the partial sums written), finish (flops = T' + (2 d + 2) nreg (2 nreg + 4 N), bytes = 8 (T' + (2 d + 2) 3 N nreg)) -- and of gpemu_sens_main_var: prep, then per block of mb rows tvec (flops = 6 mb N, bytes = 8 mb' Np, mb' = mb rounded up to 64) and band finish (flops = mb (2 Np + 2 nreg^2), bytes = 8 mb (Np + 64)); the corner and the band's product report under GPEMU_PROF_GEMM */
+/* GPEMU_PROF_SENS*, under a measure (gpemu_sens_set_measure): in every sweep a GAUSSIAN coordinate's pair factor counts 12
+ * flops (one exp among 11 others) where a uniform one counts 19 (one exp and two erf or erfc among 16): 19 d above becomes
+ * 19 d_u + 12 d_g, and in the pair sweeps the 8 / 16 factors of a block are taken in the proportion d_u : d_g.  The prep and
+ * finish counts are kept as they are (a Gaussian coordinate's tables cost one exp, not two erf and two exp: an upper bound). */
 int gpemu_prof_begin(gpemu_ctx *ctx, int kernel_class);
 int gpemu_prof_end(gpemu_ctx *ctx, int *nlaunches, double *total_ms, double *flops, double *bytes);
 

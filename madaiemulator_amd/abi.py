@@ -25,6 +25,7 @@ PROF_LGO = 13
 PROF_SENS = 14
 PROF_SENS_POST = 15
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
+MEASURE_UNIFORM, MEASURE_GAUSS = 0, 1
 RESULT_RING = 4
 
 _dp = C.POINTER(C.c_double)
@@ -159,6 +160,8 @@ SYMBOLS = {
     "gpemu_sens_pairs_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "gpemu_sens_pairs_post_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_joint": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "gpemu_sens_set_measure": (C.c_int, [C.c_void_p, _ip]),
+    "gpemu_sens_get_measure": (C.c_int, [C.c_void_p, _ip]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -513,6 +516,23 @@ class Context:
 
     def sens_release(self):
         self._chk(self.L.gpemu_sens_release(self.h))
+
+    # the input measure of every sens_* entry: one kind per coordinate, MEASURE_UNIFORM (lo, hi: the bounds)
+    # or MEASURE_GAUSS (lo: the mean, hi: the standard deviation)
+    def sens_set_measure(self, kind=None):
+        """kind: d values of MEASURE_UNIFORM / MEASURE_GAUSS, or None for all uniform; set_model resets it"""
+        if kind is None:
+            self._chk(self.L.gpemu_sens_set_measure(self.h, None))
+            return
+        kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        if kind.size != self.d:
+            raise GpemuError(ERR_ARG, "sens_set_measure: one kind per coordinate")
+        self._chk(self.L.gpemu_sens_set_measure(self.h, kind.ctypes.data_as(_ip)))
+
+    def sens_get_measure(self):
+        kind = np.zeros(max(self.d, 1), dtype=np.int32)
+        self._chk(self.L.gpemu_sens_get_measure(self.h, kind.ctypes.data_as(_ip)))
+        return kind[:self.d].copy()
 
     # emulator uncertainty of the same quantities (DESIGN.md 4.15): S_u = E Var*[E[f | x_u]] of the posterior process f
     def sens_post(self, lo, hi):

@@ -394,6 +394,7 @@ extern "C" int gpemu_set_model(gpemu_ctx *ctx, int kind, int order, int N, int d
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	free_model(ctx);
+	std::fill(ctx->sens_kind, ctx->sens_kind + GPEMU_MAX_PARAMS, GPEMU_MEASURE_UNIFORM);   // d may change: the measure starts over
 	ctx->res_seq = 0;                       // batches of the previous model can no longer be collected (their sizes are gone)
 	ctx->kind = kind; ctx->order = order; ctx->N = N; ctx->d = d; ctx->nreg = nreg; ctx->nrhs = nreg + 1;
 	ctx->Np = round_up(N, LEAF);
@@ -2168,17 +2169,56 @@ static int sens_check(gpemu_ctx *a, gpemu_ctx *b, const double *lo, const double
 		return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts hold different designs");
 	if (a->order != b->order) return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts differ in their regression order");
 	const int d = a->d;
-	for (int l = 0; l < d; l++)
-		if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > lo[l]) || !std::isfinite(hi[l] - lo[l]))
+	int ngauss = 0;
+	for (int l = 0; l < d; l++) {
+		if (a->sens_kind[l] != b->sens_kind[l]) return fail(a, GPEMU_ERR_ARG, "sensitivity: the two contexts differ in their input measure");
+		if (a->sens_kind[l] == GPEMU_MEASURE_GAUSS) {
+			// lo: the mean, hi: the standard deviation
+			if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > 0.0))
+				return fail(a, GPEMU_ERR_ARG, "sensitivity: a Gaussian coordinate needs a finite mean and a finite standard deviation > 0");
+			ngauss++;
+		} else if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > lo[l]) || !std::isfinite(hi[l] - lo[l]))
 			return fail(a, GPEMU_ERR_ARG, "sensitivity: every bound must be finite, with hi > lo");
+	}
 	memset(bx, 0, sizeof *bx);
 	bx->d = d;
+	bx->meas = ngauss == 0 ? 0 : (ngauss == d ? 1 : 2);
 	for (int l = 0; l < d; l++) {
+		bx->kind[l] = a->sens_kind[l];
 		bx->s[l] = 2.0 * a->pred_cov.w[l] * a->pred_cov.w[l];      // w = sqrt(1/2) e^-theta: s = e^(-2 theta)
 		bx->t[l] = 2.0 * b->pred_cov.w[l] * b->pred_cov.w[l];
 		bx->lo[l] = lo[l];
 		bx->hi[l] = hi[l];
 	}
+	return GPEMU_OK;
+}
+
+// flops of the pair factors of one pair of points (the rule at GPEMU_PROF_SENS*): a uniform coordinate's is one exp and two
+// erf / erfc among 16 flops, 19; a Gaussian one's is one exp among 11, 12.  ncoord: how many factors the pair evaluates (d in
+// the sweep of gpemu_sens_cov; the blocks' 8 and 16 in the pair sweep), taken in the kinds' proportion
+static double sens_pair_flops(const SensBox &bx, double ncoord)
+{
+	int ng = 0;
+	for (int l = 0; l < bx.d; l++) ng += bx.kind[l] == GPEMU_MEASURE_GAUSS;
+	return ncoord * (19.0 * (bx.d - ng) + 12.0 * ng) / bx.d;
+}
+
+extern "C" int gpemu_sens_set_measure(gpemu_ctx *ctx, const int *kind)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	if (!ctx->dX) return fail(ctx, GPEMU_ERR_STATE, "model not set");
+	for (int l = 0; kind && l < ctx->d; l++)
+		if (kind[l] != GPEMU_MEASURE_UNIFORM && kind[l] != GPEMU_MEASURE_GAUSS)
+			return fail(ctx, GPEMU_ERR_ARG, "sensitivity: a measure kind is GPEMU_MEASURE_UNIFORM or GPEMU_MEASURE_GAUSS");
+	for (int l = 0; l < ctx->d; l++) ctx->sens_kind[l] = kind ? kind[l] : GPEMU_MEASURE_UNIFORM;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sens_get_measure(const gpemu_ctx *ctx, int *kind)
+{
+	if (!ctx || !kind) return GPEMU_ERR_ARG;
+	if (!ctx->dX) return GPEMU_ERR_STATE;
+	std::copy(ctx->sens_kind, ctx->sens_kind + ctx->d, kind);
 	return GPEMU_OK;
 }
 
@@ -2197,7 +2237,7 @@ static int sens_prep(gpemu_ctx *a, const SensBox &bx, int cls = GPEMU_PROF_SENS)
 {
 	const int N = a->N, d = a->d;
 	int rc = grow(a, a->dSensPrep, sens_prep_elems(N, d));
-	if (!rc) rc = grow(a, a->dSensCst, (size_t)SENS_CST * GPEMU_MAX_PARAMS);
+	if (!rc) rc = grow(a, a->dSensCst, (size_t)SENS_CST_ROWS * GPEMU_MAX_PARAMS);
 	if (rc) return rc;
 	// per point and coordinate of either context two erf and two exp with some forty flops around them; the tables out
 	ProfScope ps(a, cls, 2.0 * N * d * 44.0, 8.0 * ((double)sens_prep_elems(N, d) + (double)N * d));
@@ -2219,8 +2259,8 @@ extern "C" int gpemu_sens_cov_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo, 
 	const double *gamA = a->dLinvAug + (size_t)Np * Np, *gamB = b->dLinvAug + (size_t)Np * Np;
 	{
 		// per pair and coordinate: one exp and two erf / erfc (counted as one flop each) among 16 flops, then 2 (2 d + 1) for the sums
-		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (19.0 * d + 2.0), 8.0 * (double)sens_part_elems(N, d));
-		HIPCHK(a, launch_sens_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPrep, a->dSensCst, a->dSensPart));
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (sens_pair_flops(bx, d) + 2.0), 8.0 * (double)sens_part_elems(N, d));
+		HIPCHK(a, launch_sens_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPrep, a->dSensCst, bx.meas, a->dSensPart));
 	}
 	{
 		ProfScope ps(a, GPEMU_PROF_SENS, (double)sens_part_elems(N, d), 8.0 * (double)sens_part_elems(N, d));
@@ -2401,8 +2441,9 @@ extern "C" int gpemu_sens_post_dev(gpemu_ctx *ctx, const double *lo, const doubl
 	}
 	{
 		// the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; P read, the sums written
-		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (20.0 * d + 3.0), 8.0 * (ntl * 4096.0 + (double)npart));
-		HIPCHK(ctx, launch_sens_sweep_weighted(ctx->stream, ctx->dX, N, d, ctx->dSensPrep, ctx->dSensCst, ctx->dSensP, ctx->dSensPostPart));
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (sens_pair_flops(bx, d) + d + 3.0), 8.0 * (ntl * 4096.0 + (double)npart));
+		HIPCHK(ctx, launch_sens_sweep_weighted(ctx->stream, ctx->dX, N, d, ctx->dSensPrep, ctx->dSensCst, bx.meas, ctx->dSensP,
+		                                       ctx->dSensPostPart));
 	}
 	{
 		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, (double)npart + (2.0 * d + 2.0) * nreg * (2.0 * nreg + 4.0 * N),
@@ -2539,8 +2580,8 @@ extern "C" int gpemu_sens_pairs_dev(gpemu_ctx *a, gpemu_ctx *b, const double *lo
 	{
 		// per pair of points: the II values of gpemu_sens_cov (19 flops each) for 8 coordinates per diagonal block and 16 per
 		// other block, then 3 flops per pair of coordinates (both launches under one scope when d > 8)
-		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (19.0 * nii + 3.0 * npairs), 8.0 * (double)sens_pair_part_elems(N, d));
-		HIPCHK(a, launch_sens_pair_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPex2, a->dSensCst, nullptr, a->dSensPairPart));
+		ProfScope ps(a, GPEMU_PROF_SENS, (double)N * N * (sens_pair_flops(bx, nii) + 3.0 * npairs), 8.0 * (double)sens_pair_part_elems(N, d));
+		HIPCHK(a, launch_sens_pair_sweep(a->stream, a->dX, N, d, gamA, gamB, a->dSensPex2, a->dSensCst, bx.meas, nullptr, a->dSensPairPart));
 	}
 	{
 		ProfScope ps(a, GPEMU_PROF_SENS, (double)sens_pair_part_elems(N, d), 8.0 * (double)sens_pair_part_elems(N, d));
@@ -2595,9 +2636,9 @@ extern "C" int gpemu_sens_pairs_post_dev(gpemu_ctx *ctx, const double *lo, const
 		HIPCHK(ctx, launch_sens_pmat(ctx->stream, ctx->dS, (long)ctx->S_dim, Rp, Q, N, nreg, ctx->dSensG, ctx->dSensP));
 	}
 	{
-		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (20.0 * nii + 3.0 * npairs),
+		ProfScope ps(ctx, GPEMU_PROF_SENS_POST, ntl * 4096.0 * (sens_pair_flops(bx, nii) + nii + 3.0 * npairs),
 		             8.0 * ntl * (4096.0 * nb * (nb + 1.0) / 2.0 + npairs));
-		HIPCHK(ctx, launch_sens_pair_sweep(ctx->stream, ctx->dX, N, d, nullptr, nullptr, ctx->dSensPex2, ctx->dSensCst, ctx->dSensP,
+		HIPCHK(ctx, launch_sens_pair_sweep(ctx->stream, ctx->dX, N, d, nullptr, nullptr, ctx->dSensPex2, ctx->dSensCst, bx.meas, ctx->dSensP,
 		                                   ctx->dSensPairPart));
 	}
 	{

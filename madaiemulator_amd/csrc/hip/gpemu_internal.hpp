@@ -43,13 +43,20 @@ struct CovParams {
 
 // The box and the two contexts' squared inverse lengths s_l = exp(-2 theta_{2+l}) of a sensitivity call, handed to its
 // prep kernel by value (kernels_sens.hip); SENS_CST: rows of the per-coordinate constants that kernel leaves for the sweep
+// kind[l]: the input measure of coordinate l (GPEMU_MEASURE_*: for a Gaussian one lo is the mean and hi the standard
+// deviation); meas: 0 every coordinate uniform, 1 every coordinate Gaussian, 2 both kinds (the sweeps' MEAS parameter)
 struct SensBox {
 	int d;
-	int pad_;
+	int meas;
 	double s[GPEMU_MAX_PARAMS], t[GPEMU_MAX_PARAMS];
 	double lo[GPEMU_MAX_PARAMS], hi[GPEMU_MAX_PARAMS];
+	int kind[GPEMU_MAX_PARAMS];
 };
+// rows 0 .. SENS_CST - 1 are what a sweep's pair factor reads (the all-uniform and the all-Gaussian sweep stage these alone),
+// row SENS_CST_KIND the coordinate's kind (0.0 / 1.0; the mixed sweep stages it too), row SENS_CST_S the squared inverse
+// length s of context a itself (the one-context finishes of a Gaussian coordinate: row 0 no longer holds s / 2 there)
 constexpr int SENS_CST = 7;
+constexpr int SENS_CST_KIND = 7, SENS_CST_S = 8, SENS_CST_ROWS = 9;
 
 // C[m x n] = beta*C + alpha * A[m x K] * B[n x K]^T over k in [k0,k1)
 struct GemmArgs {
@@ -324,6 +331,9 @@ struct gpemu_ctx {
 	// pair sweeps' partial sums (npairs per tile), dSensPairOut the npairs results of the host entries
 	gpemu::DevBuf<double> dSensPex2, dSensPairPart, dSensPairOut;
 	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
+	// the input measure of the sensitivity entries per coordinate (gpemu_sens_set_measure): GPEMU_MEASURE_*,
+	// all uniform from gpemu_set_model on; kept by gpemu_set_training, the prediction set-ups and gpemu_sens_release
+	int sens_kind[GPEMU_MAX_PARAMS] = {};
 	gpemu::DevBuf<double> dS;    // corners of (Rp+Np)^2 for explicit inverse / gradient (one per batch element in flight)
 	size_t S_dim = 0;            // their side and leading dimension
 
@@ -476,13 +486,13 @@ hipError_t launch_lgo_finish(hipStream_t s, const double *T, long tstride, int n
                              double *mean, double *var, double *werr, double *stat, int *info_out);
 
 // ---- kernels_sens.hip: closed-form sensitivity analysis of the posterior mean
-// prep: sens_prep_elems doubles, table q (I, J^1, J^2, J^3, Pex) of context c at ((c * 5 + q) * d + l) * N + i; cst: SENS_CST
-// rows of GPEMU_MAX_PARAMS; part: sens_part_elems doubles, 2 d + 1 sums per 64 x 64 tile; out: e0a, e0b, cov_all, first[d], rest[d]
+// prep: sens_prep_elems doubles, table q (I, J^1, J^2, J^3, Pex) of context c at ((c * 5 + q) * d + l) * N + i; cst: SENS_CST_ROWS
+// rows of GPEMU_MAX_PARAMS; meas: SensBox::meas of the call, which picks the sweep's instantiation; part: sens_part_elems doubles, 2 d + 1 sums per 64 x 64 tile; out: e0a, e0b, cov_all, first[d], rest[d]
 size_t sens_prep_elems(int N, int d);
 size_t sens_part_elems(int N, int d);
 hipError_t launch_sens_prep(hipStream_t s, const double *X, int N, const SensBox &bx, double *prep, double *cst);
 hipError_t launch_sens_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *prep,
-                             const double *cst, double *part);
+                             const double *cst, int meas, double *part);
 hipError_t launch_sens_finish(hipStream_t s, const double *part, int N, int d, int order, const double *gamA, const double *betaA,
                               double ampA, const double *gamB, const double *betaB, double ampB, const double *prep, const double *cst,
                               double *out);
@@ -493,8 +503,8 @@ hipError_t launch_sens_main(hipStream_t s, const double *X, int N, int d, int or
 // sens_post_part_elems doubles, 2 d + 2 sums per lower tile; out: s_none, s_all, first[d], rest[d]
 size_t sens_post_part_elems(int N, int d);
 hipError_t launch_sens_pmat(hipStream_t s, const double *S, long lds, int Rp, const double *Q, int N, int nreg, double *G, double *Pw);
-hipError_t launch_sens_sweep_weighted(hipStream_t s, const double *X, int N, int d, const double *prep, const double *cst, const double *Pw,
-                                      double *part);
+hipError_t launch_sens_sweep_weighted(hipStream_t s, const double *X, int N, int d, const double *prep, const double *cst, int meas,
+                                      const double *Pw, double *part);
 hipError_t launch_sens_post_finish(hipStream_t s, const double *part, int N, int d, int order, int nreg, double amp, const double *prep,
                                    const double *cst, const double *G, const double *Q, double *out);
 // the band: rows r0 .. r0 + mb of the d ngrid + 1 into Kq (mbp rows of Np); then the finish over V = Kq LinvAug^T
@@ -509,7 +519,7 @@ size_t sens_pex2_elems(int N, int d);
 size_t sens_pair_part_elems(int N, int d);
 hipError_t launch_sens_pair_prep(hipStream_t s, const double *prep, int N, int d, double *pex2);
 hipError_t launch_sens_pair_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pex2,
-                                  const double *cst, const double *Pw, double *part);
+                                  const double *cst, int meas, const double *Pw, double *part);
 hipError_t launch_sens_pair_finish(hipStream_t s, const double *part, int N, int d, int order, const double *gamA, const double *betaA,
                                    double ampA, const double *gamB, const double *betaB, double ampB, const double *prep, const double *cst,
                                    double *out);

@@ -6,6 +6,8 @@
 // No atomics, no workgroup waits for another; every sum has one order, so two calls return the same bits.
 // Second half: the emulator uncertainty of the same quantities (gpemu_sens_post / gpemu_sens_main_var) -- the
 // sweep again, weighted by an element of P = C^-1 - W Q W^T per pair, and the confidence band of the main-effect curves.
+// The input measure (gpemu_sens_set_measure) is per coordinate: uniform on [lo, hi] or Gaussian N(lo, hi^2).
+// It enters the per-point tables, the pair factor II_l, the moments E x^p and the prior double integral UU_l, nothing else.
 #include "gpemu_internal.hpp"
 
 #include <cmath>
@@ -43,7 +45,13 @@ __device__ __forceinline__ double block_sum(double v, double *red)
 //   I_l(i), J^1_l(i), J^2_l(i), J^3_l(i)  = (1/w_l) int x^p k_l(x_il, x) dx,  and  Pex_l(i) = prod_{l' != l} I_l'(i)
 // (prefix and suffix products, no division), table q of context c at prep + ((c * 5 + q) * d + l) * N + i.
 // J^p by  s int x^p k = s x_i int x^{p-1} k + (p-1) int x^{p-2} k - [x^{p-1} k]_lo^hi.
-// Workgroup (0, 0) also leaves the sweep's per-coordinate constants (SENS_CST rows of GPEMU_MAX_PARAMS) in cst.
+// Workgroup (0, 0) also leaves the sweep's per-coordinate constants (SENS_CST_ROWS rows of GPEMU_MAX_PARAMS) in cst.
+// A Gaussian coordinate, x ~ N(mu, sg^2) (mu = lo, sg = hi), with D1 = 1 + s sg^2 and D2 = 1 + (s + t) sg^2:
+//   I = D1^-1/2 exp(-(s / D1) (x_i - mu)^2 / 2),   J^1 = I c,  J^2 = I (c^2 + v),  J^3 = I (c^3 + 3 c v),
+//   c = (s sg^2 x_i + mu) / D1,  v = sg^2 / D1  -- mean and variance of the product of the kernel and the density --
+// and the same seven rows of cst hold the Gaussian pair factor's constants:
+//   II = D2^-1/2 exp(-[h (x - x')^2 + fa (x - mu)^2 + fb (x' - mu)^2] / 2),   h = s t sg^2 / D2,  fa = s / D2,  fb = t / D2.
+// Everything is written in sg^2, so a very wide and a very narrow measure stay finite.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sens_prep_kernel(const double *X, int N, SensBox bx, double *prep, double *cst)
 {
@@ -51,19 +59,43 @@ __global__ __launch_bounds__(256) void sens_prep_kernel(const double *X, int N, 
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (blockIdx.x == 0 && c == 0 && threadIdx.x < d) {
 		const int l = threadIdx.x;
-		const double s = bx.s[l], t = bx.t[l], st = s + t, al = sqrt(0.5 * st);
-		cst[0 * GPEMU_MAX_PARAMS + l] = s * t / st;                               // h: exp(-h (x - x')^2 / 2)
-		cst[1 * GPEMU_MAX_PARAMS + l] = s / st;                                   // c = fa x + fb x'
-		cst[2 * GPEMU_MAX_PARAMS + l] = t / st;
-		cst[3 * GPEMU_MAX_PARAMS + l] = al;
-		cst[4 * GPEMU_MAX_PARAMS + l] = sqrt(M_PI / (2.0 * st)) / (bx.hi[l] - bx.lo[l]);
-		cst[5 * GPEMU_MAX_PARAMS + l] = bx.lo[l];
-		cst[6 * GPEMU_MAX_PARAMS + l] = bx.hi[l];
+		if (bx.kind[l] == GPEMU_MEASURE_GAUSS) {
+			const double s = bx.s[l], t = bx.t[l], mu = bx.lo[l], sg = bx.hi[l], D2 = 1.0 + (s + t) * (sg * sg);
+			cst[0 * GPEMU_MAX_PARAMS + l] = s * t * (sg * sg) / D2;                   // h
+			cst[1 * GPEMU_MAX_PARAMS + l] = s / D2;                                   // fa
+			cst[2 * GPEMU_MAX_PARAMS + l] = t / D2;                                   // fb
+			cst[3 * GPEMU_MAX_PARAMS + l] = 0.0;
+			cst[4 * GPEMU_MAX_PARAMS + l] = 1.0 / sqrt(D2);
+			cst[5 * GPEMU_MAX_PARAMS + l] = mu;
+			cst[6 * GPEMU_MAX_PARAMS + l] = sg;
+		} else {
+			const double s = bx.s[l], t = bx.t[l], st = s + t, al = sqrt(0.5 * st);
+			cst[0 * GPEMU_MAX_PARAMS + l] = s * t / st;                               // h: exp(-h (x - x')^2 / 2)
+			cst[1 * GPEMU_MAX_PARAMS + l] = s / st;                                   // c = fa x + fb x'
+			cst[2 * GPEMU_MAX_PARAMS + l] = t / st;
+			cst[3 * GPEMU_MAX_PARAMS + l] = al;
+			cst[4 * GPEMU_MAX_PARAMS + l] = sqrt(M_PI / (2.0 * st)) / (bx.hi[l] - bx.lo[l]);
+			cst[5 * GPEMU_MAX_PARAMS + l] = bx.lo[l];
+			cst[6 * GPEMU_MAX_PARAMS + l] = bx.hi[l];
+		}
+		cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + l] = bx.kind[l] == GPEMU_MEASURE_GAUSS ? 1.0 : 0.0;
+		cst[SENS_CST_S * GPEMU_MAX_PARAMS + l] = bx.s[l];
 	}
 	if (i >= N) return;
 	double *tab = prep + (long)c * 5 * d * N + i;
 	const long q = (long)d * N;                                                   // one table
 	for (int l = 0; l < d; l++) {
+		if (bx.kind[l] == GPEMU_MEASURE_GAUSS) {
+			const double s = c ? bx.t[l] : bx.s[l], mu = bx.lo[l], v2 = bx.hi[l] * bx.hi[l], D1 = 1.0 + s * v2;
+			const double x = X[(long)i * d + l], dm = x - mu;
+			const double I0 = exp(-0.5 * (s / D1) * dm * dm) / sqrt(D1);
+			const double cm = (s * v2 * x + mu) / D1, v = v2 / D1;
+			tab[0 * q + (long)l * N] = I0;
+			tab[1 * q + (long)l * N] = I0 * cm;
+			tab[2 * q + (long)l * N] = I0 * (cm * cm + v);
+			tab[3 * q + (long)l * N] = I0 * (cm * (cm * cm + 3.0 * v));
+			continue;
+		}
 		const double s = c ? bx.t[l] : bx.s[l], lo = bx.lo[l], hi = bx.hi[l], w = hi - lo;
 		const double x = X[(long)i * d + l], r = sqrt(0.5 * s);
 		const double K0 = sqrt(M_PI / (2.0 * s)) * erf_diff(r * (lo - x), r * (hi - x));
@@ -108,8 +140,26 @@ __global__ __launch_bounds__(256) void sens_prep_kernel(const double *X, int N, 
 // sens_lower_tile), whose sums count twice off the diagonal, and one sum more per tile, the rank-one
 // sum P_ii' prod_l I_l(i) prod_l I_l(i') at index 2 d + 1.  gamA and gamB are not read.  Everything weighted sits under
 // `if constexpr`: the unweighted instantiation is the kernel it was before there was a second one.
+// MEAS: 0 every coordinate uniform -- the code above, as it was; 1 every coordinate Gaussian -- the pair
+// factor is pref_l exp(-[h_l (x - x')^2 + fa_l (x - mu_l)^2 + fb_l (x' - mu_l)^2] / 2), one exp of three terms <= 0, and the
+// instantiation holds no erf or erfc code; 2 both kinds -- a branch per coordinate on its kind, which is the same for every
+// lane (the coordinate index is), with the kind row of cst staged beside the seven others.
 // ---------------------------------------------------------------------------
 constexpr int SENS_CHUNK = 16;
+
+// the pair factor II_l of one coordinate from its seven constants c0 .. c6 (rows 0 .. 6 of cst) and, MEAS = 2, its kind
+template <int MEAS>
+__device__ __forceinline__ double sens_pair_factor(double xa, double xb, double c0, double c1, double c2, double c3, double c4, double c5,
+                                                   double c6, double kind)
+{
+	const double dx = xa - xb;
+	if (MEAS == 1 || (MEAS == 2 && kind != 0.0)) {
+		const double da = xa - c5, db = xb - c5;
+		return c4 * exp(-0.5 * fma(c0 * dx, dx, fma(c1 * da, da, c2 * db * db)));
+	}
+	const double c = c1 * xa + c2 * xb;
+	return exp(-0.5 * c0 * dx * dx) * c4 * erf_diff(c3 * (c5 - c), c3 * (c6 - c));
+}
 
 // lower tile t = tr (tr + 1) / 2 + tc, tc <= tr, of a launch over the lower 64 x 64 tiles alone
 __device__ __forceinline__ void sens_lower_tile(int t, int &tr, int &tc)
@@ -121,21 +171,22 @@ __device__ __forceinline__ void sens_lower_tile(int t, int &tr, int &tc)
 	tc = t - r * (r + 1) / 2;
 }
 
-template <int DM, bool WEIGHTED>
+template <int DM, bool WEIGHTED, int MEAS>
 __global__ __launch_bounds__(256) void sens_sweep_kernel(const double *X, int N, int d, const double *gamA, const double *gamB,
                                                          const double *prepA, const double *prepB, const double *cst, double *part,
                                                          const double *Pw)
 {
 	constexpr int UN = DM <= 16 ? DM : 1;
 	constexpr int RS = 2 * DM + 1 + (WEIGHTED ? 1 : 0);                           // sums a wave leaves in red
-	__shared__ double cst_s[SENS_CST * DM];
+	constexpr int CR = MEAS == 2 ? SENS_CST_KIND + 1 : SENS_CST;                  // rows of cst staged: the mixed form reads the kind
+	__shared__ double cst_s[CR * DM];
 	__shared__ double xb_s[SENS_CHUNK * DM], wr_s[SENS_CHUNK * DM], wf_s[SENS_CHUNK * DM], gb_s[SENS_CHUNK];
 	__shared__ double red[4 * RS];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	int tr = blockIdx.y, tc = blockIdx.x;
 	if constexpr (WEIGHTED) sens_lower_tile(blockIdx.x, tr, tc);
 	const long q = (long)d * N;
-	for (int e = tid; e < SENS_CST * d; e += 256) cst_s[(e / d) * DM + e % d] = cst[(e / d) * GPEMU_MAX_PARAMS + e % d];
+	for (int e = tid; e < CR * d; e += 256) cst_s[(e / d) * DM + e % d] = cst[(e / d) * GPEMU_MAX_PARAMS + e % d];
 	const int row = tr * 64 + lane;
 	const bool rowv = row < N;
 	const int dl = DM <= 16 ? DM : d;                                             // (the unrolled forms run to DM under a guard: no early exit)
@@ -183,10 +234,17 @@ __global__ __launch_bounds__(256) void sens_sweep_kernel(const double *X, int N,
 #pragma unroll UN
 			for (int l = 0; l < dl; l++) {
 				if (l >= d) continue;
-				const double dx = xr[l] - xc[l];
-				const double c = cst_s[1 * DM + l] * xr[l] + cst_s[2 * DM + l] * xc[l], al = cst_s[3 * DM + l];
-				const double v = exp(-0.5 * cst_s[0 * DM + l] * dx * dx) * cst_s[4 * DM + l] *
-				                 erf_diff(al * (cst_s[5 * DM + l] - c), al * (cst_s[6 * DM + l] - c));
+				double v;
+				if constexpr (MEAS == 0) {
+					const double dx = xr[l] - xc[l];
+					const double c = cst_s[1 * DM + l] * xr[l] + cst_s[2 * DM + l] * xc[l], al = cst_s[3 * DM + l];
+					v = exp(-0.5 * cst_s[0 * DM + l] * dx * dx) * cst_s[4 * DM + l] *
+					    erf_diff(al * (cst_s[5 * DM + l] - c), al * (cst_s[6 * DM + l] - c));
+				} else {
+					v = sens_pair_factor<MEAS>(xr[l], xc[l], cst_s[0 * DM + l], cst_s[1 * DM + l], cst_s[2 * DM + l], cst_s[3 * DM + l],
+					                           cst_s[4 * DM + l], cst_s[5 * DM + l], cst_s[6 * DM + l],
+					                           MEAS == 2 ? cst_s[(CR - 1) * DM + l] : 0.0);
+				}
 				a[l] = v;
 				pre[l] = run;
 				run *= v;
@@ -267,11 +325,35 @@ __device__ __forceinline__ double sens_moment(double lo, double hi, int p)
 	return (a - b) / ((p + 1) * (hi - lo));
 }
 
+// E x_l^p under the measure of coordinate l, from the rows of cst: the box's moment above, or for a Gaussian coordinate
+// m_0 = 1, m_1 = mu, m_n = mu m_{n-1} + (n - 1) sg^2 m_{n-2}
+__device__ __forceinline__ double sens_moment(const double *cst, int l, int p)
+{
+	const double lo = cst[5 * GPEMU_MAX_PARAMS + l], hi = cst[6 * GPEMU_MAX_PARAMS + l];
+	if (cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + l] != 0.0) {
+		double m0 = 1.0, m1 = lo;
+		for (int n = 2; n <= p; n++) {
+			const double m = fma(lo, m1, (n - 1) * (hi * hi) * m0);
+			m0 = m1;
+			m1 = m;
+		}
+		return p ? m1 : m0;
+	}
+	return sens_moment(lo, hi, p);
+}
+
+// the squared inverse length s_l of a one-context call: a uniform coordinate keeps 2 (s t / (s + t)) of row 0 (s = t: s / 2),
+// a Gaussian one, whose row 0 holds something else, takes the row of its own
+__device__ __forceinline__ double sens_len(const double *cst, int l)
+{
+	return cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + l] != 0.0 ? cst[SENS_CST_S * GPEMU_MAX_PARAMS + l] : 2.0 * cst[l];
+}
+
 // E q_l of the side whose polynomial coefficients are beta
-__device__ __forceinline__ double sens_eq(const double *beta, int order, int d, int l, double lo, double hi)
+__device__ __forceinline__ double sens_eq(const double *beta, int order, int d, int l, const double *cst)
 {
 	double v = 0.0;
-	for (int p = 1; p <= order; p++) v = fma(beta[1 + (p - 1) * d + l], sens_moment(lo, hi, p), v);
+	for (int p = 1; p <= order; p++) v = fma(beta[1 + (p - 1) * d + l], sens_moment(cst, l, p), v);
 	return v;
 }
 
@@ -302,14 +384,13 @@ __global__ __launch_bounds__(256) void sens_finish_kernel(const double *part, in
 {
 	__shared__ double red[256];
 	const int k = blockIdx.x, np = 2 * d + 1;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
 	double kk = 0.0;
 	for (int t = threadIdx.x; t < ntiles; t += 256) kk += part[(long)t * np + k];
 	kk = block_sum(kk, red);
 	const double Fa = sens_kernel_mean(a, N, d, red), Fb = sens_kernel_mean(b, N, d, red);
 	double sumD = 0.0, Sa = a.beta[0], Sb = b.beta[0];
 	for (int l = 0; l < d; l++) {
-		const double Eqa = sens_eq(a.beta, order, d, l, lo[l], hi[l]), Eqb = sens_eq(b.beta, order, d, l, lo[l], hi[l]);
+		const double Eqa = sens_eq(a.beta, order, d, l, cst), Eqb = sens_eq(b.beta, order, d, l, cst);
 		Sa += Eqa;
 		Sb += Eqb;
 		const bool inu = k == 0 || (k <= d ? l == k - 1 : l != k - 1 - d);
@@ -318,7 +399,7 @@ __global__ __launch_bounds__(256) void sens_finish_kernel(const double *part, in
 		for (int p = 1; p <= order; p++)
 			for (int r = 1; r <= order; r++)
 				cq = fma(a.beta[1 + (p - 1) * d + l] * b.beta[1 + (r - 1) * d + l],
-				         sens_moment(lo[l], hi[l], p + r) - sens_moment(lo[l], hi[l], p) * sens_moment(lo[l], hi[l], r), cq);
+				         sens_moment(cst, l, p + r) - sens_moment(cst, l, p) * sens_moment(cst, l, r), cq);
 		const double Hab = sens_poly_kernel(a, b, order, N, d, l, red), Hba = sens_poly_kernel(b, a, order, N, d, l, red);
 		sumD += cq + (Hab - Eqa * Fb) + (Hba - Eqb * Fa);
 	}
@@ -337,8 +418,7 @@ __global__ __launch_bounds__(256) void sens_main_kernel(const double *X, SensSid
 {
 	__shared__ double red[256];
 	const int g = blockIdx.x, j = blockIdx.y;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
-	const double sj = 2.0 * cst[j];                                               // (one context, s = t: row 0 holds s t / (s + t) = s / 2)
+	const double sj = sens_len(cst, j);
 	const double x = grid[(long)j * ngrid + g];
 	const long q = (long)d * N;
 	double v = 0.0;
@@ -349,7 +429,7 @@ __global__ __launch_bounds__(256) void sens_main_kernel(const double *X, SensSid
 	const double kern = a.A * block_sum(v, red);
 	double S = a.beta[0], rest = a.beta[0];
 	for (int l = 0; l < d; l++) {
-		const double Eq = sens_eq(a.beta, order, d, l, lo[l], hi[l]);
+		const double Eq = sens_eq(a.beta, order, d, l, cst);
 		S += Eq;
 		if (l != j) rest += Eq;
 	}
@@ -378,12 +458,20 @@ __device__ __forceinline__ double sens_uu(double s, double w)
 	return 2.0 / (w * w) * (w * sqrt(M_PI / (2.0 * s)) * erf(a) + expm1(-a * a) / s);
 }
 
-// E h_a under the box: 1 for the constant, E x_l^p for a = 1 + (p - 1) d + l
-__device__ __forceinline__ double sens_eh(int a, int d, const double *lo, const double *hi)
+// UU_l under the measure of coordinate l (one context): the box's above, or (1 + 2 s sg^2)^-1/2 for a Gaussian coordinate
+__device__ __forceinline__ double sens_uu(const double *cst, int l)
+{
+	const double lo = cst[5 * GPEMU_MAX_PARAMS + l], hi = cst[6 * GPEMU_MAX_PARAMS + l];
+	if (cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + l] != 0.0) return 1.0 / sqrt(1.0 + 2.0 * cst[SENS_CST_S * GPEMU_MAX_PARAMS + l] * (hi * hi));
+	return sens_uu(2.0 * cst[l], hi - lo);                                        // (s = t: row 0 of cst holds s / 2)
+}
+
+// E h_a under the measure: 1 for the constant, E x_l^p for a = 1 + (p - 1) d + l
+__device__ __forceinline__ double sens_eh(int a, int d, const double *cst)
 {
 	if (a == 0) return 1.0;
 	const int l = (a - 1) % d, p = (a - 1) / d + 1;
-	return sens_moment(lo[l], hi[l], p);
+	return sens_moment(cst, l, p);
 }
 
 // ---------------------------------------------------------------------------
@@ -450,24 +538,23 @@ __global__ __launch_bounds__(256) void sens_post_finish_kernel(const double *par
 {
 	__shared__ double red[256], eh[GPEMU_MAX_PARAMS];
 	const int k = blockIdx.x, np = 2 * d + 2, tid = threadIdx.x;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
 	const long q = (long)d * N;
 	(void)order;
 	auto inu = [&](int l) { return k == 0 || (k <= d ? l == k - 1 : (k <= 2 * d ? l != k - 1 - d : false)); };
-	if (tid < nreg) eh[tid] = sens_eh(tid, d, lo, hi);
+	if (tid < nreg) eh[tid] = sens_eh(tid, d, cst);
 	double kk = 0.0;
 	for (int t = tid; t < ntiles; t += 256) kk += part[(long)t * np + k];
 	kk = block_sum(kk, red);                                                      // (its barriers publish eh)
 	double cc = A;
 	for (int l = 0; l < d; l++)
-		if (!inu(l)) cc *= sens_uu(2.0 * cst[l], hi[l] - lo[l]);                  // (s = t: row 0 of cst holds s / 2)
+		if (!inu(l)) cc *= sens_uu(cst, l);
 	double hq = 0.0;
 	for (int e = tid; e < nreg * nreg; e += 256) {
 		const int a = e / nreg, b = e % nreg;
 		double hm = eh[a] * eh[b];
 		if (a > 0 && b > 0 && (a - 1) % d == (b - 1) % d && inu((a - 1) % d)) {
 			const int l = (a - 1) % d;
-			hm = sens_moment(lo[l], hi[l], (a - 1) / d + (b - 1) / d + 2);
+			hm = sens_moment(cst, l, (a - 1) / d + (b - 1) / d + 2);
 		}
 		hq = fma(Q[e], hm, hq);
 	}
@@ -505,7 +592,8 @@ __global__ __launch_bounds__(256) void sens_tvec_kernel(const double *X, const d
 		else {
 			const int j = gr / ngrid;
 			const double dx = grid[gr] - X[(long)col * d + j];
-			v = A * (exp(-cst[j] * dx * dx) * prep[4 * q + (long)j * N + col]);   // (row 0 of cst: s / 2)
+			const double hs = cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + j] != 0.0 ? 0.5 * cst[SENS_CST_S * GPEMU_MAX_PARAMS + j] : cst[j];
+			v = A * (exp(-hs * dx * dx) * prep[4 * q + (long)j * N + col]);       // (row 0 of cst: s / 2 on a uniform coordinate)
 		}
 	}
 	Kq[(long)row * Np + col] = v;
@@ -524,7 +612,6 @@ __global__ __launch_bounds__(256) void sens_band_finish_kernel(const double *V, 
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const int row = min(blockIdx.x * 4 + wave, mb - 1);                           // (a spare wave repeats the last row and stores nothing)
 	const bool store = blockIdx.x * 4 + wave < mb && lane == 0;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
 	const double *v = V + (long)row * ldv;
 	double ss = 0.0;
 	for (int i = lane * 2; i < Np; i += 128) {
@@ -536,7 +623,7 @@ __global__ __launch_bounds__(256) void sens_band_finish_kernel(const double *V, 
 	const double x = j >= 0 ? grid[gr] : 0.0;
 	double hm = 0.0, ra = 0.0;
 	if (lane < nreg) {
-		hm = sens_eh(lane, d, lo, hi);
+		hm = sens_eh(lane, d, cst);
 		if (lane > 0 && (lane - 1) % d == j) {
 			hm = x;
 			for (int p = 1; p < (lane - 1) / d + 1; p++) hm *= x;
@@ -558,7 +645,7 @@ __global__ __launch_bounds__(256) void sens_band_finish_kernel(const double *V, 
 	if (store) {
 		double cc = A;
 		for (int l = 0; l < d; l++)
-			if (l != j) cc *= sens_uu(2.0 * cst[l], hi[l] - lo[l]);
+			if (l != j) cc *= sens_uu(cst, l);
 		if (main) main[gr] = mean + v[Np];
 		var[gr] = (cc - ss) + reg;
 	}
@@ -578,36 +665,43 @@ hipError_t launch_sens_prep(hipStream_t s, const double *X, int N, const SensBox
 	return hipGetLastError();
 }
 
-hipError_t launch_sens_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *prep,
-                             const double *cst, double *part)
+// the sweep's instantiation for d (8, 16 or the rolled form) and the call's measure (SensBox::meas)
+template <bool WEIGHTED, int MEAS>
+static void sens_sweep_launch(hipStream_t s, dim3 grid, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pa,
+                              const double *pb, const double *cst, double *part, const double *Pw)
 {
-	if (N < 1 || d < 1 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	if (d <= 8)
+		hipLaunchKernelGGL((sens_sweep_kernel<8, WEIGHTED, MEAS>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+	else if (d <= 16)
+		hipLaunchKernelGGL((sens_sweep_kernel<16, WEIGHTED, MEAS>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+	else
+		hipLaunchKernelGGL((sens_sweep_kernel<GPEMU_MAX_PARAMS, WEIGHTED, MEAS>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+}
+
+hipError_t launch_sens_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *prep,
+                             const double *cst, int meas, double *part)
+{
+	if (N < 1 || d < 1 || d > GPEMU_MAX_PARAMS || meas < 0 || meas > 2) return hipErrorInvalidValue;
 	const int nt = (N + 63) / 64;
 	const dim3 grid(nt, nt);
 	const double *pa = prep, *pb = prep + (size_t)5 * d * N;
 	const double *none = nullptr;
-	if (d <= 8)
-		hipLaunchKernelGGL((sens_sweep_kernel<8, false>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, none);
-	else if (d <= 16)
-		hipLaunchKernelGGL((sens_sweep_kernel<16, false>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, none);
-	else
-		hipLaunchKernelGGL((sens_sweep_kernel<GPEMU_MAX_PARAMS, false>), grid, dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, none);
+	if (meas == 0) sens_sweep_launch<false, 0>(s, grid, X, N, d, gamA, gamB, pa, pb, cst, part, none);
+	else if (meas == 1) sens_sweep_launch<false, 1>(s, grid, X, N, d, gamA, gamB, pa, pb, cst, part, none);
+	else sens_sweep_launch<false, 2>(s, grid, X, N, d, gamA, gamB, pa, pb, cst, part, none);
 	return hipGetLastError();
 }
 
-hipError_t launch_sens_sweep_weighted(hipStream_t s, const double *X, int N, int d, const double *prep, const double *cst, const double *Pw,
-                                      double *part)
+hipError_t launch_sens_sweep_weighted(hipStream_t s, const double *X, int N, int d, const double *prep, const double *cst, int meas,
+                                      const double *Pw, double *part)
 {
-	if (N < 1 || d < 1 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	if (N < 1 || d < 1 || d > GPEMU_MAX_PARAMS || meas < 0 || meas > 2) return hipErrorInvalidValue;
 	const int nt = (N + 63) / 64;
 	const dim3 grid(nt * (nt + 1) / 2);
 	const double *none = nullptr;
-	if (d <= 8)
-		hipLaunchKernelGGL((sens_sweep_kernel<8, true>), grid, dim3(256), 0, s, X, N, d, none, none, prep, prep, cst, part, Pw);
-	else if (d <= 16)
-		hipLaunchKernelGGL((sens_sweep_kernel<16, true>), grid, dim3(256), 0, s, X, N, d, none, none, prep, prep, cst, part, Pw);
-	else
-		hipLaunchKernelGGL((sens_sweep_kernel<GPEMU_MAX_PARAMS, true>), grid, dim3(256), 0, s, X, N, d, none, none, prep, prep, cst, part, Pw);
+	if (meas == 0) sens_sweep_launch<true, 0>(s, grid, X, N, d, none, none, prep, prep, cst, part, Pw);
+	else if (meas == 1) sens_sweep_launch<true, 1>(s, grid, X, N, d, none, none, prep, prep, cst, part, Pw);
+	else sens_sweep_launch<true, 2>(s, grid, X, N, d, none, none, prep, prep, cst, part, Pw);
 	return hipGetLastError();
 }
 
@@ -718,14 +812,16 @@ __global__ __launch_bounds__(256) void sens_pair_prep_kernel(const double *prep,
 // never stored; rows and columns >= N are computed on zero coordinates with zero weights: finite values times 0.
 // WEIGHTED (gpemu_sens_pairs_post; one context): P_ii' from sens_pmat_kernel in place of gamma_i gamma'_i', one workgroup
 // per LOWER tile (blockIdx.x), sums counted twice off the diagonal.
+// MEAS: as for sens_sweep_kernel; a block of 8 x 8 coordinates may hold both kinds, and takes the branch per coordinate.
 // ---------------------------------------------------------------------------
-template <bool DIAG, bool WEIGHTED>
+template <bool DIAG, bool WEIGHTED, int MEAS>
 __global__ __launch_bounds__(256) void sens_pair_sweep_kernel(const double *X, int N, int d, const double *gamA, const double *gamB,
                                                               const double *pex2A, const double *pex2B, const double *cst, double *part,
                                                               const double *Pw)
 {
 	constexpr int B = SENS_PB, NC = DIAG ? B : 2 * B, NP = B * B;
-	__shared__ double cst_s[SENS_CST * 2 * B], xb_s[SENS_CHUNK * 2 * B], w_s[SENS_CHUNK * NP], red[4 * NP];
+	constexpr int CR = MEAS == 2 ? SENS_CST_KIND + 1 : SENS_CST;                  // rows of cst staged: the mixed form reads the kind
+	__shared__ double cst_s[CR * 2 * B], xb_s[SENS_CHUNK * 2 * B], w_s[SENS_CHUNK * NP], red[4 * NP];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	int tr = blockIdx.y, tc = blockIdx.x;
 	if constexpr (WEIGHTED) sens_lower_tile(blockIdx.x, tr, tc);
@@ -737,7 +833,7 @@ __global__ __launch_bounds__(256) void sens_pair_sweep_kernel(const double *X, i
 	const int npairs = d * (d - 1) / 2;
 	// slot t of the NC coordinates: the block Ja first, then (off the diagonal) the block Kb
 	auto coord = [&](int t) { return (t < B ? Ja : Kb) * B + (t & (B - 1)); };
-	for (int e = tid; e < SENS_CST * NC; e += 256) {
+	for (int e = tid; e < CR * NC; e += 256) {
 		const int r = e / NC, t = e % NC, l = coord(t);
 		cst_s[r * 2 * B + t] = l < d ? cst[r * GPEMU_MAX_PARAMS + l] : 0.0;
 	}
@@ -779,10 +875,16 @@ __global__ __launch_bounds__(256) void sens_pair_sweep_kernel(const double *X, i
 			for (int t = 0; t < NC; t++) {
 				a[t] = 0.0;
 				if (coord(t) >= d) continue;
-				const double dx = xr[t] - xc[t];
-				const double c = cst_s[1 * 2 * B + t] * xr[t] + cst_s[2 * 2 * B + t] * xc[t], al = cst_s[3 * 2 * B + t];
-				a[t] = exp(-0.5 * cst_s[0 * 2 * B + t] * dx * dx) * cst_s[4 * 2 * B + t] *
-				       erf_diff(al * (cst_s[5 * 2 * B + t] - c), al * (cst_s[6 * 2 * B + t] - c));
+				if constexpr (MEAS == 0) {
+					const double dx = xr[t] - xc[t];
+					const double c = cst_s[1 * 2 * B + t] * xr[t] + cst_s[2 * 2 * B + t] * xc[t], al = cst_s[3 * 2 * B + t];
+					a[t] = exp(-0.5 * cst_s[0 * 2 * B + t] * dx * dx) * cst_s[4 * 2 * B + t] *
+					       erf_diff(al * (cst_s[5 * 2 * B + t] - c), al * (cst_s[6 * 2 * B + t] - c));
+				} else {
+					a[t] = sens_pair_factor<MEAS>(xr[t], xc[t], cst_s[0 * 2 * B + t], cst_s[1 * 2 * B + t], cst_s[2 * 2 * B + t],
+					                              cst_s[3 * 2 * B + t], cst_s[4 * 2 * B + t], cst_s[5 * 2 * B + t], cst_s[6 * 2 * B + t],
+					                              MEAS == 2 ? cst_s[(CR - 1) * 2 * B + t] : 0.0);
+				}
 			}
 			[[maybe_unused]] double pw = 1.0;
 			if constexpr (WEIGHTED) pw = Pw[(long)(tc * 64 + ch * SENS_CHUNK + cc) * ldp + row];
@@ -824,15 +926,15 @@ __global__ __launch_bounds__(256) void sens_pair_sweep_kernel(const double *X, i
 }
 
 // D_l of sens_finish_kernel, by its instructions in its order
-__device__ double sens_dl(const SensSide &a, const SensSide &b, int order, int N, int d, int l, double lo, double hi, double Fa, double Fb,
+__device__ double sens_dl(const SensSide &a, const SensSide &b, int order, int N, int d, int l, const double *cst, double Fa, double Fb,
                           double *red)
 {
-	const double Eqa = sens_eq(a.beta, order, d, l, lo, hi), Eqb = sens_eq(b.beta, order, d, l, lo, hi);
+	const double Eqa = sens_eq(a.beta, order, d, l, cst), Eqb = sens_eq(b.beta, order, d, l, cst);
 	double cq = 0.0;                                                              // Cov(q^a_l, q^b_l)
 	for (int p = 1; p <= order; p++)
 		for (int r = 1; r <= order; r++)
 			cq = fma(a.beta[1 + (p - 1) * d + l] * b.beta[1 + (r - 1) * d + l],
-			         sens_moment(lo, hi, p + r) - sens_moment(lo, hi, p) * sens_moment(lo, hi, r), cq);
+			         sens_moment(cst, l, p + r) - sens_moment(cst, l, p) * sens_moment(cst, l, r), cq);
 	const double Hab = sens_poly_kernel(a, b, order, N, d, l, red), Hba = sens_poly_kernel(b, a, order, N, d, l, red);
 	return cq + (Hab - Eqa * Fb) + (Hba - Eqb * Fa);
 }
@@ -846,7 +948,6 @@ __global__ __launch_bounds__(256) void sens_pair_finish_kernel(const double *par
 {
 	__shared__ double red[256];
 	const int p = blockIdx.x, np = d * (d - 1) / 2;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
 	int j, k;
 	sens_pair_coords(p, d, j, k);
 	double kk = 0.0;
@@ -855,8 +956,8 @@ __global__ __launch_bounds__(256) void sens_pair_finish_kernel(const double *par
 	const double Fa = sens_kernel_mean(a, N, d, red), Fb = sens_kernel_mean(b, N, d, red);
 	double sumD = 0.0;
 	if (order > 0) {
-		sumD += sens_dl(a, b, order, N, d, j, lo[j], hi[j], Fa, Fb, red);
-		sumD += sens_dl(a, b, order, N, d, k, lo[k], hi[k], Fa, Fb, red);
+		sumD += sens_dl(a, b, order, N, d, j, cst, Fa, Fb, red);
+		sumD += sens_dl(a, b, order, N, d, k, cst, Fa, Fb, red);
 	}
 	if (threadIdx.x == 0) out[p] = sumD + (a.A * b.A * kk - Fa * Fb);
 }
@@ -871,25 +972,24 @@ __global__ __launch_bounds__(256) void sens_pair_post_finish_kernel(const double
 {
 	__shared__ double red[256], eh[GPEMU_MAX_PARAMS];
 	const int p = blockIdx.x, np = d * (d - 1) / 2, tid = threadIdx.x;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
 	const long q = (long)d * N;
 	int j, k;
 	sens_pair_coords(p, d, j, k);
 	auto inu = [&](int l) { return l == j || l == k; };
-	if (tid < nreg) eh[tid] = sens_eh(tid, d, lo, hi);
+	if (tid < nreg) eh[tid] = sens_eh(tid, d, cst);
 	double kk = 0.0;
 	for (int t = tid; t < ntiles; t += 256) kk += part[(long)t * np + p];
 	kk = block_sum(kk, red);                                                      // (its barriers publish eh)
 	double cc = A;
 	for (int l = 0; l < d; l++)
-		if (!inu(l)) cc *= sens_uu(2.0 * cst[l], hi[l] - lo[l]);                  // (s = t: row 0 of cst holds s / 2)
+		if (!inu(l)) cc *= sens_uu(cst, l);
 	double hq = 0.0;
 	for (int e = tid; e < nreg * nreg; e += 256) {
 		const int a = e / nreg, b = e % nreg;
 		double hm = eh[a] * eh[b];
 		if (a > 0 && b > 0 && (a - 1) % d == (b - 1) % d && inu((a - 1) % d)) {
 			const int l = (a - 1) % d;
-			hm = sens_moment(lo[l], hi[l], (a - 1) / d + (b - 1) / d + 2);
+			hm = sens_moment(cst, l, (a - 1) / d + (b - 1) / d + 2);
 		}
 		hq = fma(Q[e], hm, hq);
 	}
@@ -922,8 +1022,7 @@ __global__ __launch_bounds__(256) void sens_joint_kernel(const double *X, SensSi
 {
 	__shared__ double red[256];
 	const int g = blockIdx.x;
-	const double *lo = cst + 5 * GPEMU_MAX_PARAMS, *hi = cst + 6 * GPEMU_MAX_PARAMS;
-	const double sj = 2.0 * cst[j], sk = 2.0 * cst[k];                            // (one context, s = t: row 0 holds s / 2)
+	const double sj = sens_len(cst, j), sk = sens_len(cst, k);
 	const double x = xj[g], z = xk[g];
 	const long q = (long)d * N;
 	double vj = 0.0, vi = 0.0;
@@ -937,7 +1036,7 @@ __global__ __launch_bounds__(256) void sens_joint_kernel(const double *X, SensSi
 	const double kern = a.A * block_sum(vj, red), kint = a.A * block_sum(vi, red);
 	double S = a.beta[0], rest = a.beta[0];
 	for (int l = 0; l < d; l++) {
-		const double Eq = sens_eq(a.beta, order, d, l, lo[l], hi[l]);
+		const double Eq = sens_eq(a.beta, order, d, l, cst);
 		S += Eq;
 		if (l != j && l != k) rest += Eq;
 	}
@@ -969,22 +1068,31 @@ hipError_t launch_sens_pair_prep(hipStream_t s, const double *prep, int N, int d
 
 // the diagonal coordinate blocks, then (d > SENS_PB) the blocks Ja < Kb; Pw = nullptr: unweighted over the full square of
 // tiles, else weighted over the lower tiles (gamA, gamB not read, pex2 of context 0 on both sides)
-hipError_t launch_sens_pair_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pex2,
-                                  const double *cst, const double *Pw, double *part)
+template <int MEAS>
+static void sens_pair_sweep_launch(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pa,
+                                   const double *pb, const double *cst, const double *Pw, double *part)
 {
-	if (N < 1 || d < 2 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
 	const int nt = (N + 63) / 64, nb = (d + SENS_PB - 1) / SENS_PB, noff = nb * (nb - 1) / 2;
-	const double *pa = pex2, *pb = Pw ? pex2 : pex2 + sens_pex2_elems(N, d) / 2;
 	if (Pw) {
 		const int ntl = nt * (nt + 1) / 2;
-		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, true>), dim3(ntl, 1, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, true, MEAS>), dim3(ntl, 1, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
 		if (noff)
-			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, true>), dim3(ntl, 1, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, true, MEAS>), dim3(ntl, 1, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
 	} else {
-		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, false>), dim3(nt, nt, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+		hipLaunchKernelGGL((sens_pair_sweep_kernel<true, false, MEAS>), dim3(nt, nt, nb), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
 		if (noff)
-			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, false>), dim3(nt, nt, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
+			hipLaunchKernelGGL((sens_pair_sweep_kernel<false, false, MEAS>), dim3(nt, nt, noff), dim3(256), 0, s, X, N, d, gamA, gamB, pa, pb, cst, part, Pw);
 	}
+}
+
+hipError_t launch_sens_pair_sweep(hipStream_t s, const double *X, int N, int d, const double *gamA, const double *gamB, const double *pex2,
+                                  const double *cst, int meas, const double *Pw, double *part)
+{
+	if (N < 1 || d < 2 || d > GPEMU_MAX_PARAMS || meas < 0 || meas > 2) return hipErrorInvalidValue;
+	const double *pa = pex2, *pb = Pw ? pex2 : pex2 + sens_pex2_elems(N, d) / 2;
+	if (meas == 0) sens_pair_sweep_launch<0>(s, X, N, d, gamA, gamB, pa, pb, cst, Pw, part);
+	else if (meas == 1) sens_pair_sweep_launch<1>(s, X, N, d, gamA, gamB, pa, pb, cst, Pw, part);
+	else sens_pair_sweep_launch<2>(s, X, N, d, gamA, gamB, pa, pb, cst, Pw, part);
 	return hipGetLastError();
 }
 

@@ -133,6 +133,15 @@ static void check_box(const char *method, const std::vector<double> &lo, const s
 	}
 }
 
+void emulator::SetSensitivityMeasure(const std::vector<int> &kind)
+{
+	if (!kind.empty() && (int)kind.size() != number_params) {
+		std::cerr << "Error::SetSensitivityMeasure called with a vector that has not one kind per parameter" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	emulate_sensitivity_measure_multi(the_emulator, kind.empty() ? NULL : kind.data());
+}
+
 void emulator::QueryEmulatorSensitivity(const std::vector<double> &lo, const std::vector<double> &hi, std::vector<double> &Means,
                                         std::vector<double> &Variances, std::vector<std::vector<double> > &FirstOrder,
                                         std::vector<std::vector<double> > &Total)

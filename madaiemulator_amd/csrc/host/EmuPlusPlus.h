@@ -56,6 +56,10 @@ public:
 	// the joint covariance at xpoints first (no noise); coinciding points end in the layer's fatal exit.
 	void DrawEmulator(const std::vector<std::vector<double> > &xpoints, const std::vector<std::vector<std::vector<double> > > &Normals,
 	                  std::vector<std::vector<std::vector<double> > > &Draws);
+	// the input measure of every sensitivity method below, per parameter: 0 uniform on [lo_j, hi_j] (the default), 1 Gaussian with
+	// MEAN lo_j and STANDARD DEVIATION hi_j (libemu.h: emulate_sensitivity_measure_multi); an empty vector: all uniform.  It holds
+	// for every later call until it is set again.  A vector of another length or another kind ends in the layer's fatal exit.
+	void SetSensitivityMeasure(const std::vector<int> &kind);
 	// sensitivity analysis of the posterior mean over the box [lo, hi] (number_params entries each; independent uniform inputs),
 	// in closed form, power-exponential covariance only (libemu.h: emulate_sensitivity_multi).  Per output t: Means[t] = E0,
 	// Variances[t] = V, FirstOrder[t][j] = V_j / V and Total[t][j] = VT_j / V, the first-order and total-effect Sobol indices of

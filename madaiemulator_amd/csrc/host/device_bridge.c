@@ -1233,6 +1233,15 @@ void emulate_sensitivity(emulator_struct *e, const double *lo, const double *hi,
 	check(en, rc, "emulate_sensitivity");
 }
 
+/* the input measure of every emulate_sensitivity*, emulate_main_effects* and emulate_interaction_surface* call on e from now on
+ * (gpemu_sens_set_measure in gpemu.h): kind[j] = GPEMU_MEASURE_UNIFORM or GPEMU_MEASURE_GAUSS per parameter, NULL for all
+ * uniform.  The state lives in the emulator's device context, which keeps it for as long as the emulator_struct lives. */
+void emulate_sensitivity_measure(emulator_struct *e, const int *kind)
+{
+	struct entry *en = entry_of(e, "emulate_sensitivity_measure");
+	check(en, gpemu_sens_set_measure(en->ctx, kind), "emulate_sensitivity_measure");
+}
+
 void emulate_main_effects(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main)
 {
 	struct entry *en = entry_of(e, "emulate_main_effects");

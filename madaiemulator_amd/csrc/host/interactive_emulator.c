@@ -32,7 +32,7 @@
 struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
-	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile;
+	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile, *priorfile;
 	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
@@ -58,7 +58,7 @@ static const char useage[] =
 	"      integer per training point, the group it is left out with, 0 .. number of groups - 1, or -1 for never)\n"
 	"  --holdout, --folds and --groups exclude each other.\n"
 	"or\n"
-	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--uncertainty] [--pairs] [--surface=j,k] [--pca_output] [--quiet]  (main effects and Sobol\n"
+	"  interactive_emulator sensitivity MODEL_SNAPSHOT_FILE [--box=FILE] [--grid=G] [--uncertainty] [--pairs] [--surface=j,k] [--prior=FILE] [--pca_output] [--quiet]  (main effects and Sobol\n"
 	"      indices of the posterior mean, in closed form, for independent uniform inputs on a box: FILE holds one line \"lo hi\" per\n"
 	"      parameter, default the range of the design.  Per output one line: variance, the first-order indices, the total\n"
 	"      indices (NaN where the variance is 0); with --grid=G then, per output and parameter, the main-effect curve on G equally\n"
@@ -69,6 +69,8 @@ static const char useage[] =
 	"      pairs of parameters (0,1), (0,2), .., (d-2,d-1) (NaN where the variance is 0), and with --uncertainty then, per output, one\n"
 	"      line with the expected interaction variances over the expected variance.  --surface=j,k with --grid=G appends, per output,\n"
 	"      G lines of G values: the interaction effect of parameters j and k on the grid, row a at the a-th value of parameter j.\n"
+	"      --prior=FILE in place of --box: one line per parameter, \"uniform LO HI\" or \"gaussian MEAN SD\" (SD > 0): the input measure\n"
+	"      of each parameter, independent of the others; the curve and the surface of a Gaussian parameter run over MEAN -+ 2 SD.\n"
 	"      Power-exponential covariance only)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
@@ -405,7 +407,20 @@ static int validate_lgo(struct cmdLineOpts *o)
  * "sd(E0) IMSE E*[V] E*[V_0]/E*[V] .. E*[VT_0]/E*[V] .." -- the posterior standard deviation of the mean, the box average of the
  * posterior variance, the expected variance of the emulated function and its expected first-order and total parts over it --;
  * and with --grid=G every curve is followed by a line of G posterior standard deviations of its values.  Without the flag the
- * output is what it was before the flag existed. */
+ * output is what it was before the flag existed.
+ * --prior=FILE (emulate_sensitivity_measure_multi) in place of --box=FILE: per parameter "uniform LO HI" or "gaussian MEAN SD",
+ * the input measure of that parameter.  lo / hi then hold MEAN / SD of a Gaussian parameter, as every emulate_sensitivity*
+ * function reads them; glo / ghi are where its curve and surface run, MEAN -+ 2 SD (the box itself for a uniform parameter).
+ * Without --prior every byte of output is what it was before the flag existed. */
+/* a box or prior file that cannot be used, its message already written: status 1 by the layer's teardown-free exit (fatal.c).
+ * A return from main would run exit()'s handlers, the HIP runtime's among them, beside the warm-start thread, which at this
+ * point is usually still inside the runtime's start-up: the process then ends in abort() and not with status 1. */
+static int bad_measure_file(void)
+{
+	gpemu_host_exit(EXIT_FAILURE);
+	return EXIT_FAILURE;
+}
+
 static int sensitivity(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -421,14 +436,30 @@ static int sensitivity(struct cmdLineOpts *o)
 	if ((o->pairs || o->surface) && d < 2) return perr("--pairs and --surface need a model with two parameters or more");
 	if (o->surface && (G < 1 || o->surfJ == o->surfK || o->surfJ < 0 || o->surfK < 0 || o->surfJ >= d || o->surfK >= d))
 		return perr("--surface=j,k needs two different parameters of 0 .. d - 1, and --grid=G");
+	if (o->boxfile && o->priorfile) { perr("--box=FILE and --prior=FILE exclude each other"); return bad_measure_file(); }
 	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
-	if (o->boxfile) {
+	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
+	if (o->priorfile) {
+		FILE *pf = fopen(o->priorfile, "r");
+		if (!pf) { perr("Error opening the prior file"); return bad_measure_file(); }
+		for (int j = 0; j < d; j++) {
+			char word[16];
+			int ok = fscanf(pf, "%15s %lf %lf", word, &lo[j], &hi[j]) == 3 && isfinite(lo[j]) && isfinite(hi[j]);
+			if (ok && !strcmp(word, "gaussian")) { kind[j] = 1 /* GPEMU_MEASURE_GAUSS */; ok = hi[j] > 0.0; }
+			else if (ok) ok = !strcmp(word, "uniform") && hi[j] > lo[j];
+			if (!ok) {
+				fprintf(stderr, "the prior file needs %d lines \"uniform LO HI\" with LO < HI or \"gaussian MEAN SD\" with SD > 0, one per parameter\n", d);
+				return bad_measure_file();
+			}
+		}
+		fclose(pf);
+	} else if (o->boxfile) {
 		FILE *bf = fopen(o->boxfile, "r");
-		if (!bf) return perr("Error opening the box file");
+		if (!bf) { perr("Error opening the box file"); return bad_measure_file(); }
 		for (int j = 0; j < d; j++)
 			if (fscanf(bf, "%lf %lf", &lo[j], &hi[j]) != 2 || !(hi[j] > lo[j])) {
 				fprintf(stderr, "the box file needs %d lines \"lo hi\" with lo < hi, one per parameter\n", d);
-				return EXIT_FAILURE;
+				return bad_measure_file();
 			}
 		fclose(bf);
 	} else {
@@ -445,11 +476,21 @@ static int sensitivity(struct cmdLineOpts *o)
 			}
 		}
 	}
+	/* where the curves and the surface run */
+	double *glo = (double *)malloc(sizeof(double) * (size_t)d), *ghi = (double *)malloc(sizeof(double) * (size_t)d);
+	for (int j = 0; j < d; j++) {
+		glo[j] = kind[j] ? lo[j] - 2.0 * hi[j] : lo[j];
+		ghi[j] = kind[j] ? lo[j] + 2.0 * hi[j] : hi[j];
+	}
 	multi_emulator *emu = alloc_multi_emulator(model);
+	if (o->priorfile) emulate_sensitivity_measure_multi(emu, kind);
 	FILE *out = stdout;
 	if (!o->quietFlag) {
 		fprintf(out, "%d\n", d);
-		for (int j = 0; j < d; j++) fprintf(out, "%s%d %.17g %.17g\n", "param_", j, lo[j], hi[j]);
+		for (int j = 0; j < d; j++) {
+			if (o->priorfile) fprintf(out, "%s%d %s %.17g %.17g\n", "param_", j, kind[j] ? "gaussian" : "uniform", lo[j], hi[j]);
+			else fprintf(out, "%s%d %.17g %.17g\n", "param_", j, lo[j], hi[j]);
+		}
 		fprintf(out, "%d\n", nout);
 	}
 	double *e0 = (double *)malloc(sizeof(double) * (size_t)nout), *var = (double *)malloc(sizeof(double) * (size_t)nout);
@@ -477,7 +518,7 @@ static int sensitivity(struct cmdLineOpts *o)
 		double *grid = (double *)malloc(sizeof(double) * (size_t)d * G), *mainv = (double *)malloc(sizeof(double) * (size_t)d * G * nout);
 		double *sdv = o->uncertainty ? (double *)malloc(sizeof(double) * (size_t)d * G * nout) : NULL;
 		for (int j = 0; j < d; j++)
-			for (int g = 0; g < G; g++) grid[(size_t)j * G + g] = G > 1 ? lo[j] + g * (hi[j] - lo[j]) / (G - 1) : 0.5 * (lo[j] + hi[j]);
+			for (int g = 0; g < G; g++) grid[(size_t)j * G + g] = G > 1 ? glo[j] + g * (ghi[j] - glo[j]) / (G - 1) : 0.5 * (glo[j] + ghi[j]);
 		if (sdv) emulate_main_effects_band_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv, sdv);
 		else emulate_main_effects_multi(emu, o->pcaOutputFlag, lo, hi, G, grid, e0, mainv);
 		for (int t = 0; t < nout; t++) {
@@ -521,8 +562,8 @@ static int sensitivity(struct cmdLineOpts *o)
 		double *jt = (double *)malloc(sizeof(double) * 2 * (size_t)G * G * nout), *it = jt + (size_t)G * G * nout;
 		const int sj = o->surfJ, sk = o->surfK;
 		for (int g = 0; g < G; g++) {
-			gj[g] = G > 1 ? lo[sj] + g * (hi[sj] - lo[sj]) / (G - 1) : 0.5 * (lo[sj] + hi[sj]);
-			gk[g] = G > 1 ? lo[sk] + g * (hi[sk] - lo[sk]) / (G - 1) : 0.5 * (lo[sk] + hi[sk]);
+			gj[g] = G > 1 ? glo[sj] + g * (ghi[sj] - glo[sj]) / (G - 1) : 0.5 * (glo[sj] + ghi[sj]);
+			gk[g] = G > 1 ? glo[sk] + g * (ghi[sk] - glo[sk]) / (G - 1) : 0.5 * (glo[sk] + ghi[sk]);
 		}
 		emulate_interaction_surface_multi(emu, o->pcaOutputFlag, lo, hi, sj, sk, G, gj, gk, e0, jt, it);
 		for (int t = 0; t < nout; t++)
@@ -533,7 +574,7 @@ static int sensitivity(struct cmdLineOpts *o)
 		free(gj); free(jt);
 	}
 	fflush(out);
-	free(lo); free(hi); free(e0); free(var); free(first); free(total);
+	free(lo); free(hi); free(glo); free(ghi); free(kind); free(e0); free(var); free(first); free(total);
 	free_multi_emulator(emu);
 	return 0;
 }
@@ -593,6 +634,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"uncertainty", no_argument, NULL, 1009},
 		/* ... second order: the indices of all pairs of parameters, the interaction effect of one pair on the grid */
 		{"pairs", no_argument, NULL, 1010},                   {"surface", required_argument, NULL, 1011},
+		/* ... under a measure per parameter, uniform or Gaussian, in place of the box */
+		{"prior", required_argument, NULL, 1012},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -626,6 +669,7 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 			o->surface = 1;
 			if (sscanf(optarg, "%d,%d", &o->surfJ, &o->surfK) != 2) o->surfJ = o->surfK = -1;
 			break;
+		case 1012: o->priorfile = optarg; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;

@@ -311,6 +311,13 @@ void emulate_lgo_collect(emulator_struct *e, void *dev, int ngroups, double *mea
  * E[m | x_j = grid[j * ngrid + g]], row j of grid holding the values of x_j.  A Matern model, a bad box: gpemu_host_fatal. */
 void emulate_sensitivity(emulator_struct *e, const double *lo, const double *hi, double *e0, double *var, double *first, double *total);
 void emulate_main_effects(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main);
+/* extension: the input measure of the whole family above and below (gpemu_sens_set_measure in gpemu.h).  kind: nparams values,
+ * GPEMU_MEASURE_UNIFORM (0, the default) or GPEMU_MEASURE_GAUSS (1), or NULL for all uniform.  From this call on, every
+ * emulate_sensitivity*, emulate_main_effects* and emulate_interaction_surface* function reads lo[j] / hi[j] of a Gaussian
+ * parameter as its MEAN / STANDARD DEVIATION (sd > 0; hi <= lo is fine there), and a grid value on it may be any finite real.
+ * The state lives in the emulator's device context: no struct changes, and it lasts until the emulator_struct is freed or set
+ * again.  A kind outside {0, 1}: gpemu_host_fatal.  emulate_sensitivity_measure_multi (below) sets every component. */
+void emulate_sensitivity_measure(emulator_struct *e, const int *kind);
 /* the covariances behind emulate_sensitivity in two halves, for one emulator (b = a or NULL) or for two on the same design:
  * gpemu_sens_cov_dev is enqueued on a's stream, *dev_out is the device buffer the results wait in; collect returns e0[2] (E0 of
  * a, of b), *cov_all = Cov(m^a, m^b), cov_first[j] = Cov(E[m^a | x_j], E[m^b | x_j]), cov_rest[j] = Cov(E[m^a | x_-j], E[m^b | x_-j]) */
@@ -423,6 +430,9 @@ void emulate_lgo_multi(multi_emulator *emu, int pca_space, int ngroups, const in
  * posterior uncertainty, where the components ARE independent; here it would drop every cross term. */
 void emulate_sensitivity_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, double *e0_out, double *var_out,
                                double *first_out, double *total_out);
+/* the input measure of every *_multi sensitivity function of emu from now on: emulate_sensitivity_measure on every component
+ * (the kinds are per parameter, the same for all components); lo / hi then mean mean / sd on a Gaussian parameter */
+void emulate_sensitivity_measure_multi(multi_emulator *emu, const int *kind);
 /* main-effect curves of every output: main_out is (nparams x ngrid) x (nr or nt), element ((j * ngrid + g) * nout + t); e0_out
  * nr or nt values.  Observable space by the mean half of the rule (linear in the components), training mean added. */
 void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,

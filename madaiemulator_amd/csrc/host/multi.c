@@ -760,6 +760,12 @@ void emulate_sensitivity_multi(multi_emulator *emu, int pca_space, const double 
 	free(dev); free(cv); free(e0);
 }
 
+/* the input measure of every sensitivity call on emu from now on: every component gets the same kinds (libemu.h) */
+void emulate_sensitivity_measure_multi(multi_emulator *emu, const int *kind)
+{
+	for (size_t c = 0; c < (size_t)emu->nr; c++) emulate_sensitivity_measure(emu->emu_struct_array[c], kind);
+}
+
 /* main-effect curves of every output: the components one after the other (gpemu_sens_main waits for its result), then the mean
  * half of the rule -- a conditional mean is linear in the components -- with the training mean added */
 void emulate_main_effects_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
