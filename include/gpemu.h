@@ -47,6 +47,7 @@ typedef struct gpemu_ctx gpemu_ctx;
 int  gpemu_ctx_create(gpemu_ctx **out, int device);
 void gpemu_ctx_destroy(gpemu_ctx *ctx);
 const char *gpemu_last_error(const gpemu_ctx *ctx);
+int  gpemu_ctx_device(const gpemu_ctx *ctx);   /* the HIP device the context was created on, -1 for NULL */
 const char *gpemu_version(void);
 int  gpemu_device_count(void);
 /* free / total HBM of a device in bytes (hipMemGetInfo): the host layer sizes its lock-step groups with it.  A likelihood
@@ -568,6 +569,77 @@ int gpemu_sens_joint(gpemu_ctx *ctx, const double *lo, const double *hi, int j, 
 int gpemu_sens_set_measure(gpemu_ctx *ctx, const int *kind /* d values, or NULL: all uniform */);
 int gpemu_sens_get_measure(const gpemu_ctx *ctx, int *kind /* d */);
 
+/* ---- implausibility and calibration likelihood against observations -----------------
+ * Stands in for the reference's src/libRbind/implausOverDesign.R (computeImplaus, gridImplausComb) and adds the joint quantity
+ * its interactive_mode leaves as a FIXME.  A multi-output emulator predicts y(x) = ybar + A m(x) with A = pca_evecs_r
+ * sqrt(pca_evals_r) (nt x nr, row-major) and independent components of mean m_c(x) and variance v_c(x), D(x) = diag v(x).
+ * Against observations z with covariance S (nt x nt, positive definite; or standard deviations sd: S = diag sd^2):
+ *   chi2(x)   = (z - y(x))^T (S + A D A^T)^-1 (z - y(x))
+ *   logpdf(x) = -1/2 (chi2 + log|S + A D A^T| + nt log 2 pi)       the joint log density of z: an MCMC likelihood
+ *   I_t(x)    = |z_t - y_t| / sqrt(sum_c A_tc^2 v_c + S_tt + (rel_t y_t)^2)      the reference's per-output implausibility
+ * (rel_t >= 0: a relative model error per output, the reference's errModel.sys; it enters the I_t alone).  Unlike sum_t I_t^2,
+ * chi2 keeps the correlation between outputs that the back-projection creates.  No nt x nt work per point: once per
+ * observation set (gpemu_calib_project, fp64 on the host, no device needed), with S = L_S L_S^T,
+ *   G = A^T S^-1 A,   m_hat = G^-1 A^T S^-1 (z - ybar),   Sigma_z = G^-1,   c_perp = |L_S^-1 (z - ybar - A m_hat)|^2 >= 0
+ * and per point, with delta = m(x) - m_hat and T(x) = Sigma_z + D(x),
+ *   chi2 = c_perp + delta^T T^-1 delta,      log|S + A D A^T| = log|S| + log|G| + log|T|
+ * one nr x nr Cholesky; D may be singular (a design point), nothing is a difference of large numbers.  c_perp is the misfit
+ * no parameter value can remove (nt - nr degrees of freedom).
+ * Limits: 1 <= nr <= nt, nr <= GPEMU_CALIB_MAX_R, nt <= GPEMU_CALIB_MAX_NT; beyond: GPEMU_ERR_ARG (not built).
+ *
+ * gpemu_calib_project: exactly one of S (nt x nt, both triangles; the lower one is read) and sd (nt) is given.  Outputs: mhat
+ * (nr), sigz (nr x nr, symmetric bit for bit), consts = {c_perp, log|S|, log|G|}.  GPEMU_ERR_NOT_PD with the 1-based pivot in
+ * *info when S or G is not positive definite to working precision (a pivot not above 64 eps times its diagonal element): for
+ * G that means A has no full column rank; the outputs are then NaN.  GPEMU_ERR_ARG for a NULL pointer, both or neither of S
+ * and sd, a size outside the limits, a non-finite input, sd <= 0.
+ * gpemu_calib_setup runs the projection and keeps its tables resident on the context's device (ybar, A, z, S or sd, rel: HOST
+ * arrays; rel may be NULL: none; a negative or non-finite rel is GPEMU_ERR_ARG).  The tables do not depend on the context's
+ * model -- the context gives device, stream and error text --: gpemu_set_model leaves them alone, a second set-up replaces
+ * them, gpemu_calib_release (waits for the stream) and gpemu_ctx_destroy free them.
+ * gpemu_calib_eval: mean and var are component-major, row c at offset c * ld, ld >= M: what gpemu_predict_batch_dev of
+ * component c writes.  A variance below 0 counts as 0 (kappa - |L^-1 k|^2 goes a few ulp negative at a design point).  stat
+ * is 5 x M, statistic-major: row 0 chi2, row 1 logpdf, rows 2-4 the largest, second and third largest I_t (0 where nt < 3
+ * leaves none); worst[q] = the output index of the largest I_t, the smallest index on a tie.  The sums over c run in index
+ * order from 0.0, the order of the host layer's back-projection.  A NaN among a point's inputs makes that point's five
+ * statistics NaN and its worst -1, no other point's.  A pivot <= 0 in T makes rows 0-1 of that point NaN; the call still
+ * returns GPEMU_OK.  The _dev form only enqueues on the context's stream (one launch): the caller has ordered the producers
+ * of mean and var.  GPEMU_ERR_STATE without a set-up; GPEMU_ERR_ARG for a NULL pointer, M < 1 or ld < M.
+ * How it runs: one lane owns one query.  The lower triangle of T lives in registers, in instantiations for nr rounded up to 4,
+ * 8, 12 and 16 (T padded with the identity, delta with 0: exact zeros in both sums), fully unrolled; the per-output rows of the
+ * table (A, its squares, ybar, z, S_tt, rel) pass through LDS in chunks of 64 outputs, every lane of a wave reading the same
+ * address.  Vector fp64, no matrix unit: 2 nt nr + nr^3 / 3 multiply-adds per point stand against the 2 N^2 per point and
+ * component of the sweep it follows.
+ * gpemu_calib_select: point q is kept iff stat[0][q] <= cut_chi2 and stat[1 + level][q] <= cut_I, level 1, 2 or 3 (the
+ * reference's gridImplausComb is level 1).  INFINITY disables a cut; a NaN is never kept.  idx (M ints) receives the kept q in
+ * ascending order, *count their number.  Per-workgroup counts, a scan, an ordered scatter: no atomics decide an output
+ * position.  In the _dev form stat and idx are device pointers, count is a HOST int and the call waits for it.  Needs no
+ * set-up.  GPEMU_ERR_ARG for a NULL pointer, M < 1, a level outside 1 .. 3 or a NaN cut.
+ * gpemu_calib_gather_dev: the statistics of `count` listed points, point-major, out_dev[k * 5 + s] = stat[s][idx[k]], and (where
+ * worst_dev and worst_out_dev are given) their worst outputs: what a caller downloads after a selection instead of all of
+ * stat.  Only enqueues; an index outside 0 .. M-1 leaves its row unwritten.  GPEMU_ERR_ARG for a NULL pointer, M < 1 or
+ * count < 0; count = 0 does nothing.
+ * Two identical calls of any entry return the same bits; the host and _dev entries return the same bits.
+ * Not built: nr > 16, nt > 1024; a mean-only pre-screen; the PCA truncation residual as an automatic addition to S (the caller
+ * adds it to S); gradients of logpdf with respect to x. */
+#define GPEMU_CALIB_MAX_R  16
+#define GPEMU_CALIB_MAX_NT 1024
+int gpemu_calib_project(int nt, int nr, const double *ybar /* nt */, const double *A /* nt*nr */, const double *z /* nt */,
+                        const double *S /* nt*nt or NULL */, const double *sd /* nt or NULL */, double *mhat /* nr */,
+                        double *sigz /* nr*nr */, double *consts /* 3 */, int *info);
+int gpemu_calib_setup(gpemu_ctx *ctx, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
+                      const double *sd, const double *rel /* nt or NULL */, int *info);
+int gpemu_calib_release(gpemu_ctx *ctx);
+int gpemu_calib_eval(gpemu_ctx *ctx, int M, const double *mean /* nr rows of ld, host */, const double *var, int ld,
+                     double *stat /* 5*M */, int *worst /* M */);
+int gpemu_calib_eval_dev(gpemu_ctx *ctx, int M, const double *mean_dev, const double *var_dev, int ld, double *stat_dev,
+                         int *worst_dev);
+int gpemu_calib_select(gpemu_ctx *ctx, int M, const double *stat /* 5*M host */, double cut_chi2, int level, double cut_I,
+                       int *idx /* M */, int *count);
+int gpemu_calib_select_dev(gpemu_ctx *ctx, int M, const double *stat_dev, double cut_chi2, int level, double cut_I, int *idx_dev,
+                           int *count /* HOST */);
+int gpemu_calib_gather_dev(gpemu_ctx *ctx, int M, const double *stat_dev, const int *worst_dev /* may be NULL */, int count,
+                           const int *idx_dev, double *out_dev /* count*5 */, int *worst_out_dev /* may be NULL */);
+
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle
  * read) is replaced by its inverse (both triangles); *logdet = 2 sum log L_ii; *info as gpemu_loglik. */
@@ -618,6 +690,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_LGO     13  /* the three launches per chunk of gpemu_lgo[_dev], nbc groups padded to bp: gather (bytes = 8 nbc bp Np: the rows of Z written; it reads at most the lower tiles of L^-1 besides), staging (bytes = 8 nbc bp (2 bp + 64): the lower tiles read and written, right-hand-side and identity rows written), finish (bytes = 8 nbc bp (bp / 2 + 4)); the product and the factorisation report under GPEMU_PROF_GEMM / _LEAF / _POTRF */
 #define GPEMU_PROF_SENS    14  /* the three launches of gpemu_sens_cov[_dev] -- prep (flops = 88 N d: both contexts, two erf and two exp per point and coordinate counted as one flop each; bytes = 8 (10 N d + N d): the tables written, the design read), sweep (flops = N^2 (19 d + 2): per pair and coordinate one exp and two erf or erfc counted as one flop each among 16 others, then the 2 d + 1 sums; bytes = 8 T: the T = ceil(N / 64)^2 (2 d + 1) partial sums written), finish (flops = T, bytes = 8 T) -- and the two of gpemu_sens_main: prep, curves (flops = 6 N d ngrid, bytes = 16 d ngrid) */
 #define GPEMU_PROF_SENS_POST 15 /* the four launches of gpemu_sens_post[_dev], L = n (n + 1) / 2 lower tiles with n = ceil(N / 64) -- prep (as GPEMU_PROF_SENS), pmat (flops = L (128 nreg^2 + 4096 (2 nreg + 1)): G for the tile's 64 rows, then a product of length nreg per pair; bytes = 8 * 8192 L: the corner's tile read, P's written), weighted sweep (flops = 4096 L (20 d + 3): the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; bytes = 8 (4096 L + T'), T' = L (2 d + 2): P read, the partial sums written), finish (flops = T' + (2 d + 2) nreg (2 nreg + 4 N), bytes = 8 (T' + (2 d + 2) 3 N nreg)) -- and of gpemu_sens_main_var: prep, then per block of mb rows tvec (flops = 6 mb N, bytes = 8 mb' Np, mb' = mb rounded up to 64) and band finish (flops = mb (2 Np + 2 nreg^2), bytes = 8 mb (Np + 64)); the corner and the band's product report under GPEMU_PROF_GEMM */
+#define GPEMU_PROF_CALIB   16  /* the launch of gpemu_calib_eval[_dev] (flops = M (4 nt R + 8 nt + R^3 / 3 + 2 R^2), R = nr rounded up to 4: two multiply-adds per output and component, the finish of an output, the Cholesky and the solve in T; bytes = 8 M (2 nr + 5) + 4 M: mean and var read, stat and worst written) and the three of gpemu_calib_select[_dev], bracketed as ONE entry: count (16 M bytes: two rows of stat read), scan (8 ceil(M / 1024)), scatter (16 M + 4 kept, counted with kept = M), bytes = 36 M + 8 ceil(M / 1024), no flops */
 /* GPEMU_PROF_SENS*, under a measure (gpemu_sens_set_measure): in every sweep a GAUSSIAN coordinate's pair factor counts 12
  * flops (one exp among 11 others) where a uniform one counts 19 (one exp and two erf or erfc among 16): 19 d above becomes
  * 19 d_u + 12 d_g, and in the pair sweeps the 8 / 16 factors of a block are taken in the proportion d_u : d_g.  The prep and

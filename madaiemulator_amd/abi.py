@@ -24,6 +24,8 @@ PROF_JOINT = 12
 PROF_LGO = 13
 PROF_SENS = 14
 PROF_SENS_POST = 15
+PROF_CALIB = 16
+CALIB_MAX_R, CALIB_MAX_NT = 16, 1024
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 MEASURE_UNIFORM, MEASURE_GAUSS = 0, 1
 RESULT_RING = 4
@@ -162,6 +164,15 @@ SYMBOLS = {
     "gpemu_sens_joint": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gpemu_sens_set_measure": (C.c_int, [C.c_void_p, _ip]),
     "gpemu_sens_get_measure": (C.c_int, [C.c_void_p, _ip]),
+    "gpemu_calib_project": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpemu_calib_setup": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpemu_calib_release": (C.c_int, [C.c_void_p]),
+    "gpemu_calib_eval": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip]),
+    "gpemu_calib_eval_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gpemu_calib_select": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, C.c_double, _ip, _ip]),
+    "gpemu_calib_select_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_void_p, _ip]),
+    "gpemu_calib_gather_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_ctx_device": (C.c_int, [C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpemu_symm_invalidate": (C.c_int, [C.c_void_p]),
@@ -249,6 +260,28 @@ def predict_setup_batch(ctxs, thetas):
     if rc not in (OK, ERR_NOT_PD, ERR_REGRESSION):
         raise GpemuError(rc, ctxs[0].L.gpemu_last_error(ctxs[0].h).decode())
     return beta, info, status, rc
+
+
+def _opt(x):
+    return None if x is None else _a(x)
+
+
+def _po(a):
+    return None if a is None else _p(a)
+
+
+def calib_project(ybar, A, z, S=None, sd=None, nt=None, nr=None):
+    """gpemu_calib_project (host arithmetic, no device): the once-per-observation-set tables of the calibration entries
+    -> dict(mhat[nr], sigz[nr, nr], c_perp, logdet_S, logdet_G, info, status); status is OK, ERR_NOT_PD (info = the 1-based
+    pivot) or ERR_ARG.  nt, nr default to A's shape."""
+    A = _a(A)
+    nt = A.shape[0] if nt is None else nt
+    nr = A.shape[1] if nr is None else nr
+    ybar, z, S, sd = _opt(ybar), _opt(z), _opt(S), _opt(sd)
+    mhat, sigz, consts = np.full(max(nr, 1), np.nan), np.full((max(nr, 1), max(nr, 1)), np.nan), np.full(3, np.nan)
+    info = C.c_int(0)
+    rc = load().gpemu_calib_project(nt, nr, _po(ybar), _p(A), _po(z), _po(S), _po(sd), _p(mhat), _p(sigz), _p(consts), C.byref(info))
+    return dict(mhat=mhat, sigz=sigz, c_perp=consts[0], logdet_S=consts[1], logdet_G=consts[2], info=info.value, status=rc)
 
 
 class Context:
@@ -516,6 +549,52 @@ class Context:
 
     def sens_release(self):
         self._chk(self.L.gpemu_sens_release(self.h))
+
+    # implausibility and calibration likelihood against observations; the tables are the context's, not the model's
+    def calib_setup(self, ybar, A, z, S=None, sd=None, rel=None, nt=None, nr=None, allow=()):
+        """observations z with covariance S (or standard deviations sd) for outputs ybar + A m; rel: relative model error per
+        output -> (status, info)"""
+        A = _a(A)
+        nt = A.shape[0] if nt is None else nt
+        nr = A.shape[1] if nr is None else nr
+        ybar, z, S, sd, rel = _opt(ybar), _opt(z), _opt(S), _opt(sd), _opt(rel)
+        info = C.c_int(0)
+        rc = self.L.gpemu_calib_setup(self.h, nt, nr, _po(ybar), _p(A), _po(z), _po(S), _po(sd), _po(rel), C.byref(info))
+        self._chk(rc, allow=allow)
+        if rc == OK:
+            self.calib_nr = nr
+        return rc, info.value
+
+    def calib_release(self):
+        self._chk(self.L.gpemu_calib_release(self.h))
+
+    def calib_eval(self, mean, var, M=None):
+        """mean, var: nr rows (component-major) of ld >= M columns -> (stat[5, M]: chi2, logpdf, top three I_t; worst[M])"""
+        mean, var = np.atleast_2d(_a(mean)), np.atleast_2d(_a(var))
+        ld = mean.shape[1]
+        M = ld if M is None else M
+        stat, worst = np.full((5, max(M, 1)), np.nan), np.full(max(M, 1), -2, dtype=np.int32)
+        self._chk(self.L.gpemu_calib_eval(self.h, M, _p(mean), _p(var), ld, _p(stat), worst.ctypes.data_as(_ip)))
+        return stat, worst
+
+    def calib_eval_dev(self, M, mean_dev, var_dev, ld, stat_dev, worst_dev):
+        self._chk(self.L.gpemu_calib_eval_dev(self.h, M, mean_dev, var_dev, ld, stat_dev, worst_dev))
+
+    def calib_select(self, stat, cut_chi2=np.inf, level=1, cut_I=np.inf):
+        """stat[5, M] as calib_eval returns it -> the kept point indices, ascending"""
+        stat = _a(stat).reshape(5, -1)
+        M = stat.shape[1]
+        idx, n = np.full(max(M, 1), -1, dtype=np.int32), C.c_int(0)
+        self._chk(self.L.gpemu_calib_select(self.h, M, _p(stat), cut_chi2, level, cut_I, idx.ctypes.data_as(_ip), C.byref(n)))
+        return idx[:n.value].copy()
+
+    def calib_gather_dev(self, M, stat_dev, worst_dev, count, idx_dev, out_dev, worst_out_dev):
+        self._chk(self.L.gpemu_calib_gather_dev(self.h, M, stat_dev, worst_dev, count, idx_dev, out_dev, worst_out_dev))
+
+    def calib_select_dev(self, M, stat_dev, cut_chi2, level, cut_I, idx_dev):
+        n = C.c_int(0)
+        self._chk(self.L.gpemu_calib_select_dev(self.h, M, stat_dev, cut_chi2, level, cut_I, idx_dev, C.byref(n)))
+        return n.value
 
     # the input measure of every sens_* entry (DESIGN.md 4.17): one kind per coordinate, MEASURE_UNIFORM (lo, hi: the bounds)
     # or MEASURE_GAUSS (lo: the mean, hi: the standard deviation)

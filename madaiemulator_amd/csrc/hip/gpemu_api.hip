@@ -310,6 +310,7 @@ extern "C" int gpemu_set_mode(gpemu_ctx *ctx, int flags)
 extern "C" int gpemu_get_mode(const gpemu_ctx *ctx) { return ctx ? ctx->mode : 0; }
 
 extern "C" const char *gpemu_last_error(const gpemu_ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
+extern "C" int gpemu_ctx_device(const gpemu_ctx *ctx) { return ctx ? ctx->device : -1; }
 
 extern "C" int gpemu_sync(gpemu_ctx *ctx)
 {
@@ -2937,6 +2938,141 @@ extern "C" int gpemu_loglik_grad(gpemu_ctx *ctx, const double *thetas, int nthet
 extern "C" int gpemu_grad(gpemu_ctx *ctx, const double *thetas, int nthetas, double *grad, int *info)
 {
 	return gpemu_loglik_grad(ctx, thetas, nthetas, nullptr, nullptr, nullptr, grad, info);
+}
+
+// ---------------------------------------------------------------------------
+// implausibility and calibration likelihood against observations (gpemu.h).  The set-up is host arithmetic
+// (gpemu_calib_project, kernels_calib.hip) and one upload of the table; an evaluation is one launch, a selection three.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_calib_setup(gpemu_ctx *ctx, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
+                                 const double *sd, const double *rel, int *info)
+{
+	if (info) *info = 0;
+	if (!ctx || !info) return GPEMU_ERR_ARG;
+	if (rel && nt >= 1 && nt <= GPEMU_CALIB_MAX_NT)
+		for (int t = 0; t < nt; t++)
+			if (!(rel[t] >= 0.0) || !std::isfinite(rel[t])) return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_setup: rel must be finite and >= 0");
+	if (nt < 1 || nr < 1) return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_setup: bad argument");
+	std::vector<double> mhat(GPEMU_CALIB_MAX_R), sigz(GPEMU_CALIB_MAX_R * GPEMU_CALIB_MAX_R);
+	double consts[3];
+	const int rc = gpemu_calib_project(nt, nr, ybar, A, z, S, sd, mhat.data(), sigz.data(), consts, info);
+	if (rc == GPEMU_ERR_NOT_PD) return fail(ctx, rc, "gpemu_calib_setup: S or A^T S^-1 A is not positive definite");
+	if (rc) return fail(ctx, rc, "gpemu_calib_setup: bad argument (NULL pointer, size beyond the limits, non-finite input, sd <= 0)");
+	std::vector<double> sdiag(nt), tab(calib_table_elems(nt, nr));
+	for (int t = 0; t < nt; t++) sdiag[t] = S ? S[(size_t)t * nt + t] : sd[t] * sd[t];
+	calib_fill_table(nt, nr, ybar, A, z, sdiag.data(), rel, mhat.data(), sigz.data(), consts, tab.data());
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	// work enqueued against the old table ends before the new one replaces it (the upload below reads pageable memory: it
+	// has completed when the call returns)
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->calib_nt = 0;
+	const int gr = grow(ctx, ctx->dCalibTab, tab.size());
+	if (gr) return gr;
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCalibTab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->calib_nt = nt; ctx->calib_nr = nr;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->calib_nt = ctx->calib_nr = 0;
+	ctx->dCalibTab.reset(); ctx->dCalibIO.reset();
+	ctx->dCalibIdx.reset(); ctx->dCalibCnt.reset();
+	ctx->hCalibCnt.reset();
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_eval_dev(gpemu_ctx *ctx, int M, const double *mean_dev, const double *var_dev, int ld, double *stat_dev,
+                                    int *worst_dev)
+{
+	if (!ctx || !mean_dev || !var_dev || !stat_dev || !worst_dev || M < 1 || ld < M) return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_eval: bad argument");
+	if (!ctx->calib_nt) return fail(ctx, GPEMU_ERR_STATE, "gpemu_calib_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const double nt = ctx->calib_nt, nr = ctx->calib_nr, R = calib_pad(ctx->calib_nr);
+	if (prof_on(ctx, GPEMU_PROF_CALIB)) ctx->prof.tag.push_back("calib_eval");
+	ProfScope ps(ctx, GPEMU_PROF_CALIB, (double)M * (4.0 * nt * R + 8.0 * nt + R * R * R / 3.0 + 2.0 * R * R),
+	             8.0 * M * (2.0 * nr + 5.0) + 4.0 * M);
+	HIPCHK(ctx, launch_calib_eval(ctx->stream, ctx->dCalibTab, ctx->calib_nt, ctx->calib_nr, M, mean_dev, var_dev, ld, stat_dev, worst_dev));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_eval(gpemu_ctx *ctx, int M, const double *mean, const double *var, int ld, double *stat, int *worst)
+{
+	if (!ctx || !mean || !var || !stat || !worst || M < 1 || ld < M) return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_eval: bad argument");
+	if (!ctx->calib_nt) return fail(ctx, GPEMU_ERR_STATE, "gpemu_calib_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t nr = (size_t)ctx->calib_nr, m = (size_t)M, in = nr * m;     // the device copies are packed: leading dimension M
+	int rc = grow(ctx, ctx->dCalibIO, 2 * in + 5 * m);
+	if (!rc) rc = grow(ctx, ctx->dCalibIdx, m);
+	if (rc) return rc;
+	double *dm = ctx->dCalibIO, *dv = dm + in, *ds = dv + in;
+	HIPCHK(ctx, hipMemcpy2DAsync(dm, m * sizeof(double), mean, (size_t)ld * sizeof(double), m * sizeof(double), nr, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(dv, m * sizeof(double), var, (size_t)ld * sizeof(double), m * sizeof(double), nr, hipMemcpyHostToDevice, ctx->stream));
+	rc = gpemu_calib_eval_dev(ctx, M, dm, dv, M, ds, ctx->dCalibIdx);
+	if (rc) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(stat, ds, 5 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(worst, ctx->dCalibIdx, m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_select_dev(gpemu_ctx *ctx, int M, const double *stat_dev, double cut_chi2, int level, double cut_I, int *idx_dev,
+                                      int *count)
+{
+	if (count) *count = 0;
+	if (!ctx || !stat_dev || !idx_dev || !count || M < 1 || level < 1 || level > 3 || cut_chi2 != cut_chi2 || cut_I != cut_I)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_select: bad argument");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int nb = calib_select_blocks(M);
+	int rc = grow(ctx, ctx->dCalibCnt, (size_t)nb + 1);
+	if (!rc) rc = grow(ctx, ctx->hCalibCnt, 1);
+	if (rc) return rc;
+	{
+		if (prof_on(ctx, GPEMU_PROF_CALIB)) ctx->prof.tag.push_back("calib_select");
+		ProfScope ps(ctx, GPEMU_PROF_CALIB, 0.0, 36.0 * M + 8.0 * nb);
+		HIPCHK(ctx, launch_calib_select(ctx->stream, stat_dev, M, cut_chi2, level, cut_I, ctx->dCalibCnt, idx_dev));
+	}
+	HIPCHK(ctx, hipMemcpyAsync(ctx->hCalibCnt, ctx->dCalibCnt + nb, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	*count = ctx->hCalibCnt[0];
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_gather_dev(gpemu_ctx *ctx, int M, const double *stat_dev, const int *worst_dev, int count, const int *idx_dev,
+                                      double *out_dev, int *worst_out_dev)
+{
+	if (!ctx || !stat_dev || !idx_dev || !out_dev || M < 1 || count < 0) return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_gather: bad argument");
+	if (!count) return GPEMU_OK;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, launch_calib_gather(ctx->stream, stat_dev, worst_dev, M, count, idx_dev, out_dev, worst_dev ? worst_out_dev : nullptr));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_select(gpemu_ctx *ctx, int M, const double *stat, double cut_chi2, int level, double cut_I, int *idx, int *count)
+{
+	if (count) *count = 0;
+	if (!ctx || !stat || !idx || !count || M < 1 || level < 1 || level > 3 || cut_chi2 != cut_chi2 || cut_I != cut_I)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_select: bad argument");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t m = (size_t)M;
+	int rc = grow(ctx, ctx->dCalibIO, 5 * m);
+	if (!rc) rc = grow(ctx, ctx->dCalibIdx, m);
+	if (rc) return rc;
+	// the two rows the cuts read: chi2 and the level-th largest implausibility, at their places in a 5 x M layout
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCalibIO, stat, m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dCalibIO + (size_t)(1 + level) * m, stat + (size_t)(1 + level) * m, m * sizeof(double),
+	                           hipMemcpyHostToDevice, ctx->stream));
+	rc = gpemu_calib_select_dev(ctx, M, ctx->dCalibIO, cut_chi2, level, cut_I, ctx->dCalibIdx, count);
+	if (rc) return rc;
+	if (*count > 0) {
+		HIPCHK(ctx, hipMemcpyAsync(idx, ctx->dCalibIdx, (size_t)*count * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	return GPEMU_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -331,6 +331,14 @@ struct gpemu_ctx {
 	// pair sweeps' partial sums (npairs per tile), dSensPairOut the npairs results of the host entries
 	gpemu::DevBuf<double> dSensPex2, dSensPairPart, dSensPairOut;
 	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
+	// calibration against observations (gpemu_calib_*): dCalibTab the resident table of one observation set
+	// (kernels_calib.hip has its layout; calib_nt > 0: set up), independent of the model: gpemu_set_model leaves it alone,
+	// gpemu_calib_release and the end of the context free it.  dCalibIO / dCalibIdx the host entries' device copies of mean,
+	// var and stat / of worst or idx; dCalibCnt the selection's per-workgroup counts, then the total; hCalibCnt that total, pinned
+	int calib_nt = 0, calib_nr = 0;
+	gpemu::DevBuf<double> dCalibTab, dCalibIO;
+	gpemu::DevBuf<int> dCalibIdx, dCalibCnt;
+	gpemu::PinnedBuf<int> hCalibCnt;
 	// the input measure of the sensitivity entries per coordinate (gpemu_sens_set_measure): GPEMU_MEASURE_*,
 	// all uniform from gpemu_set_model on; kept by gpemu_set_training, the prediction set-ups and gpemu_sens_release
 	int sens_kind[GPEMU_MAX_PARAMS] = {};
@@ -529,5 +537,19 @@ hipError_t launch_sens_pair_post_finish(hipStream_t s, const double *part, int N
 hipError_t launch_sens_joint(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
                              const double *prep, const double *pex2, const double *cst, int j, int k, int npts, const double *xj,
                              const double *xk, double *e0, double *joint, double *inter);
+
+// ---- kernels_calib.hip: implausibility and calibration likelihood against observations
+// the device table of one observation set: calib_table_elems doubles, filled on the host from gpemu_calib_project's outputs
+// (sdiag: S_tt per output); eval: mean, var component-major with leading dimension ld, stat 5 x M, worst M; select: counts
+// calib_select_blocks(M) + 1 ints (the total kept is left in the last one), idx M ints
+int calib_pad(int nr);
+size_t calib_table_elems(int nt, int nr);
+void calib_fill_table(int nt, int nr, const double *ybar, const double *A, const double *z, const double *sdiag, const double *rel,
+                      const double *mhat, const double *sigz, const double *consts, double *tab);
+hipError_t launch_calib_eval(hipStream_t s, const double *tab, int nt, int nr, int M, const double *mean, const double *var, long ld,
+                             double *stat, int *worst);
+int calib_select_blocks(int M);
+hipError_t launch_calib_gather(hipStream_t s, const double *stat, const int *worst, int M, int count, const int *idx, double *out, int *wout);
+hipError_t launch_calib_select(hipStream_t s, const double *stat, int M, double cut_chi2, int level, double cut_I, int *counts, int *idx);
 
 } // namespace gpemu

@@ -17,13 +17,18 @@ void emulator::init(const std::string &path, bool pca)
 	the_model = load_multi_modelstruct(fptr);
 	fclose(fptr);
 	the_emulator = alloc_multi_emulator(the_model);
+	the_observations = NULL;
 	number_outputs = pca ? the_model->nr : the_model->nt;
 	number_params = the_model->nparams;
 }
 
 emulator::emulator(std::string path) { init(path, false); }
 emulator::emulator(std::string path, bool PcaOnly) { init(path, PcaOnly); }
-emulator::~emulator() { free_multi_emulator(the_emulator); }
+emulator::~emulator()
+{
+	free_observations(the_observations);
+	free_multi_emulator(the_emulator);
+}
 
 // the one complaint of the Query* methods about a point's length, under the name of the method that was called
 static void wrong_dimensions(const char *method)
@@ -122,6 +127,61 @@ void emulator::QueryEmulatorCovariance(const std::vector<std::vector<double> > &
 		for (int i = 0; i < number_outputs; i++) Means[q][i] = m[q * number_outputs + i];
 	Covariances.assign(number_outputs, std::vector<double>());
 	for (int i = 0; i < number_outputs; i++) Covariances[i].assign(c.begin() + (size_t)i * np * np, c.begin() + (size_t)(i + 1) * np * np);
+}
+
+void emulator::SetObservations(const std::vector<double> &Values, const std::vector<double> &StandardDeviations,
+                               const std::vector<double> &Covariance, const std::vector<double> &RelativeErrors)
+{
+	const size_t nt = (size_t)the_model->nt;
+	const bool cov = !Covariance.empty();
+	if (Values.size() != nt || (cov ? Covariance.size() != nt * nt : StandardDeviations.size() != nt)
+	    || (!RelativeErrors.empty() && RelativeErrors.size() != nt)) {
+		std::cerr << "Error::SetObservations called with vectors that do not match the number of outputs" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	free_observations(the_observations);
+	the_observations = alloc_observations(the_model, Values.data(), cov ? NULL : StandardDeviations.data(), cov ? Covariance.data() : NULL,
+	                                      RelativeErrors.empty() ? NULL : RelativeErrors.data());
+}
+
+// the observation set the two calibration methods need
+static void need_observations(const char *method, const gpemu_observations *obs)
+{
+	if (obs) return;
+	std::cerr << "Error::" << method << " called before SetObservations" << std::endl;
+	gpemu_host_exit(EXIT_FAILURE);
+}
+
+void emulator::QueryEmulatorImplausibility(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Statistics,
+                                           std::vector<int> &WorstOutput)
+{
+	need_observations("QueryEmulatorImplausibility", the_observations);
+	const size_t np = xpoints.size();
+	std::vector<double> st(np * 5 + 1);
+	std::vector<double> flat = flatten("QueryEmulatorImplausibility", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
+	WorstOutput.assign(np, 0);
+	if (np) emulate_points_multi_implausibility(the_emulator, the_observations, &view, st.data(), WorstOutput.data());
+	Statistics.assign(np, std::vector<double>(5));
+	for (size_t q = 0; q < np; q++)
+		for (int s = 0; s < 5; s++) Statistics[q][s] = st[q * 5 + s];
+}
+
+void emulator::QueryEmulatorNonImplausible(const std::vector<std::vector<double> > &xpoints, double CutChi2, int Level, double CutI,
+                                           std::vector<int> &Kept, std::vector<std::vector<double> > &Statistics)
+{
+	need_observations("QueryEmulatorNonImplausible", the_observations);
+	const size_t np = xpoints.size();
+	std::vector<double> st(np * 5 + 1);
+	std::vector<double> flat = flatten("QueryEmulatorNonImplausible", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
+	Kept.assign(np + 1, 0);
+	int nkeep = 0;
+	if (np) emulate_points_multi_nonimplausible(the_emulator, the_observations, &view, CutChi2, Level, CutI, Kept.data(), st.data(), &nkeep);
+	Kept.resize((size_t)nkeep);
+	Statistics.assign((size_t)nkeep, std::vector<double>(5));
+	for (int q = 0; q < nkeep; q++)
+		for (int s = 0; s < 5; s++) Statistics[q][s] = st[(size_t)q * 5 + s];
 }
 
 // the box of the two sensitivity methods, checked to have number_params entries on either side

@@ -99,6 +99,19 @@ public:
 	                                     const std::vector<double> &gk, std::vector<double> &Means,
 	                                     std::vector<std::vector<std::vector<double> > > &Joint,
 	                                     std::vector<std::vector<std::vector<double> > > &Interaction);
+	// calibration against observations (libemu.h: alloc_observations, emulate_points_multi_implausibility, _nonimplausible).
+	// SetObservations: Values (nt observed outputs, observable space whatever PcaOnly says) with StandardDeviations (nt) or, if
+	// not empty, Covariance (nt x nt row-major, replaces the squared standard deviations), and RelativeErrors (nt, or empty: none);
+	// replaces an earlier set.  A malformed set ends in the layer's fatal exit.  Statistics[q] = {chi2, joint log density,
+	// largest, second and third largest per-output implausibility}, WorstOutput[q] the output of the largest.
+	// QueryEmulatorNonImplausible keeps point q iff chi2 <= CutChi2 and the Level-th largest implausibility (1, 2 or 3) <= CutI
+	// (INFINITY disables a cut): Kept holds the indices in ascending order, Statistics their rows; only those leave the device.
+	void SetObservations(const std::vector<double> &Values, const std::vector<double> &StandardDeviations,
+	                     const std::vector<double> &Covariance, const std::vector<double> &RelativeErrors);
+	void QueryEmulatorImplausibility(const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Statistics,
+	                                 std::vector<int> &WorstOutput);
+	void QueryEmulatorNonImplausible(const std::vector<std::vector<double> > &xpoints, double CutChi2, int Level, double CutI,
+	                                 std::vector<int> &Kept, std::vector<std::vector<double> > &Statistics);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }
@@ -112,5 +125,6 @@ private:
 	std::string StateFilePath;
 	multi_modelstruct *the_model;
 	multi_emulator *the_emulator;
+	gpemu_observations *the_observations;
 };
 #endif

@@ -1404,6 +1404,97 @@ void emulate_interaction_surface(emulator_struct *e, const double *lo, const dou
 	check(en, rc, "emulate_interaction_surface");
 }
 
+/* ---- calibration against observations (gpemu_calib_* in gpemu.h; the observation sets of multi.c).  An observation set has a
+ * device context of its own, registered under its pointer: on the device a context of the calling thread lands on, which is
+ * component 0's (alloc_multi_emulator places component 0 there).  gpemu_host_release(key) ends it. */
+void gpemu_host_calib_setup(const void *key, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
+                            const double *sd, const double *rel)
+{
+	struct entry *en = lookup(key, 1);
+	int info = 0;
+	const int rc = gpemu_calib_setup(en->ctx, nt, nr, ybar, A, z, S, sd, rel, &info);
+	if (rc == GPEMU_ERR_NOT_PD)
+		gpemu_host_fatal("alloc_observations: the observation covariance, or A^T S^-1 A, is not positive definite (pivot %d)\n", info);
+	if (rc) die(en->ctx, rc, "alloc_observations");
+}
+
+/* One block of np points (row-major, np x d) through every component and the calibration epilogue.  The points go up once per
+ * device; every component's gpemu_predict_batch_dev writes its rows of a component-major buffer (means, then variances) on the
+ * observation set's device -- a component elsewhere writes next to its queries and its two rows cross through the host --; all
+ * are started before the first is waited for; then ONE evaluation launch.  select = 0: stat (np x 5, point-major) and worst
+ * (np, may be NULL) come back.  select = 1: the selection runs on the device and only the kept points' indices (idx, ascending,
+ * block-relative) and statistics (stat, nkeep x 5) and worst outputs come back.  No np x nt array exists anywhere. */
+void gpemu_host_calib_block(const void *key, emulator_struct **es, int nr, int np, int d, const double *q, int select, double cut_chi2,
+                            int level, double cut_I, double *stat, int *worst, int *idx, int *nkeep)
+{
+	struct entry *ob = lookup(key, 0);
+	if (!ob) gpemu_host_fatal("emulate_points_multi_implausibility: the observation set was not made by alloc_observations\n");
+	const size_t n = (size_t)np, r = (size_t)nr;
+	const int dev0 = gpemu_ctx_device(ob->ctx);
+	struct entry **en = (struct entry **)malloc(sizeof(struct entry *) * r);
+	void **xq = (void **)calloc(r, sizeof(void *));           /* xq[c] != NULL: component c owns the upload on its device */
+	void *blk = NULL;
+	/* on the observation set's device: means (nr x np), variances (nr x np), stat (5 x np), the gathered rows (np x 5), then
+	 * worst, idx and the gathered worst (np ints each) */
+	int rc = gpemu_dev_alloc(ob->ctx, (2 * r + 10) * n * sizeof(double) + 3 * n * sizeof(int), &blk);
+	if (rc) die(ob->ctx, rc, "emulate_points_multi_implausibility");
+	double *dm = (double *)blk, *dv = dm + r * n, *ds = dv + r * n, *dg = ds + 5 * n;
+	int *dw = (int *)(dg + 5 * n), *di = dw + n, *dgw = di + n;
+	for (size_t c = 0; c < r; c++) {
+		en[c] = entry_of(es[c], "emulate_points_multi_implausibility");
+		const int dev = gpemu_ctx_device(en[c]->ctx);
+		size_t o = 0;
+		while (o < c && gpemu_ctx_device(en[o]->ctx) != dev) o++;        /* the first component on this device holds its queries */
+		if (o == c) {
+			/* queries, and for a device other than the observation set's two rows of results behind them */
+			rc = gpemu_dev_alloc(en[c]->ctx, (n * (size_t)d + (dev == dev0 ? 0 : 2 * n * r)) * sizeof(double), &xq[c]);
+			if (!rc) rc = gpemu_dev_upload(en[c]->ctx, xq[c], q, n * (size_t)d * sizeof(double));
+			check(en[c], rc, "emulate_points_multi_implausibility");
+		}
+		double *x = (double *)xq[o];
+		if (dev == dev0) rc = gpemu_predict_batch_dev(en[c]->ctx, np, x, dm + c * n, dv + c * n);
+		else rc = gpemu_predict_batch_dev(en[c]->ctx, np, x, x + n * (size_t)d + 2 * c * n, x + n * (size_t)d + (2 * c + 1) * n);
+		check(en[c], rc, "emulate_points_multi_implausibility");
+	}
+	double *hop = NULL;
+	for (size_t c = 0; c < r; c++) {
+		const int dev = gpemu_ctx_device(en[c]->ctx);
+		if (dev == dev0) { check(en[c], gpemu_sync(en[c]->ctx), "emulate_points_multi_implausibility"); continue; }
+		size_t o = 0;
+		while (gpemu_ctx_device(en[o]->ctx) != dev) o++;
+		if (!hop) hop = (double *)malloc(sizeof(double) * 2 * n);
+		rc = gpemu_dev_download(en[c]->ctx, hop, (double *)xq[o] + n * (size_t)d + 2 * c * n, 2 * n * sizeof(double));
+		check(en[c], rc, "emulate_points_multi_implausibility");
+		rc = gpemu_dev_upload(ob->ctx, dm + c * n, hop, n * sizeof(double));
+		if (!rc) rc = gpemu_dev_upload(ob->ctx, dv + c * n, hop + n, n * sizeof(double));
+		if (rc) die(ob->ctx, rc, "emulate_points_multi_implausibility");
+	}
+	free(hop);
+	rc = gpemu_calib_eval_dev(ob->ctx, np, dm, dv, np, ds, dw);
+	int kept = np;
+	if (!rc && select) rc = gpemu_calib_select_dev(ob->ctx, np, ds, cut_chi2, level, cut_I, di, &kept);
+	if (!rc && select) rc = gpemu_calib_gather_dev(ob->ctx, np, ds, dw, kept, di, dg, dgw);
+	if (!rc && select && kept) {
+		rc = gpemu_dev_download(ob->ctx, idx, di, (size_t)kept * sizeof(int));
+		if (!rc) rc = gpemu_dev_download(ob->ctx, stat, dg, (size_t)kept * 5 * sizeof(double));
+		if (!rc && worst) rc = gpemu_dev_download(ob->ctx, worst, dgw, (size_t)kept * sizeof(int));
+	}
+	if (!rc && !select) {
+		double *h = (double *)malloc(sizeof(double) * 5 * n);
+		rc = gpemu_dev_download(ob->ctx, h, ds, 5 * n * sizeof(double));
+		for (size_t p = 0; !rc && p < n; p++)
+			for (int s = 0; s < 5; s++) stat[p * 5 + s] = h[(size_t)s * n + p];
+		free(h);
+		if (!rc && worst) rc = gpemu_dev_download(ob->ctx, worst, dw, n * sizeof(int));
+	}
+	if (rc) die(ob->ctx, rc, "emulate_points_multi_implausibility");
+	if (nkeep) *nkeep = kept;
+	for (size_t c = 0; c < r; c++)
+		if (xq[c]) check(en[c], gpemu_dev_free(en[c]->ctx, xq[c]), "emulate_points_multi_implausibility");
+	if (gpemu_dev_free(ob->ctx, blk)) die(ob->ctx, rc, "emulate_points_multi_implausibility");
+	free(xq); free(en);
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

@@ -32,7 +32,9 @@
 struct cmdLineOpts {
 	int regOrder, covFn, quietFlag, pcaOutputFlag, binaryFlag;
 	double pca_variance;
-	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile, *priorfile;
+	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile, *priorfile, *obsfile;
+	double cutI, cutChi2;
+	int level;
 	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
@@ -72,6 +74,11 @@ static const char useage[] =
 	"      --prior=FILE in place of --box: one line per parameter, \"uniform LO HI\" or \"gaussian MEAN SD\" (SD > 0): the input measure\n"
 	"      of each parameter, independent of the others; the curve and the surface of a Gaussian parameter run over MEAN -+ 2 SD.\n"
 	"      Power-exponential covariance only)\n"
+	"or\n"
+	"  interactive_emulator implausibility MODEL_SNAPSHOT_FILE --observations=FILE [--cut=C] [--level=k] [--chi2=C2] [--quiet]  (points from\n"
+	"      stdin to the end of input; one line per point whose k-th largest implausibility is <= C (default 3, k = 1) and whose joint\n"
+	"      chi^2 is <= C2 (default: no cut): index, parameters, chi^2, log likelihood, the three largest implausibilities, the worst\n"
+	"      output.  FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -83,6 +90,8 @@ static const char useage[] =
 	"  (-q) --quiet: run without any extraneous output\n"
 	"  (-z) --pca_output: emulator output is left in the pca space\n"
 	"  --binary: points are read and results written as raw doubles (the reference's BINARY_INTERACTIVE_MODE build)\n"
+	"  --observations=FILE: after a point's pairs its joint implausibility (chi^2), log likelihood and maximum implausibility\n"
+	"      against the observations of FILE (the format of `implausibility`); not with --pca_output\n"
 	"general options:\n"
 	"  -h -? print this dialogue\n"
 	"environment: GPEMU_DEVICE (HIP device), GPEMU_SEED, GPEMU_RESTARTS, GPEMU_JOBS, GPEMU_LOCKSTEP (restart threads\n"
@@ -154,7 +163,9 @@ static int estimate_thetas(struct cmdLineOpts *o)
 }
 
 /* one batch of waiting points through every component's emulator (multivar_support.c:103-157, batched) */
-struct emu_call { multi_emulator *emu; int pca_space, d; };
+struct emu_call { multi_emulator *emu; int pca_space, d; gpemu_observations *obs; };
+struct obs_file { int nt, has_cov; double *z, *sd, *rel, *cov; };
+static int read_observation_file(const char *name, int nt_model, struct obs_file *of);      /* below, with `implausibility` */
 
 static void emu_points(void *user, int np, const double *pts, double *mean, double *var)
 {
@@ -163,19 +174,44 @@ static void emu_points(void *user, int np, const double *pts, double *mean, doub
 	emulate_points_multi(c->emu, &view, c->pca_space, mean, var);
 }
 
+/* --observations: joint implausibility (chi^2), log likelihood and maximum implausibility of the same batch, behind its pairs
+ * (a second sweep of the batch: the calibration entry keeps its means and variances on the device) */
+static void emu_points_extra(void *user, int np, const double *pts, double *extra)
+{
+	struct emu_call *c = (struct emu_call *)user;
+	gsl_matrix view = gpemu_matrix_view((double *)pts, (size_t)np, (size_t)c->d);
+	double *st = (double *)malloc(sizeof(double) * 5 * (size_t)np);
+	emulate_points_multi_implausibility(c->emu, c->obs, &view, st, NULL);
+	for (int q = 0; q < np; q++) {
+		extra[(size_t)q * 3] = st[(size_t)q * 5];
+		extra[(size_t)q * 3 + 1] = st[(size_t)q * 5 + 1];
+		extra[(size_t)q * 3 + 2] = st[(size_t)q * 5 + 2];
+	}
+	free(st);
+}
+
 static int interactive_mode(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
 	if (!fp) return perr("Error opening file");
 	const double t_start = wall_s();
-	gpemu_host_warm_start();                             /* the HIP runtime starts while the snapshot is being parsed */
+	if (o->obsfile && o->pcaOutputFlag) return perr("--pca_output and --observations exclude each other: observations live in observable space");
+	/* the HIP runtime starts while the snapshot is being parsed -- unless an observation file has to be judged first: it is
+	 * parsed (against the snapshot's number of outputs) before any device is touched */
+	if (!o->obsfile) gpemu_host_warm_start();
 	/* nobody in this program reads emulator_struct.cinverse (the reference's interactive_mode does not either): spare every
 	 * component the N x N download (512 MB at N = 8192) -- the library keeps filling it for callers that link libEmu */
 	setenv("GPEMU_SKIP_CINVERSE", "1", 0);
 	multi_modelstruct *model = load_multi_modelstruct(fp);
 	fclose(fp);
+	struct obs_file of;
+	if (o->obsfile) {
+		if (!read_observation_file(o->obsfile, model->nt, &of)) return EXIT_FAILURE;
+		gpemu_host_warm_start();
+	}
 	const double t_loaded = wall_s();
 	multi_emulator *emu = alloc_multi_emulator(model);
+	gpemu_observations *obs = o->obsfile ? alloc_observations(model, of.z, of.has_cov ? NULL : of.sd, of.has_cov ? of.cov : NULL, of.rel) : NULL;
 	const double t_ready = wall_s();
 	const int d = model->nparams, nt = model->nt;
 	const int nout = o->pcaOutputFlag ? model->nr : nt;
@@ -183,22 +219,26 @@ static int interactive_mode(struct cmdLineOpts *o)
 	if (!o->quietFlag) {
 		fprintf(out, "%d\n", d);
 		for (int i = 0; i < d; i++) fprintf(out, "%s%d\n", "param_", i);
-		fprintf(out, "%d\n", 2 * nt);
+		fprintf(out, "%d\n", 2 * nt + (obs ? 3 : 0));
 		for (int i = 0; i < nt; i++) fprintf(out, "%s_%d\n%s_%d\n", "mean", i, "variance", i);
+		if (obs) fprintf(out, "joint_implausibility\nlog_likelihood\nmax_implausibility\n");
 	}
 	fflush(out);
 	/* the loop itself (interactive_emulator.c:414-441 of the reference): points already waiting on stdin are answered as
 	 * one device batch, a lone point at once; reading/parsing, the device and formatting/writing overlap (interactive_io.c).
 	 * The reference always prints nt pairs; in pca mode entries nr..nt-1 are whatever its vectors held: zeros here. */
-	struct emu_call call = {emu, o->pcaOutputFlag, d};
+	struct emu_call call = {emu, o->pcaOutputFlag, d, obs};
 	struct gpemu_io_stats st;
-	const int rc = gpemu_host_interactive_loop(STDIN_FILENO, STDOUT_FILENO, d, nout, nt, o->binaryFlag, emu_points, &call, &st);
+	const int rc = obs ? gpemu_host_interactive_loop_extra(STDIN_FILENO, STDOUT_FILENO, d, nout, nt, o->binaryFlag, emu_points, 3, emu_points_extra,
+	                                                       &call, &st)
+	                   : gpemu_host_interactive_loop(STDIN_FILENO, STDOUT_FILENO, d, nout, nt, o->binaryFlag, emu_points, &call, &st);
 	const char *want = getenv("GPEMU_IO_STATS");
 	if (want && atoi(want) > 0)
 		fprintf(stderr, "# interactive stats: points %ld batches %ld max_batch %d parse_s %.6f device_s %.6f format_s %.6f wall_s %.6f "
 		        "load_snapshot_s %.6f alloc_multi_emulator_s %.6f components %d\n",
 		        st.points, st.batches, st.max_batch, st.parse_seconds, st.compute_seconds, st.format_seconds, st.wall_seconds,
 		        t_loaded - t_start, t_ready - t_loaded, model->nr);
+	free_observations(obs);
 	free_multi_emulator(emu);
 	return rc == 0 ? 0 : EXIT_FAILURE;
 }
@@ -579,6 +619,122 @@ static int sensitivity(struct cmdLineOpts *o)
 	return 0;
 }
 
+/* The observation file of `implausibility` (and of alloc_observations' callers): line 1 the number of outputs nt; then nt
+ * lines "value sd [rel]" (sd > 0; rel >= 0, a relative model error, 0 where it is left out); then, optionally, a line
+ * "covariance" and nt rows of nt numbers that replace sd^2.  Host logic only.  Returns 1, or 0 with the complaint on stderr. */
+static int obs_complain(const char *what, int line)
+{
+	fprintf(stderr, "the observation file, line %d: %s\n(line 1: the number of outputs; then one line \"value sd [rel]\" per output, sd > 0, rel >= 0; "
+	        "optionally a line \"covariance\" and one row of the covariance matrix per output)\n", line, what);
+	return 0;
+}
+
+static int read_observation_file(const char *name, int nt_model, struct obs_file *of)
+{
+	FILE *f = fopen(name, "r");
+	if (!f) { fprintf(stderr, "Error opening the observation file\n"); return 0; }
+	char buf[65536], tail[8];
+	int line = 1, nt = 0;
+	memset(of, 0, sizeof *of);
+	if (!fgets(buf, sizeof buf, f) || sscanf(buf, "%d %7s", &nt, tail) != 1 || nt < 1) { fclose(f); return obs_complain("the number of outputs is missing", line); }
+	if (nt != nt_model) { fclose(f); fprintf(stderr, "the observation file has %d outputs, the model %d\n", nt, nt_model); return 0; }
+	of->nt = nt;
+	of->z = (double *)calloc((size_t)nt, sizeof(double)); of->sd = (double *)calloc((size_t)nt, sizeof(double));
+	of->rel = (double *)calloc((size_t)nt, sizeof(double)); of->cov = (double *)calloc((size_t)nt * nt, sizeof(double));
+	for (int t = 0; t < nt; t++) {
+		line++;
+		if (!fgets(buf, sizeof buf, f)) { fclose(f); return obs_complain("the file ends before every output has its line", line); }
+		const int n = sscanf(buf, "%lf %lf %lf %7s", &of->z[t], &of->sd[t], &of->rel[t], tail);
+		if (n != 2 && n != 3) { fclose(f); return obs_complain("two or three numbers are needed", line); }
+		if (n == 2) of->rel[t] = 0.0;
+		if (!isfinite(of->z[t]) || !isfinite(of->sd[t]) || !(of->sd[t] > 0.0) || !isfinite(of->rel[t]) || of->rel[t] < 0.0) {
+			fclose(f);
+			return obs_complain("a finite value, sd > 0 and rel >= 0 are needed", line);
+		}
+	}
+	while (fgets(buf, sizeof buf, f)) {                   /* blank lines, then nothing or the covariance block */
+		line++;
+		char word[32];
+		if (sscanf(buf, "%31s", word) != 1) continue;
+		if (strcmp(word, "covariance") || of->has_cov) { fclose(f); return obs_complain("\"covariance\" or the end of the file is expected here", line); }
+		of->has_cov = 1;
+		for (int t = 0; t < nt; t++) {
+			line++;
+			if (!fgets(buf, sizeof buf, f)) { fclose(f); return obs_complain("the covariance matrix ends early", line); }
+			char *p = buf, *end;
+			for (int u = 0; u < nt; u++) {
+				of->cov[(size_t)t * nt + u] = strtod(p, &end);
+				if (end == p || !isfinite(of->cov[(size_t)t * nt + u])) { fclose(f); return obs_complain("a row of the covariance matrix needs one finite number per output", line); }
+				p = end;
+			}
+			if (sscanf(p, "%7s", tail) == 1) { fclose(f); return obs_complain("a row of the covariance matrix has too many entries", line); }
+		}
+	}
+	fclose(f);
+	return 1;
+}
+
+/* History matching / calibration against observations (not in the reference's C; its R: libRbind/implausOverDesign.R): points
+ * are read from stdin to the end of input, d numbers each; for every point with chi^2 <= --chi2 (default: no cut) and level-th
+ * largest per-output implausibility <= --cut (defaults 3 and level 1: the customary 3 sigma cut on the maximum implausibility;
+ * the reference's plots cut its SQUARED quantity at 1.8) one line "index p_0 .. p_{d-1} chi2 log_likelihood I1 I2 I3 worst" is
+ * written.  The selection runs on the device; only the survivors come back.  stderr: the fraction kept, and c_perp with its
+ * nt - r degrees of freedom, the misfit no parameter value can remove.  The observation file is parsed before any device is
+ * touched. */
+static int implausibility(struct cmdLineOpts *o)
+{
+	if (!o->obsfile) return perr("implausibility needs --observations=FILE");
+	if (o->pcaOutputFlag) return perr("--pca_output and --observations exclude each other: observations live in observable space");
+	if (o->level < 1 || o->level > 3 || o->cutI != o->cutI || o->cutChi2 != o->cutChi2) return perr("--level=k needs k in 1 .. 3, --cut and --chi2 a number or inf");
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	struct obs_file of;
+	if (!read_observation_file(o->obsfile, model->nt, &of)) return EXIT_FAILURE;
+	const int d = model->nparams;
+	size_t cap = 1024, n = 0;
+	double *v = (double *)malloc(sizeof(double) * cap), x;
+	while (fscanf(stdin, "%lf", &x) == 1) {
+		if (n == cap) v = (double *)realloc(v, sizeof(double) * (cap *= 2));
+		v[n++] = x;
+	}
+	if (!feof(stdin) || n % (size_t)d) return perr("implausibility: stdin must hold whole points, d numbers each, and nothing else");
+	const size_t np = n / (size_t)d;
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_emulator *emu = alloc_multi_emulator(model);
+	gpemu_observations *obs = alloc_observations(model, of.z, of.has_cov ? NULL : of.sd, of.has_cov ? of.cov : NULL, of.rel);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "# index");
+		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
+		fprintf(out, " joint_implausibility log_likelihood max_implausibility second_implausibility third_implausibility worst_output\n");
+	}
+	int nkeep = 0;
+	if (np) {
+		gsl_matrix pts = gpemu_matrix_view(v, np, (size_t)d);
+		int *idx = (int *)malloc(sizeof(int) * np), *worst = (int *)malloc(sizeof(int) * np);
+		double *st = (double *)malloc(sizeof(double) * 5 * np);
+		emulate_points_multi_nonimplausible_worst(emu, obs, &pts, o->cutChi2, o->level, o->cutI, idx, st, worst, &nkeep);
+		for (int k = 0; k < nkeep; k++) {
+			fprintf(out, "%d", idx[k]);
+			for (int j = 0; j < d; j++) fprintf(out, " %.17g", v[(size_t)idx[k] * d + j]);
+			fprintf(out, " %.17g %.17g %.17g %.17g %.17g %d\n", st[k * 5], st[k * 5 + 1], st[k * 5 + 2], st[k * 5 + 3], st[k * 5 + 4], worst[k]);
+		}
+		free(idx); free(worst); free(st);
+	}
+	fflush(out);
+	double c_perp; int dof;
+	gpemu_host_observations_misfit(obs, &c_perp, &dof);
+	fprintf(stderr, "# implausibility: kept %d of %zu points (fraction %.6g); c_perp %.17g with %d degrees of freedom\n", nkeep, np,
+	        np ? (double)nkeep / (double)np : 0.0, c_perp, dof);
+	free(v);
+	free_observations(obs);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static int print_thetas(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -636,9 +792,13 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"pairs", no_argument, NULL, 1010},                   {"surface", required_argument, NULL, 1011},
 		/* ... under a measure per parameter, uniform or Gaussian, in place of the box */
 		{"prior", required_argument, NULL, 1012},
+		/* implausibility: the observation file, the cut on the level-th largest implausibility, the cut on the joint chi^2 */
+		{"observations", required_argument, NULL, 1013},      {"cut", required_argument, NULL, 1014},
+		{"level", required_argument, NULL, 1015},             {"chi2", required_argument, NULL, 1016},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
+	o->cutI = 3.0; o->cutChi2 = INFINITY; o->level = 1;
 	int idx, opt;
 	while ((opt = getopt_long(argc, argv, optString, longOpts, &idx)) != -1) {
 		switch (opt) {
@@ -670,6 +830,10 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 			if (sscanf(optarg, "%d,%d", &o->surfJ, &o->surfK) != 2) o->surfJ = o->surfK = -1;
 			break;
 		case 1012: o->priorfile = optarg; break;
+		case 1013: o->obsfile = optarg; break;
+		case 1014: o->cutI = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
+		case 1015: o->level = atoi(optarg); break;
+		case 1016: o->cutChi2 = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
@@ -701,6 +865,7 @@ int main(int argc, char **argv)
 	else if (!strcmp(o->run_mode, "print_thetas")) rc = print_thetas(o);
 	else if (!strcmp(o->run_mode, "validate")) rc = validate(o);
 	else if (!strcmp(o->run_mode, "sensitivity")) rc = sensitivity(o);
+	else if (!strcmp(o->run_mode, "implausibility")) rc = implausibility(o);
 	else { free(o); return perr(useage); }
 	free(o);
 	return rc;

@@ -33,7 +33,7 @@
 #define IO_HELPERS_MAX 7
 #define IO_PAR_MIN 4096               /* numbers in a batch from which the helpers are woken */
 
-struct io_slot { int np, last; double *pts, *mean, *var; };
+struct io_slot { int np, last; double *pts, *mean, *var, *extra; };   /* extra: np x nextra, NULL when nextra = 0 */
 
 struct io_queue { struct io_slot *item[IO_SLOTS]; int head, count; pthread_mutex_t mu; pthread_cond_t cv; };
 
@@ -135,8 +135,9 @@ static double now_s(void)
 
 /* ---- the pipeline ---- */
 struct io_state {
-	int fd_in, fd_out, efd, d, nout, nprint, binary, nhelp;
+	int fd_in, fd_out, efd, d, nout, nprint, nextra, binary, nhelp;
 	gpemu_points_fn fn;
+	gpemu_points_extra_fn fn_extra;
 	void *user;
 	struct io_queue free_q, work_q, out_q;
 	int inflight;                       /* batches handed to the device stage and not finished (atomic) */
@@ -248,22 +249,27 @@ static void *reader_main(void *a)
 	return NULL;
 }
 
-/* "%.17f\n" of mean and variance, nprint pairs per point (pairs beyond nout are zeros: pca-space output keeps nt pairs) */
+/* "%.17f\n" of mean and variance, nprint pairs per point (pairs beyond nout are zeros: pca-space output keeps nt pairs), then
+ * the point's nextra extra values, one "%.17f\n" each */
 struct fmt_job { struct io_state *S; struct io_slot *s; char *buf[IO_HELPERS_MAX + 1]; size_t cap[IO_HELPERS_MAX + 1], len[IO_HELPERS_MAX + 1]; };
 
 static void fmt_part(void *a, int part, int nparts)
 {
 	struct fmt_job *j = (struct fmt_job *)a;
 	const struct io_state *S = j->S;
-	const int np = j->s->np, nout = S->nout, nprint = S->nprint;
+	const int np = j->s->np, nout = S->nout, nprint = S->nprint, nextra = S->nextra;
 	const int lo = (int)((long)np * part / nparts), hi = (int)((long)np * (part + 1) / nparts);
 	size_t used = 0;
 	for (int q = lo; q < hi; q++)
-		for (int i = 0; i < nprint; i++) {
+		for (int i = 0; i < nprint + nextra; i++) {
 			if (j->cap[part] - used < 800) {                    /* two numbers of up to 328 characters each */
 				j->cap[part] = j->cap[part] * 2 + 4096;
 				j->buf[part] = (char *)realloc(j->buf[part], j->cap[part]);
 				if (!j->buf[part]) { perror("realloc"); gpemu_host_exit(EXIT_FAILURE); }
+			}
+			if (i >= nprint) {
+				used += (size_t)snprintf(j->buf[part] + used, j->cap[part] - used, "%.17f\n", j->s->extra[(size_t)q * nextra + (i - nprint)]);
+				continue;
 			}
 			const double m = i < nout ? j->s->mean[(size_t)q * nout + i] : 0.0, v = i < nout ? j->s->var[(size_t)q * nout + i] : 0.0;
 			used += (size_t)snprintf(j->buf[part] + used, j->cap[part] - used, "%.17f\n%.17f\n", m, v);
@@ -290,22 +296,25 @@ static void *writer_main(void *a)
 	struct fmt_job job;
 	memset(&job, 0, sizeof job);
 	job.S = S;
-	double *bin = S->binary ? (double *)malloc(sizeof(double) * 2 * (size_t)IO_BATCH_MAX * S->nprint) : NULL;
+	const size_t per = 2 * (size_t)S->nprint + (size_t)S->nextra;        /* doubles per point */
+	double *bin = S->binary ? (double *)malloc(sizeof(double) * (size_t)IO_BATCH_MAX * per) : NULL;
 	for (;;) {
 		struct io_slot *s = q_pop(&S->out_q);
 		const int last = s->last;
 		if (s->np > 0 && !S->write_failed) {
 			const double t0 = now_s();
 			if (S->binary) {
-				for (int q = 0; q < s->np; q++)
+				for (int q = 0; q < s->np; q++) {
 					for (int i = 0; i < S->nprint; i++) {
-						bin[2 * ((size_t)q * S->nprint + i)] = i < S->nout ? s->mean[(size_t)q * S->nout + i] : 0.0;
-						bin[2 * ((size_t)q * S->nprint + i) + 1] = i < S->nout ? s->var[(size_t)q * S->nout + i] : 0.0;
+						bin[(size_t)q * per + 2 * (size_t)i] = i < S->nout ? s->mean[(size_t)q * S->nout + i] : 0.0;
+						bin[(size_t)q * per + 2 * (size_t)i + 1] = i < S->nout ? s->var[(size_t)q * S->nout + i] : 0.0;
 					}
-				if (write_all(S->fd_out, (const char *)bin, sizeof(double) * 2 * (size_t)s->np * S->nprint)) S->write_failed = 1;
+					for (int i = 0; i < S->nextra; i++) bin[(size_t)q * per + 2 * (size_t)S->nprint + i] = s->extra[(size_t)q * S->nextra + i];
+				}
+				if (write_all(S->fd_out, (const char *)bin, sizeof(double) * (size_t)s->np * per)) S->write_failed = 1;
 			} else {
 				job.s = s;
-				const int serial = (long)s->np * S->nprint * 2 < IO_PAR_MIN;
+				const int serial = (long)s->np * (S->nprint * 2 + S->nextra) < IO_PAR_MIN;
 				pool_run(&pool, fmt_part, &job, serial);
 				const int nparts = serial ? 1 : pool.nhelp + 1;
 				for (int p = 0; p < nparts && !S->write_failed; p++)
@@ -325,11 +334,18 @@ static void *writer_main(void *a)
 int gpemu_host_interactive_loop(int fd_in, int fd_out, int nparams, int nout, int nprint, int binary, gpemu_points_fn fn,
                                 void *user, struct gpemu_io_stats *stats)
 {
-	if (nparams < 1 || nout < 1 || nprint < nout || !fn) return -1;
+	return gpemu_host_interactive_loop_extra(fd_in, fd_out, nparams, nout, nprint, binary, fn, 0, NULL, user, stats);
+}
+
+int gpemu_host_interactive_loop_extra(int fd_in, int fd_out, int nparams, int nout, int nprint, int binary, gpemu_points_fn fn,
+                                      int nextra, gpemu_points_extra_fn fn_extra, void *user, struct gpemu_io_stats *stats)
+{
+	if (nparams < 1 || nout < 1 || nprint < nout || !fn || nextra < 0 || (nextra > 0) != (fn_extra != NULL)) return -1;
 	struct io_state *S = (struct io_state *)calloc(1, sizeof *S);
 	if (!sep_tab[' ']) { const char *sp = " \t\r\n,;"; for (; *sp; sp++) sep_tab[(unsigned char)*sp] = 1; }
 	S->fd_in = fd_in; S->fd_out = fd_out; S->d = nparams; S->nout = nout; S->nprint = nprint; S->binary = binary != 0;
 	S->fn = fn; S->user = user;
+	S->nextra = nextra; S->fn_extra = fn_extra;
 	S->efd = eventfd(0, EFD_NONBLOCK);
 	if (S->efd < 0) { free(S); return -1; }
 	{
@@ -346,7 +362,8 @@ int gpemu_host_interactive_loop(int fd_in, int fd_out, int nparams, int nout, in
 		slots[i].pts = (double *)malloc(sizeof(double) * (size_t)IO_BATCH_MAX * nparams);
 		slots[i].mean = (double *)malloc(sizeof(double) * (size_t)IO_BATCH_MAX * nout);
 		slots[i].var = (double *)malloc(sizeof(double) * (size_t)IO_BATCH_MAX * nout);
-		if (!slots[i].pts || !slots[i].mean || !slots[i].var) { perror("malloc"); gpemu_host_exit(EXIT_FAILURE); }
+		slots[i].extra = nextra ? (double *)malloc(sizeof(double) * (size_t)IO_BATCH_MAX * nextra) : NULL;
+		if (!slots[i].pts || !slots[i].mean || !slots[i].var || (nextra && !slots[i].extra)) { perror("malloc"); gpemu_host_exit(EXIT_FAILURE); }
 		q_push(&S->free_q, &slots[i]);
 	}
 	const double t0 = now_s();
@@ -358,6 +375,7 @@ int gpemu_host_interactive_loop(int fd_in, int fd_out, int nparams, int nout, in
 		if (s->np > 0) {
 			const double c0 = now_s();
 			fn(user, s->np, s->pts, s->mean, s->var);
+			if (nextra) fn_extra(user, s->np, s->pts, s->extra);
 			S->st.compute_seconds += now_s() - c0;
 			S->st.points += s->np;
 			S->st.batches++;
@@ -372,7 +390,7 @@ int gpemu_host_interactive_loop(int fd_in, int fd_out, int nparams, int nout, in
 	S->st.wall_seconds = now_s() - t0;
 	if (stats) *stats = S->st;
 	const int failed = S->write_failed;
-	for (int i = 0; i < IO_SLOTS; i++) { free(slots[i].pts); free(slots[i].mean); free(slots[i].var); }
+	for (int i = 0; i < IO_SLOTS; i++) { free(slots[i].pts); free(slots[i].mean); free(slots[i].var); free(slots[i].extra); }
 	close(S->efd);
 	free(S);
 	return failed ? -2 : 0;

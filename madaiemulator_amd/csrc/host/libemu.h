@@ -412,6 +412,39 @@ void emulate_points_multi_holdout(multi_emulator *emu, gsl_matrix *points, const
  * c draws with z[c] from its own factor), out is ndraw x npoints x nr in PCA space or ndraw x npoints x nt in observable space:
  * training_mean + evecs diag(sqrt(evals)) draw_pca through gpemu_host_backproject (not squared, mean added) */
 void emulate_points_multi_draw(multi_emulator *emu, int pca_space, int npoints, int ndraw, const double *z, double *out);
+/* extension: implausibility and calibration likelihood against observations (gpemu_calib_* in gpemu.h; the
+ * reference does this in R only: libRbind/implausOverDesign.R).  An observation set: z (nt values) with either standard
+ * deviations sd (nt) or a covariance cov (nt x nt, row-major, replaces sd^2) -- exactly one of the two --, and optionally a
+ * relative model error rel (nt, >= 0: the reference's errModel.sys; NULL: none).  alloc_observations builds A = pca_evecs_r
+ * sqrt(pca_evals_r) and ybar = training_mean exactly as gpemu_host_backproject does (the factor u * sqrt(lam) formed first),
+ * runs the projection and keeps its tables on the device of component 0.  nr <= 16, nt <= 1024; beyond, a malformed set or a
+ * covariance that is not positive definite: a message and the layer's exit.  gpemu_host_observations_misfit: c_perp, the
+ * misfit no parameter value can remove, and its degrees of freedom nt - nr. */
+typedef struct gpemu_observations gpemu_observations;
+gpemu_observations *alloc_observations(multi_modelstruct *m, const double *z, const double *sd, const double *cov, const double *rel);
+void free_observations(gpemu_observations *obs);
+void gpemu_host_observations_misfit(const gpemu_observations *obs, double *c_perp, int *dof);
+/* the reference's confidence rule (implausOverDesign.R): a relative error sig / qnorm(1 - sig / 2) for 0 < sig < 1, NaN otherwise */
+double gpemu_host_confidence_to_rel(double sig);
+/* stat_out: npoints x 5 per point {chi2, joint log density, largest, second and third largest per-output implausibility};
+ * worst_out (npoints, may be NULL): the output of the largest.  The points go up once per device, every component's
+ * gpemu_predict_batch_dev writes its row of a component-major device buffer (all started before the first is waited for; a
+ * component on another device has its row moved across through the host), then one evaluation launch; 5 npoints doubles and
+ * npoints ints come back.  No npoints x nt array exists anywhere.  Any npoints (blocks of 262144). */
+void emulate_points_multi_implausibility(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double *stat_out, int *worst_out);
+/* the same with the selection on the device: point q is kept iff chi2 <= cut_chi2 and the level-th largest implausibility
+ * (level 1, 2 or 3) <= cut_I; INFINITY disables a cut, a NaN is never kept.  idx_out (room for npoints) receives the kept
+ * indices in ascending order, stat_out (room for npoints x 5) their statistics, *nkeep their number: only these are downloaded. */
+void emulate_points_multi_nonimplausible(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double cut_chi2, int level,
+                                         double cut_I, int *idx_out, double *stat_out, int *nkeep);
+/* ... and the kept points' worst outputs (worst_out: room for npoints, may be NULL) */
+void emulate_points_multi_nonimplausible_worst(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double cut_chi2, int level,
+                                               double cut_I, int *idx_out, double *stat_out, int *worst_out, int *nkeep);
+/* (device_bridge.c: the observation set's device context and one block of points) */
+void gpemu_host_calib_setup(const void *key, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
+                            const double *sd, const double *rel);
+void gpemu_host_calib_block(const void *key, emulator_struct **es, int nr, int np, int d, const double *q, int select, double cut_chi2,
+                            int level, double cut_I, double *stat, int *worst, int *idx, int *nkeep);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);
@@ -566,6 +599,12 @@ typedef void (*gpemu_points_fn)(void *user, int npoints, const double *points, d
 struct gpemu_io_stats { long points, batches; int max_batch; double parse_seconds, compute_seconds, format_seconds, wall_seconds; };
 int gpemu_host_interactive_loop(int fd_in, int fd_out, int nparams, int nout, int nprint, int binary, gpemu_points_fn fn,
                                 void *user, struct gpemu_io_stats *stats);
+/* the same with nextra further values per point behind its nprint pairs ("%.17f\n" each, or raw doubles): fn_extra is called
+ * right after fn on the same batch and fills extra (npoints x nextra, row-major).  nextra = 0 with fn_extra = NULL is
+ * gpemu_host_interactive_loop, byte for byte.  -1 for nextra < 0 or a function without values / values without a function. */
+typedef void (*gpemu_points_extra_fn)(void *user, int npoints, const double *points, double *extra);
+int gpemu_host_interactive_loop_extra(int fd_in, int fd_out, int nparams, int nout, int nprint, int binary, gpemu_points_fn fn,
+                                      int nextra, gpemu_points_extra_fn fn_extra, void *user, struct gpemu_io_stats *stats);
 
 #ifdef __cplusplus
 }

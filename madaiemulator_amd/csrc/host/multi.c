@@ -614,6 +614,109 @@ void gpemu_host_project_observations(const multi_modelstruct *m, size_t np, cons
 		}
 }
 
+/* ---- implausibility and calibration likelihood against observations (libemu.h; gpemu_calib_* in gpemu.h) */
+struct gpemu_observations { int nt, nr; double c_perp, logdet_S, logdet_G; };
+
+gpemu_observations *alloc_observations(multi_modelstruct *m, const double *z, const double *sd, const double *cov, const double *rel)
+{
+	const size_t nt = (size_t)m->nt, nr = (size_t)m->nr;
+	if (!z || (sd == NULL) == (cov == NULL)) gpemu_host_fatal("alloc_observations: z and exactly one of sd and cov are needed\n");
+	if (m->nr > GPEMU_CALIB_MAX_R || m->nt > GPEMU_CALIB_MAX_NT)
+		gpemu_host_fatal("alloc_observations: nr = %d, nt = %d: more than %d components or %d outputs is not built\n", m->nr, m->nt,
+		                 GPEMU_CALIB_MAX_R, GPEMU_CALIB_MAX_NT);
+	double *A = doubles(nt * nr), *ybar = doubles(nt), mhat[GPEMU_CALIB_MAX_R], sigz[GPEMU_CALIB_MAX_R * GPEMU_CALIB_MAX_R], consts[3];
+	for (size_t t = 0; t < nt; t++) {
+		ybar[t] = gsl_vector_get(m->training_mean, t);
+		for (size_t c = 0; c < nr; c++) A[t * nr + c] = gsl_matrix_get(m->pca_evecs_r, t, c) * sqrt(gsl_vector_get(m->pca_evals_r, c));
+	}
+	int info = 0;
+	const int rc = gpemu_calib_project(m->nt, m->nr, ybar, A, z, cov, sd, mhat, sigz, consts, &info);
+	if (rc == GPEMU_ERR_NOT_PD)
+		gpemu_host_fatal("alloc_observations: the observation covariance, or A^T S^-1 A, is not positive definite (pivot %d)\n", info);
+	if (rc) gpemu_host_fatal("alloc_observations: non-finite input or a standard deviation <= 0\n");
+	for (size_t t = 0; rel && t < nt; t++)
+		if (!(rel[t] >= 0.0) || !isfinite(rel[t])) gpemu_host_fatal("alloc_observations: rel[%zu] must be finite and >= 0\n", t);
+	gpemu_observations *obs = (gpemu_observations *)malloc(sizeof *obs);
+	obs->nt = m->nt; obs->nr = m->nr;
+	obs->c_perp = consts[0]; obs->logdet_S = consts[1]; obs->logdet_G = consts[2];
+	gpemu_host_calib_setup(obs, m->nt, m->nr, ybar, A, z, cov, sd, rel);
+	free(A); free(ybar);
+	return obs;
+}
+
+void free_observations(gpemu_observations *obs)
+{
+	if (!obs) return;
+	gpemu_host_release(obs);
+	free(obs);
+}
+
+void gpemu_host_observations_misfit(const gpemu_observations *obs, double *c_perp, int *dof)
+{
+	if (c_perp) *c_perp = obs->c_perp;
+	if (dof) *dof = obs->nt - obs->nr;
+}
+
+/* x with erfc(x / sqrt 2) = sig, that is qnorm(1 - sig / 2): erfc is monotone, so bisection on [0, 40] to the last bit */
+double gpemu_host_confidence_to_rel(double sig)
+{
+	if (!(sig > 0.0 && sig < 1.0)) return NAN;
+	double lo = 0.0, hi = 40.0;
+	for (int it = 0; it < 200 && lo < hi; it++) {
+		const double mid = 0.5 * (lo + hi);
+		if (mid <= lo || mid >= hi) break;
+		if (erfc(mid * M_SQRT1_2) > sig) lo = mid; else hi = mid;
+	}
+	return sig / (0.5 * (lo + hi));
+}
+
+#define CALIB_HOST_BLOCK 262144
+static void calib_points(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, int select, double cut_chi2, int level,
+                         double cut_I, double *stat_out, int *worst_out, int *idx_out, int *nkeep, const char *who)
+{
+	if (!emu || !obs || !points || !stat_out) gpemu_host_fatal("%s: a NULL argument\n", who);
+	if (obs->nr != emu->nr || obs->nt != emu->nt) gpemu_host_fatal("%s: the observation set belongs to another model\n", who);
+	if (select && (!idx_out || !nkeep || level < 1 || level > 3 || cut_chi2 != cut_chi2 || cut_I != cut_I))
+		gpemu_host_fatal("%s: idx_out, nkeep, a level in 1 .. 3 and cuts that are not NaN are needed\n", who);
+	const size_t np = points->size1, d = points->size2;
+	size_t kept = 0;
+	double *q = doubles((np < CALIB_HOST_BLOCK ? np : CALIB_HOST_BLOCK) * d + 1);
+	for (size_t p0 = 0; p0 < np; p0 += CALIB_HOST_BLOCK) {
+		const size_t nb = np - p0 < CALIB_HOST_BLOCK ? np - p0 : CALIB_HOST_BLOCK;
+		for (size_t p = 0; p < nb; p++)
+			for (size_t j = 0; j < d; j++) q[p * d + j] = gsl_matrix_get(points, p0 + p, j);
+		if (!select) {
+			gpemu_host_calib_block(obs, emu->emu_struct_array, emu->nr, (int)nb, (int)d, q, 0, 0.0, 1, 0.0, stat_out + p0 * 5,
+			                       worst_out ? worst_out + p0 : NULL, NULL, NULL);
+			continue;
+		}
+		int k = 0;
+		gpemu_host_calib_block(obs, emu->emu_struct_array, emu->nr, (int)nb, (int)d, q, 1, cut_chi2, level, cut_I, stat_out + kept * 5,
+		                       worst_out ? worst_out + kept : NULL, idx_out + kept, &k);
+		for (int i = 0; i < k; i++) idx_out[kept + (size_t)i] += (int)p0;
+		kept += (size_t)k;
+	}
+	free(q);
+	if (nkeep) *nkeep = (int)kept;
+}
+
+void emulate_points_multi_implausibility(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double *stat_out, int *worst_out)
+{
+	calib_points(emu, obs, points, 0, 0.0, 1, 0.0, stat_out, worst_out, NULL, NULL, "emulate_points_multi_implausibility");
+}
+
+void emulate_points_multi_nonimplausible(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double cut_chi2, int level,
+                                         double cut_I, int *idx_out, double *stat_out, int *nkeep)
+{
+	calib_points(emu, obs, points, 1, cut_chi2, level, cut_I, stat_out, NULL, idx_out, nkeep, "emulate_points_multi_nonimplausible");
+}
+
+void emulate_points_multi_nonimplausible_worst(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double cut_chi2, int level,
+                                               double cut_I, int *idx_out, double *stat_out, int *worst_out, int *nkeep)
+{
+	calib_points(emu, obs, points, 1, cut_chi2, level, cut_I, stat_out, worst_out, idx_out, nkeep, "emulate_points_multi_nonimplausible");
+}
+
 void emulate_points_multi_holdout(multi_emulator *emu, gsl_matrix *points, const double *Y, const double *noise_pca, double *mean_out,
                                   double *var_out, double *werr_out, double *maha_out, double *logdet_out, double *logpdf_out,
                                   double *logpdf_sum)
