@@ -620,7 +620,28 @@ int gpemu_sens_get_measure(const gpemu_ctx *ctx, int *kind /* d */);
  * count < 0; count = 0 does nothing.
  * Two identical calls of any entry return the same bits; the host and _dev entries return the same bits.
  * Not built: nr > 16, nt > 1024; a mean-only pre-screen; the PCA truncation residual as an automatic addition to S (the caller
- * adds it to S); gradients of logpdf with respect to x. */
+ * adds it to S).
+ *
+ * Gradients with respect to the query's coordinates.  With u = T^-1 delta and tau_c = (T^-1)_cc, for
+ * coordinate j
+ *   d chi2 / dx_j   =   2 sum_c u_c dm_c/dx_j  -      sum_c u_c^2 dv_c/dx_j
+ *   d logpdf / dx_j =   - sum_c u_c dm_c/dx_j  +  1/2 sum_c (u_c^2 - tau_c) dv_c/dx_j
+ * (c_perp, log|S| and log|G| are constants; d log|T| / dx_j = sum_c tau_c dv_c/dx_j).
+ * gpemu_calib_grad: mean and var are exactly the inputs of gpemu_calib_eval; gmean and gvar hold component c's M x d row-major
+ * block at offset c * ldg, ldg >= M * d: what gpemu_predict_mean_grad_dev and gpemu_predict_var_grad_dev of component c write.
+ * gchi2 and glogpdf are M x d, point-major, g[q * d + j]; either may be NULL, not both.  A variance below 0 counts as 0 and
+ * its dv_c then has weight 0: the derivative of the function gpemu_calib_eval evaluates.  A NaN among a point's means or
+ * variances, or a pivot <= 0 in T, makes all 2 d values of that point NaN and no other point's; a non-finite gradient input
+ * reaches its own (q, j) only.  Components beyond nr of the padded instantiation are never read.  The sums over c run in index
+ * order from 0.0.  Two identical calls return the same bits, the host and the _dev form return the same bits, a point's bits
+ * depend neither on M nor on its position in the call nor on which outputs are asked for; gpemu_calib_eval and every other
+ * entry return the bits they returned before.  The _dev form only enqueues on the context's stream (one launch).
+ * GPEMU_ERR_STATE without a set-up; GPEMU_ERR_ARG for a NULL input, both outputs NULL, M < 1, d < 1, ld < M or ldg < M * d.
+ * How it runs: phase 1, one lane one query: the Cholesky of the evaluation in registers, u by the forward and the back solve,
+ * tau_c as the squared norm of column c of L^-1 formed one column at a time; the weights go to LDS.  Phase 2, the workgroup's
+ * lanes over the flat tile of its queries' outputs: every load of gmean, gvar and every store is unit-stride across the wave
+ * for any d.  No atomics; 16 nr d bytes are read per point.
+ * Not built: derivatives of the I_t (a max-type statistic); second derivatives; a sampler or optimiser on top. */
 #define GPEMU_CALIB_MAX_R  16
 #define GPEMU_CALIB_MAX_NT 1024
 int gpemu_calib_project(int nt, int nr, const double *ybar /* nt */, const double *A /* nt*nr */, const double *z /* nt */,
@@ -633,6 +654,11 @@ int gpemu_calib_eval(gpemu_ctx *ctx, int M, const double *mean /* nr rows of ld,
                      double *stat /* 5*M */, int *worst /* M */);
 int gpemu_calib_eval_dev(gpemu_ctx *ctx, int M, const double *mean_dev, const double *var_dev, int ld, double *stat_dev,
                          int *worst_dev);
+int gpemu_calib_grad(gpemu_ctx *ctx, int M, int d, const double *mean /* nr rows of ld, host */, const double *var, int ld,
+                     const double *gmean /* nr blocks of ldg, host */, const double *gvar, long ldg,
+                     double *gchi2 /* M*d, may be NULL */, double *glogpdf /* M*d, may be NULL */);
+int gpemu_calib_grad_dev(gpemu_ctx *ctx, int M, int d, const double *mean_dev, const double *var_dev, int ld,
+                         const double *gmean_dev, const double *gvar_dev, long ldg, double *gchi2_dev, double *glogpdf_dev);
 int gpemu_calib_select(gpemu_ctx *ctx, int M, const double *stat /* 5*M host */, double cut_chi2, int level, double cut_I,
                        int *idx /* M */, int *count);
 int gpemu_calib_select_dev(gpemu_ctx *ctx, int M, const double *stat_dev, double cut_chi2, int level, double cut_I, int *idx_dev,

@@ -169,6 +169,9 @@ SYMBOLS = {
     "gpemu_calib_release": (C.c_int, [C.c_void_p]),
     "gpemu_calib_eval": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip]),
     "gpemu_calib_eval_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gpemu_calib_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_long, _dp, _dp]),
+    "gpemu_calib_grad_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long,
+                                       C.c_void_p, C.c_void_p]),
     "gpemu_calib_select": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, C.c_double, _ip, _ip]),
     "gpemu_calib_select_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_void_p, _ip]),
     "gpemu_calib_gather_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -579,6 +582,24 @@ class Context:
 
     def calib_eval_dev(self, M, mean_dev, var_dev, ld, stat_dev, worst_dev):
         self._chk(self.L.gpemu_calib_eval_dev(self.h, M, mean_dev, var_dev, ld, stat_dev, worst_dev))
+
+    def calib_grad(self, mean, var, gmean, gvar, M=None, d=None, want=(True, True)):
+        """mean, var as calib_eval takes them; gmean, gvar: nr blocks (component-major) of ldg >= M * d values, component c's
+        M x d row-major gradients (or nr x M x d arrays) -> (gchi2[M, d], glogpdf[M, d]); want: which of the two are asked
+        for (the other is None)"""
+        mean, var = np.atleast_2d(_a(mean)), np.atleast_2d(_a(var))
+        gmean, gvar = _a(gmean), _a(gvar)
+        ld = mean.shape[1]
+        M = ld if M is None else M
+        d = gmean.shape[2] if d is None else d
+        gmean, gvar = gmean.reshape(mean.shape[0], -1), gvar.reshape(mean.shape[0], -1)
+        ldg = gmean.shape[1]
+        out = [np.full((max(M, 1), max(d, 1)), np.nan) if w else None for w in want]
+        self._chk(self.L.gpemu_calib_grad(self.h, M, d, _p(mean), _p(var), ld, _p(gmean), _p(gvar), ldg, _po(out[0]), _po(out[1])))
+        return out[0], out[1]
+
+    def calib_grad_dev(self, M, d, mean_dev, var_dev, ld, gmean_dev, gvar_dev, ldg, gchi2_dev, glogpdf_dev):
+        self._chk(self.L.gpemu_calib_grad_dev(self.h, M, d, mean_dev, var_dev, ld, gmean_dev, gvar_dev, ldg, gchi2_dev, glogpdf_dev))
 
     def calib_select(self, stat, cut_chi2=np.inf, level=1, cut_I=np.inf):
         """stat[5, M] as calib_eval returns it -> the kept point indices, ascending"""

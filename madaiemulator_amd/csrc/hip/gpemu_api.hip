@@ -2942,7 +2942,8 @@ extern "C" int gpemu_grad(gpemu_ctx *ctx, const double *thetas, int nthetas, dou
 
 // ---------------------------------------------------------------------------
 // implausibility and calibration likelihood against observations (gpemu.h).  The set-up is host arithmetic
-// (gpemu_calib_project, kernels_calib.hip) and one upload of the table; an evaluation is one launch, a selection three.
+// (gpemu_calib_project, kernels_calib.hip) and one upload of the table; an evaluation is one launch, a selection three, the
+// gradient of chi2 and logpdf one.
 // ---------------------------------------------------------------------------
 extern "C" int gpemu_calib_setup(gpemu_ctx *ctx, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
                                  const double *sd, const double *rel, int *info)
@@ -3016,6 +3017,49 @@ extern "C" int gpemu_calib_eval(gpemu_ctx *ctx, int M, const double *mean, const
 	if (rc) return rc;
 	HIPCHK(ctx, hipMemcpyAsync(stat, ds, 5 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(worst, ctx->dCalibIdx, m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// gradients of chi2 and logpdf with respect to the query coordinates: one launch
+extern "C" int gpemu_calib_grad_dev(gpemu_ctx *ctx, int M, int d, const double *mean_dev, const double *var_dev, int ld,
+                                    const double *gmean_dev, const double *gvar_dev, long ldg, double *gchi2_dev, double *glogpdf_dev)
+{
+	if (!ctx || !mean_dev || !var_dev || !gmean_dev || !gvar_dev || (!gchi2_dev && !glogpdf_dev) || M < 1 || d < 1 || ld < M ||
+	    ldg < (long)M * d)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_grad: bad argument");
+	if (!ctx->calib_nt) return fail(ctx, GPEMU_ERR_STATE, "gpemu_calib_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const double nr = ctx->calib_nr, R = calib_pad(ctx->calib_nr);
+	if (prof_on(ctx, GPEMU_PROF_CALIB)) ctx->prof.tag.push_back("calib_grad");
+	ProfScope ps(ctx, GPEMU_PROF_CALIB, (double)M * (R * R * R / 2.0 + 3.0 * R * R + 8.0 * nr * d),
+	             8.0 * M * (2.0 * nr + 2.0 * nr * d + (gchi2_dev ? d : 0) + (glogpdf_dev ? d : 0)));
+	HIPCHK(ctx, launch_calib_grad(ctx->stream, ctx->dCalibTab, ctx->calib_nr, M, d, mean_dev, var_dev, ld, gmean_dev, gvar_dev, ldg,
+	                              gchi2_dev, glogpdf_dev));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_calib_grad(gpemu_ctx *ctx, int M, int d, const double *mean, const double *var, int ld, const double *gmean,
+                                const double *gvar, long ldg, double *gchi2, double *glogpdf)
+{
+	if (!ctx || !mean || !var || !gmean || !gvar || (!gchi2 && !glogpdf) || M < 1 || d < 1 || ld < M || ldg < (long)M * d)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_calib_grad: bad argument");
+	if (!ctx->calib_nt) return fail(ctx, GPEMU_ERR_STATE, "gpemu_calib_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	// the device copies are packed: leading dimensions M and M * d
+	const size_t nr = (size_t)ctx->calib_nr, m = (size_t)M, in = nr * m, md = m * (size_t)d, gin = nr * md;
+	int rc = grow(ctx, ctx->dCalibIO, 2 * in + 2 * gin + 2 * md);
+	if (rc) return rc;
+	double *dm = ctx->dCalibIO, *dv = dm + in, *dgm = dv + in, *dgv = dgm + gin, *dc = dgv + gin, *dl = dc + md;
+	const size_t w = m * sizeof(double), wg = md * sizeof(double);
+	HIPCHK(ctx, hipMemcpy2DAsync(dm, w, mean, (size_t)ld * sizeof(double), w, nr, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(dv, w, var, (size_t)ld * sizeof(double), w, nr, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(dgm, wg, gmean, (size_t)ldg * sizeof(double), wg, nr, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(dgv, wg, gvar, (size_t)ldg * sizeof(double), wg, nr, hipMemcpyHostToDevice, ctx->stream));
+	rc = gpemu_calib_grad_dev(ctx, M, d, dm, dv, M, dgm, dgv, (long)md, gchi2 ? dc : nullptr, glogpdf ? dl : nullptr);
+	if (rc) return rc;
+	if (gchi2) HIPCHK(ctx, hipMemcpyAsync(gchi2, dc, wg, hipMemcpyDeviceToHost, ctx->stream));
+	if (glogpdf) HIPCHK(ctx, hipMemcpyAsync(glogpdf, dl, wg, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }

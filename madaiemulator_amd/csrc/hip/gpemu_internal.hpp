@@ -548,6 +548,10 @@ void calib_fill_table(int nt, int nr, const double *ybar, const double *A, const
                       const double *mhat, const double *sigz, const double *consts, double *tab);
 hipError_t launch_calib_eval(hipStream_t s, const double *tab, int nt, int nr, int M, const double *mean, const double *var, long ld,
                              double *stat, int *worst);
+// grad: gmean, gvar component-major blocks of M x d with leading dimension ldg; gchi2, glogpdf M x d,
+// point-major, either may be null
+hipError_t launch_calib_grad(hipStream_t s, const double *tab, int nr, int M, int d, const double *mean, const double *var, long ld,
+                             const double *gmean, const double *gvar, long ldg, double *gchi2, double *glogpdf);
 int calib_select_blocks(int M);
 hipError_t launch_calib_gather(hipStream_t s, const double *stat, const int *worst, int M, int count, const int *idx, double *out, int *wout);
 hipError_t launch_calib_select(hipStream_t s, const double *stat, int M, double cut_chi2, int level, double cut_I, int *counts, int *idx);

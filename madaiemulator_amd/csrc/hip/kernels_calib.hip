@@ -2,8 +2,10 @@
 //
 // Host part: gpemu_calib_project, the once-per-observation-set arithmetic in fp64 (no device), and the layout of the device
 // table it feeds.  Device part: the evaluation kernel (one lane owns one query: an r x r Cholesky in registers for the joint
-// statistics, the per-output implausibilities from table rows streamed through LDS) and the three launches of the selection
-// (per-workgroup counts, their scan, the ordered scatter: no atomics, a call repeated returns the same bits).
+// statistics, the per-output implausibilities from table rows streamed through LDS), the three launches of the selection
+// (per-workgroup counts, their scan, the ordered scatter: no atomics, a call repeated returns the same bits) and the gradient
+// of chi2 and logpdf with respect to the query's coordinates (the same Cholesky per lane, then the workgroup's
+// lanes over the flat tile of outputs).
 #include "gpemu_internal.hpp"
 
 #include <cmath>
@@ -302,6 +304,138 @@ hipError_t launch_calib_eval(hipStream_t s, const double *tab, int nt, int nr, i
 		hipLaunchKernelGGL((calib_eval_kernel<12, 64>), dim3((M + 63) / 64), dim3(64), 0, s, tab, nt, nr, M, mean, var, ld, stat, worst);
 	else if (R == 16)
 		hipLaunchKernelGGL((calib_eval_kernel<16, 64>), dim3((M + 63) / 64), dim3(64), 0, s, tab, nt, nr, M, mean, var, ld, stat, worst);
+	else
+		return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// gradient of chi2 and logpdf with respect to the query's coordinates.  With u = T^-1 delta and
+// tau_c = (T^-1)_cc:   d chi2 / dx_j = 2 sum_c u_c dm_c/dx_j - sum_c u_c^2 dv_c/dx_j,
+//                      d logpdf / dx_j = - sum_c u_c dm_c/dx_j + 1/2 sum_c (u_c^2 - tau_c) dv_c/dx_j.
+// Phase 1, one lane one query: the Cholesky of calib_eval_kernel with the inverse pivots kept on the diagonal, u by the
+// forward and the back solve, tau_c as the squared norm of column c of L^-1, one column at a time (R registers, never L^-1
+// whole).  Two weights per component go to LDS, [c][lane]: u_c and tau_c; tau_c = -1 (it is > 0 otherwise) marks a variance
+// below 0, whose dv_c has weight 0 in both sums; a NaN input or a pivot <= 0 makes all of the point's weights NaN.
+// Phase 2, the workgroup's lanes over the flat tile of its queries' nq * d outputs: element e is query e / d, coordinate e % d,
+// at offset q0 * d + e in every component's block and in both outputs: unit stride across the wave for any d.  The sums over
+// c run in index order from 0.0 and are the same instructions whichever outputs are asked for; components >= nr are not read.
+// ---------------------------------------------------------------------------
+template <int R, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void calib_grad_kernel(const double *__restrict__ tab, int nr, int M, int d,
+                                                           const double *__restrict__ mean, const double *__restrict__ var, long ld,
+                                                           const double *__restrict__ gmean, const double *__restrict__ gvar, long ldg,
+                                                           double *__restrict__ gchi2, double *__restrict__ glogpdf)
+{
+	__shared__ double wu[R * BLOCK], wt[R * BLOCK];
+	const long q0 = (long)blockIdx.x * BLOCK;
+	const long q = q0 + threadIdx.x;
+	const long qq = q < M ? q : (long)M - 1;     // a lane beyond M repeats the last query; nothing reads its weights
+	const double *mh = tab + 4, *sg = tab + 4 + R;
+	{
+		double T[R * (R + 1) / 2], y[R];
+		unsigned neg = 0;
+		bool bad = false;
+#pragma unroll
+		for (int i = 0, k = 0; i < R; i++) {
+			double m = 0.0, v = 0.0;
+			if (i < nr) {
+				m = mean[(long)i * ld + qq];
+				const double x = var[(long)i * ld + qq];
+				if (x < 0.0) neg |= 1u << i;
+				v = x < 0.0 ? 0.0 : x;            // (keeps a NaN)
+			}
+			bad = bad || (m != m) || (v != v);
+#pragma unroll
+			for (int j = 0; j <= i; j++, k++) T[k] = sg[k] + (i == j ? v : 0.0);
+			y[i] = m - mh[i];
+		}
+		// T = L L^T in place, 1 / L_jj on the diagonal; y = L^-1 delta
+#pragma unroll
+		for (int j = 0; j < R; j++) {
+			const int jj = j * (j + 1) / 2;
+			double p = T[jj + j], yj = y[j];
+#pragma unroll
+			for (int k = 0; k < j; k++) {
+				p -= T[jj + k] * T[jj + k];
+				yj -= T[jj + k] * y[k];
+			}
+			bad = bad || !(p > 0.0);
+			const double inv = 1.0 / sqrt(p);
+			T[jj + j] = inv;
+			y[j] = yj * inv;
+#pragma unroll
+			for (int i = j + 1; i < R; i++) {
+				const int ii = i * (i + 1) / 2;
+				double s = T[ii + j];
+#pragma unroll
+				for (int k = 0; k < j; k++) s -= T[ii + k] * T[jj + k];
+				T[ii + j] = s * inv;
+			}
+		}
+		// u = L^-T y, in place
+#pragma unroll
+		for (int i = R - 1; i >= 0; i--) {
+			double s = y[i];
+#pragma unroll
+			for (int k = i + 1; k < R; k++) s -= T[k * (k + 1) / 2 + i] * y[k];
+			y[i] = s * T[i * (i + 1) / 2 + i];
+		}
+		// tau_c = |column c of L^-1|^2: x_c = 1 / L_cc, x_i = -(sum_{c <= k < i} L_ik x_k) / L_ii
+#pragma unroll
+		for (int c = 0; c < R; c++) {
+			double x[R];
+			x[c] = T[c * (c + 1) / 2 + c];
+			double tau = x[c] * x[c];
+#pragma unroll
+			for (int i = c + 1; i < R; i++) {
+				const int ii = i * (i + 1) / 2;
+				double s = 0.0;
+#pragma unroll
+				for (int k = c; k < i; k++) s -= T[ii + k] * x[k];
+				x[i] = s * T[ii + i];
+				tau += x[i] * x[i];
+			}
+			if ((neg >> c) & 1u) tau = -1.0;
+			wu[c * BLOCK + threadIdx.x] = bad ? NAN : y[c];
+			wt[c * BLOCK + threadIdx.x] = bad ? NAN : tau;
+		}
+	}
+	__syncthreads();
+	const long rest = (long)M - q0;
+	const int nq = rest < BLOCK ? (int)rest : BLOCK;
+	const long base = q0 * d;
+	for (int e = threadIdx.x; e < nq * d; e += BLOCK) {        // nq * d <= 256 * d: inside an int for every d the library takes
+		const int ql = e / d;
+		double sm = 0.0, s2 = 0.0, sb = 0.0;
+#pragma unroll
+		for (int c = 0; c < R; c++)
+			if (c < nr) {
+				const double u = wu[c * BLOCK + ql], tau = wt[c * BLOCK + ql];
+				const double gm = gmean[(long)c * ldg + base + e], gv = gvar[(long)c * ldg + base + e];
+				const double u2 = u * u;
+				const bool off = tau < 0.0;
+				sm += u * gm;
+				s2 += (off ? 0.0 : u2) * gv;
+				sb += (off ? 0.0 : u2 - tau) * gv;
+			}
+		if (gchi2) gchi2[base + e] = 2.0 * sm - s2;
+		if (glogpdf) glogpdf[base + e] = 0.5 * sb - sm;
+	}
+}
+
+hipError_t launch_calib_grad(hipStream_t s, const double *tab, int nr, int M, int d, const double *mean, const double *var, long ld,
+                             const double *gmean, const double *gvar, long ldg, double *gchi2, double *glogpdf)
+{
+	const int R = calib_pad(nr);
+	if (R == 4)
+		hipLaunchKernelGGL((calib_grad_kernel<4, 256>), dim3((M + 255) / 256), dim3(256), 0, s, tab, nr, M, d, mean, var, ld, gmean, gvar, ldg, gchi2, glogpdf);
+	else if (R == 8)
+		hipLaunchKernelGGL((calib_grad_kernel<8, 256>), dim3((M + 255) / 256), dim3(256), 0, s, tab, nr, M, d, mean, var, ld, gmean, gvar, ldg, gchi2, glogpdf);
+	else if (R == 12)
+		hipLaunchKernelGGL((calib_grad_kernel<12, 64>), dim3((M + 63) / 64), dim3(64), 0, s, tab, nr, M, d, mean, var, ld, gmean, gvar, ldg, gchi2, glogpdf);
+	else if (R == 16)
+		hipLaunchKernelGGL((calib_grad_kernel<16, 64>), dim3((M + 63) / 64), dim3(64), 0, s, tab, nr, M, d, mean, var, ld, gmean, gvar, ldg, gchi2, glogpdf);
 	else
 		return hipErrorInvalidValue;
 	return hipGetLastError();

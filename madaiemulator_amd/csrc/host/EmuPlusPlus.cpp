@@ -184,6 +184,23 @@ void emulator::QueryEmulatorNonImplausible(const std::vector<std::vector<double>
 		for (int s = 0; s < 5; s++) Statistics[q][s] = st[(size_t)q * 5 + s];
 }
 
+void emulator::QueryEmulatorLogLikelihoodGradient(const std::vector<std::vector<double> > &xpoints, std::vector<double> &LogLikelihoods,
+                                                  std::vector<std::vector<double> > &Gradients)
+{
+	need_observations("QueryEmulatorLogLikelihoodGradient", the_observations);
+	const size_t np = xpoints.size(), d = (size_t)number_params;
+	std::vector<double> st(np * 5 + 1), g(np * d + 1);
+	std::vector<double> flat = flatten("QueryEmulatorLogLikelihoodGradient", xpoints, number_params);
+	gsl_matrix view = gpemu_matrix_view(flat.data(), np, number_params);
+	if (np) emulate_points_multi_logpdf_grad(the_emulator, the_observations, &view, st.data(), g.data(), NULL);
+	LogLikelihoods.assign(np, 0.0);
+	Gradients.assign(np, std::vector<double>(d));
+	for (size_t q = 0; q < np; q++) {
+		LogLikelihoods[q] = st[q * 5 + 1];
+		for (size_t j = 0; j < d; j++) Gradients[q][j] = g[q * d + j];
+	}
+}
+
 // the box of the two sensitivity methods, checked to have number_params entries on either side
 static void check_box(const char *method, const std::vector<double> &lo, const std::vector<double> &hi, int number_params)
 {

@@ -112,6 +112,11 @@ public:
 	                                 std::vector<int> &WorstOutput);
 	void QueryEmulatorNonImplausible(const std::vector<std::vector<double> > &xpoints, double CutChi2, int Level, double CutI,
 	                                 std::vector<int> &Kept, std::vector<std::vector<double> > &Statistics);
+	// the joint log density of the observations at every point and its gradient with respect to the point's parameters
+	// (libemu.h: emulate_points_multi_logpdf_grad): LogLikelihoods[q] is Statistics[q][1] of QueryEmulatorImplausibility bit
+	// for bit, Gradients[q][j] its derivative in the units of xpoints.  Requires SetObservations.
+	void QueryEmulatorLogLikelihoodGradient(const std::vector<std::vector<double> > &xpoints, std::vector<double> &LogLikelihoods,
+	                                        std::vector<std::vector<double> > &Gradients);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

@@ -1495,6 +1495,84 @@ void gpemu_host_calib_block(const void *key, emulator_struct **es, int nr, int n
 	free(xq); free(en);
 }
 
+/* One block of np points through every component's two gradient sweeps and the gradient launch (gpemu_calib_grad_dev, DESIGN.md
+ * 4.19), structured like gpemu_host_calib_block.  The points go up once per device; component c runs gpemu_predict_var_grad_dev
+ * (m_c, v_c, dv_c/dx) and gpemu_predict_mean_grad_dev (dm_c/dx) into its rows and blocks of component-major buffers on the
+ * observation set's device -- a component elsewhere writes behind its queries and its results cross through the host --; with
+ * stat it also runs gpemu_predict_batch_dev into rows of their own, so that the evaluation reads the bits
+ * gpemu_host_calib_block reads (the variance-gradient sweep's m and v agree with them to rounding only); all are started before
+ * the first is waited for.  Then gpemu_calib_eval_dev (with stat) and ONE gpemu_calib_grad_dev; np x d values per gradient
+ * array come back (and 5 np of stat).  Device memory on the observation set's device: (2 nr (d + 1 + [stat]) + 2 d + 6) np
+ * doubles: 152 MB at emulate_points_multi_logpdf_grad's block of 16384 points with nr = 16, d = 32 and stat. */
+void gpemu_host_calib_grad_block(const void *key, emulator_struct **es, int nr, int np, int d, const double *q, double *stat,
+                                 double *glogpdf, double *gchi2)
+{
+	static const char who[] = "emulate_points_multi_logpdf_grad";
+	struct entry *ob = lookup(key, 0);
+	if (!ob) gpemu_host_fatal("%s: the observation set was not made by alloc_observations\n", who);
+	const size_t n = (size_t)np, r = (size_t)nr, nd = n * (size_t)d, st = stat ? 1 : 0;
+	const size_t per = 2 * n + 2 * nd + 2 * n * st;            /* one component's results: m, v, dm, dv (, the evaluation's m, v) */
+	const int dev0 = gpemu_ctx_device(ob->ctx);
+	struct entry **en = (struct entry **)malloc(sizeof(struct entry *) * r);
+	void **xq = (void **)calloc(r, sizeof(void *));           /* xq[c] != NULL: component c owns the upload on its device */
+	void *blk = NULL;
+	int rc = gpemu_dev_alloc(ob->ctx, (r * per + 5 * n + 2 * nd) * sizeof(double) + n * sizeof(int), &blk);
+	if (rc) die(ob->ctx, rc, who);
+	double *dm = (double *)blk, *dv = dm + r * n, *dgm = dv + r * n, *dgv = dgm + r * nd, *dm2 = dgv + r * nd, *dv2 = dm2 + r * n * st;
+	double *ds = dv2 + r * n * st, *dgc = ds + 5 * n, *dgl = dgc + nd;
+	int *dw = (int *)(dgl + nd);
+	for (size_t c = 0; c < r; c++) {
+		en[c] = entry_of(es[c], who);
+		const int dev = gpemu_ctx_device(en[c]->ctx);
+		size_t o = 0;
+		while (o < c && gpemu_ctx_device(en[o]->ctx) != dev) o++;        /* the first component on this device holds its queries */
+		if (o == c) {
+			rc = gpemu_dev_alloc(en[c]->ctx, (nd + (dev == dev0 ? 0 : r * per)) * sizeof(double), &xq[c]);
+			if (!rc) rc = gpemu_dev_upload(en[c]->ctx, xq[c], q, nd * sizeof(double));
+			check(en[c], rc, who);
+		}
+		double *x = (double *)xq[o], *far = x + nd + c * per;
+		const int here = dev == dev0;
+		rc = gpemu_predict_var_grad_dev(en[c]->ctx, np, x, here ? dm + c * n : far, here ? dv + c * n : far + n, here ? dgv + c * nd : far + 2 * n + nd);
+		if (!rc) rc = gpemu_predict_mean_grad_dev(en[c]->ctx, np, x, NULL, here ? dgm + c * nd : far + 2 * n);
+		if (!rc && st) rc = gpemu_predict_batch_dev(en[c]->ctx, np, x, here ? dm2 + c * n : far + 2 * n + 2 * nd, here ? dv2 + c * n : far + 3 * n + 2 * nd);
+		check(en[c], rc, who);
+	}
+	double *hop = NULL;
+	for (size_t c = 0; c < r; c++) {
+		const int dev = gpemu_ctx_device(en[c]->ctx);
+		if (dev == dev0) { check(en[c], gpemu_sync(en[c]->ctx), who); continue; }
+		size_t o = 0;
+		while (gpemu_ctx_device(en[o]->ctx) != dev) o++;
+		if (!hop) hop = (double *)malloc(sizeof(double) * per);
+		check(en[c], gpemu_dev_download(en[c]->ctx, hop, (double *)xq[o] + nd + c * per, per * sizeof(double)), who);
+		rc = gpemu_dev_upload(ob->ctx, dm + c * n, hop, n * sizeof(double));
+		if (!rc) rc = gpemu_dev_upload(ob->ctx, dv + c * n, hop + n, n * sizeof(double));
+		if (!rc) rc = gpemu_dev_upload(ob->ctx, dgm + c * nd, hop + 2 * n, nd * sizeof(double));
+		if (!rc) rc = gpemu_dev_upload(ob->ctx, dgv + c * nd, hop + 2 * n + nd, nd * sizeof(double));
+		if (!rc && st) rc = gpemu_dev_upload(ob->ctx, dm2 + c * n, hop + 2 * n + 2 * nd, n * sizeof(double));
+		if (!rc && st) rc = gpemu_dev_upload(ob->ctx, dv2 + c * n, hop + 3 * n + 2 * nd, n * sizeof(double));
+		if (rc) die(ob->ctx, rc, who);
+	}
+	free(hop);
+	rc = st ? gpemu_calib_eval_dev(ob->ctx, np, dm2, dv2, np, ds, dw) : 0;
+	if (!rc) rc = gpemu_calib_grad_dev(ob->ctx, np, d, dm, dv, np, dgm, dgv, (long)nd, gchi2 ? dgc : NULL, dgl);
+	if (!rc && st) {
+		double *h = (double *)malloc(sizeof(double) * 5 * n);
+		rc = gpemu_dev_download(ob->ctx, h, ds, 5 * n * sizeof(double));
+		for (size_t p = 0; !rc && p < n; p++)
+			for (int s = 0; s < 5; s++) stat[p * 5 + s] = h[(size_t)s * n + p];
+		free(h);
+	}
+	if (!rc) rc = gpemu_dev_download(ob->ctx, glogpdf, dgl, nd * sizeof(double));
+	if (!rc && gchi2) rc = gpemu_dev_download(ob->ctx, gchi2, dgc, nd * sizeof(double));
+	if (rc) die(ob->ctx, rc, who);
+	for (size_t c = 0; c < r; c++)
+		if (xq[c]) check(en[c], gpemu_dev_free(en[c]->ctx, xq[c]), who);
+	if ((rc = gpemu_dev_free(ob->ctx, blk))) die(ob->ctx, rc, who);
+	free(xq); free(en);
+}
+
 /* emulator_struct.c:124-143 */
 void emulate_point(emulator_struct *e, gsl_vector *point, double *mean, double *variance)
 {

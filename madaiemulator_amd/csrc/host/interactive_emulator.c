@@ -34,7 +34,7 @@ struct cmdLineOpts {
 	double pca_variance;
 	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile, *priorfile, *obsfile;
 	double cutI, cutChi2;
-	int level;
+	int level, gradientFlag;
 	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
@@ -75,10 +75,11 @@ static const char useage[] =
 	"      of each parameter, independent of the others; the curve and the surface of a Gaussian parameter run over MEAN -+ 2 SD.\n"
 	"      Power-exponential covariance only)\n"
 	"or\n"
-	"  interactive_emulator implausibility MODEL_SNAPSHOT_FILE --observations=FILE [--cut=C] [--level=k] [--chi2=C2] [--quiet]  (points from\n"
+	"  interactive_emulator implausibility MODEL_SNAPSHOT_FILE --observations=FILE [--cut=C] [--level=k] [--chi2=C2] [--gradient] [--quiet]  (points from\n"
 	"      stdin to the end of input; one line per point whose k-th largest implausibility is <= C (default 3, k = 1) and whose joint\n"
 	"      chi^2 is <= C2 (default: no cut): index, parameters, chi^2, log likelihood, the three largest implausibilities, the worst\n"
-	"      output.  FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
+	"      output; with --gradient, behind them the d components of the log likelihood's gradient with respect to the parameters.\n"
+	"      FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -709,7 +710,9 @@ static int implausibility(struct cmdLineOpts *o)
 	if (!o->quietFlag) {
 		fprintf(out, "# index");
 		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
-		fprintf(out, " joint_implausibility log_likelihood max_implausibility second_implausibility third_implausibility worst_output\n");
+		fprintf(out, " joint_implausibility log_likelihood max_implausibility second_implausibility third_implausibility worst_output");
+		for (int j = 0; o->gradientFlag && j < d; j++) fprintf(out, " dlog_likelihood_dparam_%d", j);
+		fprintf(out, "\n");
 	}
 	int nkeep = 0;
 	if (np) {
@@ -717,12 +720,24 @@ static int implausibility(struct cmdLineOpts *o)
 		int *idx = (int *)malloc(sizeof(int) * np), *worst = (int *)malloc(sizeof(int) * np);
 		double *st = (double *)malloc(sizeof(double) * 5 * np);
 		emulate_points_multi_nonimplausible_worst(emu, obs, &pts, o->cutChi2, o->level, o->cutI, idx, st, worst, &nkeep);
+		double *g = NULL;
+		if (o->gradientFlag && nkeep) {
+			/* --gradient: the survivors alone go through the two gradient sweeps */
+			double *kv = (double *)malloc(sizeof(double) * (size_t)nkeep * d);
+			for (int k = 0; k < nkeep; k++) memcpy(kv + (size_t)k * d, v + (size_t)idx[k] * d, sizeof(double) * d);
+			gsl_matrix kept = gpemu_matrix_view(kv, (size_t)nkeep, (size_t)d);
+			g = (double *)malloc(sizeof(double) * (size_t)nkeep * d);
+			emulate_points_multi_logpdf_grad(emu, obs, &kept, NULL, g, NULL);
+			free(kv);
+		}
 		for (int k = 0; k < nkeep; k++) {
 			fprintf(out, "%d", idx[k]);
 			for (int j = 0; j < d; j++) fprintf(out, " %.17g", v[(size_t)idx[k] * d + j]);
-			fprintf(out, " %.17g %.17g %.17g %.17g %.17g %d\n", st[k * 5], st[k * 5 + 1], st[k * 5 + 2], st[k * 5 + 3], st[k * 5 + 4], worst[k]);
+			fprintf(out, " %.17g %.17g %.17g %.17g %.17g %d", st[k * 5], st[k * 5 + 1], st[k * 5 + 2], st[k * 5 + 3], st[k * 5 + 4], worst[k]);
+			for (int j = 0; g && j < d; j++) fprintf(out, " %.17g", g[(size_t)k * d + j]);
+			fprintf(out, "\n");
 		}
-		free(idx); free(worst); free(st);
+		free(idx); free(worst); free(st); free(g);
 	}
 	fflush(out);
 	double c_perp; int dof;
@@ -795,6 +810,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		/* implausibility: the observation file, the cut on the level-th largest implausibility, the cut on the joint chi^2 */
 		{"observations", required_argument, NULL, 1013},      {"cut", required_argument, NULL, 1014},
 		{"level", required_argument, NULL, 1015},             {"chi2", required_argument, NULL, 1016},
+		/* ... and the gradient of the log likelihood behind every printed line */
+		{"gradient", no_argument, NULL, 1017},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -834,6 +851,7 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1014: o->cutI = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
 		case 1015: o->level = atoi(optarg); break;
 		case 1016: o->cutChi2 = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
+		case 1017: o->gradientFlag = 1; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
@@ -842,6 +860,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 	if (optind >= argc) exit(perr(useage));
 	if ((o->holdoutfile != NULL) + o->foldsGiven + (o->groupsfile != NULL) > 1) exit(perr(useage));
 	o->run_mode = argv[optind];
+	if (o->gradientFlag && (strcmp(o->run_mode, "implausibility") || o->binaryFlag))
+		exit(perr("--gradient belongs to `implausibility` and prints text: not with another mode, not with --binary"));
 	if (!strcmp(o->run_mode, "estimate_thetas")) {
 		if (optind + 2 >= argc) exit(perr(useage));
 		o->inputfile = argv[optind + 1];

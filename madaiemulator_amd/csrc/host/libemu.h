@@ -440,6 +440,20 @@ void emulate_points_multi_nonimplausible(multi_emulator *emu, gpemu_observations
 /* ... and the kept points' worst outputs (worst_out: room for npoints, may be NULL) */
 void emulate_points_multi_nonimplausible_worst(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double cut_chi2, int level,
                                                double cut_I, int *idx_out, double *stat_out, int *worst_out, int *nkeep);
+/* the gradient of the joint log density with respect to the points' coordinates (gpemu_calib_grad in gpemu.h):
+ * grad_logpdf_out[p * nparams + j] = d logpdf(x_p) / d x_j, grad_chi2_out (may be NULL) likewise for chi2, in the units of
+ * `points` -- the units emulate_points_multi_grad returns --; stat_out (npoints x 5, may be NULL) as
+ * emulate_points_multi_implausibility returns it, bit for bit (its sweep then runs as well).  The points go up once per
+ * device; every component's mean-gradient and variance-gradient sweeps write component-major device buffers on the observation
+ * set's device (all started before the first is waited for; a component on another device crosses through the host); then one
+ * gradient launch; npoints x nparams doubles per array come back.  Any npoints, in blocks of 16384: the gradient buffers,
+ * 2 nr npoints nparams doubles, bound the block -- 152 MB on the observation set's device at nr = 16, nparams = 32.  The
+ * per-output implausibilities are not differentiated (a max-type statistic).  A NULL argument or an observation set of another
+ * model: a message with this entry's name and the layer's exit. */
+void emulate_points_multi_logpdf_grad(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double *stat_out,
+                                      double *grad_logpdf_out, double *grad_chi2_out);
+void gpemu_host_calib_grad_block(const void *key, emulator_struct **es, int nr, int np, int d, const double *q, double *stat,
+                                 double *glogpdf, double *gchi2);
 /* (device_bridge.c: the observation set's device context and one block of points) */
 void gpemu_host_calib_setup(const void *key, int nt, int nr, const double *ybar, const double *A, const double *z, const double *S,
                             const double *sd, const double *rel);

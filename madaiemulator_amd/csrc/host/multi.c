@@ -717,6 +717,27 @@ void emulate_points_multi_nonimplausible_worst(multi_emulator *emu, gpemu_observ
 	calib_points(emu, obs, points, 1, cut_chi2, level, cut_I, stat_out, worst_out, idx_out, nkeep, "emulate_points_multi_nonimplausible");
 }
 
+/* the gradient of the joint log density (and of chi2) with respect to the points' coordinates (libemu.h): blocks of
+ * CALIB_GRAD_HOST_BLOCK points through gpemu_host_calib_grad_block */
+#define CALIB_GRAD_HOST_BLOCK 16384
+void emulate_points_multi_logpdf_grad(multi_emulator *emu, gpemu_observations *obs, gsl_matrix *points, double *stat_out,
+                                      double *grad_logpdf_out, double *grad_chi2_out)
+{
+	static const char who[] = "emulate_points_multi_logpdf_grad";
+	if (!emu || !obs || !points || !grad_logpdf_out) gpemu_host_fatal("%s: a NULL argument\n", who);
+	if (obs->nr != emu->nr || obs->nt != emu->nt) gpemu_host_fatal("%s: the observation set belongs to another model\n", who);
+	const size_t np = points->size1, d = points->size2;
+	double *q = doubles((np < CALIB_GRAD_HOST_BLOCK ? np : CALIB_GRAD_HOST_BLOCK) * d + 1);
+	for (size_t p0 = 0; p0 < np; p0 += CALIB_GRAD_HOST_BLOCK) {
+		const size_t nb = np - p0 < CALIB_GRAD_HOST_BLOCK ? np - p0 : CALIB_GRAD_HOST_BLOCK;
+		for (size_t p = 0; p < nb; p++)
+			for (size_t j = 0; j < d; j++) q[p * d + j] = gsl_matrix_get(points, p0 + p, j);
+		gpemu_host_calib_grad_block(obs, emu->emu_struct_array, emu->nr, (int)nb, (int)d, q, stat_out ? stat_out + p0 * 5 : NULL,
+		                            grad_logpdf_out + p0 * d, grad_chi2_out ? grad_chi2_out + p0 * d : NULL);
+	}
+	free(q);
+}
+
 void emulate_points_multi_holdout(multi_emulator *emu, gsl_matrix *points, const double *Y, const double *noise_pca, double *mean_out,
                                   double *var_out, double *werr_out, double *maha_out, double *logdet_out, double *logpdf_out,
                                   double *logpdf_sum)
