@@ -497,6 +497,40 @@ int gpemu_sens_post_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HO
 int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int ngrid, const double *grid /* d*ngrid host */,
                         double *main /* d*ngrid, may be NULL */, double *var /* d*ngrid */, double *var_e0 /* may be NULL */);
 
+/* ---- expected reduction of the IMSE by one more run, in closed form -----------------
+ * s_all of gpemu_sens_post says whether more model runs are needed; these entries say where to put one.  Conditioning the
+ * posterior process on a run at x* is a rank-one update of its covariance, so for each of npoints candidates
+ *   gain(x*) = E_x[c*(x, x*)^2] / v(x*) = s_all(design) - s_all(design + {x*}),     hyper-parameters as they are,
+ * with the conventions of the entries above (no k-vector clamp, no nugget rule inside c), the measure of the context
+ * (gpemu_sens_set_measure; lo / hi as in the gpemu_sens_* family), and for k* = k(x*), h* = h(x*)
+ *   u = L^-1 k*,  r = h* - W^T k*,  b = Q r,  a = L^-T u + W b,   c*(x, x*) = c(x, x*) - k(x)^T a + h(x)^T b,
+ *   var = v(x*) = A - |u|^2 + r^T Q r + nugget      (the variance a new run at x* is observed with),
+ *   num = A^2 prod_l II_l(x*, x*) - 2 A^2 sum_i a_i w_i + 2 A sum_al b_al HK*_al + A^2 a^T K a - 2 A sum_al b_al (a^T HK_al) + b^T Hm b,
+ * K_ii' = prod_l II_l(x_i, x_i'), w_i = prod_l II_l(x_i, x*), HK_al,i = E[h_al(x) prod_l k_l(x_il, x_l)] (HK* the same at x*),
+ * Hm = E[h h^T].  gain = num / var; where var rounds to <= 0 (nugget 0 on a design point) gain is 0; num and var (either may
+ * be NULL) are returned as computed.  var is gpemu_predict_batch's variance up to the clamp.
+ * How it runs, on the context's stream: the per-point tables of gpemu_sens_cov for the design; [K ; HK] over 64 x 64 tiles
+ * and Hm, kept on the context (8 Np (Np + 64) bytes) and rebuilt when the set-up, the box or the kinds differ from the last
+ * call's; then per block of up to 16 384 candidates the same tables for the candidates, the unclamped k rows, the prediction's
+ * product with [L^-1; gamma; W^T] and the second triangular product of gpemu_predict_var_grad (its transposed copy of L^-1,
+ * made on first use) for a, T = a [K | HK] (the third M N^2 product), a sweep over 64 candidates x 64 design points per
+ * workgroup for sum_i a_i (T_i - 2 w_i) and a finish of one wave per candidate.  d <= 16 keeps the candidate's coordinates in
+ * registers; a larger d takes the rolled form.  It uses the prediction batch buffers in stream order, as gpemu_predict_cov_dev
+ * does; a pending prediction batch stays collectable.  Memory per block of mb candidates: 8 mb (2 Np + 10 d + 192 + ceil(N/64))
+ * bytes of its own.  No atomics, no workgroup waits for another; two calls return the same bits, so do the host and _dev entries,
+ * a candidate alone and in a batch, and a context set up by gpemu_predict_setup_batch.  gpemu_sens_release frees its buffers.
+ * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL ctx, lo, hi, xq or gain and npoints < 1, whatever
+ * the state; GPEMU_ERR_STATE without a prediction set-up; then GPEMU_ERR_ARG for a Matern model, a non-finite bound, hi_l <= lo_l
+ * or a Gaussian coordinate with sd <= 0.
+ * Not built: greedy batches of K runs with the covariance downdated between picks; the gradient of gain with respect to x* and
+ * any optimiser over it; Matern kernels; gain for a target other than the IMSE (Sobol-index uncertainty, a calibration region);
+ * correlated Gaussian measures. */
+int gpemu_design_gain(gpemu_ctx *ctx, const double *lo, const double *hi /* d each, host */, int npoints,
+                      const double *xq /* npoints*d host */, double *gain /* npoints */, double *num /* npoints or NULL */,
+                      double *var /* npoints or NULL */);
+int gpemu_design_gain_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HOST */, int npoints, const double *xq_dev,
+                          double *gain_dev, double *num_dev /* or NULL */, double *var_dev /* or NULL */);
+
 /* ---- second-order Sobol indices and interaction surfaces, in closed form -----------------
  * VT_j - V_j > 0 says that parameter j interacts with something; these entries say with which parameter, and what the
  * interaction looks like.  For u = {j, k} every conditional expectation still factorises into the one-dimensional integrals
@@ -717,6 +751,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_SENS    14  /* the three launches of gpemu_sens_cov[_dev] -- prep (flops = 88 N d: both contexts, two erf and two exp per point and coordinate counted as one flop each; bytes = 8 (10 N d + N d): the tables written, the design read), sweep (flops = N^2 (19 d + 2): per pair and coordinate one exp and two erf or erfc counted as one flop each among 16 others, then the 2 d + 1 sums; bytes = 8 T: the T = ceil(N / 64)^2 (2 d + 1) partial sums written), finish (flops = T, bytes = 8 T) -- and the two of gpemu_sens_main: prep, curves (flops = 6 N d ngrid, bytes = 16 d ngrid) */
 #define GPEMU_PROF_SENS_POST 15 /* the four launches of gpemu_sens_post[_dev], L = n (n + 1) / 2 lower tiles with n = ceil(N / 64) -- prep (as GPEMU_PROF_SENS), pmat (flops = L (128 nreg^2 + 4096 (2 nreg + 1)): G for the tile's 64 rows, then a product of length nreg per pair; bytes = 8 * 8192 L: the corner's tile read, P's written), weighted sweep (flops = 4096 L (20 d + 3): the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; bytes = 8 (4096 L + T'), T' = L (2 d + 2): P read, the partial sums written), finish (flops = T' + (2 d + 2) nreg (2 nreg + 4 N), bytes = 8 (T' + (2 d + 2) 3 N nreg)) -- and of gpemu_sens_main_var: prep, then per block of mb rows tvec (flops = 6 mb N, bytes = 8 mb' Np, mb' = mb rounded up to 64) and band finish (flops = mb (2 Np + 2 nreg^2), bytes = 8 mb (Np + 64)); the corner and the band's product report under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_CALIB   16  /* the launch of gpemu_calib_eval[_dev] (flops = M (4 nt R + 8 nt + R^3 / 3 + 2 R^2), R = nr rounded up to 4: two multiply-adds per output and component, the finish of an output, the Cholesky and the solve in T; bytes = 8 M (2 nr + 5) + 4 M: mean and var read, stat and worst written) and the three of gpemu_calib_select[_dev], bracketed as ONE entry: count (16 M bytes: two rows of stat read), scan (8 ceil(M / 1024)), scatter (16 M + 4 kept, counted with kept = M), bytes = 36 M + 8 ceil(M / 1024), no flops */
+#define GPEMU_PROF_DESIGN  17  /* the launches of gpemu_design_gain[_dev] that are its own: prep (as GPEMU_PROF_SENS), kmat when [K ; HK] is rebuilt (flops = 19 d N^2 / 2, bytes = 8 Np (Np + 64)), then per block of mb candidates their prep, kvec (flops = mb N (3 d + 2), bytes = 8 mb' Np), the transpose of a (bytes = 16 mb' Np), the cross sweep (flops = mb N (19 d + 4), bytes = 8 mb (2 N + ceil(N / 64))) and the finish (flops = mb (2 Np + 2 nreg^2 + 19 d), bytes = 8 mb (Np + 64)); the three products report under GPEMU_PROF_GEMM */
 /* GPEMU_PROF_SENS*, under a measure (gpemu_sens_set_measure): in every sweep a GAUSSIAN coordinate's pair factor counts 12
  * flops (one exp among 11 others) where a uniform one counts 19 (one exp and two erf or erfc among 16): 19 d above becomes
  * 19 d_u + 12 d_g, and in the pair sweeps the 8 / 16 factors of a block are taken in the proportion d_u : d_g.  The prep and
@@ -975,6 +1010,10 @@ int gpemu_test_pred_state(gpemu_ctx *ctx, double *beta, double *gamma);
 /* the same for gpemu_sens_post: P = C^-1 - W Q W^T (N*N, both triangles), G = W Q (N*nreg) and Q (nreg*nreg), bit for bit what
  * the last call's weighted sweep and finish multiplied by.  GPEMU_ERR_STATE before the first gpemu_sens_post of a model. */
 int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P /* N*N, both triangles */, double *G /* N*nreg */, double *Q /* nreg*nreg */);
+/* the same for gpemu_design_gain: the rows of a = L^-T u + W Q r and of b = Q r of the last block of the last call, bit for bit
+ * what its third product, sweep and finish multiplied by; npoints: that block's candidates (a call of up to 16 384 has one
+ * block).  GPEMU_ERR_STATE when no block of this size was the last. */
+int gpemu_test_design_state(gpemu_ctx *ctx, int npoints, double *a_out /* npoints*N */, double *b_out /* npoints*nreg */);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

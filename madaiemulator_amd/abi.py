@@ -25,6 +25,7 @@ PROF_LGO = 13
 PROF_SENS = 14
 PROF_SENS_POST = 15
 PROF_CALIB = 16
+PROF_DESIGN = 17
 CALIB_MAX_R, CALIB_MAX_NT = 16, 1024
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 MEASURE_UNIFORM, MEASURE_GAUSS = 0, 1
@@ -157,6 +158,9 @@ SYMBOLS = {
     "gpemu_sens_post_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_main_var": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpemu_test_sens_post_state": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "gpemu_design_gain": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpemu_design_gain_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_test_design_state": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "gpemu_sens_pairs": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp]),
     "gpemu_sens_pairs_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_pairs_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -672,6 +676,27 @@ class Context:
         if lo.size != self.d or hi.size != self.d:
             raise GpemuError(ERR_ARG, f"{what}: one bound pair per coordinate")
         return lo, hi
+
+    # expected reduction of the IMSE (s_all of sens_post) by one more run at each candidate
+    def design_gain(self, lo, hi, Xq):
+        """Xq[M, d] -> dict(gain[M], num[M], var[M]): gain = num / var = s_all(design) - s_all(design + {x*})"""
+        lo, hi = self._box("design_gain", lo, hi)
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        gain, num, var = np.empty(M), np.empty(M), np.empty(M)
+        self._chk(self.L.gpemu_design_gain(self.h, _p(lo), _p(hi), M, _p(Xq), _p(gain), _p(num), _p(var)))
+        return dict(gain=gain, num=num, var=var)
+
+    def design_gain_dev(self, lo, hi, M, xq_dev, gain_dev, num_dev=None, var_dev=None):
+        """lo, hi: HOST bounds; xq_dev (M x d), gain_dev, num_dev, var_dev (M each; the last two may be None): device memory"""
+        lo, hi = self._box("design_gain_dev", lo, hi)
+        self._chk(self.L.gpemu_design_gain_dev(self.h, _p(lo), _p(hi), M, xq_dev, gain_dev, num_dev, var_dev))
+
+    def design_state(self, M):
+        """-> (a[M, N], b[M, nreg]) bit for bit as the last block of the last design_gain read them (parity tests)"""
+        a, b = np.empty((M, self.N)), np.empty((M, self.nreg))
+        self._chk(self.L.gpemu_test_design_state(self.h, M, _p(a), _p(b)))
+        return a, b
 
     def sens_pairs(self, lo, hi, other=None):
         """-> cov_pair[d (d - 1) / 2] of this context and `other` (default: itself) on one design"""

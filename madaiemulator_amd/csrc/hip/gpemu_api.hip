@@ -276,6 +276,11 @@ static void free_model(gpemu_ctx *ctx)
 	                &ctx->dSensPostPart, &ctx->dSensPex2, &ctx->dSensPairPart, &ctx->dSensPairOut})
 		b->reset();
 	ctx->sens_post_N = 0;
+	for (auto *b : {&ctx->dDesignKH, &ctx->dDesignHm, &ctx->dDesignPrepQ, &ctx->dDesignA, &ctx->dDesignT, &ctx->dDesignR, &ctx->dDesignB,
+	                &ctx->dDesignPart, &ctx->dDesignOut})
+		b->reset();
+	ctx->design_serial = 0;
+	ctx->design_mb = 0;
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -1116,6 +1121,7 @@ static int build_prediction_state(gpemu_ctx *src, int b, gpemu_ctx *dst, const C
 	dst->pred_ready = true;
 	dst->cinv_ready = false;
 	dst->linvT_ready = false;
+	dst->pred_serial++;                               // (gpemu_design_gain: what it keeps belongs to one set-up)
 	dst->last_thetas.assign(thetas, thetas + nthetas);
 	return GPEMU_OK;
 }
@@ -2332,6 +2338,11 @@ extern "C" int gpemu_sens_release(gpemu_ctx *ctx)
 	                &ctx->dSensPostPart, &ctx->dSensPex2, &ctx->dSensPairPart, &ctx->dSensPairOut})
 		b->reset();
 	ctx->sens_post_N = 0;
+	for (auto *b : {&ctx->dDesignKH, &ctx->dDesignHm, &ctx->dDesignPrepQ, &ctx->dDesignA, &ctx->dDesignT, &ctx->dDesignR, &ctx->dDesignB,
+	                &ctx->dDesignPart, &ctx->dDesignOut})
+		b->reset();
+	ctx->design_serial = 0;
+	ctx->design_mb = 0;
 	return GPEMU_OK;
 }
 
@@ -2536,6 +2547,143 @@ extern "C" int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P, double *G, 
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	for (size_t i = 0; i < N; i++)
 		for (size_t j = i + 1; j < N; j++) P[j * N + i] = P[i * N + j];
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// expected reduction of the IMSE by one more run at each of M candidates (gpemu.h).  The tables of the design
+// and [K ; HK], Hm (kept while the set-up, the box and the kinds stay); then per block of up to PRED_BATCH_MAX candidates, through
+// dKq and dV in stream order as gpemu_predict_cov_dev uses them: the candidates' own tables, the unclamped k rows, V = Kq LinvAug^T
+// and Q r as in gpemu_predict_var_grad_dev (K never split), that entry's second product for a^T, its transpose, T = a [K | HK],
+// the cross sweep and the finish.  Everything else it writes is its own (dDesign*) or the sensitivity entries' tables.
+// ---------------------------------------------------------------------------
+static int design_check(gpemu_ctx *ctx, const double *lo, const double *hi, int npoints, const void *xq, const void *gain, SensBox *bx)
+{
+	if (!ctx || !lo || !hi || !xq || !gain || npoints < 1) return GPEMU_ERR_ARG;
+	return sens_check(ctx, ctx, lo, hi, bx);
+}
+
+extern "C" int gpemu_design_gain_dev(gpemu_ctx *ctx, const double *lo, const double *hi, int npoints, const double *xq_dev, double *gain_dev,
+                                     double *num_dev, double *var_dev)
+{
+	SensBox bx;
+	if (const int rc = design_check(ctx, lo, hi, npoints, xq_dev, gain_dev, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np, Rp = ctx->Rp, nreg = ctx->nreg, M = npoints;
+	const int cap = std::min(PRED_BATCH_MAX, round_up(M, 64)), ntc = (N + 63) / 64;
+	const long ldv = (long)Np + Rp, ldt = (long)Np + 64;
+	if (ctx->dDesignKH.size() < design_kh_elems(Np) || ctx->dDesignHm.size() < 64 * 64) ctx->design_serial = 0;
+	int rc = ensure_pred_batch(ctx, cap);
+	if (!rc) rc = grow(ctx, ctx->dDesignKH, design_kh_elems(Np), false, "out of device memory for the design's pair integrals (8 Np (Np + 64) bytes)");
+	if (!rc) rc = grow(ctx, ctx->dDesignHm, 64 * 64);
+	if (!rc) rc = grow(ctx, ctx->dDesignPrepQ, sens_prep_elems(cap, d));
+	if (!rc) rc = grow(ctx, ctx->dDesignA, (size_t)cap * Np);
+	if (!rc) rc = grow(ctx, ctx->dDesignT, (size_t)cap * ldt);
+	if (!rc) rc = grow(ctx, ctx->dDesignR, (size_t)cap * Rp);
+	if (!rc) rc = grow(ctx, ctx->dDesignB, (size_t)cap * 64);
+	if (!rc) rc = grow(ctx, ctx->dDesignPart, (size_t)ntc * cap);
+	if (!rc) rc = ensure_linv_transposed(ctx);
+	if (rc) return rc;
+	const bool prof = prof_on(ctx, GPEMU_PROF_DESIGN);
+	if (prof) ctx->prof.tag.push_back("sens_prep");
+	if ((rc = sens_prep(ctx, bx, GPEMU_PROF_DESIGN))) return rc;
+	if (ctx->design_serial != ctx->pred_serial || memcmp(&ctx->design_box, &bx, sizeof bx) != 0) {
+		ctx->design_serial = 0;
+		if (prof) ctx->prof.tag.push_back("design_kmat");
+		// per pair of the lower tiles d pair factors; K, its mirror image and the HK rows written
+		ProfScope ps(ctx, GPEMU_PROF_DESIGN, 0.5 * N * (double)N * sens_pair_flops(bx, d), 8.0 * (double)design_kh_elems(Np));
+		HIPCHK(ctx, launch_design_kmat(ctx->stream, ctx->dX, N, Np, d, nreg, ctx->dSensPrep, ctx->dSensCst, bx.meas, ctx->dDesignKH,
+		                               ctx->dDesignHm));
+		ctx->design_serial = ctx->pred_serial;
+		ctx->design_box = bx;
+	}
+	for (int q0 = 0; q0 < M; q0 += cap) {
+		const int mb = std::min(cap, M - q0), mbp = round_up(mb, 64);
+		const double *xq = xq_dev + (size_t)q0 * d;
+		if (prof) for (const char *t : {"sens_prep_candidates", "design_kvec"}) ctx->prof.tag.push_back(t);
+		{
+			ProfScope ps(ctx, GPEMU_PROF_DESIGN, 2.0 * mb * d * 44.0, 8.0 * ((double)sens_prep_elems(mb, d) + (double)mb * d));
+			HIPCHK(ctx, launch_sens_prep(ctx->stream, xq, mb, bx, ctx->dDesignPrepQ, ctx->dSensCst));
+		}
+		{
+			ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)mb * N * (3.0 * d + 2.0), 8.0 * (double)mbp * Np);
+			HIPCHK(ctx, launch_design_kvec(ctx->stream, ctx->dX, N, Np, d, ctx->dSensCst, ctx->pred_cov.amp, xq, mb, mbp, ctx->dKq));
+		}
+		HIPCHK(ctx, launch_aug_product(ctx, aug_product_args(ctx, mb)));
+		HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, mb, Np, Rp, nreg, d, xq, ctx->dBetaQ, ctx->dDesignR));
+		// a^T (Np x mbp) = LinvAugT . [u | 0 | Q r]^T, exactly the second product of gpemu_predict_var_grad_dev
+		GemmArgs t{};
+		t.C = ctx->dKq; t.ldc = mbp;
+		t.A = ctx->dLinvAugT; t.lda = ldv;
+		t.B = ctx->dV; t.ldb = ldv;
+		t.m = Np; t.n = mb; t.k0 = 0; t.k1 = Np + Rp; t.alpha = 1.0; t.beta = 0;
+		t.kstart_mode = 1; t.kstart_off = 0;
+		HIPCHK(ctx, gemm(ctx, t));
+		if (prof) ctx->prof.tag.push_back("design_transpose");
+		{
+			ProfScope ps(ctx, GPEMU_PROF_DESIGN, 0.0, 16.0 * (double)mbp * Np);
+			HIPCHK(ctx, launch_transpose_rect(ctx->stream, ctx->dDesignA, Np, ctx->dKq, mbp, Np, mbp));
+		}
+		// T (mb x (Np + 64)) = a [K | HK]
+		GemmArgs g{};
+		g.C = ctx->dDesignT; g.ldc = ldt;
+		g.A = ctx->dDesignA; g.lda = Np;
+		g.B = ctx->dDesignKH; g.ldb = Np;
+		g.m = mb; g.n = Np + 64; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+		HIPCHK(ctx, gemm(ctx, g));
+		if (prof) for (const char *t2 : {"design_cross", "design_finish"}) ctx->prof.tag.push_back(t2);
+		{
+			// per pair d pair factors and the fused multiply-add; a and T read, one partial per candidate and tile column written
+			ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)mb * N * (sens_pair_flops(bx, d) + 4.0), 8.0 * (double)mb * (2.0 * N + ntc));
+			HIPCHK(ctx, launch_design_cross(ctx->stream, ctx->dX, N, d, xq, mb, ctx->dSensCst, bx.meas, ctx->dDesignA, Np, ctx->dDesignT, ldt,
+			                                ctx->dDesignPart, cap));
+		}
+		{
+			ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)mb * (2.0 * Np + 2.0 * nreg * nreg + sens_pair_flops(bx, d)), 8.0 * (double)mb * (double)ldv);
+			HIPCHK(ctx, launch_design_finish(ctx->stream, ctx->dDesignPart, cap, N, ctx->dV, ldv, ctx->dDesignR, Rp, ctx->dDesignT, ldt,
+			                                 ctx->dDesignPrepQ, xq, mb, Np, d, nreg, ctx->dSensCst, bx.meas, ctx->dDesignHm, ctx->pred_cov.amp,
+			                                 ctx->kappa, gain_dev + q0, num_dev ? num_dev + q0 : nullptr, var_dev ? var_dev + q0 : nullptr,
+			                                 ctx->dDesignB));
+		}
+		ctx->design_mb = mb;
+	}
+	return GPEMU_OK;
+}
+
+// host buffers: candidates and results through a buffer of the entry's own, so that a pending prediction batch keeps its staging
+extern "C" int gpemu_design_gain(gpemu_ctx *ctx, const double *lo, const double *hi, int npoints, const double *xq, double *gain, double *num,
+                                 double *var)
+{
+	SensBox bx;
+	if (const int rc = design_check(ctx, lo, hi, npoints, xq, gain, &bx)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t M = (size_t)npoints, d = (size_t)ctx->d;
+	if (const int rc = grow(ctx, ctx->dDesignOut, M * (d + 3))) return rc;
+	double *dx = ctx->dDesignOut, *dg = dx + M * d, *dn = dg + M, *dv = dn + M;
+	HIPCHK(ctx, hipMemcpyAsync(dx, xq, M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (const int rc = gpemu_design_gain_dev(ctx, lo, hi, npoints, dx, dg, dn, dv)) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(gain, dg, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (num) HIPCHK(ctx, hipMemcpyAsync(num, dn, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (var) HIPCHK(ctx, hipMemcpyAsync(var, dv, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// a (npoints x N) and b (npoints x nreg) exactly as the last block of the last gpemu_design_gain read them (parity tests: the
+// reference starts from the bits the products and the sweep multiplied by); npoints: that block's candidates
+extern "C" int gpemu_test_design_state(gpemu_ctx *ctx, int npoints, double *a_out, double *b_out)
+{
+	if (!ctx || !a_out || !b_out || npoints < 1) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->design_mb != npoints || !ctx->dDesignA || !ctx->dDesignB || ctx->design_serial != ctx->pred_serial)
+		return fail(ctx, GPEMU_ERR_STATE, "no gpemu_design_gain block of this size");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t N = (size_t)ctx->N, nreg = (size_t)ctx->nreg, Np = (size_t)ctx->Np;
+	HIPCHK(ctx, hipMemcpy2DAsync(a_out, N * sizeof(double), ctx->dDesignA, Np * sizeof(double), N * sizeof(double), (size_t)npoints,
+	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(b_out, nreg * sizeof(double), ctx->dDesignB, 64 * sizeof(double), nreg * sizeof(double), (size_t)npoints,
+	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }
 

@@ -331,6 +331,15 @@ struct gpemu_ctx {
 	// pair sweeps' partial sums (npairs per tile), dSensPairOut the npairs results of the host entries
 	gpemu::DevBuf<double> dSensPex2, dSensPairPart, dSensPairOut;
 	hipEvent_t sens_ev = nullptr, sens_ev2 = nullptr;
+	// expected IMSE reduction of candidate runs (gpemu_design_gain).  dDesignKH: [K ; HK], (Np + 64) x Np, and
+	// dDesignHm (64 x 64), kept between calls: design_serial / design_box say which set-up (pred_serial), box and kinds they
+	// were built for (0: none).  Per block of candidates: dDesignPrepQ the candidates' own tables, dDesignA the rows of a
+	// (mb' x Np), dDesignT = a [K | HK] (mb' x (Np + 64)), dDesignR the r rows, dDesignB the b rows (64 each), dDesignPart the
+	// cross sweep's partials; dDesignOut gain, num, var of the host entry; design_mb: the candidates of the last block (0: none)
+	gpemu::DevBuf<double> dDesignKH, dDesignHm, dDesignPrepQ, dDesignA, dDesignT, dDesignR, dDesignB, dDesignPart, dDesignOut;
+	unsigned long long pred_serial = 0, design_serial = 0;   // pred_serial: counts the prediction set-ups of this context
+	gpemu::SensBox design_box{};
+	int design_mb = 0;
 	// calibration against observations (gpemu_calib_*): dCalibTab the resident table of one observation set
 	// (kernels_calib.hip has its layout; calib_nt > 0: set up), independent of the model: gpemu_set_model leaves it alone,
 	// gpemu_calib_release and the end of the context free it.  dCalibIO / dCalibIdx the host entries' device copies of mean,
@@ -537,6 +546,22 @@ hipError_t launch_sens_pair_post_finish(hipStream_t s, const double *part, int N
 hipError_t launch_sens_joint(hipStream_t s, const double *X, int N, int d, int order, const double *gam, const double *beta, double amp,
                              const double *prep, const double *pex2, const double *cst, int j, int k, int npts, const double *xj,
                              const double *xk, double *e0, double *joint, double *inter);
+
+// ---- kernels_design.hip: expected IMSE reduction of candidate runs
+// KH: design_kh_elems doubles, rows [0, Np) = K (Np x Np, zero from N on), rows Np + al = HK_al; Hm: 64 x 64; prep: the design's
+// tables of context 0, prepq: those of the block's mb candidates; Am (mb x lda): the rows of a, Tm (mb x ldt) = a [K | HK];
+// part: ceil(N / 64) rows of pstride >= mb partials; V, R: the prediction's [u | . | Q r] rows and the r rows of predict_qr
+size_t design_kh_elems(int Np);
+hipError_t launch_design_kmat(hipStream_t s, const double *X, int N, int Np, int d, int nreg, const double *prep, const double *cst, int meas,
+                              double *KH, double *Hm);
+hipError_t launch_design_kvec(hipStream_t s, const double *X, int N, int Np, int d, const double *cst, double amp, const double *Xq, int mb,
+                              int mbp, double *Kq);
+hipError_t launch_design_cross(hipStream_t s, const double *X, int N, int d, const double *Xq, int mb, const double *cst, int meas,
+                               const double *Am, long lda, const double *Tm, long ldt, double *part, long pstride);
+hipError_t launch_design_finish(hipStream_t s, const double *part, long pstride, int N, const double *V, long ldv, const double *R, long ldr,
+                                const double *Tm, long ldt, const double *prepq, const double *Xq, int mb, int Np, int d, int nreg,
+                                const double *cst, int meas, const double *Hm, double amp, double kappa, double *gain, double *num, double *var,
+                                double *bkeep);
 
 // ---- kernels_calib.hip: implausibility and calibration likelihood against observations
 // the device table of one observation set: calib_table_elems doubles, filled on the host from gpemu_calib_project's outputs

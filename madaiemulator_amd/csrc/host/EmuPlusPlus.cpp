@@ -279,6 +279,20 @@ void emulator::QueryEmulatorSensitivityUncertainty(const std::vector<double> &lo
 		}
 }
 
+void emulator::QueryEmulatorDesignGain(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
+                                       std::vector<std::vector<double> > &Gains, std::vector<double> &TotalGains)
+{
+	check_box("QueryEmulatorDesignGain", lo, hi, number_params);
+	const size_t no = (size_t)number_outputs, np = xpoints.size();
+	Gains.assign(np, std::vector<double>(no));
+	TotalGains.assign(np, 0.0);
+	if (np == 0) return;
+	std::vector<double> flat = flatten("QueryEmulatorDesignGain", xpoints, number_params), g(np * no);
+	emulate_design_gain_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), (int)np, flat.data(), g.data(), TotalGains.data());
+	for (size_t q = 0; q < np; q++)
+		for (size_t t = 0; t < no; t++) Gains[q][t] = g[q * no + t];
+}
+
 void emulator::QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
                                             std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,
                                             std::vector<std::vector<std::vector<double> > > &Bands)

@@ -79,6 +79,10 @@ public:
 	                                         std::vector<double> &IntegratedVariances, std::vector<double> &ExpectedVariances,
 	                                         std::vector<std::vector<double> > &ExpectedFirstOrder,
 	                                         std::vector<std::vector<double> > &ExpectedTotal);
+	// where to put the next model run (libemu.h: emulate_design_gain_multi): Gains[q][t] = how much IntegratedVariances[t] drops
+	// when the design gets one more run at xpoints[q], the hyper-parameters as they are; TotalGains[q] its sum over the outputs
+	void QueryEmulatorDesignGain(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
+	                             std::vector<std::vector<double> > &Gains, std::vector<double> &TotalGains);
 	// QueryEmulatorMainEffects with Bands[t][j][g] = the posterior standard deviation of E[output t | x_j = grid[j][g]]
 	void QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
 	                                  std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,

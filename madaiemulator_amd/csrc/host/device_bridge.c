@@ -1326,6 +1326,14 @@ void emulate_main_effects_band(emulator_struct *e, const double *lo, const doubl
 	for (size_t i = 0; i < n; i++) sd[i] = sqrt(sd[i] > 0.0 ? sd[i] : 0.0);
 }
 
+/* the expected drop of *imse by one more run at each candidate (gpemu_design_gain in gpemu.h) */
+void emulate_design_gain(emulator_struct *e, const double *lo, const double *hi, int npoints, const double *points, double *gain,
+                         double *num, double *var)
+{
+	struct entry *en = entry_of(e, "emulate_design_gain");
+	check(en, gpemu_design_gain(en->ctx, lo, hi, npoints, points, gain, num, var), "emulate_design_gain");
+}
+
 /* second order (gpemu_sens_pairs / gpemu_sens_pairs_post / gpemu_sens_joint in gpemu.h): pairs j < k at
  * p = j (2 d - j - 1) / 2 + (k - j - 1).  vpair[p] = V_jk = Var(E[m | x_j, x_k]), inter[p] = V_jk - V_j - V_k */
 void emulate_sensitivity_pairs(emulator_struct *e, const double *lo, const double *hi, double *vpair, double *inter)

@@ -35,6 +35,7 @@ struct cmdLineOpts {
 	char *run_mode, *inputfile, *statefile, *holdoutfile, *groupsfile, *boxfile, *priorfile, *obsfile;
 	double cutI, cutChi2;
 	int level, gradientFlag;
+	int best, bestGiven;
 	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
@@ -80,6 +81,12 @@ static const char useage[] =
 	"      chi^2 is <= C2 (default: no cut): index, parameters, chi^2, log likelihood, the three largest implausibilities, the worst\n"
 	"      output; with --gradient, behind them the d components of the log likelihood's gradient with respect to the parameters.\n"
 	"      FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
+	"or\n"
+	"  interactive_emulator design MODEL_SNAPSHOT_FILE [--box=FILE | --prior=FILE] [--best=K] [--pca_output] [--quiet]  (where to put the next model\n"
+	"      run: candidate points from stdin to the end of input; one line per candidate: index, parameters, the expected drop of the\n"
+	"      integrated posterior variance summed over the outputs if the model were run there, and that integrated variance as it\n"
+	"      is now.  --best=K prints the K candidates with the largest drop, largest first, ties in input order.  The measure as for\n"
+	"      `sensitivity`.  Power-exponential covariance only)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -462,24 +469,12 @@ static int bad_measure_file(void)
 	return EXIT_FAILURE;
 }
 
-static int sensitivity(struct cmdLineOpts *o)
+/* the input measure of `sensitivity` and `design`: --prior=FILE, --box=FILE or the range of the design into lo, hi and kind (d each,
+ * kind zeroed by the caller).  0, or the status to end with, its message already written. */
+static int read_measure(const struct cmdLineOpts *o, const multi_modelstruct *model, double *lo, double *hi, int *kind)
 {
-	FILE *fp = fopen(o->statefile, "r");
-	if (!fp) return perr("Error opening file");
-	gpemu_host_warm_start();
-	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
-	multi_modelstruct *model = load_multi_modelstruct(fp);
-	fclose(fp);
-	const int d = model->nparams, nt = model->nt, N = model->nmodel_points, G = o->grid;
-	const int nout = o->pcaOutputFlag ? model->nr : nt;
-	if (model->cov_fn_index > 1) return perr("sensitivity: the closed form exists for the power-exponential covariance only");
-	if (G < 0) return perr("--grid=G needs G >= 1");
-	if ((o->pairs || o->surface) && d < 2) return perr("--pairs and --surface need a model with two parameters or more");
-	if (o->surface && (G < 1 || o->surfJ == o->surfK || o->surfJ < 0 || o->surfK < 0 || o->surfJ >= d || o->surfK >= d))
-		return perr("--surface=j,k needs two different parameters of 0 .. d - 1, and --grid=G");
+	const int d = model->nparams, N = model->nmodel_points;
 	if (o->boxfile && o->priorfile) { perr("--box=FILE and --prior=FILE exclude each other"); return bad_measure_file(); }
-	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
-	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
 	if (o->priorfile) {
 		FILE *pf = fopen(o->priorfile, "r");
 		if (!pf) { perr("Error opening the prior file"); return bad_measure_file(); }
@@ -516,6 +511,30 @@ static int sensitivity(struct cmdLineOpts *o)
 				return EXIT_FAILURE;
 			}
 		}
+	}
+	return 0;
+}
+
+static int sensitivity(struct cmdLineOpts *o)
+{
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	const int d = model->nparams, nt = model->nt, G = o->grid;
+	const int nout = o->pcaOutputFlag ? model->nr : nt;
+	if (model->cov_fn_index > 1) return perr("sensitivity: the closed form exists for the power-exponential covariance only");
+	if (G < 0) return perr("--grid=G needs G >= 1");
+	if ((o->pairs || o->surface) && d < 2) return perr("--pairs and --surface need a model with two parameters or more");
+	if (o->surface && (G < 1 || o->surfJ == o->surfK || o->surfJ < 0 || o->surfK < 0 || o->surfJ >= d || o->surfK >= d))
+		return perr("--surface=j,k needs two different parameters of 0 .. d - 1, and --grid=G");
+	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
+	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
+	{
+		const int rc = read_measure(o, model, lo, hi, kind);
+		if (rc) return rc;
 	}
 	/* where the curves and the surface run */
 	double *glo = (double *)malloc(sizeof(double) * (size_t)d), *ghi = (double *)malloc(sizeof(double) * (size_t)d);
@@ -750,6 +769,80 @@ static int implausibility(struct cmdLineOpts *o)
 	return 0;
 }
 
+/* Where to put the next model run (emulate_design_gain_multi): candidates from stdin, d numbers each.  stdout, per candidate, one
+ * line "index param_0 .. param_{d-1} gain imse": gain the expected drop of the integrated posterior variance, summed over the
+ * outputs, if the model were run there (hyper-parameters as they are), imse that integrated variance as it is now (the same on
+ * every line).  --best=K: the K candidates with the largest gain, largest first, ties in input order. */
+static const double *design_key;
+static int design_order(const void *a, const void *b)
+{
+	const int i = *(const int *)a, j = *(const int *)b;
+	if (design_key[i] != design_key[j]) return design_key[i] > design_key[j] ? -1 : 1;
+	return i < j ? -1 : (i > j);
+}
+
+static int design(struct cmdLineOpts *o)
+{
+	if (o->bestGiven && o->best < 1) return perr("--best=K needs K >= 1");
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	const int d = model->nparams, nout = o->pcaOutputFlag ? model->nr : model->nt;
+	if (model->cov_fn_index > 1) return perr("design: the closed form exists for the power-exponential covariance only");
+	size_t cap = 1024, n = 0;
+	double *v = (double *)malloc(sizeof(double) * cap), x;
+	while (fscanf(stdin, "%lf", &x) == 1) {
+		if (n == cap) v = (double *)realloc(v, sizeof(double) * (cap *= 2));
+		v[n++] = x;
+	}
+	if (!feof(stdin) || n % (size_t)d) return perr("design: stdin must hold whole points, d numbers each, and nothing else");
+	const size_t np = n / (size_t)d;
+	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
+	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
+	{
+		const int rc = read_measure(o, model, lo, hi, kind);
+		if (rc) return rc;
+	}
+	multi_emulator *emu = alloc_multi_emulator(model);
+	if (o->priorfile) emulate_sensitivity_measure_multi(emu, kind);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "# index");
+		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
+		fprintf(out, " expected_imse_reduction imse\n");
+	}
+	if (np) {
+		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
+		double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
+		emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
+		double now = 0.0;
+		for (int t = 0; t < nout; t++) now += imse[t];
+		double *gain = (double *)malloc(sizeof(double) * np * (size_t)nout), *total = (double *)malloc(sizeof(double) * np);
+		emulate_design_gain_multi(emu, o->pcaOutputFlag, lo, hi, (int)np, v, gain, total);
+		int *idx = (int *)malloc(sizeof(int) * np);
+		for (size_t q = 0; q < np; q++) idx[q] = (int)q;
+		size_t nprint = np;
+		if (o->bestGiven) {
+			design_key = total;
+			qsort(idx, np, sizeof(int), design_order);
+			if ((size_t)o->best < np) nprint = (size_t)o->best;
+		}
+		for (size_t k = 0; k < nprint; k++) {
+			fprintf(out, "%d", idx[k]);
+			for (int j = 0; j < d; j++) fprintf(out, " %.17g", v[(size_t)idx[k] * d + j]);
+			fprintf(out, " %.17g %.17g\n", total[idx[k]], now);
+		}
+		free(ve0); free(ef); free(gain); free(total); free(idx);
+	}
+	fflush(out);
+	free(v); free(lo); free(hi); free(kind);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static int print_thetas(struct cmdLineOpts *o)
 {
 	FILE *fp = fopen(o->statefile, "r");
@@ -812,6 +905,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"level", required_argument, NULL, 1015},             {"chi2", required_argument, NULL, 1016},
 		/* ... and the gradient of the log likelihood behind every printed line */
 		{"gradient", no_argument, NULL, 1017},
+		/* design: only the K candidates that gain most */
+		{"best", required_argument, NULL, 1018},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
@@ -852,6 +947,7 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1015: o->level = atoi(optarg); break;
 		case 1016: o->cutChi2 = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
 		case 1017: o->gradientFlag = 1; break;
+		case 1018: o->best = atoi(optarg); o->bestGiven = 1; break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
@@ -886,6 +982,7 @@ int main(int argc, char **argv)
 	else if (!strcmp(o->run_mode, "validate")) rc = validate(o);
 	else if (!strcmp(o->run_mode, "sensitivity")) rc = sensitivity(o);
 	else if (!strcmp(o->run_mode, "implausibility")) rc = implausibility(o);
+	else if (!strcmp(o->run_mode, "design")) rc = design(o);
 	else { free(o); return perr(useage); }
 	free(o);
 	return rc;

@@ -339,6 +339,12 @@ void emulate_main_effects_var(emulator_struct *e, const double *lo, const double
                               double *var, double *var_e0);
 void emulate_main_effects_band(emulator_struct *e, const double *lo, const double *hi, int ngrid, const double *grid, double *e0, double *main,
                                double *sd);
+/* extension: where to put the next model run (gpemu_design_gain in gpemu.h).  gain[q] = how much *imse of
+ * emulate_sensitivity_uncertainty drops when the design gets one more run at points[q] (npoints x nparams, row-major), the
+ * hyper-parameters as they are; num and var (either may be NULL) its numerator E_x[c*(x, x*)^2] and the variance the run would be
+ * observed with.  lo / hi and the measure as in the emulate_sensitivity* family. */
+void emulate_design_gain(emulator_struct *e, const double *lo, const double *hi, int npoints, const double *points, double *gain,
+                         double *num, double *var);
 /* extension: second-order Sobol indices and interaction surfaces in closed form (gpemu_sens_pairs / gpemu_sens_pairs_post /
  * gpemu_sens_joint in gpemu.h).  total[j] > first[j] says that parameter j interacts; these say with which parameter.  Pairs j < k
  * are numbered p = j (2 nparams - j - 1) / 2 + (k - j - 1), npairs = nparams (nparams - 1) / 2; nparams >= 2.
@@ -495,6 +501,12 @@ void emulate_sensitivity_uncertainty_multi(multi_emulator *emu, int pca_space, c
                                            double *imse_out, double *evar_out, double *efirst_out, double *etotal_out);
 void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int ngrid, const double *grid,
                                      double *e0_out, double *main_out, double *sd_out);
+/* the expected drop of every output's IMSE by one more run at each of npoints candidates (points: npoints x nparams, row-major):
+ * gain_out[q * nout + t], nout = nt (nr in PCA space).  One run observes every component and the components are independent a
+ * posteriori, so the result takes the squared rule of gpemu_host_backproject, gain(y_t) = sum_c B_tc^2 gain_c; total_out[q]
+ * (may be NULL) is its sum over the outputs. */
+void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
+                               double *gain_out, double *total_out);
 /* second order per output: vpair_out, inter_out, evpair_out, einter_out are npairs values each, output-major, as
  * emulate_sensitivity_pairs / _uncertainty define them.  Observable space exactly as for emulate_sensitivity_multi /
  * _uncertainty_multi: the plug-in half keeps all cross terms between components, sum_{c,c'} B_tc B_tc' cov_pair(c, c') (every pair

@@ -949,6 +949,27 @@ void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const d
 	free(mp); free(vp); free(mc); free(vc); free(ep);
 }
 
+/* The expected drop of every output's IMSE by one more run at each candidate (libemu.h): the components one after the other
+ * (gpemu_design_gain waits for its result), then the squared half of the rule -- a run observes every component, and the
+ * components are independent a posteriori. */
+void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
+                               double *gain_out, double *total_out)
+{
+	const size_t nr = (size_t)emu->nr, np = (size_t)(npoints > 0 ? npoints : 0), nout = pca_space ? nr : (size_t)emu->nt;
+	double *gp = doubles((np ? np : 1) * nr), *gc = doubles(np ? np : 1);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_design_gain(emu->emu_struct_array[c], lo, hi, npoints, points, gc, NULL, NULL);
+		place_component(gp, gc, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 1, 0, np, 1, gp, gain_out);
+	for (size_t q = 0; total_out && q < np; q++) {
+		double s = 0.0;
+		for (size_t t = 0; t < nout; t++) s += gain_out[q * nout + t];
+		total_out[q] = s;
+	}
+	free(gp); free(gc);
+}
+
 /* Second order for every output (libemu.h): vpair_out[t * npairs + p] = V_jk of output t, inter_out the interaction variances
  * V_jk - V_j - V_k.  As emulate_sensitivity_multi: in observable space the full quadratic form over all pairs of components,
  *   V_jk(y_t) = sum_{c,c'} B_tc B_tc' cov_pair(c, c'),
