@@ -675,7 +675,8 @@ int gpemu_sens_get_measure(const gpemu_ctx *ctx, int *kind /* d */);
  * tau_c as the squared norm of column c of L^-1 formed one column at a time; the weights go to LDS.  Phase 2, the workgroup's
  * lanes over the flat tile of its queries' outputs: every load of gmean, gvar and every store is unit-stride across the wave
  * for any d.  No atomics; 16 nr d bytes are read per point.
- * Not built: derivatives of the I_t (a max-type statistic); second derivatives; a sampler or optimiser on top. */
+ * Not built: derivatives of the I_t (a max-type statistic); second derivatives; an optimiser on top (the sampler
+ * below uses no gradient). */
 #define GPEMU_CALIB_MAX_R  16
 #define GPEMU_CALIB_MAX_NT 1024
 int gpemu_calib_project(int nt, int nr, const double *ybar /* nt */, const double *A /* nt*nr */, const double *z /* nt */,
@@ -699,6 +700,85 @@ int gpemu_calib_select_dev(gpemu_ctx *ctx, int M, const double *stat_dev, double
                            int *count /* HOST */);
 int gpemu_calib_gather_dev(gpemu_ctx *ctx, int M, const double *stat_dev, const int *worst_dev /* may be NULL */, int count,
                            const int *idx_dev, double *out_dev /* count*5 */, int *worst_out_dev /* may be NULL */);
+
+/* ---- posterior samples of the parameters: ensemble MCMC on the device -----------------
+ * The affine-invariant ensemble sampler of Goodman & Weare 2010 (the stretch move) in the parallel half-ensemble form of
+ * Foreman-Mackey et al. 2013, over log posterior = logpdf of gpemu_calib_eval + log prior.  No gradient, no proposal scale to
+ * tune; a half-step evaluates W / 2 proposals in ONE gpemu_predict_batch_dev sweep per component plus ONE gpemu_calib_eval_dev
+ * launch, and proposals, random numbers, the accept step and the trace stay on the device.
+ *
+ * Random numbers, specified to the bit: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 and 0xBB67AE85), key (seed & 0xffffffff, seed >> 32).  A uniform is made from two words,
+ *   U(a, b) = (((uint64) a << 20 | b >> 12) + 0.5) 2^-52
+ * strictly inside (0, 1), exact in fp64, the same bits on host and device.  Walker k at global step t: counter (k, t &
+ * 0xffffffff, t >> 32, 0) gives words w0 .. w3, u1 = U(w0, w1), u2 = U(w2, w3); counter (k, t lo, t hi, 1) gives u3 = U(w0, w1).
+ * A walker is active in exactly one half-step of a step: no counter repeats.  gpemu_philox4x32 and gpemu_sample_uniforms (u =
+ * {u1, u2, u3}) are that generator on the host, the kernels' own body: they need no device.  GPEMU_ERR_ARG for a NULL pointer.
+ *
+ * State: x is W x d row-major, W even; lp is W values, log likelihood + log prior; half 0 is walkers 0 .. W/2 - 1, half 1 the rest.
+ * gpemu_sample_set_prior(ctx, d, kind, lo, hi): a per-coordinate prior table resident on the context, in the convention of
+ * gpemu_sens_set_measure (kind NULL: all uniform; for GPEMU_MEASURE_GAUSS lo is the mean and hi the standard deviation), with
+ * its argument checks: GPEMU_ERR_ARG for a kind outside {0, 1}, lo >= hi on a uniform coordinate, a standard deviation <= 0, a
+ * non-finite value, d outside 1 .. GPEMU_MAX_PARAMS, a NULL lo or hi.  Log prior of a point: a uniform coordinate gives
+ * -log(hi - lo) inside [lo, hi], ends included, -inf outside (a NaN is outside); a Gaussian one -r^2 / 2 - log sd - log(2 pi) / 2;
+ * summed over the coordinates in index order from 0.0.  The table does not depend on the model: gpemu_set_model leaves it, a
+ * second call replaces it, gpemu_sample_release (waits for the stream; frees the run's buffers too) and gpemu_ctx_destroy free it.
+ * gpemu_sample_propose_dev, active walker k of `half`, local index i: partner j = base of the other half + min(floor(u1 W/2),
+ * W/2 - 1); z = ((a - 1) u2 + 1)^2 / a; y_i = x_j + z (x_k - x_j) into y_dev (W/2 x d row-major); aux_dev[i] = (d - 1) log z
+ * (exactly 0 for d = 1); aux_dev[W/2 + i] = log prior of y_i.  One launch; every load of the walkers' own rows and every store
+ * is unit-stride across a wave for any d (the lanes walk the flat tile of 64 walkers' coordinates); nothing outside y_dev and
+ * aux_dev is written.  z and y are formed without contraction: +, * and / round once each, as a host would.
+ * gpemu_sample_accept_dev: lp_y = loglik[i] + aux[W/2 + i]; the proposal is taken iff lp_y is finite and log u3 < aux[i] + lp_y
+ * - lp_k (strict).  Taken: row k of x becomes row i of y bit for bit, lp_k becomes lp_y, naccept[k] grows by 1; not taken:
+ * nothing of walker k changes; the other half is never touched.  One launch, no atomics: a walker has one owner.  loglik_dev is
+ * row 1 of gpemu_calib_eval_dev's stat for M = W/2, but any pointer serves.
+ * gpemu_sample_logpost_dev: lp[q] = loglik[q] + log prior of row q of x (M x d): how a run's start gets its lp.  One launch.
+ * Errors of the three: GPEMU_ERR_ARG for a NULL pointer, odd W, W < 2 (logpost: M < 1), d outside 1 .. GPEMU_MAX_PARAMS, half
+ * outside {0, 1}, a <= 1 or non-finite; GPEMU_ERR_STATE without a prior of that d.  All only enqueue on the context's stream.
+ *
+ * gpemu_calib_sample: comp[c] are the nr component contexts, each with a prediction set-up; obs holds the calibration set-up (its
+ * nr equal to the argument) and the prior; obs may be one of the components; all on one device.  Start-up: lp of x0 by
+ * gpemu_predict_batch_dev, gpemu_calib_eval_dev and gpemu_sample_logpost_dev in two half-batches of W/2; GPEMU_ERR_ARG if a start
+ * has a non-finite lp.  Then for global step g = first_step + t, t = 0 .. nsteps - 1, half 0 then half 1: propose;
+ * gpemu_predict_batch_dev of every component into component-major rows, ld = W/2; gpemu_calib_eval_dev; accept.  After step g,
+ * if g >= burn and (g + 1) % thin == 0, x and lp are appended to a device-resident trace (trace_x: nrec x W x d, trace_lp: nrec x
+ * W; either may be NULL, with both NULL nothing is staged); burn and thin count GLOBAL steps, so a run split into two calls
+ * records the same steps.  *nrec_out = the records of this call.  The trace is staged in chunks of at most 64 MiB of records
+ * (at least one record) and copied out chunk by chunk; gpemu_test_sample_chunk(ctx, records) sets another bound for tests (0: the
+ * default).  naccept counts every step of the call.  x_end, lp_end: the ensemble after the last step.
+ * The component streams and obs's stream are ordered with events (as gpemu_sens_cov orders two contexts): no host wait inside a
+ * chunk of steps; the host waits where a chunk is copied out, once after the start-up evaluation and at the end.  Every buffer
+ * of a run belongs to the sample state on obs, allocated once per call shape and reused; nothing is allocated inside the step loop.
+ * Errors: GPEMU_ERR_ARG for a NULL required pointer, nr < 1, odd W, W/2 < d + 1 (each half must span the space), nsteps < 1, burn
+ * < 0, thin < 1, a <= 1, contexts on different devices (not built) or with different d; GPEMU_ERR_STATE for a missing prediction
+ * set-up, calibration set-up or prior (of the components' d), or a calibration nr different from the argument.
+ * Guarantees: two identical calls return the same bits; a run of T steps equals, bit for bit, a run of T1 steps followed by one of
+ * T - T1 steps with first_step = T1 from the first run's x_end (the traces concatenate, naccept adds up); the run equals, bit for
+ * bit, the same sequence of the public entries issued one by one by a caller with a sync between them; every other entry
+ * returns the bits it returned before.
+ * Not built: gradient-based moves (MALA, HMC: the variance-gradient sweep costs about 20 prediction sweeps); other ensemble
+ * moves; parallel tempering; components on several devices; convergence diagnostics beyond the host layer's integrated
+ * autocorrelation time; starting from the non-implausible set; graph capture of a step. */
+int gpemu_philox4x32(const unsigned ctr[4], const unsigned key[2], unsigned out[4]);
+int gpemu_sample_uniforms(unsigned long long seed, unsigned walker, unsigned long long step, double u[3]);
+int gpemu_sample_set_prior(gpemu_ctx *ctx, int d, const int *kind /* d values, or NULL: all uniform */, const double *lo, const double *hi);
+int gpemu_sample_release(gpemu_ctx *ctx);
+int gpemu_sample_propose_dev(gpemu_ctx *ctx, int W, int d, int half, unsigned long long step, unsigned long long seed, double a,
+                             const double *x_dev /* W*d */, double *y_dev /* W/2*d */, double *aux_dev /* W */);
+int gpemu_sample_accept_dev(gpemu_ctx *ctx, int W, int d, int half, unsigned long long step, unsigned long long seed,
+                            const double *y_dev, const double *aux_dev, const double *loglik_dev /* W/2 */, double *x_dev,
+                            double *lp_dev /* W */, int *naccept_dev /* W */);
+int gpemu_sample_logpost_dev(gpemu_ctx *ctx, int M, int d, const double *x_dev /* M*d */, const double *loglik_dev /* M */,
+                             double *lp_dev /* M */);
+typedef struct gpemu_sample_args {
+	int nwalkers, nsteps, burn, thin;
+	unsigned long long seed, first_step;
+	double a;
+} gpemu_sample_args;
+int gpemu_calib_sample(gpemu_ctx *const *comp, int nr, gpemu_ctx *obs, const gpemu_sample_args *args,
+                       const double *x0 /* W*d host */, double *trace_x /* nrec*W*d or NULL */, double *trace_lp /* nrec*W or NULL */,
+                       double *x_end /* W*d */, double *lp_end /* W */, int *naccept /* W */, int *nrec_out);
+int gpemu_test_sample_chunk(gpemu_ctx *ctx, int records);
 
 /* ---- low-level compatibility with the reference's host-matrix interface (what libRbind links against) ------
  * a14 chol_inverse_cov_matrix (libEmu/emulate-fns.c:275-299): the n x n matrix a (row stride lda, lower triangle

@@ -87,6 +87,14 @@ RES_SKINNY, RES_GEMV, RES_LOO_COLSQ, RES_LOO_FINISH, RES_LGO_GATHER, RES_LGO_STA
 _RES_LEN = dict(lin="lin_len", kq="kq_len", vp="vp_len", part="part_len", z="z_len", t="t_len", mean="out_len")
 
 
+class SampleArgs(C.Structure):
+    """gpemu_sample_args of include/gpemu.h"""
+    _fields_ = ([(f, C.c_int) for f in ("nwalkers", "nsteps", "burn", "thin")] +
+                [(f, C.c_ulonglong) for f in ("seed", "first_step")] + [("a", C.c_double)])
+
+
+_up = C.POINTER(C.c_uint)
+
 # every symbol include/gpemu.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "gpemu_ctx_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -179,6 +187,18 @@ SYMBOLS = {
     "gpemu_calib_select": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int, C.c_double, _ip, _ip]),
     "gpemu_calib_select_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_void_p, _ip]),
     "gpemu_calib_gather_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_philox4x32": (C.c_int, [_up, _up, _up]),
+    "gpemu_sample_uniforms": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_ulonglong, _dp]),
+    "gpemu_sample_set_prior": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
+    "gpemu_sample_release": (C.c_int, [C.c_void_p]),
+    "gpemu_sample_propose_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_sample_accept_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_sample_logpost_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_calib_sample": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(SampleArgs), _dp, _dp, _dp, _dp, _dp,
+                                     _ip, _ip]),
+    "gpemu_test_sample_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "gpemu_ctx_device": (C.c_int, [C.c_void_p]),
     "gpemu_chol_inverse": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _ip]),
     "gpemu_symm_apply": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]),
@@ -289,6 +309,42 @@ def calib_project(ybar, A, z, S=None, sd=None, nt=None, nr=None):
     info = C.c_int(0)
     rc = load().gpemu_calib_project(nt, nr, _po(ybar), _p(A), _po(z), _po(S), _po(sd), _p(mhat), _p(sigz), _p(consts), C.byref(info))
     return dict(mhat=mhat, sigz=sigz, c_perp=consts[0], logdet_S=consts[1], logdet_G=consts[2], info=info.value, status=rc)
+
+
+def philox4x32(ctr, key):
+    """gpemu_philox4x32 (host, no device): the four output words of Philox4x32-10 for a counter of 4 and a key of 2 words"""
+    c, k, o = (np.ascontiguousarray(ctr, dtype=np.uint32), np.ascontiguousarray(key, dtype=np.uint32), np.zeros(4, dtype=np.uint32))
+    if c.size != 4 or k.size != 2:
+        raise GpemuError(ERR_ARG, "philox4x32: a counter of 4 words and a key of 2")
+    rc = load().gpemu_philox4x32(c.ctypes.data_as(_up), k.ctypes.data_as(_up), o.ctypes.data_as(_up))
+    if rc != OK:
+        raise GpemuError(rc, "gpemu_philox4x32")
+    return o
+
+
+def sample_uniforms(seed, walker, step):
+    """gpemu_sample_uniforms (host, no device): (u1, u2, u3) of a walker at a global step of the ensemble sampler"""
+    u = np.zeros(3)
+    rc = load().gpemu_sample_uniforms(seed, walker, step, _p(u))
+    if rc != OK:
+        raise GpemuError(rc, "gpemu_sample_uniforms")
+    return u
+
+
+def calib_sample(comps, obs, x0, nsteps, burn=0, thin=1, seed=0, first_step=0, a=2.0, trace=True):
+    """gpemu_calib_sample: comps the component contexts (prediction set up), obs the context with the calibration set-up and
+    the prior; x0[W, d].  -> dict(trace_x[nrec, W, d], trace_lp[nrec, W] (None without trace), x_end, lp_end, naccept, nrec)"""
+    x0 = _a(x0)
+    W, d = x0.shape
+    args = SampleArgs(nwalkers=W, nsteps=nsteps, burn=burn, thin=thin, seed=seed, first_step=first_step, a=a)
+    cap = sum(1 for g in range(first_step, first_step + max(nsteps, 0)) if g >= burn and (g + 1) % max(thin, 1) == 0)
+    tx, tl = (np.full((cap, W, d), np.nan), np.full((cap, W), np.nan)) if trace else (None, None)
+    x_end, lp_end, nacc, nrec = np.full((W, d), np.nan), np.full(W, np.nan), np.zeros(W, dtype=np.int32), C.c_int(-1)
+    hs = (C.c_void_p * len(comps))(*[c.h for c in comps])
+    obs._chk(obs.L.gpemu_calib_sample(hs, len(comps), obs.h, C.byref(args), _p(x0), _po(tx), _po(tl), _p(x_end), _p(lp_end),
+                                      nacc.ctypes.data_as(_ip), C.byref(nrec)))
+    assert nrec.value == cap
+    return dict(trace_x=tx, trace_lp=tl, x_end=x_end, lp_end=lp_end, naccept=nacc, nrec=nrec.value)
 
 
 class Context:
@@ -623,6 +679,28 @@ class Context:
 
     # the input measure of every sens_* entry: one kind per coordinate, MEASURE_UNIFORM (lo, hi: the bounds)
     # or MEASURE_GAUSS (lo: the mean, hi: the standard deviation)
+    # the ensemble sampler's prior and primitives; the run itself is abi.calib_sample
+    def sample_set_prior(self, lo, hi, kind=None, allow=()):
+        lo, hi = _a(lo).ravel(), _a(hi).ravel()
+        kp = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        return self._chk(self.L.gpemu_sample_set_prior(self.h, lo.size, None if kp is None else kp.ctypes.data_as(_ip), _p(lo), _p(hi)),
+                         allow=allow)
+
+    def sample_release(self):
+        self._chk(self.L.gpemu_sample_release(self.h))
+
+    def sample_propose_dev(self, W, d, half, step, seed, a, x_dev, y_dev, aux_dev):
+        self._chk(self.L.gpemu_sample_propose_dev(self.h, W, d, half, step, seed, a, x_dev, y_dev, aux_dev))
+
+    def sample_accept_dev(self, W, d, half, step, seed, y_dev, aux_dev, loglik_dev, x_dev, lp_dev, naccept_dev):
+        self._chk(self.L.gpemu_sample_accept_dev(self.h, W, d, half, step, seed, y_dev, aux_dev, loglik_dev, x_dev, lp_dev, naccept_dev))
+
+    def sample_logpost_dev(self, M, d, x_dev, loglik_dev, lp_dev):
+        self._chk(self.L.gpemu_sample_logpost_dev(self.h, M, d, x_dev, loglik_dev, lp_dev))
+
+    def test_sample_chunk(self, records):
+        self._chk(self.L.gpemu_test_sample_chunk(self.h, records))
+
     def sens_set_measure(self, kind=None):
         """kind: d values of MEASURE_UNIFORM / MEASURE_GAUSS, or None for all uniform; set_model resets it"""
         if kind is None:

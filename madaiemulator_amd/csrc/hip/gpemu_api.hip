@@ -3268,6 +3268,216 @@ extern "C" int gpemu_calib_select(gpemu_ctx *ctx, int M, const double *stat, dou
 }
 
 // ---------------------------------------------------------------------------
+// posterior samples of the parameters: the affine-invariant ensemble sampler (gpemu.h).  The prior table and
+// every buffer of a run belong to ctx->sample.  The primitives are one launch each on the context's stream; the run is their
+// sequence with the prediction sweeps of the components on the components' own streams, ordered by events.
+// ---------------------------------------------------------------------------
+extern "C" int gpemu_sample_set_prior(gpemu_ctx *ctx, int d, const int *kind, const double *lo, const double *hi)
+{
+	if (!ctx || !lo || !hi || d < 1 || d > GPEMU_MAX_PARAMS) return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_set_prior: bad argument");
+	for (int l = 0; l < d; l++) {
+		const int k = kind ? kind[l] : GPEMU_MEASURE_UNIFORM;
+		if (k != GPEMU_MEASURE_UNIFORM && k != GPEMU_MEASURE_GAUSS)
+			return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_set_prior: a kind is GPEMU_MEASURE_UNIFORM or GPEMU_MEASURE_GAUSS");
+		if (k == GPEMU_MEASURE_GAUSS) {
+			if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > 0.0))
+				return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_set_prior: a Gaussian coordinate needs a finite mean and a finite standard deviation > 0");
+		} else if (!std::isfinite(lo[l]) || !std::isfinite(hi[l]) || !(hi[l] > lo[l]) || !std::isfinite(hi[l] - lo[l]))
+			return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_set_prior: every bound must be finite, with hi > lo");
+	}
+	double tab[SAMPLE_PRIOR_ROWS * GPEMU_MAX_PARAMS];
+	sample_fill_prior(d, kind, lo, hi, tab);
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	// work enqueued against the old table ends before the new one replaces it, and the upload has completed on return
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->sample.prior_d = 0;
+	if (const int rc = grow(ctx, ctx->sample.prior, sizeof tab / sizeof tab[0])) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(ctx->sample.prior, tab, sizeof tab, hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->sample.prior_d = d;
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sample_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->sample.release();
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_test_sample_chunk(gpemu_ctx *ctx, int records)
+{
+	if (!ctx || records < 0) return GPEMU_ERR_ARG;
+	ctx->sample.chunk_records = records;
+	return GPEMU_OK;
+}
+
+// the checks the two primitives share
+static int sample_step_check(gpemu_ctx *ctx, int W, int d, int half, const char *who)
+{
+	if (W < 2 || (W & 1) || d < 1 || d > GPEMU_MAX_PARAMS || (half != 0 && half != 1)) return fail(ctx, GPEMU_ERR_ARG, who);
+	if (ctx->sample.prior_d != d) return fail(ctx, GPEMU_ERR_STATE, "gpemu_sample_set_prior has not been called for this d");
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sample_propose_dev(gpemu_ctx *ctx, int W, int d, int half, unsigned long long step, unsigned long long seed, double a,
+                                        const double *x_dev, double *y_dev, double *aux_dev)
+{
+	if (!ctx || !x_dev || !y_dev || !aux_dev || !(a > 1.0) || !std::isfinite(a)) return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_propose: bad argument");
+	if (const int rc = sample_step_check(ctx, W, d, half, "gpemu_sample_propose: bad argument")) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, launch_sample_propose(ctx->stream, ctx->sample.prior, W, d, half, step, seed, a, x_dev, y_dev, aux_dev));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sample_accept_dev(gpemu_ctx *ctx, int W, int d, int half, unsigned long long step, unsigned long long seed,
+                                       const double *y_dev, const double *aux_dev, const double *loglik_dev, double *x_dev, double *lp_dev,
+                                       int *naccept_dev)
+{
+	if (!ctx || !y_dev || !aux_dev || !loglik_dev || !x_dev || !lp_dev || !naccept_dev)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_accept: bad argument");
+	if (const int rc = sample_step_check(ctx, W, d, half, "gpemu_sample_accept: bad argument")) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, launch_sample_accept(ctx->stream, W, d, half, step, seed, y_dev, aux_dev, loglik_dev, x_dev, lp_dev, naccept_dev));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_sample_logpost_dev(gpemu_ctx *ctx, int M, int d, const double *x_dev, const double *loglik_dev, double *lp_dev)
+{
+	if (!ctx || !x_dev || !loglik_dev || !lp_dev || M < 1 || d < 1 || d > GPEMU_MAX_PARAMS)
+		return fail(ctx, GPEMU_ERR_ARG, "gpemu_sample_logpost: bad argument");
+	if (ctx->sample.prior_d != d) return fail(ctx, GPEMU_ERR_STATE, "gpemu_sample_set_prior has not been called for this d");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, launch_sample_logpost(ctx->stream, ctx->sample.prior, M, d, x_dev, loglik_dev, lp_dev));
+	return GPEMU_OK;
+}
+
+// the trace records of a chunk unless the test hook says otherwise: 64 MiB of staged records, one at the least
+constexpr size_t SAMPLE_CHUNK_BYTES = (size_t)64 << 20;
+
+// the log likelihood of the h points at xq into row 1 of the state's stat: every component's sweep on its own stream behind
+// the obs stream's pending work, the obs stream behind the sweeps, the evaluation.  Nothing waits on the host.
+static int sample_loglik(gpemu_ctx *const *comp, int nr, gpemu_ctx *obs, int h, const double *xq)
+{
+	SampleState &st = obs->sample;
+	HIPCHK(obs, hipEventRecord(st.ev_obs, obs->stream));
+	for (int c = 0; c < nr; c++) {
+		gpemu_ctx *cc = comp[c];
+		if (cc != obs) HIPCHK(obs, hipStreamWaitEvent(cc->stream, st.ev_obs, 0));
+		const int rc = gpemu_predict_batch_dev(cc, h, xq, st.mean + (size_t)c * h, st.var + (size_t)c * h);
+		if (rc) return cc == obs ? rc : fail(obs, rc, gpemu_last_error(cc));
+		if (cc != obs) {
+			HIPCHK(obs, hipEventRecord(st.ev_comp[c], cc->stream));
+			HIPCHK(obs, hipStreamWaitEvent(obs->stream, st.ev_comp[c], 0));
+		}
+	}
+	return gpemu_calib_eval_dev(obs, h, st.mean, st.var, h, st.stat, st.worst);
+}
+
+extern "C" int gpemu_calib_sample(gpemu_ctx *const *comp, int nr, gpemu_ctx *obs, const gpemu_sample_args *args, const double *x0,
+                                  double *trace_x, double *trace_lp, double *x_end, double *lp_end, int *naccept, int *nrec_out)
+{
+	if (nrec_out) *nrec_out = 0;
+	if (!obs) return GPEMU_ERR_ARG;
+	if (!comp || !args || !x0 || !x_end || !lp_end || !naccept || !nrec_out || nr < 1)
+		return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: bad argument");
+	for (int c = 0; c < nr; c++)
+		if (!comp[c]) return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: bad argument");
+	const int W = args->nwalkers, h = W / 2;
+	if (W < 2 || (W & 1) || args->nsteps < 1 || args->burn < 0 || args->thin < 1 || !(args->a > 1.0) || !std::isfinite(args->a))
+		return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: bad argument");
+	for (int c = 0; c < nr; c++)
+		if (!comp[c]->pred_ready) return fail(obs, GPEMU_ERR_STATE, "gpemu_calib_sample: a component has no prediction set-up");
+	const int d = comp[0]->d;
+	for (int c = 0; c < nr; c++) {
+		if (comp[c]->device != obs->device) return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: the contexts are on different devices (not built)");
+		if (comp[c]->d != d) return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: the components differ in d");
+	}
+	if (h < d + 1) return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: each half of the walkers needs at least d + 1 of them");
+	if (!obs->calib_nt) return fail(obs, GPEMU_ERR_STATE, "gpemu_calib_setup has not been called");
+	if (obs->calib_nr != nr) return fail(obs, GPEMU_ERR_STATE, "gpemu_calib_sample: the calibration set-up has another number of components");
+	if (obs->sample.prior_d != d) return fail(obs, GPEMU_ERR_STATE, "gpemu_sample_set_prior has not been called for this d");
+	HIPCHK(obs, hipSetDevice(obs->device));
+
+	// which global steps are recorded: burn and thin count global steps
+	const unsigned long long g0 = args->first_step, thin = (unsigned long long)args->thin, burn = (unsigned long long)args->burn;
+	auto recorded = [&](unsigned long long g) { return g >= burn && (g + 1) % thin == 0; };
+	int nrec = 0;
+	for (int t = 0; t < args->nsteps; t++) nrec += recorded(g0 + (unsigned long long)t);
+	const bool keep = (trace_x || trace_lp) && nrec > 0;
+	const size_t wd = (size_t)W * d;
+	size_t chunk = obs->sample.chunk_records > 0 ? (size_t)obs->sample.chunk_records
+	                                             : std::max<size_t>(1, SAMPLE_CHUNK_BYTES / (sizeof(double) * (wd + W)));
+	chunk = std::min(chunk, (size_t)std::max(nrec, 1));
+
+	// the state: allocated once per call shape, nothing inside the step loop
+	SampleState &st = obs->sample;
+	int rc = grow(obs, st.x, wd);
+	if (!rc) rc = grow(obs, st.lp, W);
+	if (!rc) rc = grow(obs, st.nacc, W);
+	if (!rc) rc = grow(obs, st.y, (size_t)h * d);
+	if (!rc) rc = grow(obs, st.aux, W);
+	if (!rc) rc = grow(obs, st.mean, (size_t)nr * h);
+	if (!rc) rc = grow(obs, st.var, (size_t)nr * h);
+	if (!rc) rc = grow(obs, st.stat, 5 * (size_t)h);
+	if (!rc) rc = grow(obs, st.worst, h);
+	if (!rc && keep) rc = grow(obs, st.trx, chunk * wd);
+	if (!rc && keep) rc = grow(obs, st.trlp, chunk * W);
+	if (rc) return rc;
+	if (!st.ev_obs) HIPCHK(obs, hipEventCreateWithFlags(&st.ev_obs, hipEventDisableTiming));
+	while ((int)st.ev_comp.size() < nr) {
+		hipEvent_t e;
+		HIPCHK(obs, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		st.ev_comp.push_back(e);
+	}
+
+	// start-up: lp of x0 in two half-batches through the same two entries, then the one host wait before the steps
+	HIPCHK(obs, hipMemcpyAsync(st.x, x0, wd * sizeof(double), hipMemcpyHostToDevice, obs->stream));
+	HIPCHK(obs, hipMemsetAsync(st.nacc, 0, (size_t)W * sizeof(int), obs->stream));
+	for (int half = 0; half < 2; half++) {
+		const double *xh = st.x + (size_t)half * h * d;
+		if ((rc = sample_loglik(comp, nr, obs, h, xh))) return rc;
+		if ((rc = gpemu_sample_logpost_dev(obs, h, d, xh, st.stat + h, st.lp + (size_t)half * h))) return rc;
+	}
+	HIPCHK(obs, hipMemcpyAsync(lp_end, st.lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, obs->stream));
+	HIPCHK(obs, hipStreamSynchronize(obs->stream));
+	for (int k = 0; k < W; k++)
+		if (!std::isfinite(lp_end[k])) return fail(obs, GPEMU_ERR_ARG, "gpemu_calib_sample: a start has a non-finite log posterior");
+
+	size_t filled = 0, done = 0;    // records staged in the chunk, records already copied out
+	auto flush = [&]() -> int {
+		if (trace_x) HIPCHK(obs, hipMemcpyAsync(trace_x + done * wd, st.trx, filled * wd * sizeof(double), hipMemcpyDeviceToHost, obs->stream));
+		if (trace_lp) HIPCHK(obs, hipMemcpyAsync(trace_lp + done * W, st.trlp, filled * W * sizeof(double), hipMemcpyDeviceToHost, obs->stream));
+		HIPCHK(obs, hipStreamSynchronize(obs->stream));
+		done += filled;
+		filled = 0;
+		return GPEMU_OK;
+	};
+	for (int t = 0; t < args->nsteps; t++) {
+		const unsigned long long g = g0 + (unsigned long long)t;
+		for (int half = 0; half < 2; half++) {
+			if ((rc = gpemu_sample_propose_dev(obs, W, d, half, g, args->seed, args->a, st.x, st.y, st.aux))) return rc;
+			if ((rc = sample_loglik(comp, nr, obs, h, st.y))) return rc;
+			if ((rc = gpemu_sample_accept_dev(obs, W, d, half, g, args->seed, st.y, st.aux, st.stat + h, st.x, st.lp, st.nacc))) return rc;
+		}
+		if (keep && recorded(g)) {
+			HIPCHK(obs, hipMemcpyAsync(st.trx + filled * wd, st.x, wd * sizeof(double), hipMemcpyDeviceToDevice, obs->stream));
+			HIPCHK(obs, hipMemcpyAsync(st.trlp + filled * W, st.lp, (size_t)W * sizeof(double), hipMemcpyDeviceToDevice, obs->stream));
+			if (++filled == chunk && (rc = flush())) return rc;
+		}
+	}
+	if (filled && (rc = flush())) return rc;
+	HIPCHK(obs, hipMemcpyAsync(x_end, st.x, wd * sizeof(double), hipMemcpyDeviceToHost, obs->stream));
+	HIPCHK(obs, hipMemcpyAsync(lp_end, st.lp, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, obs->stream));
+	HIPCHK(obs, hipMemcpyAsync(naccept, st.nacc, (size_t)W * sizeof(int), hipMemcpyDeviceToHost, obs->stream));
+	HIPCHK(obs, hipStreamSynchronize(obs->stream));
+	*nrec_out = nrec;
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
 // profiling
 // ---------------------------------------------------------------------------
 extern "C" int gpemu_prof_begin(gpemu_ctx *ctx, int cls)

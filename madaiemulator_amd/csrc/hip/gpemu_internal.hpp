@@ -214,6 +214,37 @@ struct PredPending {
 	int M = 0;
 };
 
+// The ensemble sampler's state on a context (gpemu_sample_* / gpemu_calib_sample): the owner of everything
+// those entries keep.  prior: the per-coordinate table of gpemu_sample_set_prior (kernels_sample.hip has its layout; prior_d > 0:
+// set), independent of the model as the calibration table is.  The rest belongs to gpemu_calib_sample, sized by the call's
+// shape (W, d, nr, trace records of a chunk) and reused while it fits: x, lp, nacc the ensemble; y, aux a half-step's proposals;
+// mean, var (nr rows of W / 2), stat, worst its evaluation; trx, trlp the staged trace records; ev_obs: the component streams
+// behind the proposal, ev_comp[c]: this stream behind component c's sweep.  chunk_records: the test hook's bound (0: default).
+struct SampleState {
+	int prior_d = 0;
+	DevBuf<double> prior;
+	DevBuf<double> x, lp, y, aux, mean, var, stat, trx, trlp;
+	DevBuf<int> nacc, worst;
+	hipEvent_t ev_obs = nullptr;
+	std::vector<hipEvent_t> ev_comp;
+	int chunk_records = 0;
+	SampleState() = default;
+	SampleState(const SampleState &) = delete;
+	SampleState &operator=(const SampleState &) = delete;
+	// the run's buffers and events (the caller has waited for the stream); the prior stays
+	void release_run()
+	{
+		for (auto *b : {&x, &lp, &y, &aux, &mean, &var, &stat, &trx, &trlp}) b->reset();
+		nacc.reset(); worst.reset();
+		if (ev_obs) (void)hipEventDestroy(ev_obs);
+		for (auto e : ev_comp) (void)hipEventDestroy(e);
+		ev_obs = nullptr;
+		ev_comp.clear();
+	}
+	void release() { release_run(); prior.reset(); prior_d = 0; }
+	~SampleState() { release(); }
+};
+
 } // namespace gpemu
 
 struct gpemu_ctx {
@@ -348,6 +379,7 @@ struct gpemu_ctx {
 	gpemu::DevBuf<double> dCalibTab, dCalibIO;
 	gpemu::DevBuf<int> dCalibIdx, dCalibCnt;
 	gpemu::PinnedBuf<int> hCalibCnt;
+	gpemu::SampleState sample;   // the ensemble sampler (gpemu_sample_*, gpemu_calib_sample)
 	// the input measure of the sensitivity entries per coordinate (gpemu_sens_set_measure): GPEMU_MEASURE_*,
 	// all uniform from gpemu_set_model on; kept by gpemu_set_training, the prediction set-ups and gpemu_sens_release
 	int sens_kind[GPEMU_MAX_PARAMS] = {};
@@ -580,5 +612,16 @@ hipError_t launch_calib_grad(hipStream_t s, const double *tab, int nr, int M, in
 int calib_select_blocks(int M);
 hipError_t launch_calib_gather(hipStream_t s, const double *stat, const int *worst, int M, int count, const int *idx, double *out, int *wout);
 hipError_t launch_calib_select(hipStream_t s, const double *stat, int M, double cut_chi2, int level, double cut_I, int *counts, int *idx);
+
+// ---- kernels_sample.hip: the ensemble sampler's launches
+// prior: SAMPLE_PRIOR_ROWS rows of GPEMU_MAX_PARAMS, filled on the host by sample_fill_prior (kind may be null: all uniform);
+// x: W x d, y: W / 2 x d, aux: (d - 1) log z of the W / 2 active walkers, then the log prior of their proposals
+constexpr int SAMPLE_PRIOR_ROWS = 4;
+void sample_fill_prior(int d, const int *kind, const double *lo, const double *hi, double *tab);
+hipError_t launch_sample_propose(hipStream_t s, const double *prior, int W, int d, int half, unsigned long long step,
+                                 unsigned long long seed, double a, const double *x, double *y, double *aux);
+hipError_t launch_sample_accept(hipStream_t s, int W, int d, int half, unsigned long long step, unsigned long long seed, const double *y,
+                                const double *aux, const double *loglik, double *x, double *lp, int *nacc);
+hipError_t launch_sample_logpost(hipStream_t s, const double *prior, int M, int d, const double *x, const double *loglik, double *lp);
 
 } // namespace gpemu

@@ -201,6 +201,32 @@ void emulator::QueryEmulatorLogLikelihoodGradient(const std::vector<std::vector<
 	}
 }
 
+double emulator::SamplePosterior(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<int> &kind, int Walkers,
+                                 int Steps, int Burn, int Thin, unsigned long long Seed, double Stretch,
+                                 const std::vector<std::vector<double> > &Starts, std::vector<std::vector<double> > &Samples,
+                                 std::vector<double> &LogPosteriors, std::vector<std::vector<double> > &Summary)
+{
+	need_observations("SamplePosterior", the_observations);
+	const size_t d = (size_t)number_params;
+	if (lo.size() != d || hi.size() != d || (!kind.empty() && kind.size() != d) || (!Starts.empty() && (int)Starts.size() != Walkers)) {
+		std::cerr << "Error::SamplePosterior called with a prior that has not one entry per parameter, or with starts that are not one per walker" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	gpemu_host_sample_args args = {Walkers, Steps, Burn, Thin, Seed, 0ull, Stretch};
+	const size_t nrec = (size_t)gpemu_host_sample_nrec(&args), W = Walkers > 0 ? (size_t)Walkers : 0;
+	std::vector<double> flat = flatten("SamplePosterior", Starts, number_params);
+	std::vector<double> tx(nrec * W * d + 1), tl(nrec * W + 1), sm(6 * d);
+	double accept = 0.0;
+	emulate_sample_posterior_multi(the_emulator, the_observations, lo.data(), hi.data(), kind.empty() ? NULL : kind.data(), &args,
+	                               Starts.empty() ? NULL : flat.data(), tx.data(), tl.data(), NULL, &accept, sm.data());
+	Samples.assign(nrec * W, std::vector<double>(d));
+	for (size_t r = 0; r < nrec * W; r++) Samples[r].assign(tx.begin() + r * d, tx.begin() + (r + 1) * d);
+	LogPosteriors.assign(tl.begin(), tl.begin() + nrec * W);
+	Summary.assign(6, std::vector<double>(d));
+	for (size_t s = 0; s < 6; s++) Summary[s].assign(sm.begin() + s * d, sm.begin() + (s + 1) * d);
+	return accept;
+}
+
 // the box of the two sensitivity methods, checked to have number_params entries on either side
 static void check_box(const char *method, const std::vector<double> &lo, const std::vector<double> &hi, int number_params)
 {

@@ -121,6 +121,16 @@ public:
 	// for bit, Gradients[q][j] its derivative in the units of xpoints.  Requires SetObservations.
 	void QueryEmulatorLogLikelihoodGradient(const std::vector<std::vector<double> > &xpoints, std::vector<double> &LogLikelihoods,
 	                                        std::vector<std::vector<double> > &Gradients);
+	// posterior samples of the parameters by the ensemble sampler on the device (libemu.h: emulate_sample_posterior_multi), after
+	// SetObservations.  lo, hi, kind: the prior per parameter (kind empty: all uniform on [lo, hi]; kind[j] = 1: Gaussian with mean
+	// lo[j] and standard deviation hi[j]).  Starts: Walkers rows of number_params, or empty: drawn from the prior.  Samples[r] is
+	// the r-th recorded sample (recorded step r / Walkers, walker r % Walkers), LogPosteriors[r] its log posterior; Summary has
+	// six rows of number_params: mean, standard deviation, the 2.5 / 50 / 97.5 % quantiles, the integrated autocorrelation time
+	// of the ensemble mean.  Returns the accepted fraction of the proposals.
+	double SamplePosterior(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<int> &kind, int Walkers,
+	                       int Steps, int Burn, int Thin, unsigned long long Seed, double Stretch,
+	                       const std::vector<std::vector<double> > &Starts, std::vector<std::vector<double> > &Samples,
+	                       std::vector<double> &LogPosteriors, std::vector<std::vector<double> > &Summary);
 	void getEmulatorPCA(std::vector<double> *pca_evals, std::vector<std::vector<double> > *pca_evecs,
 	                    std::vector<double> *pca_mean);
 	int getRegressionOrder(void) { return the_model->regression_order; }

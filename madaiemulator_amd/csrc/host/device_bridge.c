@@ -1503,6 +1503,31 @@ void gpemu_host_calib_block(const void *key, emulator_struct **es, int nr, int n
 	free(xq); free(en);
 }
 
+/* The ensemble sampler over the observation set's log likelihood and a per-parameter prior (gpemu_calib_sample):
+ * the prior goes onto the observation set's context, the components' contexts run their sweeps on their own streams.  Every
+ * component must sit on the observation set's device: several devices are not built, a message and the layer's exit. */
+void gpemu_host_calib_sample(const void *key, emulator_struct **es, int nr, int d, const int *kind, const double *lo, const double *hi,
+                             const gpemu_host_sample_args *args, const double *x0, double *trace_x, double *trace_lp, double *x_end,
+                             double *lp_end, int *naccept, int *nrec)
+{
+	static const char who[] = "emulate_sample_posterior_multi";
+	struct entry *ob = lookup(key, 0);
+	if (!ob) gpemu_host_fatal("%s: the observation set was not made by alloc_observations\n", who);
+	gpemu_ctx **comp = (gpemu_ctx **)malloc(sizeof(gpemu_ctx *) * (size_t)nr);
+	for (int c = 0; c < nr; c++) {
+		comp[c] = entry_of(es[c], who)->ctx;
+		if (gpemu_ctx_device(comp[c]) != gpemu_ctx_device(ob->ctx))
+			gpemu_host_fatal("%s: component %d sits on device %d, the observation set on device %d: sampling with components on "
+			                 "several devices is not built\n", who, c, gpemu_ctx_device(comp[c]), gpemu_ctx_device(ob->ctx));
+	}
+	int rc = gpemu_sample_set_prior(ob->ctx, d, kind, lo, hi);
+	if (rc) die(ob->ctx, rc, who);
+	const gpemu_sample_args ga = {args->nwalkers, args->nsteps, args->burn, args->thin, args->seed, args->first_step, args->a};
+	rc = gpemu_calib_sample(comp, nr, ob->ctx, &ga, x0, trace_x, trace_lp, x_end, lp_end, naccept, nrec);
+	if (rc) die(ob->ctx, rc, who);
+	free(comp);
+}
+
 /* One block of np points through every component's two gradient sweeps and the gradient launch (gpemu_calib_grad_dev, DESIGN.md
  * 4.19), structured like gpemu_host_calib_block.  The points go up once per device; component c runs gpemu_predict_var_grad_dev
  * (m_c, v_c, dv_c/dx) and gpemu_predict_mean_grad_dev (dm_c/dx) into its rows and blocks of component-major buffers on the

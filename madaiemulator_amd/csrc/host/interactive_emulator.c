@@ -36,6 +36,9 @@ struct cmdLineOpts {
 	double cutI, cutChi2;
 	int level, gradientFlag;
 	int best, bestGiven;
+	int walkers, steps, burn, thin, walkersGiven, burnGiven;
+	unsigned long long seed;
+	double stretch;
 	int folds, foldsGiven, grid, uncertainty, pairs, surface, surfJ, surfK;
 };
 
@@ -87,6 +90,15 @@ static const char useage[] =
 	"      integrated posterior variance summed over the outputs if the model were run there, and that integrated variance as it\n"
 	"      is now.  --best=K prints the K candidates with the largest drop, largest first, ties in input order.  The measure as for\n"
 	"      `sensitivity`.  Power-exponential covariance only)\n"
+	"or\n"
+	"  interactive_emulator sample MODEL_SNAPSHOT_FILE --observations=FILE [--box=FILE | --prior=FILE] [--walkers=W] [--steps=T] [--burn=B] [--thin=K] [--seed=S] [--stretch=a] [--quiet]\n"
+	"      (posterior samples of the parameters given the observations of FILE (the format of `implausibility`), by the affine-invariant\n"
+	"      ensemble sampler on the device.  The prior as the measure of `sensitivity`: --box, --prior, or uniform on the range of the\n"
+	"      design.  W walkers (even, W / 2 >= d + 1; default max(64, 4 d)) start from draws of the prior and take T steps (default\n"
+	"      1000); from step B on (default T / 4) every K-th step (default 1) is recorded.  stdout: one line per recorded sample, the d\n"
+	"      parameters and the log posterior; stderr: the accepted fraction and per parameter mean, standard deviation, the 2.5 / 50 /\n"
+	"      97.5 % quantiles and the integrated autocorrelation time.  --seed=S (default 1) picks the random numbers, --stretch=a > 1\n"
+	"      (default 2) the scale of the stretch move)\n"
 	"\n"
 	"INPUT_MODEL_FILE can be \"-\" to read from standard input.\n"
 	"\n"
@@ -877,6 +889,71 @@ static int print_thetas(struct cmdLineOpts *o)
 	return 0;
 }
 
+/* Posterior samples of the parameters given observations (emulate_sample_posterior_multi; the reference stops at the toy
+ * Metropolis steps of r-fns/metropolis.R).  Every refusal is decided on the host before a device is touched.  stdout: one line per
+ * recorded sample -- recorded step after recorded step, walker after walker --, the d parameters and the log posterior in %.17g.
+ * stderr: the summary, and a warning where the recorded steps are fewer than 50 integrated autocorrelation times. */
+static int sample(struct cmdLineOpts *o)
+{
+	if (!o->obsfile) return perr("sample needs --observations=FILE");
+	if (o->pcaOutputFlag) return perr("--pca_output and --observations exclude each other: observations live in observable space");
+	if (o->boxfile && o->priorfile) return perr("--box=FILE and --prior=FILE exclude each other");
+	if (o->walkersGiven && (o->walkers < 2 || (o->walkers & 1))) return perr("--walkers=W needs an even W >= 2");
+	if (!(o->stretch > 1.0) || !isfinite(o->stretch)) return perr("--stretch=a needs a finite a > 1");
+	if (o->steps < 1 || o->thin < 1 || (o->burnGiven && o->burn < 0)) return perr("--steps=T needs T >= 1, --thin=K K >= 1, --burn=B B >= 0");
+	FILE *fp = fopen(o->statefile, "r");
+	if (!fp) return perr("Error opening file");
+	multi_modelstruct *model = load_multi_modelstruct(fp);
+	fclose(fp);
+	const int d = model->nparams;
+	const int W = o->walkersGiven ? o->walkers : (4 * d > 64 ? 4 * d : 64);
+	if (W / 2 < d + 1) {
+		fprintf(stderr, "--walkers=%d for %d parameters: each half of the walkers needs at least d + 1 of them, W >= %d\n", W, d, 2 * (d + 1));
+		return EXIT_FAILURE;
+	}
+	struct obs_file of;
+	if (!read_observation_file(o->obsfile, model->nt, &of)) return EXIT_FAILURE;
+	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
+	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
+	{
+		const int rc = read_measure(o, model, lo, hi, kind);
+		if (rc) return rc;
+	}
+	gpemu_host_sample_args args = {W, o->steps, o->burnGiven ? o->burn : o->steps / 4, o->thin, o->seed, 0ull, o->stretch};
+	const size_t nrec = (size_t)gpemu_host_sample_nrec(&args);
+	gpemu_host_warm_start();
+	setenv("GPEMU_SKIP_CINVERSE", "1", 0);               /* (as interactive_mode: nobody here reads emulator_struct.cinverse) */
+	multi_emulator *emu = alloc_multi_emulator(model);
+	gpemu_observations *obs = alloc_observations(model, of.z, of.has_cov ? NULL : of.sd, of.has_cov ? of.cov : NULL, of.rel);
+	double *tx = (double *)malloc(sizeof(double) * (nrec * (size_t)W * d + 1)), *tl = (double *)malloc(sizeof(double) * (nrec * (size_t)W + 1));
+	double *sm = (double *)malloc(sizeof(double) * 6 * (size_t)d), accept = 0.0;
+	emulate_sample_posterior_multi(emu, obs, lo, hi, kind, &args, NULL, tx, tl, NULL, &accept, sm);
+	FILE *out = stdout;
+	if (!o->quietFlag) {
+		fprintf(out, "#");
+		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
+		fprintf(out, " log_posterior\n");
+	}
+	for (size_t r = 0; r < nrec * (size_t)W; r++) {
+		for (int j = 0; j < d; j++) fprintf(out, "%.17g ", tx[r * d + j]);
+		fprintf(out, "%.17g\n", tl[r]);
+	}
+	fflush(out);
+	fprintf(stderr, "# sample: %d walkers, %d steps, %zu recorded (burn %d, thin %d), seed %llu, accepted fraction %.6g\n", W, args.nsteps, nrec,
+	        args.burn, args.thin, args.seed, accept);
+	for (int j = 0; j < d; j++) {
+		fprintf(stderr, "# param_%d mean %.17g sd %.17g q2.5 %.17g q50 %.17g q97.5 %.17g tau %.6g\n", j, sm[j], sm[d + j], sm[2 * d + j],
+		        sm[3 * d + j], sm[4 * d + j], sm[5 * d + j]);
+		if (nrec && (double)nrec < 50.0 * sm[5 * d + j])
+			fprintf(stderr, "# warning: param_%d: %zu recorded steps are fewer than 50 autocorrelation times (%.6g): run longer\n", j, nrec,
+			        50.0 * sm[5 * d + j]);
+	}
+	free(tx); free(tl); free(sm); free(lo); free(hi); free(kind);
+	free_observations(obs);
+	free_multi_emulator(emu);
+	return 0;
+}
+
 static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 {
 	static const char *optString = "r:c:v:zqh?";
@@ -907,10 +984,15 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"gradient", no_argument, NULL, 1017},
 		/* design: only the K candidates that gain most */
 		{"best", required_argument, NULL, 1018},
+		/* sample: the ensemble, the run and its random numbers */
+		{"walkers", required_argument, NULL, 1019},           {"steps", required_argument, NULL, 1020},
+		{"burn", required_argument, NULL, 1021},              {"thin", required_argument, NULL, 1022},
+		{"seed", required_argument, NULL, 1023},              {"stretch", required_argument, NULL, 1024},
 		{NULL, no_argument, NULL, 0}};
 	struct cmdLineOpts *o = (struct cmdLineOpts *)calloc(1, sizeof *o);
 	o->pca_variance = 0.99;
 	o->cutI = 3.0; o->cutChi2 = INFINITY; o->level = 1;
+	o->steps = 1000; o->thin = 1; o->seed = 1; o->stretch = 2.0;
 	int idx, opt;
 	while ((opt = getopt_long(argc, argv, optString, longOpts, &idx)) != -1) {
 		switch (opt) {
@@ -948,6 +1030,12 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1016: o->cutChi2 = !strcmp(optarg, "inf") ? INFINITY : atof(optarg); break;
 		case 1017: o->gradientFlag = 1; break;
 		case 1018: o->best = atoi(optarg); o->bestGiven = 1; break;
+		case 1019: o->walkers = atoi(optarg); o->walkersGiven = 1; break;
+		case 1020: o->steps = atoi(optarg); break;
+		case 1021: o->burn = atoi(optarg); o->burnGiven = 1; break;
+		case 1022: o->thin = atoi(optarg); break;
+		case 1023: o->seed = strtoull(optarg, NULL, 0); break;
+		case 1024: o->stretch = atof(optarg); break;
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;
@@ -983,6 +1071,7 @@ int main(int argc, char **argv)
 	else if (!strcmp(o->run_mode, "sensitivity")) rc = sensitivity(o);
 	else if (!strcmp(o->run_mode, "implausibility")) rc = implausibility(o);
 	else if (!strcmp(o->run_mode, "design")) rc = design(o);
+	else if (!strcmp(o->run_mode, "sample")) rc = sample(o);
 	else { free(o); return perr(useage); }
 	free(o);
 	return rc;

@@ -465,6 +465,39 @@ void gpemu_host_calib_setup(const void *key, int nt, int nr, const double *ybar,
                             const double *sd, const double *rel);
 void gpemu_host_calib_block(const void *key, emulator_struct **es, int nr, int np, int d, const double *q, int select, double cut_chi2,
                             int level, double cut_I, double *stat, int *worst, int *idx, int *nkeep);
+/* extension: posterior samples of the parameters by the affine-invariant ensemble sampler on the device (gpemu_calib_sample in
+ * gpemu.h; sample.c).  Log posterior = the joint log density of obs at the point + the log of an independent
+ * prior per parameter: lo, hi, kind (nparams each) in the convention of emulate_sensitivity_measure -- kind NULL: all uniform on
+ * [lo, hi]; for GPEMU_MEASURE_GAUSS (1) lo is the mean and hi the standard deviation.  args: the run (nwalkers even, nwalkers / 2
+ * >= nparams + 1; nsteps; burn and thin count global steps; seed; first_step; the stretch scale a > 1).  x0: nwalkers x nparams
+ * starts, or NULL: drawn from the prior with the sampler's generator at counters (k, j, 0, 2) for parameter j of walker k --
+ * uniform: lo + u1 (hi - lo); Gaussian: mean + sd sqrt(-2 ln u1) cos(2 pi u2) -- (gpemu_host_sample_starts, no device).
+ * Outputs, in the units of the points: trace_x (nrec x nwalkers x nparams) and trace_lp (nrec x nwalkers), nrec =
+ * gpemu_host_sample_nrec(args) records; x_end (nwalkers x nparams, may be NULL), what a following call with first_step =
+ * first_step + nsteps starts from; *accept_out the accepted fraction of the call's proposals; summary_out (may be NULL) 6 rows
+ * of nparams over the recorded samples: mean, standard deviation (divisor n), the 2.5 / 50 / 97.5 % quantiles (linear
+ * interpolation between order statistics, numpy's default), and the integrated autocorrelation time tau of the ensemble-mean
+ * series in recorded steps.  gpemu_host_autocorr_time: tau(M) = 1 + 2 sum_{t=1..M} rho(t) with Sokal's window, the smallest
+ * M >= 5 tau(M) (the last M when none is); returns 0, or 1 (tau = NaN) for a NULL pointer or n < 1; a constant series has tau 1.
+ * A start with a non-finite log posterior, a bad prior or run, an observation set of another model: a message and the layer's
+ * exit; so do components on different devices (not built). */
+/* (the fields of gpemu_sample_args in gpemu.h, which this header does not need) */
+typedef struct gpemu_host_sample_args {
+	int nwalkers, nsteps, burn, thin;
+	unsigned long long seed, first_step;
+	double a;
+} gpemu_host_sample_args;
+int gpemu_host_sample_nrec(const gpemu_host_sample_args *args);
+void gpemu_host_sample_starts(unsigned long long seed, int nwalkers, int nparams, const int *kind, const double *lo, const double *hi,
+                              double *x0_out);
+int gpemu_host_autocorr_time(const double *series, int n, double *tau);
+void emulate_sample_posterior_multi(multi_emulator *emu, gpemu_observations *obs, const double *lo, const double *hi, const int *kind,
+                                    const gpemu_host_sample_args *args, const double *x0, double *trace_x, double *trace_lp,
+                                    double *x_end, double *accept_out, double *summary_out);
+/* (device_bridge.c: the prior onto the observation set's context, then the run) */
+void gpemu_host_calib_sample(const void *key, emulator_struct **es, int nr, int d, const int *kind, const double *lo, const double *hi,
+                             const gpemu_host_sample_args *args, const double *x0, double *trace_x, double *trace_lp, double *x_end,
+                             double *lp_end, int *naccept, int *nrec);
 /* extension: leave-one-out at every training point of a multi-output emulator; outputs are nmodel_points x nr in PCA space,
  * or nmodel_points x nt in observable space (every component's leave-one-out result through the same back-projection) */
 void emulate_loo_multi(multi_emulator *emu, int pca_space, double *mean_out, double *var_out);
