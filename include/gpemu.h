@@ -522,14 +522,61 @@ int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int 
  * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL ctx, lo, hi, xq or gain and npoints < 1, whatever
  * the state; GPEMU_ERR_STATE without a prediction set-up; then GPEMU_ERR_ARG for a Matern model, a non-finite bound, hi_l <= lo_l
  * or a Gaussian coordinate with sd <= 0.
- * Not built: greedy batches of K runs with the covariance downdated between picks; the gradient of gain with respect to x* and
- * any optimiser over it; Matern kernels; gain for a target other than the IMSE (Sobol-index uncertainty, a calibration region);
+ * Not built: the gradient of gain with respect to x* and any optimiser over it (greedy batches: gpemu_design_batch below);
+ * Matern kernels; gain for a target other than the IMSE (Sobol-index uncertainty, a calibration region);
  * correlated Gaussian measures. */
 int gpemu_design_gain(gpemu_ctx *ctx, const double *lo, const double *hi /* d each, host */, int npoints,
                       const double *xq /* npoints*d host */, double *gain /* npoints */, double *num /* npoints or NULL */,
                       double *var /* npoints or NULL */);
 int gpemu_design_gain_dev(gpemu_ctx *ctx, const double *lo, const double *hi /* HOST */, int npoints, const double *xq_dev,
                           double *gain_dev, double *num_dev /* or NULL */, double *var_dev /* or NULL */);
+
+/* ---- greedy batches of K runs: conditional IMSE gains, picks on the device -----------------
+ * The top K candidates of gpemu_design_gain sit next to each other: the first run there removes most of what the others would
+ * gain.  These entries pick nbatch of npoints candidates one after the other, each the arg-max of the gain CONDITIONAL on the
+ * picks before it, without a refit.  With Sigma(q, s) = c*(x_q, x_s) and G(q, s) = E_x[c*(x, x_q) c*(x, x_s)] (both from the
+ * rows a_q, T_q, w_q of the first pass and a handful of vectors of s; G(q, q) = num_q, Sigma(q, q) = var_q - nugget) the state
+ * per candidate is lambda_q, mu_q in R^j after j picks, and a j x j matrix E shared by all candidates:
+ *   v_S(q) = var_q - |lambda_q|^2,   num_S(q) = num_q - 2 lambda_q . mu_q + lambda_q^T E lambda_q,   gain_S(q) = num_S(q) / v_S(q)
+ * (0 where v_S(q) rounds to <= 0); the pick s is the arg-max of sum_c weight_c gain_S,c(q) over the candidates not yet picked,
+ * ties to the lowest index, NaN never preferred; then with rho = sqrt(v_S(s))
+ *   lambda_q,new = (Sigma(q, s) - lambda_q . lambda_s) / rho,   mu_q,new = (G(q, s) - mu_q . lambda_s) / rho,
+ *   E_i,new = (mu_s,i - (E lambda_s)_i) / rho,   E_new,new = num_S(s) / v_S(s).
+ * A pick whose v_S rounds to <= 0 changes nothing (its lambda, mu and column of E are 0).  pick_gain[j] is the further drop of
+ * the (weighted) IMSE by pick j: the sum of the first j equals s_all(design) - s_all(design + the first j picks), the hyper-
+ * parameters as they are.  The contexts are the independent components of a multi-output emulator on one design (as
+ * gpemu_sens_pairs requires of two contexts: same device, design, order and input measure); one run observes all of them, each
+ * keeps its own state, and weight (NULL: all 1) weighs their gains.  Where fewer than nbatch candidates have a positive gain
+ * the picks go on by the same rule (among equal gains the lowest index not yet picked).
+ * Outputs: pick[j] the index of pick j, pick_gain[j] its weighted gain, pick_gain_ctx[j * nctx + c] (may be NULL) the
+ * contexts' own, gain_first[q] (may be NULL) the weighted gain before any pick -- for one context and weight 1 the bits of
+ * gpemu_design_gain -- and gain_last[q] (may be NULL) the weighted gain conditional on all nbatch picks, -inf for a picked q.
+ * How it runs, per context on its own stream: one block of gpemu_design_gain_dev (its launches, its bits), a launch for the rows
+ * of w; per pick a gather (the pick's a, w, fresh unclamped k rows, b, h, T^HK, HK*, Hm b, lambda, the new column of E), the
+ * column kernel (the rows of a, T^K and w of every candidate streamed once for the four dots a_q . k_s, a_q . w_s, w_q . a_s,
+ * T^K_q . a_s: 24 M' Np bytes, bandwidth-bound), and the update (one wave per candidate: the short terms, the new lambda and
+ * mu, v_S, num_S and gain, the quadratic form carried forward in O(j)).  The arg-max is one launch on ctxs[0]'s stream, which
+ * waits on the other streams by events; they wait on its event.  The host takes no part between picks.  No atomics, no
+ * workgroup waits for another; every sum has one order: two calls return the same bits, so do the host and _dev entries, the
+ * first j picks of a longer batch and a batch of j, and contexts set up by gpemu_predict_setup_batch.
+ * Memory per context beyond gpemu_design_gain's: 8 M' Np bytes for w, 16 M nbatch for lambda and mu, 512 KiB for E,
+ * 8 (3 Np + 1024 + 7 M) for the gather, the dots and the running state.  gpemu_sens_release frees it.
+ * Limits: 1 <= npoints <= 16 384 (one block), 1 <= nbatch <= min(npoints, 256).
+ * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL ctxs, ctxs[c], lo, hi, xq, pick or pick_gain,
+ * nctx < 1 and counts out of range, whatever the state; GPEMU_ERR_STATE for a context without a prediction set-up; then
+ * GPEMU_ERR_ARG for a Matern model, a bad box, sd <= 0, differing designs, orders, measures or devices, a context listed
+ * twice, a negative or non-finite weight.
+ * Not built: more than one block of candidates; exchange or other non-greedy criteria; the gradient of the gain; Matern kernels. */
+int gpemu_design_batch(gpemu_ctx *const *ctxs, int nctx, const double *weight /* nctx host, or NULL: all 1 */, const double *lo,
+                       const double *hi /* d each, host */, int npoints, const double *xq /* npoints*d host */, int nbatch,
+                       int *pick /* nbatch */, double *pick_gain /* nbatch: the weighted sum */,
+                       double *pick_gain_ctx /* nbatch*nctx or NULL */, double *gain_first /* npoints or NULL */,
+                       double *gain_last /* npoints or NULL */);
+/* the same with xq, pick, pick_gain, pick_gain_ctx, gain_first and gain_last in device memory; the results are complete behind
+ * ctxs[0]'s stream */
+int gpemu_design_batch_dev(gpemu_ctx *const *ctxs, int nctx, const double *weight /* HOST */, const double *lo, const double *hi /* HOST */,
+                           int npoints, const double *xq_dev, int nbatch, int *pick_dev, double *pick_gain_dev, double *pick_gain_ctx_dev,
+                           double *gain_first_dev, double *gain_last_dev);
 
 /* ---- second-order Sobol indices and interaction surfaces, in closed form -----------------
  * VT_j - V_j > 0 says that parameter j interacts with something; these entries say with which parameter, and what the
@@ -1094,6 +1141,9 @@ int gpemu_test_sens_post_state(gpemu_ctx *ctx, double *P /* N*N, both triangles 
  * what its third product, sweep and finish multiplied by; npoints: that block's candidates (a call of up to 16 384 has one
  * block).  GPEMU_ERR_STATE when no block of this size was the last. */
 int gpemu_test_design_state(gpemu_ctx *ctx, int npoints, double *a_out /* npoints*N */, double *b_out /* npoints*nreg */);
+/* the same for gpemu_design_batch: lambda and mu (npoints x nbatch each) and E (nbatch x nbatch) of this context's part in the
+ * last call, bit for bit; GPEMU_ERR_STATE where the last call had other sizes */
+int gpemu_test_design_batch_state(gpemu_ctx *ctx, int npoints, int nbatch, double *lam_out, double *mu_out, double *e_out);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

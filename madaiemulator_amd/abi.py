@@ -169,6 +169,10 @@ SYMBOLS = {
     "gpemu_design_gain": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpemu_design_gain_dev": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_test_design_state": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "gpemu_design_batch": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_void_p, _dp, _dp, _dp, _dp]),
+    "gpemu_design_batch_dev": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_test_design_batch_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpemu_sens_pairs": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp]),
     "gpemu_sens_pairs_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_pairs_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -287,6 +291,39 @@ def predict_setup_batch(ctxs, thetas):
     if rc not in (OK, ERR_NOT_PD, ERR_REGRESSION):
         raise GpemuError(rc, ctxs[0].L.gpemu_last_error(ctxs[0].h).decode())
     return beta, info, status, rc
+
+
+def design_batch(ctxs, lo, hi, Xq, nbatch, weight=None):
+    """gpemu_design_batch: nbatch greedy picks among the candidates Xq[M, d] for the contexts of one design (weight: one per context,
+    None: all 1) -> dict(pick[nbatch], pick_gain[nbatch], pick_gain_ctx[nbatch, nctx], gain_first[M], gain_last[M])"""
+    n, lead = len(ctxs), ctxs[0]
+    lo, hi = lead._box("design_batch", lo, hi)
+    Xq = _a(Xq).reshape(-1, lead.d)
+    M = Xq.shape[0]
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    w = None if weight is None else _a(weight).ravel()
+    if w is not None and w.size != n:
+        raise ValueError("design_batch: one weight per context")
+    pick = np.full(nbatch, -1, dtype=np.int32)
+    out = dict(pick=pick, pick_gain=np.empty(nbatch), pick_gain_ctx=np.empty((nbatch, n)), gain_first=np.empty(M), gain_last=np.empty(M))
+    rc = lead.L.gpemu_design_batch(hs, n, _po(w), _p(lo), _p(hi), M, _p(Xq), nbatch, pick.ctypes.data_as(C.c_void_p), _p(out["pick_gain"]),
+                                   _p(out["pick_gain_ctx"]), _p(out["gain_first"]), _p(out["gain_last"]))
+    if rc != OK:
+        raise GpemuError(rc, lead.L.gpemu_last_error(lead.h).decode())
+    return out
+
+
+def design_batch_dev(ctxs, lo, hi, M, xq_dev, nbatch, pick_dev, pick_gain_dev, pick_gain_ctx_dev=None, gain_first_dev=None,
+                     gain_last_dev=None, weight=None):
+    """lo, hi, weight: HOST; everything else device memory (results complete behind ctxs[0]'s stream)"""
+    n, lead = len(ctxs), ctxs[0]
+    lo, hi = lead._box("design_batch_dev", lo, hi)
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    w = None if weight is None else _a(weight).ravel()
+    rc = lead.L.gpemu_design_batch_dev(hs, n, _po(w), _p(lo), _p(hi), M, xq_dev, nbatch, pick_dev, pick_gain_dev, pick_gain_ctx_dev,
+                                       gain_first_dev, gain_last_dev)
+    if rc != OK:
+        raise GpemuError(rc, lead.L.gpemu_last_error(lead.h).decode())
 
 
 def _opt(x):
@@ -775,6 +812,12 @@ class Context:
         a, b = np.empty((M, self.N)), np.empty((M, self.nreg))
         self._chk(self.L.gpemu_test_design_state(self.h, M, _p(a), _p(b)))
         return a, b
+
+    def design_batch_state(self, M, nbatch):
+        """-> (lambda[M, nbatch], mu[M, nbatch], E[nbatch, nbatch]) of this context's part in the last design_batch, bit for bit"""
+        lam, mu, E = np.empty((M, nbatch)), np.empty((M, nbatch)), np.empty((nbatch, nbatch))
+        self._chk(self.L.gpemu_test_design_batch_state(self.h, M, nbatch, _p(lam), _p(mu), _p(E)))
+        return lam, mu, E
 
     def sens_pairs(self, lo, hi, other=None):
         """-> cov_pair[d (d - 1) / 2] of this context and `other` (default: itself) on one design"""

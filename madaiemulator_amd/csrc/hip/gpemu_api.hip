@@ -281,6 +281,10 @@ static void free_model(gpemu_ctx *ctx)
 		b->reset();
 	ctx->design_serial = 0;
 	ctx->design_mb = 0;
+	for (auto *b : {&ctx->dBatchW, &ctx->dBatchLam, &ctx->dBatchMu, &ctx->dBatchE, &ctx->dBatchSv, &ctx->dBatchDots, &ctx->dBatchSt, &ctx->dBatchTab,
+	                &ctx->dBatchIO})
+		b->reset();
+	ctx->batch_mb = ctx->batch_nb = 0;
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -2343,6 +2347,10 @@ extern "C" int gpemu_sens_release(gpemu_ctx *ctx)
 		b->reset();
 	ctx->design_serial = 0;
 	ctx->design_mb = 0;
+	for (auto *b : {&ctx->dBatchW, &ctx->dBatchLam, &ctx->dBatchMu, &ctx->dBatchE, &ctx->dBatchSv, &ctx->dBatchDots, &ctx->dBatchSt, &ctx->dBatchTab,
+	                &ctx->dBatchIO})
+		b->reset();
+	ctx->batch_mb = ctx->batch_nb = 0;
 	return GPEMU_OK;
 }
 
@@ -2683,6 +2691,183 @@ extern "C" int gpemu_test_design_state(gpemu_ctx *ctx, int npoints, double *a_ou
 	                             hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipMemcpy2DAsync(b_out, nreg * sizeof(double), ctx->dDesignB, 64 * sizeof(double), nreg * sizeof(double), (size_t)npoints,
 	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// greedy batches of nbatch runs (gpemu.h).  Per context, on its own stream: the first pass is one block of
+// gpemu_design_gain_dev, with num, var and gain landing in the running state (dBatchSt), then the rows of w; per pick the
+// gather, the column kernel and the update.  The arg-max over the weighted gains runs on ctxs[0]'s stream, which waits on the
+// other streams by events (each context's sens_ev); they wait on its event (ctxs[0]'s sens_ev2) before they read the pick.
+// The host takes no part between picks.
+// ---------------------------------------------------------------------------
+static int design_batch_check(gpemu_ctx *const *ctxs, int nctx, const double *weight, const double *lo, const double *hi, int npoints,
+                              const void *xq, int nbatch, const void *pick, const void *pick_gain, std::vector<SensBox> *bxs)
+{
+	if (!ctxs || nctx < 1 || !lo || !hi || !xq || !pick || !pick_gain) return GPEMU_ERR_ARG;
+	for (int c = 0; c < nctx; c++)
+		if (!ctxs[c]) return GPEMU_ERR_ARG;
+	if (npoints < 1 || npoints > PRED_BATCH_MAX || nbatch < 1 || nbatch > std::min(npoints, 256)) return GPEMU_ERR_ARG;
+	gpemu_ctx *lead = ctxs[0];
+	for (int c = 0; c < nctx; c++)
+		if (!ctxs[c]->pred_ready) return fail(lead, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	bxs->resize(nctx);
+	for (int c = 0; c < nctx; c++) {
+		SensBox pair;
+		if (const int rc = sens_check(lead, ctxs[c], lo, hi, &pair)) return rc;       // the same design, order, kinds and device
+		if (const int rc = sens_check(ctxs[c], ctxs[c], lo, hi, &(*bxs)[c])) return rc;
+		for (int e = 0; e < c; e++)
+			if (ctxs[e] == ctxs[c]) return fail(lead, GPEMU_ERR_ARG, "design batch: a context is listed twice");
+	}
+	for (int c = 0; weight && c < nctx; c++)
+		if (!std::isfinite(weight[c]) || weight[c] < 0.0) return fail(lead, GPEMU_ERR_ARG, "design batch: a weight must be finite and >= 0");
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_design_batch_dev(gpemu_ctx *const *ctxs, int nctx, const double *weight, const double *lo, const double *hi, int npoints,
+                                      const double *xq_dev, int nbatch, int *pick_dev, double *pick_gain_dev, double *pick_gain_ctx_dev,
+                                      double *gain_first_dev, double *gain_last_dev)
+{
+	std::vector<SensBox> bxs;
+	if (const int rc = design_batch_check(ctxs, nctx, weight, lo, hi, npoints, xq_dev, nbatch, pick_dev, pick_gain_dev, &bxs)) return rc;
+	gpemu_ctx *lead = ctxs[0];
+	HIPCHK(lead, hipSetDevice(lead->device));
+	const int M = npoints, mbp = round_up(M, 64), N = lead->N, d = lead->d, Np = lead->Np, nreg = lead->nreg;
+	const long ldt = (long)Np + 64, ldl = nbatch;
+	HIPCHK(lead, hipStreamSynchronize(lead->stream));                                 // (an earlier call's arg-max may still read the contexts' gains)
+	for (int c = 0; c < nctx; c++) {
+		gpemu_ctx *ctx = ctxs[c];
+		ctx->batch_mb = ctx->batch_nb = 0;
+		int rc = grow(ctx, ctx->dBatchW, (size_t)mbp * Np, false, "out of device memory for the rows of w (8 M' Np bytes)");
+		if (!rc) rc = grow(ctx, ctx->dBatchLam, (size_t)M * nbatch);
+		if (!rc) rc = grow(ctx, ctx->dBatchMu, (size_t)M * nbatch);
+		if (!rc) rc = grow(ctx, ctx->dBatchE, 256 * 256);
+		if (!rc) rc = grow(ctx, ctx->dBatchSv, design_batch_sv_elems(Np));
+		if (!rc) rc = grow(ctx, ctx->dBatchDots, 4 * (size_t)M);
+		if (!rc) rc = grow(ctx, ctx->dBatchSt, 3 * (size_t)M);
+		if (!rc && !ctx->sens_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sens_ev, hipEventDisableTiming));
+		if (!rc && !ctx->sens_ev2) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sens_ev2, hipEventDisableTiming));
+		if (rc) return rc;
+	}
+	// the table of the arg-max: the contexts' gain pointers, the weights, the picked marks (ints)
+	const size_t tab = 2 * (size_t)nctx + ((size_t)M + 1) / 2;
+	if (const int rc = grow(lead, lead->dBatchTab, tab)) return rc;
+	HIPCHK(lead, hipStreamSynchronize(lead->stream));                                 // (an earlier call's launches may still read the table)
+	{
+		std::vector<double> h(2 * (size_t)nctx);
+		for (int c = 0; c < nctx; c++) {
+			const double *g = ctxs[c]->dBatchSt + 2 * (size_t)M;
+			memcpy(&h[c], &g, sizeof g);
+			h[nctx + c] = weight ? weight[c] : 1.0;
+		}
+		HIPCHK(lead, hipMemcpy(lead->dBatchTab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+	}
+	const double *const *gains = reinterpret_cast<const double *const *>((double *)lead->dBatchTab);
+	const double *wdev = lead->dBatchTab + nctx;
+	int *picked = reinterpret_cast<int *>(lead->dBatchTab + 2 * (size_t)nctx);
+	HIPCHK(lead, hipMemsetAsync(picked, 0, (size_t)M * sizeof(int), lead->stream));
+	// the other streams behind what ctxs[0]'s stream holds (the caller's candidates among it)
+	HIPCHK(lead, hipEventRecord(lead->sens_ev2, lead->stream));
+	for (int c = 1; c < nctx; c++) HIPCHK(lead, hipStreamWaitEvent(ctxs[c]->stream, lead->sens_ev2, 0));
+	for (int c = 0; c < nctx; c++) {
+		gpemu_ctx *ctx = ctxs[c];
+		double *st = ctx->dBatchSt;
+		if (const int rc = gpemu_design_gain_dev(ctx, lo, hi, M, xq_dev, st + 2 * (size_t)M, st + M, st)) return rc;
+		const bool prof = prof_on(ctx, GPEMU_PROF_DESIGN);
+		if (prof) ctx->prof.tag.push_back("design_wrows");
+		ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)M * N * sens_pair_flops(bxs[c], d), 8.0 * (double)mbp * Np);
+		HIPCHK(ctx, launch_design_wrows(ctx->stream, ctx->dX, N, Np, d, ctx->dSensCst, bxs[c].meas, xq_dev, M, mbp, ctx->dBatchW));
+	}
+	for (int j = 0; j <= nbatch; j++) {
+		// the arg-max of pick j (j = nbatch: only gain_last) behind every context's update
+		for (int c = 1; c < nctx; c++) {
+			HIPCHK(lead, hipEventRecord(ctxs[c]->sens_ev, ctxs[c]->stream));
+			HIPCHK(lead, hipStreamWaitEvent(lead->stream, ctxs[c]->sens_ev, 0));
+		}
+		double *wout = j == 0 ? gain_first_dev : (j == nbatch ? gain_last_dev : nullptr);
+		if (j < nbatch || wout) {
+			if (prof_on(lead, GPEMU_PROF_DESIGN)) lead->prof.tag.push_back("design_argmax");
+			ProfScope ps(lead, GPEMU_PROF_DESIGN, 2.0 * nctx * M, 8.0 * (nctx + 1.0) * M);
+			HIPCHK(lead, launch_design_argmax(lead->stream, gains, wdev, nctx, M, picked, j < nbatch ? j : -1, pick_dev, pick_gain_dev,
+			                                  pick_gain_ctx_dev, wout));
+		}
+		if (j == nbatch) break;
+		HIPCHK(lead, hipEventRecord(lead->sens_ev2, lead->stream));
+		for (int c = 0; c < nctx; c++) {
+			gpemu_ctx *ctx = ctxs[c];
+			if (c) HIPCHK(lead, hipStreamWaitEvent(ctx->stream, lead->sens_ev2, 0));
+			double *st = ctx->dBatchSt;
+			const bool prof = prof_on(ctx, GPEMU_PROF_DESIGN);
+			if (prof) ctx->prof.tag.push_back("design_gather");
+			{
+				ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)N * (3.0 * d + 2.0), 8.0 * 5.0 * Np);
+				HIPCHK(ctx, launch_design_gather(ctx->stream, pick_dev, j, ctx->dX, N, Np, d, nreg, ctx->dSensCst, ctx->pred_cov.amp, xq_dev, M,
+				                                 ctx->dDesignA, ctx->dDesignT, ldt, ctx->dBatchW, ctx->dDesignB, ctx->dDesignPrepQ, ctx->dDesignHm,
+				                                 ctx->dBatchLam, ctx->dBatchMu, ldl, st, st + M, ctx->dBatchE, ctx->dBatchSv));
+			}
+			if (prof) ctx->prof.tag.push_back("design_column");
+			{
+				// four fused multiply-adds per column; the rows of a, T^K and w read once
+				ProfScope ps(ctx, GPEMU_PROF_DESIGN, 8.0 * (double)M * Np, 8.0 * 3.0 * (double)M * Np);
+				HIPCHK(ctx, launch_design_column(ctx->stream, ctx->dDesignA, ctx->dDesignT, ldt, ctx->dBatchW, Np, M, ctx->dBatchSv,
+				                                 ctx->dBatchDots, M));
+			}
+			if (prof) ctx->prof.tag.push_back("design_update");
+			{
+				ProfScope ps(ctx, GPEMU_PROF_DESIGN, (double)M * (12.0 * nreg + 6.0 * j + sens_pair_flops(bxs[c], d)),
+				             8.0 * (double)M * (2.0 * nreg + 2.0 * j + 12.0));
+				HIPCHK(ctx, launch_design_update(ctx->stream, j, xq_dev, M, Np, d, nreg, ctx->dSensCst, bxs[c].meas, ctx->pred_cov.amp,
+				                                 ctx->dDesignT, ldt, ctx->dDesignB, ctx->dDesignPrepQ, ctx->dBatchSv, ctx->dBatchDots, M,
+				                                 ctx->dBatchLam, ctx->dBatchMu, ldl, st, st + M, st + 2 * (size_t)M));
+			}
+		}
+	}
+	for (int c = 0; c < nctx; c++) {
+		ctxs[c]->batch_mb = M;
+		ctxs[c]->batch_nb = nbatch;
+	}
+	return GPEMU_OK;
+}
+
+// host buffers: the candidates and the results through a buffer of ctxs[0]'s own
+extern "C" int gpemu_design_batch(gpemu_ctx *const *ctxs, int nctx, const double *weight, const double *lo, const double *hi, int npoints,
+                                  const double *xq, int nbatch, int *pick, double *pick_gain, double *pick_gain_ctx, double *gain_first,
+                                  double *gain_last)
+{
+	std::vector<SensBox> bxs;
+	if (const int rc = design_batch_check(ctxs, nctx, weight, lo, hi, npoints, xq, nbatch, pick, pick_gain, &bxs)) return rc;
+	gpemu_ctx *lead = ctxs[0];
+	HIPCHK(lead, hipSetDevice(lead->device));
+	const size_t M = (size_t)npoints, d = (size_t)lead->d, nb = (size_t)nbatch, nc = (size_t)nctx;
+	if (const int rc = grow(lead, lead->dBatchIO, M * (d + 2) + nb * (nc + 1) + (nb + 1) / 2)) return rc;
+	double *dx = lead->dBatchIO, *dgf = dx + M * d, *dgl = dgf + M, *dpg = dgl + M, *dpc = dpg + nb;
+	int *dpk = reinterpret_cast<int *>(dpc + nb * nc);
+	HIPCHK(lead, hipMemcpyAsync(dx, xq, M * d * sizeof(double), hipMemcpyHostToDevice, lead->stream));
+	if (const int rc = gpemu_design_batch_dev(ctxs, nctx, weight, lo, hi, npoints, dx, nbatch, dpk, dpg, pick_gain_ctx ? dpc : nullptr,
+	                                          gain_first ? dgf : nullptr, gain_last ? dgl : nullptr))
+		return rc;
+	HIPCHK(lead, hipMemcpyAsync(pick, dpk, nb * sizeof(int), hipMemcpyDeviceToHost, lead->stream));
+	HIPCHK(lead, hipMemcpyAsync(pick_gain, dpg, nb * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
+	if (pick_gain_ctx) HIPCHK(lead, hipMemcpyAsync(pick_gain_ctx, dpc, nb * nc * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
+	if (gain_first) HIPCHK(lead, hipMemcpyAsync(gain_first, dgf, M * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
+	if (gain_last) HIPCHK(lead, hipMemcpyAsync(gain_last, dgl, M * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
+	HIPCHK(lead, hipStreamSynchronize(lead->stream));
+	return GPEMU_OK;
+}
+
+// lambda and mu (npoints x nbatch each) and E (nbatch x nbatch) of the context's part in the last gpemu_design_batch, bit for bit
+extern "C" int gpemu_test_design_batch_state(gpemu_ctx *ctx, int npoints, int nbatch, double *lam_out, double *mu_out, double *e_out)
+{
+	if (!ctx || !lam_out || !mu_out || !e_out || npoints < 1 || nbatch < 1) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->batch_mb != npoints || ctx->batch_nb != nbatch || !ctx->dBatchLam || !ctx->dBatchE || ctx->design_serial != ctx->pred_serial)
+		return fail(ctx, GPEMU_ERR_STATE, "no gpemu_design_batch of this size");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t n = (size_t)npoints * nbatch * sizeof(double), row = (size_t)nbatch * sizeof(double);
+	HIPCHK(ctx, hipMemcpyAsync(lam_out, ctx->dBatchLam, n, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(mu_out, ctx->dBatchMu, n, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(e_out, row, ctx->dBatchE, 256 * sizeof(double), row, (size_t)nbatch, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }

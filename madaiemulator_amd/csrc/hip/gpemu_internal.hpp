@@ -371,6 +371,12 @@ struct gpemu_ctx {
 	unsigned long long pred_serial = 0, design_serial = 0;   // pred_serial: counts the prediction set-ups of this context
 	gpemu::SensBox design_box{};
 	int design_mb = 0;
+	// greedy batches (gpemu_design_batch), beside the block above: dBatchW the rows of w (mb' x Np), dBatchLam and
+	// dBatchMu (mb x nbatch), dBatchE (256 x 256), dBatchSv what the gather lays out of a pick, dBatchDots the column kernel's four
+	// dots, dBatchSt v_S, num_S and gain (3 x mb); on ctxs[0] also dBatchTab (the contexts' gain pointers, the weights, the picked
+	// marks) and dBatchIO (the host entry's candidates and results).  batch_mb, batch_nb: the last call's sizes (0: none)
+	gpemu::DevBuf<double> dBatchW, dBatchLam, dBatchMu, dBatchE, dBatchSv, dBatchDots, dBatchSt, dBatchTab, dBatchIO;
+	int batch_mb = 0, batch_nb = 0;
 	// calibration against observations (gpemu_calib_*): dCalibTab the resident table of one observation set
 	// (kernels_calib.hip has its layout; calib_nt > 0: set up), independent of the model: gpemu_set_model leaves it alone,
 	// gpemu_calib_release and the end of the context free it.  dCalibIO / dCalibIdx the host entries' device copies of mean,
@@ -594,6 +600,23 @@ hipError_t launch_design_finish(hipStream_t s, const double *part, long pstride,
                                 const double *Tm, long ldt, const double *prepq, const double *Xq, int mb, int Np, int d, int nreg,
                                 const double *cst, int meas, const double *Hm, double amp, double kappa, double *gain, double *num, double *var,
                                 double *bkeep);
+// greedy batches (gpemu_design_batch).  W: the rows of w (mbp x Np); sv: design_batch_sv_elems doubles, what the
+// gather lays out of one pick; Lam, Mu: mb rows of ldl, entry j written by pick j; E: 256 x 256; dots: four rows of dstride;
+// vS, numS, gain: the running v_S, num_S and gain of every candidate; pick: the picks so far, in device memory
+size_t design_batch_sv_elems(int Np);
+hipError_t launch_design_wrows(hipStream_t s, const double *X, int N, int Np, int d, const double *cst, int meas, const double *Xq, int mb,
+                               int mbp, double *W);
+hipError_t launch_design_gather(hipStream_t s, const int *pick, int j, const double *X, int N, int Np, int d, int nreg, const double *cst,
+                                double amp, const double *Xq, int mb, const double *Am, const double *Tm, long ldt, const double *Wm,
+                                const double *Bm, const double *prepq, const double *Hm, const double *Lam, const double *Mu, long ldl,
+                                const double *vS, const double *numS, double *E, double *sv);
+hipError_t launch_design_column(hipStream_t s, const double *Am, const double *Tm, long ldt, const double *Wm, int Np, int mb, const double *sv,
+                                double *dots, long dstride);
+hipError_t launch_design_update(hipStream_t s, int j, const double *Xq, int mb, int Np, int d, int nreg, const double *cst, int meas, double amp,
+                                const double *Tm, long ldt, const double *Bm, const double *prepq, const double *sv, const double *dots,
+                                long dstride, double *Lam, double *Mu, long ldl, double *vS, double *numS, double *gain);
+hipError_t launch_design_argmax(hipStream_t s, const double *const *gains, const double *weight, int nctx, int M, int *picked, int slot,
+                                int *pick, double *pick_gain, double *pick_gain_ctx, double *wout);
 
 // ---- kernels_calib.hip: implausibility and calibration likelihood against observations
 // the device table of one observation set: calib_table_elems doubles, filled on the host from gpemu_calib_project's outputs

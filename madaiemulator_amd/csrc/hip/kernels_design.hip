@@ -236,9 +236,378 @@ __global__ __launch_bounds__(256) void design_finish_kernel(const double *part, 
 	}
 }
 
+// ===========================================================================
+// Greedy batches of K runs (gpemu_design_batch).  After the first pass above the rows of a, T and b, the
+// candidates' tables and num, var stay where they are; the rows of w are written beside them.  Per pick s and context:
+//   gather -> column -> update,   then one arg-max launch over the weighted gains of all contexts.
+// Per candidate q the state is lambda_q, mu_q (row q of Lam, Mu, ldl wide, entry j written by pick j) and the running
+// v_S(q), num_S(q); E (256 x 256, symmetric, both triangles written) is the context's.  The quadratic form is carried forward:
+//   lambda^T E lambda grows by 2 lambda_new (e . lambda_old) + E_new,new lambda_new^2,   e_i = E_i,new,
+// so a pick costs O(j) per candidate and the first j picks of a longer batch are a batch of j bit for bit.
+// ===========================================================================
+constexpr int DESIGN_SV_B = 0, DESIGN_SV_H = 64, DESIGN_SV_THK = 128, DESIGN_SV_HKS = 192, DESIGN_SV_HMB = 256, DESIGN_SV_X = 320,
+              DESIGN_SV_LAM = 384, DESIGN_SV_E = 640, DESIGN_SV_SC = 896,       // offsets behind the three Np-vectors a_s, w_s, k_s
+              DESIGN_SV_ELEMS = 1024;
+
+size_t design_batch_sv_elems(int Np) { return 3 * (size_t)Np + DESIGN_SV_ELEMS; }
+
+// h_al(x): 1, x_l, x_l^2, x_l^3 for al = 1 + (p - 1) d + l, as the prediction's regression row takes it
+__device__ __forceinline__ double design_hfun(int a, const double *x, int d)
+{
+	if (a == 0) return 1.0;
+	const int q = (a - 1) / d;
+	const double v = x[(a - 1) % d];
+	return q == 0 ? v : (q == 1 ? v * v : v * v * v);
+}
+
+// HK*_al of candidate q from the block's tables (the expression of design_finish_kernel)
+__device__ __forceinline__ double design_hk_own(const double *prepq, int q, int mb, int d, int al)
+{
+	const long tq = (long)d * mb;
+	if (al == 0) return prepq[q] * prepq[4 * tq + q];
+	const int l = (al - 1) % d, p = (al - 1) / d + 1;
+	return prepq[p * tq + (long)l * mb + q] * prepq[4 * tq + (long)l * mb + q];
+}
+
+// wrows: W[q * Np + i] = prod_l II_l(x*_q, x_i), the factor evaluated as the cross sweep evaluates it (candidate first);
+// columns i >= N and rows >= mb are 0 (mbp rows: the whole buffer is written)
+template <int MEAS>
+__global__ __launch_bounds__(256) void design_wrows_kernel(const double *X, int N, int Np, int d, const double *cst, const double *Xq, int mb,
+                                                           double *W)
+{
+	const int col = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
+	if (col >= Np) return;
+	W[(long)row * Np + col] = (row < mb && col < N) ? design_pair_product<MEAS>(Xq + (long)row * d, X + (long)col * d, d, cst) : 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// gather: everything of the pick s = pick[j] that the next two launches read, laid out contiguously in sv:
+//   a_s, w_s (rows s of Am and W; a_s zero from N on), k_s fresh and unclamped (design_kvec_kernel's expression), then 64 each
+//   of b_s, h_s, T^HK_s, HK*_s, Hm b_s and x_s, lambda_s (j), e (j: the new column of E), and rho, E_new,new, valid.
+// Workgroup 0 does the short vectors and extends E: e_i = (mu_s,i - (E lambda_s)_i) / rho, E_jj = num_S(s) / v_S(s).  A pick
+// whose v_S rounds to <= 0 carries no information: valid = 0, and its column of E, lambda and mu are 0.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void design_gather_kernel(const int *pick, int j, const double *X, int N, int Np, int d, int nreg,
+                                                            const double *cst, double A, const double *Xq, int mb, const double *Am,
+                                                            const double *Tm, long ldt, const double *Wm, const double *Bm,
+                                                            const double *prepq, const double *Hm, const double *Lam, const double *Mu,
+                                                            long ldl, const double *vS, const double *numS, double *E, double *sv)
+{
+	__shared__ double b_sh[64], lam_sh[256], mu_sh[256];
+	const int s = pick[j], tid = threadIdx.x;
+	const double *xs = Xq + (long)s * d;
+	const int i = blockIdx.x * 256 + tid;
+	if (i < Np) {
+		double k = 0.0;
+		if (i < N) {
+			double e = 0.0;
+			for (int l = 0; l < d; l++) {
+				const double dx = xs[l] - X[(long)i * d + l];
+				e = fma(cst[SENS_CST_S * GPEMU_MAX_PARAMS + l] * dx, dx, e);
+			}
+			k = A * exp(-0.5 * e);
+		}
+		sv[i] = i < N ? Am[(long)s * Np + i] : 0.0;
+		sv[Np + i] = Wm[(long)s * Np + i];
+		sv[2 * (long)Np + i] = k;
+	}
+	if (blockIdx.x != 0) return;
+	double *o = sv + 3 * (long)Np;
+	if (tid < 64) {
+		const bool v = tid < nreg;
+		const double b = v ? Bm[(long)s * 64 + tid] : 0.0;
+		b_sh[tid] = b;
+		o[DESIGN_SV_B + tid] = b;
+		o[DESIGN_SV_H + tid] = v ? design_hfun(tid, xs, d) : 0.0;
+		o[DESIGN_SV_THK + tid] = v ? Tm[(long)s * ldt + Np + tid] : 0.0;
+		o[DESIGN_SV_HKS + tid] = v ? design_hk_own(prepq, s, mb, d, tid) : 0.0;
+		o[DESIGN_SV_X + tid] = tid < d ? xs[tid] : 0.0;
+	}
+	lam_sh[tid] = tid < j ? Lam[(long)s * ldl + tid] : 0.0;
+	mu_sh[tid] = tid < j ? Mu[(long)s * ldl + tid] : 0.0;
+	__syncthreads();
+	if (tid < 64) {
+		double t = 0.0;
+		if (tid < nreg)
+			for (int be = 0; be < nreg; be++) t = fma(Hm[tid * 64 + be], b_sh[be], t);
+		o[DESIGN_SV_HMB + tid] = t;
+	}
+	const double v = vS[s], n = numS[s];
+	const bool valid = v > 0.0;
+	const double rho = valid ? sqrt(v) : 1.0;
+	o[DESIGN_SV_LAM + tid] = lam_sh[tid];
+	double e = 0.0;
+	if (tid < j && valid) {
+		double t = 0.0;
+		for (int k = 0; k < j; k++) t = fma(E[(long)k * 256 + tid], lam_sh[k], t);          // (E is symmetric: column tid of row k)
+		e = (mu_sh[tid] - t) / rho;
+	}
+	o[DESIGN_SV_E + tid] = e;
+	__syncthreads();                                                                      // every read of E above before its new entries
+	if (tid < j) {
+		E[(long)tid * 256 + j] = e;
+		E[(long)j * 256 + tid] = e;
+	}
+	if (tid == 0) {
+		const double enn = valid ? n / v : 0.0;
+		E[(long)j * 256 + j] = enn;
+		o[DESIGN_SV_SC + 0] = rho;
+		o[DESIGN_SV_SC + 1] = enn;
+		o[DESIGN_SV_SC + 2] = valid ? 1.0 : 0.0;
+	}
+}
+
+// ---------------------------------------------------------------------------
+// column: the four N-length dots of every candidate with the pick's vectors,
+//   dots[0] = a_q . k_s,  dots[1] = a_q . w_s,  dots[2] = w_q . a_s,  dots[3] = T^K_q . a_s     (dstride apart).
+// A workgroup owns 16 candidates, a wave four of them at once: the three rows of a candidate are streamed once, 16 bytes per
+// lane (eight lanes a 128-byte row piece), and each piece of the pick's vectors (from the caches: every workgroup reads the
+// same 24 Np bytes) serves four rows.  A lane adds its columns in ascending order, then the wave's butterfly: one order.  A
+// row past the last candidate repeats the last one and stores nothing.  No LDS, no atomics.  The rows are read unmasked out to
+// Np (design_cross_kernel masks col < N): the columns N .. Np - 1 of a, T^K and w meet zeros of the pick's vectors, so they must
+// be FINITE -- a's and T^K's come finite out of the products with the zero-padded L^-T and K, w's are written as zeros; the
+// cases with N = 1, 63, 65, 130, 200 of the tests would show a NaN.
+// ---------------------------------------------------------------------------
+constexpr int DESIGN_COL_ROWS = 4;
+
+__global__ __launch_bounds__(256) void design_column_kernel(const double *Am, const double *Tm, long ldt, const double *Wm, int Np, int mb,
+                                                            const double *sv, double *dots, long dstride)
+{
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int q0 = (blockIdx.x * 4 + wave) * DESIGN_COL_ROWS;
+	const double *as = sv, *ws = sv + Np, *ks = sv + 2 * (long)Np;
+	const double *ar[DESIGN_COL_ROWS], *tr[DESIGN_COL_ROWS], *wr[DESIGN_COL_ROWS];
+	double acc[DESIGN_COL_ROWS][4];
+#pragma unroll
+	for (int r = 0; r < DESIGN_COL_ROWS; r++) {
+		const long q = min(q0 + r, mb - 1);
+		ar[r] = Am + q * Np;
+		tr[r] = Tm + q * ldt;
+		wr[r] = Wm + q * Np;
+		acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+	}
+	for (int i = lane * 2; i < Np; i += 128) {
+		const double2 a_s = *reinterpret_cast<const double2 *>(as + i);
+		const double2 w_s = *reinterpret_cast<const double2 *>(ws + i);
+		const double2 k_s = *reinterpret_cast<const double2 *>(ks + i);
+#pragma unroll
+		for (int r = 0; r < DESIGN_COL_ROWS; r++) {
+			const double2 a = *reinterpret_cast<const double2 *>(ar[r] + i);
+			const double2 t = *reinterpret_cast<const double2 *>(tr[r] + i);
+			const double2 w = *reinterpret_cast<const double2 *>(wr[r] + i);
+			acc[r][0] = fma(a.y, k_s.y, fma(a.x, k_s.x, acc[r][0]));
+			acc[r][1] = fma(a.y, w_s.y, fma(a.x, w_s.x, acc[r][1]));
+			acc[r][2] = fma(w.y, a_s.y, fma(w.x, a_s.x, acc[r][2]));
+			acc[r][3] = fma(t.y, a_s.y, fma(t.x, a_s.x, acc[r][3]));
+		}
+	}
+#pragma unroll
+	for (int r = 0; r < DESIGN_COL_ROWS; r++)
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			double v = acc[r][k];
+#pragma unroll
+			for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+			if (lane == 0 && q0 + r < mb) dots[k * dstride + q0 + r] = v;
+		}
+}
+
+// ---------------------------------------------------------------------------
+// update: one wave per candidate q.  Lane al holds b_q, T^HK_q, HK*_q of basis function al and the six short products with the
+// pick's vectors; lane l the pair factor II_l(x*_q, x*_s) and the exponent term of coordinate l, multiplied and added by lane
+// order; lanes stride over the j entries of lambda_q, mu_q for lambda_q . lambda_s, mu_q . lambda_s and e . lambda_q.  Then
+//   Sigma = (A k(x_q, x_s) - a_q . k_s) + b_q . h_s
+//   G     = (A^2 (((II - w_q . a_s) - a_q . w_s) + T^K_q . a_s) + A ((HK*_q . b_s + HK*_s . b_q) - (T^HK_q . b_s + b_q . T^HK_s))) + b_q . Hm b_s
+//   lambda_new = (Sigma - lambda_q . lambda_s) / rho,   mu_new = (G - mu_q . lambda_s) / rho        (0 for a pick that is not valid)
+//   v_S -= lambda_new^2,   num_S += -2 lambda_new mu_new + 2 lambda_new (e . lambda_q) + E_new,new lambda_new^2,
+//   gain = v_S > 0 ? num_S / v_S : 0.
+// ---------------------------------------------------------------------------
+template <int MEAS>
+__global__ __launch_bounds__(256) void design_update_kernel(int j, const double *Xq, int mb, int Np, int d, int nreg, const double *cst,
+                                                            double A, const double *Tm, long ldt, const double *Bm, const double *prepq,
+                                                            const double *sv, const double *dots, long dstride, double *Lam, double *Mu,
+                                                            long ldl, double *vS, double *numS, double *gain)
+{
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int q = min(blockIdx.x * 4 + wave, mb - 1);
+	const bool store = blockIdx.x * 4 + wave < mb;
+	const double *o = sv + 3 * (long)Np;
+	double pbh = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0, p4 = 0.0, p5 = 0.0;
+	if (lane < nreg) {
+		const double bq = Bm[(long)q * 64 + lane], thk = Tm[(long)q * ldt + Np + lane], hk = design_hk_own(prepq, q, mb, d, lane);
+		const double bs = o[DESIGN_SV_B + lane];
+		pbh = bq * o[DESIGN_SV_H + lane];
+		p1 = hk * bs;
+		p2 = o[DESIGN_SV_HKS + lane] * bq;
+		p3 = thk * bs;
+		p4 = bq * o[DESIGN_SV_THK + lane];
+		p5 = bq * o[DESIGN_SV_HMB + lane];
+	}
+	double ll = 0.0, ml = 0.0, el = 0.0;
+	for (int i = lane; i < j; i += 64) {
+		const double lq = Lam[(long)q * ldl + i], ls = o[DESIGN_SV_LAM + i];
+		ll = fma(lq, ls, ll);
+		ml = fma(Mu[(long)q * ldl + i], ls, ml);
+		el = fma(lq, o[DESIGN_SV_E + i], el);
+	}
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) {
+		pbh += __shfl_xor(pbh, off);
+		p1 += __shfl_xor(p1, off);
+		p2 += __shfl_xor(p2, off);
+		p3 += __shfl_xor(p3, off);
+		p4 += __shfl_xor(p4, off);
+		p5 += __shfl_xor(p5, off);
+		ll += __shfl_xor(ll, off);
+		ml += __shfl_xor(ml, off);
+		el += __shfl_xor(el, off);
+	}
+	double f = 1.0, ex = 0.0;
+	if (lane < d) {
+		const double xa = Xq[(long)q * d + lane], xb = o[DESIGN_SV_X + lane];
+		f = sens_pair_factor<MEAS>(xa, xb, cst[0 * GPEMU_MAX_PARAMS + lane], cst[1 * GPEMU_MAX_PARAMS + lane], cst[2 * GPEMU_MAX_PARAMS + lane],
+		                           cst[3 * GPEMU_MAX_PARAMS + lane], cst[4 * GPEMU_MAX_PARAMS + lane], cst[5 * GPEMU_MAX_PARAMS + lane],
+		                           cst[6 * GPEMU_MAX_PARAMS + lane], MEAS == 2 ? cst[SENS_CST_KIND * GPEMU_MAX_PARAMS + lane] : 0.0);
+		const double dx = xa - xb;
+		ex = cst[SENS_CST_S * GPEMU_MAX_PARAMS + lane] * dx * dx;
+	}
+	double pi = 1.0, es = 0.0;
+	for (int l = 0; l < d; l++) {
+		pi *= __shfl(f, l);
+		es += __shfl(ex, l);
+	}
+	if (!store || lane != 0) return;
+	const double rho = o[DESIGN_SV_SC + 0], enn = o[DESIGN_SV_SC + 1];
+	const bool valid = o[DESIGN_SV_SC + 2] != 0.0;
+	const double d1 = dots[q], d2 = dots[dstride + q], d3 = dots[2 * dstride + q], d4 = dots[3 * dstride + q];
+	const double sig = (A * exp(-0.5 * es) - d1) + pbh;
+	const double g = (A * A * (((pi - d3) - d2) + d4) + A * ((p1 + p2) - (p3 + p4))) + p5;
+	const double ln = valid ? (sig - ll) / rho : 0.0, mn = valid ? (g - ml) / rho : 0.0;
+	Lam[(long)q * ldl + j] = ln;
+	Mu[(long)q * ldl + j] = mn;
+	const double v = vS[q] - ln * ln;
+	const double n = numS[q] + ((2.0 * ln * (el - mn)) + enn * ln * ln);
+	vS[q] = v;
+	numS[q] = n;
+	gain[q] = v > 0.0 ? n / v : 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// argmax: one workgroup over all candidates.  wsum_q = sum_c weight_c gain_c(q) in context order (the first term is the product
+// itself: one context with weight 1 keeps the bits of its gain); wout (optional) receives it, -inf for a candidate already
+// picked.  slot >= 0: the arg-max over the candidates not yet picked -- a thread over its candidates in ascending order, then
+// a fixed tree; a larger value wins, equal values go to the lower index, NaN counts as -inf -- goes to pick[slot], its weighted
+// gain to pick_gain[slot], the contexts' to pick_gain_ctx[slot * nctx ..], and the candidate is marked picked.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void design_argmax_kernel(const double *const *gains, const double *weight, int nctx, int M, int *picked,
+                                                            int slot, int *pick, double *pick_gain, double *pick_gain_ctx, double *wout)
+{
+	__shared__ double val_s[256];
+	__shared__ int idx_s[256];
+	const int tid = threadIdx.x;
+	double best = 0.0;
+	int bi = -1;
+	for (int q = tid; q < M; q += 256) {
+		double ws = weight[0] * gains[0][q];
+		for (int c = 1; c < nctx; c++) ws = fma(weight[c], gains[c][q], ws);
+		const bool taken = picked[q] != 0;
+		if (wout) wout[q] = taken ? -INFINITY : ws;
+		if (taken) continue;
+		const double v = ws != ws ? -INFINITY : ws;
+		if (bi < 0 || v > best) {
+			best = v;
+			bi = q;
+		}
+	}
+	if (slot < 0) return;
+	val_s[tid] = best;
+	idx_s[tid] = bi;
+	__syncthreads();
+	for (int off = 128; off > 0; off >>= 1) {
+		if (tid < off) {
+			const int oi = idx_s[tid + off], mi = idx_s[tid];
+			const double ov = val_s[tid + off], mv = val_s[tid];
+			if (oi >= 0 && (mi < 0 || ov > mv || (ov == mv && oi < mi))) {
+				val_s[tid] = ov;
+				idx_s[tid] = oi;
+			}
+		}
+		__syncthreads();
+	}
+	if (tid == 0) {
+		const int s = idx_s[0];                                                       // (>= 0: the entry admits no more picks than candidates)
+		pick[slot] = s;
+		picked[s] = 1;
+		double ws = weight[0] * gains[0][s];
+		for (int c = 1; c < nctx; c++) ws = fma(weight[c], gains[c][s], ws);
+		pick_gain[slot] = ws;
+		if (pick_gain_ctx)
+			for (int c = 0; c < nctx; c++) pick_gain_ctx[(long)slot * nctx + c] = gains[c][s];
+	}
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+hipError_t launch_design_wrows(hipStream_t s, const double *X, int N, int Np, int d, const double *cst, int meas, const double *Xq, int mb,
+                               int mbp, double *W)
+{
+	if (mb < 1 || mbp < mb || mbp > 65535 || N < 1 || d < 1 || d > GPEMU_MAX_PARAMS || meas < 0 || meas > 2) return hipErrorInvalidValue;
+	const dim3 grid((Np + 255) / 256, mbp);
+	if (meas == 0) hipLaunchKernelGGL(design_wrows_kernel<0>, grid, dim3(256), 0, s, X, N, Np, d, cst, Xq, mb, W);
+	else if (meas == 1) hipLaunchKernelGGL(design_wrows_kernel<1>, grid, dim3(256), 0, s, X, N, Np, d, cst, Xq, mb, W);
+	else hipLaunchKernelGGL(design_wrows_kernel<2>, grid, dim3(256), 0, s, X, N, Np, d, cst, Xq, mb, W);
+	return hipGetLastError();
+}
+
+hipError_t launch_design_gather(hipStream_t s, const int *pick, int j, const double *X, int N, int Np, int d, int nreg, const double *cst,
+                                double amp, const double *Xq, int mb, const double *Am, const double *Tm, long ldt, const double *Wm,
+                                const double *Bm, const double *prepq, const double *Hm, const double *Lam, const double *Mu, long ldl,
+                                const double *vS, const double *numS, double *E, double *sv)
+{
+	if (j < 0 || j >= 256 || ldl <= j || mb < 1 || Np % 64 || nreg < 1 || nreg > 63 || d < 1 || d > GPEMU_MAX_PARAMS) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(design_gather_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, pick, j, X, N, Np, d, nreg, cst, amp, Xq, mb, Am, Tm, ldt,
+	                   Wm, Bm, prepq, Hm, Lam, Mu, ldl, vS, numS, E, sv);
+	return hipGetLastError();
+}
+
+hipError_t launch_design_column(hipStream_t s, const double *Am, const double *Tm, long ldt, const double *Wm, int Np, int mb, const double *sv,
+                                double *dots, long dstride)
+{
+	if (mb < 1 || Np < 64 || Np % 64 || ldt % 2 || dstride < mb) return hipErrorInvalidValue;
+	const int per = 4 * DESIGN_COL_ROWS;
+	hipLaunchKernelGGL(design_column_kernel, dim3((mb + per - 1) / per), dim3(256), 0, s, Am, Tm, ldt, Wm, Np, mb, sv, dots, dstride);
+	return hipGetLastError();
+}
+
+hipError_t launch_design_update(hipStream_t s, int j, const double *Xq, int mb, int Np, int d, int nreg, const double *cst, int meas, double amp,
+                                const double *Tm, long ldt, const double *Bm, const double *prepq, const double *sv, const double *dots,
+                                long dstride, double *Lam, double *Mu, long ldl, double *vS, double *numS, double *gain)
+{
+	if (j < 0 || j >= 256 || ldl <= j || mb < 1 || nreg < 1 || nreg > 63 || d < 1 || d > GPEMU_MAX_PARAMS || meas < 0 || meas > 2)
+		return hipErrorInvalidValue;
+	const dim3 grid((mb + 3) / 4);
+	if (meas == 0)
+		hipLaunchKernelGGL(design_update_kernel<0>, grid, dim3(256), 0, s, j, Xq, mb, Np, d, nreg, cst, amp, Tm, ldt, Bm, prepq, sv, dots, dstride,
+		                   Lam, Mu, ldl, vS, numS, gain);
+	else if (meas == 1)
+		hipLaunchKernelGGL(design_update_kernel<1>, grid, dim3(256), 0, s, j, Xq, mb, Np, d, nreg, cst, amp, Tm, ldt, Bm, prepq, sv, dots, dstride,
+		                   Lam, Mu, ldl, vS, numS, gain);
+	else
+		hipLaunchKernelGGL(design_update_kernel<2>, grid, dim3(256), 0, s, j, Xq, mb, Np, d, nreg, cst, amp, Tm, ldt, Bm, prepq, sv, dots, dstride,
+		                   Lam, Mu, ldl, vS, numS, gain);
+	return hipGetLastError();
+}
+
+hipError_t launch_design_argmax(hipStream_t s, const double *const *gains, const double *weight, int nctx, int M, int *picked, int slot,
+                                int *pick, double *pick_gain, double *pick_gain_ctx, double *wout)
+{
+	if (nctx < 1 || M < 1 || slot >= 256) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(design_argmax_kernel, dim3(1), dim3(256), 0, s, gains, weight, nctx, M, picked, slot, pick, pick_gain, pick_gain_ctx,
+	                   wout);
+	return hipGetLastError();
+}
+
 size_t design_kh_elems(int Np) { return (size_t)Np * ((size_t)Np + 64); }
 
 hipError_t launch_design_kmat(hipStream_t s, const double *X, int N, int Np, int d, int nreg, const double *prep, const double *cst, int meas,

@@ -319,6 +319,22 @@ void emulator::QueryEmulatorDesignGain(const std::vector<double> &lo, const std:
 		for (size_t t = 0; t < no; t++) Gains[q][t] = g[q * no + t];
 }
 
+void emulator::QueryEmulatorDesignBatch(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
+                                        int BatchSize, std::vector<int> &Picks, std::vector<double> &PickGains)
+{
+	check_box("QueryEmulatorDesignBatch", lo, hi, number_params);
+	const size_t np = xpoints.size();
+	if (BatchSize < 1 || (size_t)BatchSize > np || BatchSize > 256 || np > 16384) {
+		std::cerr << "Error::QueryEmulatorDesignBatch needs 1 <= BatchSize <= min(number of points, 256) and at most 16384 points" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	Picks.assign((size_t)BatchSize, -1);
+	PickGains.assign((size_t)BatchSize, 0.0);
+	std::vector<double> flat = flatten("QueryEmulatorDesignBatch", xpoints, number_params);
+	emulate_design_batch_multi(the_emulator, outputPCAValues ? 1 : 0, lo.data(), hi.data(), (int)np, flat.data(), BatchSize, Picks.data(),
+	                           PickGains.data());
+}
+
 void emulator::QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
                                             std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,
                                             std::vector<std::vector<std::vector<double> > > &Bands)

@@ -83,6 +83,10 @@ public:
 	// when the design gets one more run at xpoints[q], the hyper-parameters as they are; TotalGains[q] its sum over the outputs
 	void QueryEmulatorDesignGain(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
 	                             std::vector<std::vector<double> > &Gains, std::vector<double> &TotalGains);
+	// a batch of BatchSize runs chosen greedily among xpoints (libemu.h: emulate_design_batch_multi): Picks[j] the index of pick j,
+	// PickGains[j] how much the sum of IntegratedVariances drops by it, given the picks before it
+	void QueryEmulatorDesignBatch(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
+	                              int BatchSize, std::vector<int> &Picks, std::vector<double> &PickGains);
 	// QueryEmulatorMainEffects with Bands[t][j][g] = the posterior standard deviation of E[output t | x_j = grid[j][g]]
 	void QueryEmulatorMainEffectBands(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &grid,
 	                                  std::vector<double> &Means, std::vector<std::vector<std::vector<double> > > &Curves,

@@ -1334,6 +1334,24 @@ void emulate_design_gain(emulator_struct *e, const double *lo, const double *hi,
 	check(en, gpemu_design_gain(en->ctx, lo, hi, npoints, points, gain, num, var), "emulate_design_gain");
 }
 
+/* a greedy batch of runs (gpemu_design_batch in gpemu.h) for emulators on one design that a run observes together */
+void emulate_design_batch_components(emulator_struct **es, int n, const double *weight, const double *lo, const double *hi, int npoints,
+                                     const double *points, int nbatch, int *pick_out, double *gain_out)
+{
+	struct entry *lead = entry_of(es[0], "emulate_design_batch");
+	gpemu_ctx **ctxs = (gpemu_ctx **)malloc(sizeof(gpemu_ctx *) * (size_t)(n > 0 ? n : 1));
+	for (int c = 0; c < n; c++) ctxs[c] = entry_of(es[c], "emulate_design_batch")->ctx;
+	const int rc = gpemu_design_batch(ctxs, n, weight, lo, hi, npoints, points, nbatch, pick_out, gain_out, NULL, NULL, NULL);
+	free(ctxs);
+	check(lead, rc, "emulate_design_batch");
+}
+
+void emulate_design_batch(emulator_struct *e, const double *lo, const double *hi, int npoints, const double *points, int nbatch,
+                          int *pick_out, double *gain_out)
+{
+	emulate_design_batch_components(&e, 1, NULL, lo, hi, npoints, points, nbatch, pick_out, gain_out);
+}
+
 /* second order (gpemu_sens_pairs / gpemu_sens_pairs_post / gpemu_sens_joint in gpemu.h): pairs j < k at
  * p = j (2 d - j - 1) / 2 + (k - j - 1).  vpair[p] = V_jk = Var(E[m | x_j, x_k]), inter[p] = V_jk - V_j - V_k */
 void emulate_sensitivity_pairs(emulator_struct *e, const double *lo, const double *hi, double *vpair, double *inter)

@@ -36,6 +36,7 @@ struct cmdLineOpts {
 	double cutI, cutChi2;
 	int level, gradientFlag;
 	int best, bestGiven;
+	int batch, batchGiven;           /* design --batch=K: K greedy picks (-1: not a number) */
 	int walkers, steps, burn, thin, walkersGiven, burnGiven;
 	unsigned long long seed;
 	double stretch;
@@ -85,10 +86,13 @@ static const char useage[] =
 	"      output; with --gradient, behind them the d components of the log likelihood's gradient with respect to the parameters.\n"
 	"      FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
 	"or\n"
-	"  interactive_emulator design MODEL_SNAPSHOT_FILE [--box=FILE | --prior=FILE] [--best=K] [--pca_output] [--quiet]  (where to put the next model\n"
+	"  interactive_emulator design MODEL_SNAPSHOT_FILE [--box=FILE | --prior=FILE] [--best=K] [--batch=K] [--pca_output] [--quiet]  (where to put the next model\n"
 	"      run: candidate points from stdin to the end of input; one line per candidate: index, parameters, the expected drop of the\n"
 	"      integrated posterior variance summed over the outputs if the model were run there, and that integrated variance as it\n"
-	"      is now.  --best=K prints the K candidates with the largest drop, largest first, ties in input order.  The measure as for\n"
+	"      is now.  --best=K prints the K candidates with the largest drop, largest first, ties in input order.  --batch=K chooses a\n"
+	"      batch of K runs greedily, each the largest drop GIVEN the picks before it, and prints them in pick order: index,\n"
+	"      parameters, that conditional drop, and the integrated variance after the pick (K <= 256, at most 16384 candidates;\n"
+	"      not with --best).  The measure as for\n"
 	"      `sensitivity`.  Power-exponential covariance only)\n"
 	"or\n"
 	"  interactive_emulator sample MODEL_SNAPSHOT_FILE --observations=FILE [--box=FILE | --prior=FILE] [--walkers=W] [--steps=T] [--burn=B] [--thin=K] [--seed=S] [--stretch=a] [--quiet]\n"
@@ -784,7 +788,9 @@ static int implausibility(struct cmdLineOpts *o)
 /* Where to put the next model run (emulate_design_gain_multi): candidates from stdin, d numbers each.  stdout, per candidate, one
  * line "index param_0 .. param_{d-1} gain imse": gain the expected drop of the integrated posterior variance, summed over the
  * outputs, if the model were run there (hyper-parameters as they are), imse that integrated variance as it is now (the same on
- * every line).  --best=K: the K candidates with the largest gain, largest first, ties in input order. */
+ * every line).  --best=K: the K candidates with the largest gain, largest first, ties in input order.  --batch=K: K greedy picks
+ * (emulate_design_batch_multi) in pick order, "index param_0 .. gain imse_after": the drop by the pick given the picks before it and
+ * the integrated variance once it is made. */
 static const double *design_key;
 static int design_order(const void *a, const void *b)
 {
@@ -796,6 +802,8 @@ static int design_order(const void *a, const void *b)
 static int design(struct cmdLineOpts *o)
 {
 	if (o->bestGiven && o->best < 1) return perr("--best=K needs K >= 1");
+	if (o->batchGiven && o->bestGiven) return perr("--batch=K and --best=K exclude each other");
+	if (o->batchGiven && (o->batch < 1 || o->batch > 256)) return perr("--batch=K needs a number 1 <= K <= 256");
 	FILE *fp = fopen(o->statefile, "r");
 	if (!fp) return perr("Error opening file");
 	gpemu_host_warm_start();
@@ -812,6 +820,8 @@ static int design(struct cmdLineOpts *o)
 	}
 	if (!feof(stdin) || n % (size_t)d) return perr("design: stdin must hold whole points, d numbers each, and nothing else");
 	const size_t np = n / (size_t)d;
+	if (o->batchGiven && ((size_t)o->batch > np || np > 16384))
+		return perr("design: --batch=K needs at least K candidates and at most 16384");
 	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
 	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
 	{
@@ -824,9 +834,25 @@ static int design(struct cmdLineOpts *o)
 	if (!o->quietFlag) {
 		fprintf(out, "# index");
 		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
-		fprintf(out, " expected_imse_reduction imse\n");
+		fprintf(out, o->batchGiven ? " conditional_imse_reduction imse_after\n" : " expected_imse_reduction imse\n");
 	}
-	if (np) {
+	if (np && o->batchGiven) {
+		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
+		double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
+		emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
+		double now = 0.0;
+		for (int t = 0; t < nout; t++) now += imse[t];
+		int *pick = (int *)malloc(sizeof(int) * (size_t)o->batch);
+		double *pg = (double *)malloc(sizeof(double) * (size_t)o->batch);
+		emulate_design_batch_multi(emu, o->pcaOutputFlag, lo, hi, (int)np, v, o->batch, pick, pg);
+		for (int k = 0; k < o->batch; k++) {
+			now -= pg[k];
+			fprintf(out, "%d", pick[k]);
+			for (int j = 0; j < d; j++) fprintf(out, " %.17g", v[(size_t)pick[k] * d + j]);
+			fprintf(out, " %.17g %.17g\n", pg[k], now);
+		}
+		free(ve0); free(ef); free(pick); free(pg);
+	} else if (np) {
 		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
 		double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
 		emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
@@ -984,6 +1010,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"gradient", no_argument, NULL, 1017},
 		/* design: only the K candidates that gain most */
 		{"best", required_argument, NULL, 1018},
+		/* design: a greedy batch of K runs */
+		{"batch", required_argument, NULL, 1025},
 		/* sample: the ensemble, the run and its random numbers */
 		{"walkers", required_argument, NULL, 1019},           {"steps", required_argument, NULL, 1020},
 		{"burn", required_argument, NULL, 1021},              {"thin", required_argument, NULL, 1022},
@@ -1036,6 +1064,13 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		case 1022: o->thin = atoi(optarg); break;
 		case 1023: o->seed = strtoull(optarg, NULL, 0); break;
 		case 1024: o->stretch = atof(optarg); break;
+		case 1025: {
+			char *end;
+			const long k = strtol(optarg, &end, 10);
+			o->batch = (*optarg && !*end && k >= 1 && k <= 256) ? (int)k : -1;
+			o->batchGiven = 1;
+			break;
+		}
 		case 'h':
 		case '?': exit(perr(useage));
 		default: break;

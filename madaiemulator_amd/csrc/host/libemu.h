@@ -345,6 +345,15 @@ void emulate_main_effects_band(emulator_struct *e, const double *lo, const doubl
  * observed with.  lo / hi and the measure as in the emulate_sensitivity* family. */
 void emulate_design_gain(emulator_struct *e, const double *lo, const double *hi, int npoints, const double *points, double *gain,
                          double *num, double *var);
+/* extension: a batch of nbatch runs chosen greedily among the candidates (gpemu_design_batch in gpemu.h): pick_out[j] the index
+ * of pick j, gain_out[j] the further drop of *imse by it, conditional on the picks before it -- the sum of the first j is the
+ * drop by all of them.  1 <= nbatch <= min(npoints, 256), npoints <= 16384.  emulate_design_batch_components: the same for n
+ * emulators on one design that one run observes together (the components of a multi-output model), the quantity maximised
+ * being sum_c weight[c] gain_c (weight NULL: all 1). */
+void emulate_design_batch(emulator_struct *e, const double *lo, const double *hi, int npoints, const double *points, int nbatch,
+                          int *pick_out, double *gain_out);
+void emulate_design_batch_components(emulator_struct **es, int n, const double *weight, const double *lo, const double *hi, int npoints,
+                                     const double *points, int nbatch, int *pick_out, double *gain_out);
 /* extension: second-order Sobol indices and interaction surfaces in closed form (gpemu_sens_pairs / gpemu_sens_pairs_post /
  * gpemu_sens_joint in gpemu.h).  total[j] > first[j] says that parameter j interacts; these say with which parameter.  Pairs j < k
  * are numbered p = j (2 nparams - j - 1) / 2 + (k - j - 1), npairs = nparams (nparams - 1) / 2; nparams >= 2.
@@ -540,6 +549,12 @@ void emulate_main_effects_band_multi(multi_emulator *emu, int pca_space, const d
  * (may be NULL) is its sum over the outputs. */
 void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
                                double *gain_out, double *total_out);
+/* a batch of nbatch runs chosen greedily (emulate_design_batch_components over the PCA components): every pick maximises what
+ * total_out of emulate_design_gain_multi would be given the picks before it, sum_c weight_c gain_c with weight_c = sum_t B_tc^2
+ * from gpemu_host_backproject's squared rule (all 1 in PCA space).  pick_out[j]: the candidate's index, gain_out[j]: the drop
+ * of the summed IMSE by pick j. */
+void emulate_design_batch_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
+                                int nbatch, int *pick_out, double *gain_out);
 /* second order per output: vpair_out, inter_out, evpair_out, einter_out are npairs values each, output-major, as
  * emulate_sensitivity_pairs / _uncertainty define them.  Observable space exactly as for emulate_sensitivity_multi /
  * _uncertainty_multi: the plug-in half keeps all cross terms between components, sum_{c,c'} B_tc B_tc' cov_pair(c, c') (every pair

@@ -970,6 +970,24 @@ void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double 
 	free(gp); free(gc);
 }
 
+/* A greedy batch of runs (libemu.h).  The weights are what total_out above sums: the squared rule applied to the unit vectors of
+ * the components gives B_tc^2, and weight_c is its sum over the outputs. */
+void emulate_design_batch_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
+                                int nbatch, int *pick_out, double *gain_out)
+{
+	const size_t nr = (size_t)emu->nr, nout = pca_space ? nr : (size_t)emu->nt;
+	double *unit = doubles(nr * nr), *sq = doubles(nr * nout), *weight = doubles(nr);
+	for (size_t i = 0; i < nr * nr; i++) unit[i] = i / nr == i % nr ? 1.0 : 0.0;
+	deliver(emu, pca_space, 1, 0, nr, 1, unit, sq);
+	for (size_t c = 0; c < nr; c++) {
+		double s = 0.0;
+		for (size_t t = 0; t < nout; t++) s += sq[c * nout + t];
+		weight[c] = s;
+	}
+	emulate_design_batch_components(emu->emu_struct_array, (int)nr, weight, lo, hi, npoints, points, nbatch, pick_out, gain_out);
+	free(unit); free(sq); free(weight);
+}
+
 /* Second order for every output (libemu.h): vpair_out[t * npairs + p] = V_jk of output t, inter_out the interaction variances
  * V_jk - V_j - V_k.  As emulate_sensitivity_multi: in observable space the full quadratic form over all pairs of components,
  *   V_jk(y_t) = sum_{c,c'} B_tc B_tc' cov_pair(c, c'),
