@@ -25,6 +25,11 @@ lowest index; a pick whose v_S is <= 0 conditions nothing (V would be singular).
 MARGIN, (best - second best) / (the two candidates' gain scales): the GPU tests keep only cases whose margins exceed the bars,
 so that the device's picks must equal these.
 
+`forced` takes the picks as an INPUT and returns the conditional values of every candidate and the state given a prefix of them,
+through `conditional` and `state`: long batches, whose margins fall under any bar, are checked on the device's own picks
+(tests/test_gpu_closed_form_large.py).  `carried` runs the device's recurrences in numpy, optionally with part of the update's dots
+left out (tests/test_closed_form_large_ref.py).
+
 Other routes, no closed form: `quadrature_num` (tensor quadrature of the conditioned c*^2, d <= 3) and `refit` (s_all of the
 design minus s_all of the design with the first j picks appended, both by senspostref on a numpy fit).
 
@@ -213,6 +218,57 @@ def greedy(ctx_pieces, vs, nugget, nbatch, weight=None, twin=None):
     out["last_scale"] = sc
     out["S"] = S
     return out
+
+
+def forced(ctx_pieces, vs, nugget, picks, j, weight=None, conditions=None, with_state=True):
+    """the picks are an INPUT (the device's own, say): the conditional values of every candidate given the prefix picks[:j], NON-
+    INCREMENTALLY (one `conditional` and one `state` per context, nothing carried from a shorter prefix).  conditions: per context
+    one flag per pick, whether it conditions (a pick whose v_S was <= 0 does not); None: every pick does, which holds in exact
+    arithmetic whenever nugget > 0.  ->
+    dict(gain, num, var [M, nctx] and gain_scale, num_scale, var_scale [M, nctx]; tot [M] = gain @ weight and tot_scale [M];
+    S: per context the conditioning picks; state: per context ((lambda, mu, E), (their scales)) of S, None where S is empty).
+    On greedy's own picks these are greedy's numbers bit for bit (test_designbatchref.py)."""
+    nctx = len(ctx_pieces)
+    w = np.ones(nctx) if weight is None else np.asarray(weight, float)
+    S = [[int(s) for i, s in enumerate(picks[:j]) if conditions is None or conditions[c][i]] for c in range(nctx)]
+    vals = [conditional(R.NP, *ctx_pieces[c], vs[c], nugget, S[c]) for c in range(nctx)]
+    out = dict(S=S)
+    for k in KEYS:
+        out[k] = np.stack([x[0][k] for x in vals], axis=1)
+        out[k + "_scale"] = np.stack([x[1][k] for x in vals], axis=1)
+    out["tot"], out["tot_scale"] = out["gain"] @ w, out["gain_scale"] @ w
+    if with_state:
+        out["state"] = [state(*ctx_pieces[c], vs[c], nugget, S[c]) if S[c] else None for c in range(nctx)]
+    return out
+
+
+def carried(Sig, G, v, nugget, S, keep=None):
+    """lambda, mu, E, v_S, num_S and the gains carried forward pick by pick in the recurrences the device uses, in
+    numpy:  rho = sqrt(v_S(s)),  e = (mu_s - E lambda_s) / rho,  E_new,new = num_S(s) / v_S(s),
+            lambda_new = (Sigma(., s) - lambda . lambda_s) / rho,   mu_new = (G(., s) - mu . lambda_s) / rho,
+            v_S -= lambda_new^2,   num_S += 2 lambda_new (e . lambda - mu_new) + E_new,new lambda_new^2.
+    keep = None: the whole recurrence (test_designbatchref.py holds it to `conditional` and `state`).  keep = k: the entries
+    i >= k of lambda and mu are LEFT OUT of the three dots of the update (lambda . lambda_s, mu . lambda_s, e . lambda): what an
+    update whose lanes make one trip of k entries would carry.  For the leave-out tests only.
+    -> (lambda [M, j], mu [M, j], E [j, j], v_S [M], num_S [M], gain [M])"""
+    S = list(S)
+    M, n = len(v), len(S)
+    lam, mu, E = np.zeros((M, n)), np.zeros((M, n)), np.zeros((n, n))
+    vS, numS = np.array(v, dtype=float), np.diag(G).copy()
+    for t, s in enumerate(S):
+        c = t if keep is None else min(t, keep)
+        rho = np.sqrt(vS[s])
+        ls = lam[s, :t].copy()
+        e = (mu[s, :t] - E[:t, :t] @ ls) / rho
+        E[:t, t] = E[t, :t] = e
+        E[t, t] = numS[s] / vS[s]
+        ln = (Sig[:, s] - lam[:, :c] @ ls[:c]) / rho
+        mn = (G[:, s] - mu[:, :c] @ ls[:c]) / rho
+        el = lam[:, :c] @ e[:c]
+        lam[:, t], mu[:, t] = ln, mn
+        vS = vS - ln * ln
+        numS = numS + 2 * ln * (el - mn) + E[t, t] * ln * ln
+    return lam, mu, E, vS, numS, np.where(vS > 0, numS / np.where(vS > 0, vS, 1.0), 0.0)
 
 
 # ---------------------------------------------------------------------------------------------------- no closed form

@@ -110,6 +110,60 @@ def test_two_contexts_and_weights():
     assert np.allclose(mix["pick_gain"], mix["pick_gain_ctx"] @ np.array([1.0, 0.5]), rtol=1e-14, atol=0)
 
 
+@pytest.mark.parametrize("weight", [None, [1.0, 0.5]])
+def test_forced_on_the_reference_own_picks_is_greedy(weight):
+    """`forced` takes the picks as an input; given greedy's own picks it returns greedy's numbers bit for bit: every pick's gain and
+    scale, per context and weighted, the pick itself as the arg-max among the candidates not yet picked, gain_first and gain_last"""
+    X, m, kind, lo, hi, w, Xq, a, b, v = inputs(12, 2, 2, "design")
+    m2 = dict(m, s=m["s"] * 2.5)
+    a2, b2, v2, _ = D.fit_ab(X, 2, m2["A"], m2["s"], NUGGET, Xq)
+    pcs = [DB.pieces(R.NP, X, m, lo, hi, kind, Xq, a, b), DB.pieces(R.NP, X, m2, lo, hi, kind, Xq, a2, b2)]
+    vs = [v, v2]
+    if weight is None:
+        pcs, vs = pcs[:1], vs[:1]
+    nb = len(Xq)                                                                              # every candidate: the design point among them
+    g = DB.greedy(pcs, vs, NUGGET, nb, weight)
+    conditions = [[s in g["S"][c] for s in g["pick"]] for c in range(len(pcs))]
+    for j in range(nb + 1):
+        f = DB.forced(pcs, vs, NUGGET, g["pick"], j, weight, conditions)
+        assert f["S"] == [[s for s in g["S"][c] if s in set(g["pick"][:j])] for c in range(len(pcs))]
+        if j == 0:
+            assert np.array_equal(f["tot"], g["gain_first"])
+        if j == nb:
+            assert np.all(np.isneginf(g["gain_last"])) and np.array_equal(f["tot_scale"], g["last_scale"])
+            continue
+        s = g["pick"][j]
+        assert f["tot"][s] == g["pick_gain"][j] and f["tot_scale"][s] == g["pick_scale"][j]
+        assert np.array_equal(f["gain"][s], g["pick_gain_ctx"][j]) and np.array_equal(f["gain_scale"][s], g["pick_scale_ctx"][j])
+        free = np.ones(nb, dtype=bool)
+        free[g["pick"][:j]] = False
+        assert s == int(np.argmax(np.where(free, f["tot"], -np.inf)))
+        if j:
+            (lam, mu, E), _ = f["state"][0]
+            (rl, rm, rE), _ = DB.state(*pcs[0], vs[0], NUGGET, f["S"][0])
+            assert np.array_equal(lam, rl) and np.array_equal(mu, rm) and np.array_equal(E, rE)
+    short = DB.greedy(pcs, vs, NUGGET, 3, weight)                                             # a shorter batch: gain_last of the candidates left
+    f = DB.forced(pcs, vs, NUGGET, short["pick"], 3, weight)
+    free = np.ones(nb, dtype=bool)
+    free[short["pick"]] = False
+    assert np.array_equal(f["tot"][free], short["gain_last"][free])
+
+
+@pytest.mark.parametrize("N,d,order", CASES)
+def test_the_carried_recurrence_is_the_direct_form(N, d, order):
+    """`carried` (the recurrences the device uses, the base of the leave-out tests) against `state` and `conditional`"""
+    X, m, kind, lo, hi, w, Xq, a, b, v = inputs(N, d, order, "design")
+    pc = DB.pieces(R.NP, X, m, lo, hi, kind, Xq, a, b)
+    S = DB.greedy([pc], [v], NUGGET, K)["S"][0]
+    lam, mu, E, vS, numS, gain = DB.carried(pc[0], pc[1], v, NUGGET, S)
+    (rl, rm, rE), (ls, ms, es) = DB.state(*pc, v, NUGGET, S)
+    cn, cs = DB.conditional(R.NP, *pc, v, NUGGET, S)
+    t = CANCEL * TD.bar(m, w)
+    assert np.all(np.abs(lam - rl) <= t * ls) and np.all(np.abs(mu - rm) <= t * ms) and np.all(np.abs(E - rE) <= t * es)
+    assert np.all(np.abs(vS - cn["var"]) <= t * cs["var"]) and np.all(np.abs(numS - cn["num"]) <= t * cs["num"])
+    assert np.all(np.abs(gain - cn["gain"]) <= t * cs["gain"])
+
+
 def test_two_identical_candidates():
     """of two identical candidates the lower index is picked, and its twin gains next to nothing afterwards"""
     X, m, kind, lo, hi, w, Xq, a, b, v = inputs(11, 3, 1, "design")

@@ -163,9 +163,55 @@ def selection_stat(M):
     return stat
 
 
-@pytest.mark.parametrize("M", [1, 63, 64, 65, 257, 1000, 1024, 1025, 2500])
+# 64 and 65 workgroups of 1024 points (the scan's sum across its waves), 256 and 257 (its carry into a second trip), 293
+LARGE_MS = [65536, 65537, 262144, 262145, 300001]
+KEEP_PATTERNS = ("whole-workgroups", "last-point", "workgroups-64-255-256", "everything", "nothing", "nan-in-workgroup-256")
+
+
+def keep_pattern(name, M):
+    """-> stat[5, M] whose points are kept under (cut_chi2 4, level 1, cut_I 2) by the named pattern: uneven prefix sums, where
+    selection_stat keeps about the same share of every workgroup"""
+    rng = np.random.default_rng(177 + M)
+    wg = np.arange(M) // 1024
+    if name == "whole-workgroups":                        # runs of whole workgroups kept next to runs with none, of uneven lengths
+        keep = rng.random(wg.max() + 1)[wg] < 0.5
+    elif name == "last-point":
+        keep = np.arange(M) == M - 1
+    elif name == "workgroups-64-255-256":
+        keep = np.isin(wg, (64, 255, 256)) & (rng.random(M) < 0.7)
+    elif name == "nothing":
+        keep = np.zeros(M, dtype=bool)
+    else:
+        keep = np.ones(M, dtype=bool)
+    stat = np.empty((5, M))
+    stat[0] = np.where(keep, 1.0 + rng.random(M), 5.0 + rng.random(M))
+    stat[1] = rng.standard_normal(M)
+    stat[2:] = -np.sort(-rng.random((3, M)), axis=0)
+    if name == "nan-in-workgroup-256":                    # a NaN in either row the cuts read: never kept
+        at = np.flatnonzero(wg == 256)
+        stat[0, at[::3]] = np.nan
+        stat[2, at[1::7]] = np.nan
+    return stat
+
+
+@pytest.mark.parametrize("M", [1, 63, 64, 65, 257, 1000, 1024, 1025, 2500] + LARGE_MS)
 def test_select_matches_numpy(ctx, M):
     stat = selection_stat(M)
+    if M in LARGE_MS:
+        for name in KEEP_PATTERNS:
+            st = keep_pattern(name, M)
+            got = ctx.calib_select(st, 4.0, 1, 2.0)
+            want = numpy_select(st, 4.0, 1, 2.0)
+            print(f"M {M} {name}: {want.size} kept")
+            assert np.array_equal(got, want), (M, name)
+            if name == "everything":
+                assert np.array_equal(got, np.arange(M, dtype=np.int32))
+            if name == "nothing":
+                assert got.size == 0
+            if name == "last-point":
+                assert got.tolist() == [M - 1]
+            if name == "nan-in-workgroup-256" and M > 262144:
+                assert 0 < M - got.size <= 1024 and not np.isnan(st[0, got]).any() and not np.isnan(st[2, got]).any()
     for cut_chi2, level, cut_I in [(np.inf, 1, 3.0), (4.0, 1, np.inf), (5.0, 2, 2.0), (np.inf, 3, 1.0), (np.inf, 1, np.inf),
                                    (-1.0, 1, np.inf), (np.inf, 2, -1.0)]:
         got = ctx.calib_select(stat, cut_chi2, level, cut_I)
@@ -231,6 +277,40 @@ def test_select_on_downloaded_stat_and_dev_entry(ctx):
     assert n == want.size and np.array_equal(idx[:n], want)
     assert g[:n].tobytes() == np.ascontiguousarray(stat[:, want].T).tobytes() and np.array_equal(gw[:n], worst[want])
     assert np.all(g[n:] == -7.0) and np.all(gw[n:] == -7)          # nothing beyond the count is written
+
+
+@pytest.mark.parametrize("M,name", [(2500, "whole-workgroups"), (262145, "workgroups-64-255-256"), (300001, "whole-workgroups")])
+def test_select_dev_then_gather_dev_beyond_256(ctx, M, name):
+    """gpemu_calib_select_dev then gpemu_calib_gather_dev with more than 256 survivors (the gather's workgroups >= 1), with and
+    without `worst`: every gathered row is the bits of stat[:, idx], nothing beyond the count is written"""
+    stat = keep_pattern(name, M)
+    worst = np.random.default_rng(M).integers(0, 64, M).astype(np.int32)
+    want = numpy_select(stat, 4.0, 1, 2.0)
+    assert 256 < want.size < M
+    ds, di, dw, dg, dgw = (ctx.dev_alloc(s) for s in (8 * 5 * M, 4 * M, 4 * M, 8 * 5 * M, 4 * M))
+    try:
+        ctx.upload(ds, stat)
+        ctx.upload(dw, worst)
+        ctx.upload(di, np.full(M, -1, dtype=np.int32))
+        n = ctx.calib_select_dev(M, ds, 4.0, 1, 2.0, di)
+        idx = ctx.download(di, (M,), dtype=np.int32)
+        assert n == want.size and np.array_equal(idx[:n], want) and np.all(idx[n:] == -1)
+        rows = np.ascontiguousarray(stat[:, want].T)
+        for with_worst in (True, False):
+            ctx.upload(dg, np.full((M, 5), -7.0))
+            ctx.upload(dgw, np.full(M, -7, dtype=np.int32))
+            ctx.calib_gather_dev(M, ds, dw if with_worst else None, n, di, dg, dgw)
+            ctx.sync()
+            g, gw = ctx.download(dg, (M, 5)), ctx.download(dgw, (M,), dtype=np.int32)
+            assert g[:n].tobytes() == rows.tobytes(), (M, with_worst)
+            assert np.all(g[n:] == -7.0)
+            if with_worst:
+                assert np.array_equal(gw[:n], worst[want]) and np.all(gw[n:] == -7)
+            else:
+                assert np.all(gw == -7)                   # without `worst` nothing is written there
+    finally:
+        for p in (ds, di, dw, dg, dgw):
+            ctx.dev_free(p)
 
 
 # ------------------------------------------------------------------ 4. error codes
