@@ -523,8 +523,8 @@ int gpemu_sens_main_var(gpemu_ctx *ctx, const double *lo, const double *hi, int 
  * the state; GPEMU_ERR_STATE without a prediction set-up; then GPEMU_ERR_ARG for a Matern model, a non-finite bound, hi_l <= lo_l
  * or a Gaussian coordinate with sd <= 0.
  * Not built: the gradient of gain with respect to x* and any optimiser over it (greedy batches: gpemu_design_batch below);
- * Matern kernels; gain for a target other than the IMSE (Sobol-index uncertainty, a calibration region);
- * correlated Gaussian measures. */
+ * Matern kernels in this closed form (gpemu_design_target_gain below takes them: its target is a point set); gain for a
+ * target other than the IMSE or a point set (Sobol-index uncertainty); correlated Gaussian measures. */
 int gpemu_design_gain(gpemu_ctx *ctx, const double *lo, const double *hi /* d each, host */, int npoints,
                       const double *xq /* npoints*d host */, double *gain /* npoints */, double *num /* npoints or NULL */,
                       double *var /* npoints or NULL */);
@@ -577,6 +577,54 @@ int gpemu_design_batch(gpemu_ctx *const *ctxs, int nctx, const double *weight /*
 int gpemu_design_batch_dev(gpemu_ctx *const *ctxs, int nctx, const double *weight /* HOST */, const double *lo, const double *hi /* HOST */,
                            int npoints, const double *xq_dev, int nbatch, int *pick_dev, double *pick_gain_dev, double *pick_gain_ctx_dev,
                            double *gain_first_dev, double *gain_last_dev);
+
+/* ---- gain over a weighted set of target points: variance drop where the posterior is -----------------
+ * After a calibration the next run is wanted where the emulator's variance drops over the region the observations left
+ * standing, not over the box.  That region is a weighted point set x_s, w_s >= 0, s = 1 .. S (chain samples of
+ * gpemu_calib_sample, the points gpemu_calib_select kept, quadrature nodes); no integral has to exist in closed form, so
+ * every covariance function is served.  With u = L^-1 k, r = h - W^T k (the quantities of gpemu_predict_cov) and
+ *   c*(x_s, x*) = c(x_s, x*) - u_s . u_* + r_*^T Q r_s
+ * for each of npoints candidates x*
+ *   var  = c*(x*, x*) + nugget                (the variance a run at x* is observed with; gpemu_design_gain's var),
+ *   num  = sum_s w_s c*(x_s, x*)^2,
+ *   gain = num / var = sum_s w_s [v(x_s) - v_{+x*}(x_s)],      hyper-parameters as they are,
+ * and the set entry returns v(x_s) = c*(x_s, x_s) (latent: no nugget) per target and target_var = sum_s w_s v(x_s), so that
+ * 0 <= gain <= target_var.  Conventions of gpemu_design_gain, not of gpemu_predict_cov: no k-vector clamp, no nugget rule
+ * inside c or k (a target or candidate on a design point, or on each other, gets the bare kernel value); var carries the
+ * nugget once; where var rounds to <= 0 gain is 0; num and var (either may be NULL) are returned as computed.  The weights
+ * are used as given (NULL: 1 / S each), not normalised.
+ * How it runs, on the context's stream.  gpemu_design_target_set copies coordinates and weights into the context and builds
+ * the resident store per block of up to 16 384 targets through the prediction batch buffers, as gpemu_design_gain_dev uses
+ * them: the unclamped nugget-free k rows (the stored fill, mode 0), the product with [L^-1; gamma; W^T], the prediction's
+ * finish for v, Q r per target; u (S' x Np), r and Q r are copied out, target_var is summed in one fixed order.  The store
+ * belongs to one prediction set-up: after another gpemu_predict_setup the next gain call rebuilds it from the kept
+ * coordinates.  gpemu_design_target_gain, per block of up to 16 384 candidates: the same chain (var as the prediction's finish
+ * takes it), then per panel of target columns (GPEMU_TARGET_PANEL in the environment at gpemu_ctx_create, a multiple of 64,
+ * default 2048) the full product P = U_q U_t^T on the GEMM, a sweep of one workgroup per 64 candidates x 64 targets (the tile
+ * of P read as row pieces, c through the stored fill's tile function, r . Q r from LDS, w_s c*^2 reduced over the tile's 64
+ * targets in a fixed order: one partial per candidate and target tile) and a finish that adds the partials in ascending tile
+ * order to the running num and forms the quotient behind the last panel.  No atomics, no workgroup waits for another; the sum
+ * over the targets has one order: two calls return the same bits, so do the host and _dev entries, a candidate alone and in
+ * a batch, any panel width, and a context set up by gpemu_predict_setup_batch.  A pending prediction batch stays collectable.
+ * Limits: 1 <= ntargets <= 65 536; npoints >= 1.  Memory: 8 S' (Np + 2 Rp + d + 2) bytes for the store (S' = ntargets rounded
+ * up to 64), per block of mb candidates 8 mb (64 + panel + panel / 64 + 3) more; gpemu_design_target_release, gpemu_set_model
+ * and gpemu_ctx_destroy free it.  The _set entries wait for the upload of the weights; everything else of the _dev entries is
+ * only enqueued.
+ * Errors, before anything is allocated or launched: GPEMU_ERR_ARG for a NULL ctx, xt, xq or gain, a count out of range, a
+ * negative or non-finite weight, weights that sum to 0 and (host entries: device coordinates are not read) a non-finite
+ * coordinate; then GPEMU_ERR_STATE without a prediction set-up, and for a gain call without targets.
+ * Not built: greedy batches over a target set (they need the M x S matrix kept and a rank-one pass per pick); weights in
+ * device memory; more than 65 536 targets; the gradient of the gain; targets drawn by the library itself. */
+int gpemu_design_target_set(gpemu_ctx *ctx, int ntargets, const double *xt /* ntargets*d host */,
+                            const double *weight /* ntargets host, or NULL: 1/ntargets each */, double *target_var /* 1, may be NULL */,
+                            double *var_t /* ntargets, may be NULL */);
+int gpemu_design_target_set_dev(gpemu_ctx *ctx, int ntargets, const double *xt_dev, const double *weight /* HOST or NULL */,
+                                double *target_var_dev, double *var_t_dev);
+int gpemu_design_target_gain(gpemu_ctx *ctx, int npoints, const double *xq /* npoints*d host */, double *gain /* npoints */,
+                             double *num /* npoints or NULL */, double *var /* npoints or NULL */);
+int gpemu_design_target_gain_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *gain_dev, double *num_dev /* or NULL */,
+                                 double *var_dev /* or NULL */);
+int gpemu_design_target_release(gpemu_ctx *ctx);
 
 /* ---- second-order Sobol indices and interaction surfaces, in closed form -----------------
  * VT_j - V_j > 0 says that parameter j interacts with something; these entries say with which parameter, and what the
@@ -879,6 +927,7 @@ int gpemu_sync(gpemu_ctx *ctx);
 #define GPEMU_PROF_SENS_POST 15 /* the four launches of gpemu_sens_post[_dev], L = n (n + 1) / 2 lower tiles with n = ceil(N / 64) -- prep (as GPEMU_PROF_SENS), pmat (flops = L (128 nreg^2 + 4096 (2 nreg + 1)): G for the tile's 64 rows, then a product of length nreg per pair; bytes = 8 * 8192 L: the corner's tile read, P's written), weighted sweep (flops = 4096 L (20 d + 3): the pair terms of GPEMU_PROF_SENS with one product more per coordinate and the rank-one sum; bytes = 8 (4096 L + T'), T' = L (2 d + 2): P read, the partial sums written), finish (flops = T' + (2 d + 2) nreg (2 nreg + 4 N), bytes = 8 (T' + (2 d + 2) 3 N nreg)) -- and of gpemu_sens_main_var: prep, then per block of mb rows tvec (flops = 6 mb N, bytes = 8 mb' Np, mb' = mb rounded up to 64) and band finish (flops = mb (2 Np + 2 nreg^2), bytes = 8 mb (Np + 64)); the corner and the band's product report under GPEMU_PROF_GEMM */
 #define GPEMU_PROF_CALIB   16  /* the launch of gpemu_calib_eval[_dev] (flops = M (4 nt R + 8 nt + R^3 / 3 + 2 R^2), R = nr rounded up to 4: two multiply-adds per output and component, the finish of an output, the Cholesky and the solve in T; bytes = 8 M (2 nr + 5) + 4 M: mean and var read, stat and worst written) and the three of gpemu_calib_select[_dev], bracketed as ONE entry: count (16 M bytes: two rows of stat read), scan (8 ceil(M / 1024)), scatter (16 M + 4 kept, counted with kept = M), bytes = 36 M + 8 ceil(M / 1024), no flops */
 #define GPEMU_PROF_DESIGN  17  /* the launches of gpemu_design_gain[_dev] that are its own: prep (as GPEMU_PROF_SENS), kmat when [K ; HK] is rebuilt (flops = 19 d N^2 / 2, bytes = 8 Np (Np + 64)), then per block of mb candidates their prep, kvec (flops = mb N (3 d + 2), bytes = 8 mb' Np), the transpose of a (bytes = 16 mb' Np), the cross sweep (flops = mb N (19 d + 4), bytes = 8 mb (2 N + ceil(N / 64))) and the finish (flops = mb (2 Np + 2 nreg^2 + 19 d), bytes = 8 mb (Np + 64)); the three products report under GPEMU_PROF_GEMM */
+#define GPEMU_PROF_DESIGN_TARGET 18 /* the launches of gpemu_design_target_set / _gain[_dev] that are their own: per block of mb points the k fill (flops = mb N (3 d + 2), bytes = 8 mb' Np); per panel of ns targets the sweep (flops = mb ns (3 d + 2 nreg + 25), bytes = 8 mb (ns + ceil(ns / 64))) and the finish (flops = mb ceil(ns / 64), bytes = 8 mb (ceil(ns / 64) + 3)); the sum of target_var (flops = 2 S, bytes = 16 S); the products, the prediction's finish and Q r report under GPEMU_PROF_GEMM or not at all */
 /* GPEMU_PROF_SENS*, under a measure (gpemu_sens_set_measure): in every sweep a GAUSSIAN coordinate's pair factor counts 12
  * flops (one exp among 11 others) where a uniform one counts 19 (one exp and two erf or erfc among 16): 19 d above becomes
  * 19 d_u + 12 d_g, and in the pair sweeps the 8 / 16 factors of a block are taken in the proportion d_u : d_g.  The prep and
@@ -1144,6 +1193,12 @@ int gpemu_test_design_state(gpemu_ctx *ctx, int npoints, double *a_out /* npoint
 /* the same for gpemu_design_batch: lambda and mu (npoints x nbatch each) and E (nbatch x nbatch) of this context's part in the
  * last call, bit for bit; GPEMU_ERR_STATE where the last call had other sizes */
 int gpemu_test_design_batch_state(gpemu_ctx *ctx, int npoints, int nbatch, double *lam_out, double *mu_out, double *e_out);
+/* the same for gpemu_design_target_*: the rows of u (N each), r and Q r (nreg each), bit for bit what the panel product and
+ * the sweep read.  which = 0: the resident store of the npoints targets; which = 1: the last block of candidates of the last
+ * gain call (its u and Q r rows still lie in the prediction batch buffer: call it directly behind that gain call).
+ * GPEMU_ERR_STATE where no store or block of this size is there. */
+int gpemu_test_design_target_state(gpemu_ctx *ctx, int which, int npoints, double *u_out /* npoints*N */, double *r_out /* npoints*nreg */,
+                                   double *qr_out /* npoints*nreg */);
 /* the workgroup -> tile table of a GEMM launch with tiles_m x tiles_n tiles (tri = 1: lower triangle) and super-blocks
  * of sb x sb tiles: entry q * 8 + x is the q-th tile of XCD x, (tm << 16) | tn, or -1 (unused tail slot).  Host logic
  * only (no device).  Returns the table length, or -GPEMU_ERR_ARG; writes min(length, cap) entries to out. */

@@ -26,6 +26,7 @@ PROF_SENS = 14
 PROF_SENS_POST = 15
 PROF_CALIB = 16
 PROF_DESIGN = 17
+PROF_DESIGN_TARGET = 18
 CALIB_MAX_R, CALIB_MAX_NT = 16, 1024
 MODE_EXACT_GRAD, MODE_MATERN_LOG = 1, 2
 MEASURE_UNIFORM, MEASURE_GAUSS = 0, 1
@@ -173,6 +174,12 @@ SYMBOLS = {
     "gpemu_design_batch_dev": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_test_design_batch_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "gpemu_design_target_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpemu_design_target_set_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _dp, C.c_void_p, C.c_void_p]),
+    "gpemu_design_target_gain": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpemu_design_target_gain_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_design_target_release": (C.c_int, [C.c_void_p]),
+    "gpemu_test_design_target_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpemu_sens_pairs": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp]),
     "gpemu_sens_pairs_dev": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "gpemu_sens_pairs_post": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -818,6 +825,46 @@ class Context:
         lam, mu, E = np.empty((M, nbatch)), np.empty((M, nbatch)), np.empty((nbatch, nbatch))
         self._chk(self.L.gpemu_test_design_batch_state(self.h, M, nbatch, _p(lam), _p(mu), _p(E)))
         return lam, mu, E
+
+    # gain over a weighted set of target points
+    def design_target_set(self, Xt, weight=None):
+        """Xt[S, d], weight[S] (None: 1 / S each) -> dict(target_var, var_t[S]): the resident target store of this context"""
+        Xt = _a(Xt).reshape(-1, self.d)
+        S = Xt.shape[0]
+        w = None if weight is None else _a(weight).ravel()
+        if w is not None and w.size != S:
+            raise GpemuError(ERR_ARG, "design_target_set: one weight per target")
+        tv, vt = np.empty(1), np.empty(S)
+        self._chk(self.L.gpemu_design_target_set(self.h, S, _p(Xt), _po(w), _p(tv), _p(vt)))
+        return dict(target_var=tv[0], var_t=vt)
+
+    def design_target_set_dev(self, S, xt_dev, weight=None, target_var_dev=None, var_t_dev=None):
+        """xt_dev (S x d), target_var_dev (1), var_t_dev (S): device memory, the last two may be None; weight: HOST or None"""
+        w = None if weight is None else _a(weight).ravel()
+        if w is not None and w.size != S:
+            raise GpemuError(ERR_ARG, "design_target_set_dev: one weight per target")
+        self._chk(self.L.gpemu_design_target_set_dev(self.h, S, xt_dev, _po(w), target_var_dev, var_t_dev))
+
+    def design_target_gain(self, Xq):
+        """Xq[M, d] -> dict(gain[M], num[M], var[M]): gain = num / var = the drop of the weighted variance over the targets"""
+        Xq = _a(Xq).reshape(-1, self.d)
+        M = Xq.shape[0]
+        gain, num, var = np.empty(M), np.empty(M), np.empty(M)
+        self._chk(self.L.gpemu_design_target_gain(self.h, M, _p(Xq), _p(gain), _p(num), _p(var)))
+        return dict(gain=gain, num=num, var=var)
+
+    def design_target_gain_dev(self, M, xq_dev, gain_dev, num_dev=None, var_dev=None):
+        """xq_dev (M x d), gain_dev, num_dev, var_dev (M each; the last two may be None): device memory"""
+        self._chk(self.L.gpemu_design_target_gain_dev(self.h, M, xq_dev, gain_dev, num_dev, var_dev))
+
+    def design_target_release(self):
+        self._chk(self.L.gpemu_design_target_release(self.h))
+
+    def design_target_state(self, which, npoints):
+        """-> (u[n, N], r[n, nreg], qr[n, nreg]) bit for bit as the sweep reads them: which = 0 the targets, 1 the last candidate block"""
+        u, r, qr = np.empty((npoints, self.N)), np.empty((npoints, self.nreg)), np.empty((npoints, self.nreg))
+        self._chk(self.L.gpemu_test_design_target_state(self.h, which, npoints, _p(u), _p(r), _p(qr)))
+        return u, r, qr
 
     def sens_pairs(self, lo, hi, other=None):
         """-> cov_pair[d (d - 1) / 2] of this context and `other` (default: itself) on one design"""

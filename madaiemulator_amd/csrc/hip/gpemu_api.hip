@@ -189,6 +189,8 @@ static Sched read_environment()
 	sc.panel_rows = v >= 0 && v <= 2 ? v : 1;
 	v = geti("GPEMU_PANEL_SPLIT", 1);
 	sc.panel_split = v >= 0 && v <= (1 << 16) ? v : 1;
+	v = geti("GPEMU_TARGET_PANEL", 2048);
+	sc.target_panel = v >= 64 && v <= (1 << 16) && v % 64 == 0 ? v : 2048;
 	return sc;
 }
 
@@ -259,6 +261,16 @@ static int grow(gpemu_ctx *ctx, B &buf, size_t n, bool graphed = false, const ch
 	return GPEMU_OK;
 }
 
+// the target set of gpemu_design_target_* and everything those entries keep (the caller has waited for the stream)
+static void free_targets(gpemu_ctx *ctx)
+{
+	for (auto *b : {&ctx->dTgtX, &ctx->dTgtW, &ctx->dTgtU, &ctx->dTgtR, &ctx->dTgtQr, &ctx->dTgtVar, &ctx->dTgtSum, &ctx->dTgtCR, &ctx->dTgtPanel,
+	                &ctx->dTgtPart, &ctx->dTgtScr, &ctx->dTgtIO})
+		b->reset();
+	ctx->tgt_S = ctx->tgt_mb = 0;
+	ctx->tgt_serial = 0;
+}
+
 // everything sized by the model (the per-matrix result slots, the symmetric-matrix cache and the upload ring stay)
 static void free_model(gpemu_ctx *ctx)
 {
@@ -285,6 +297,7 @@ static void free_model(gpemu_ctx *ctx)
 	                &ctx->dBatchIO})
 		b->reset();
 	ctx->batch_mb = ctx->batch_nb = 0;
+	free_targets(ctx);
 	ctx->hStage.reset();
 	ctx->hLoo.reset();
 	ctx->hMGrad.reset();
@@ -2868,6 +2881,242 @@ extern "C" int gpemu_test_design_batch_state(gpemu_ctx *ctx, int npoints, int nb
 	HIPCHK(ctx, hipMemcpyAsync(lam_out, ctx->dBatchLam, n, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipMemcpyAsync(mu_out, ctx->dBatchMu, n, hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipMemcpy2DAsync(e_out, row, ctx->dBatchE, 256 * sizeof(double), row, (size_t)nbatch, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// gain over a weighted set of target points (gpemu.h).  The store of the targets -- u, r and Q r per target, v(x_s)
+// and the target variance -- is built per block of up to PRED_BATCH_MAX targets through dKq and dV in stream order, by the chain of
+// gpemu_design_gain_dev from its k fill to launch_predict_qr with the fill of every covariance function in its place (mode 0, nugget
+// 0), and copied out of dV; it belongs to one prediction set-up (tgt_serial) and is rebuilt from the kept coordinates by the first
+// gain call after another.  Per block of candidates the same chain, then per panel of target columns P = U_q U_t^T on the GEMM,
+// the sweep and the finish.  Everything else written is the entries' own (dTgt*).
+// ---------------------------------------------------------------------------
+constexpr int TARGET_MAX = 65536;
+
+// the covariance parameters of the set-up without the nugget: c(., .) is the bare kernel value wherever two points lie
+static CovParams target_cov(const gpemu_ctx *ctx)
+{
+	CovParams p = ctx->pred_cov;
+	p.nug = 0.0;
+	return p;
+}
+
+// the chain both halves share, for the mb points xq (device): unclamped k rows, V = Kq LinvAug^T, the variance with c(x, x) =
+// kappa, then Q r into V's columns Np .. with r kept in rkeep
+static int target_chain(gpemu_ctx *ctx, const CovParams &p, const double *xq, int mb, double kappa, double *mean_scratch, double *var_out,
+                        double *rkeep)
+{
+	const int N = ctx->N, d = ctx->d, Np = ctx->Np, Rp = ctx->Rp, mbp = round_up(mb, 64);
+	const long ldv = (long)Np + Rp;
+	if (prof_on(ctx, GPEMU_PROF_DESIGN_TARGET)) ctx->prof.tag.push_back("target_kvec");
+	{
+		ProfScope ps(ctx, GPEMU_PROF_DESIGN_TARGET, (double)mb * N * (3.0 * d + 2.0), 8.0 * (double)mbp * Np);
+		HIPCHK(ctx, launch_cov_fill(ctx->stream, ctx->dKq, Np, xq, mb, mbp, ctx->dX, N, Np, d, p, 0));
+	}
+	HIPCHK(ctx, launch_aug_product(ctx, aug_product_args(ctx, mb)));
+	HIPCHK(ctx, launch_predict_finish(ctx->stream, ctx->dV, ldv, mb, Np, ctx->nreg, ctx->order, d, xq, ctx->dBetaQ, kappa, mean_scratch, var_out, 1,
+	                                  (long)mbp * ldv));
+	HIPCHK(ctx, launch_predict_qr(ctx->stream, ctx->dV, ldv, mb, Np, Rp, ctx->nreg, d, xq, ctx->dBetaQ, rkeep));
+	return GPEMU_OK;
+}
+
+// the store of the tgt_S targets in dTgtX / dTgtW for the present set-up
+static int target_build(gpemu_ctx *ctx)
+{
+	const int S = ctx->tgt_S, d = ctx->d, Np = ctx->Np, Rp = ctx->Rp, Sp = round_up(S, 64);
+	const int cap = std::min(PRED_BATCH_MAX, Sp);
+	const long ldv = (long)Np + Rp;
+	ctx->tgt_serial = 0;
+	int rc = ensure_pred_batch(ctx, cap);
+	if (!rc) rc = grow(ctx, ctx->dTgtU, (size_t)Sp * Np, false, "out of device memory for the targets' u rows (8 S' Np bytes)");
+	if (!rc) rc = grow(ctx, ctx->dTgtR, (size_t)Sp * Rp);
+	if (!rc) rc = grow(ctx, ctx->dTgtQr, (size_t)Sp * Rp);
+	if (!rc) rc = grow(ctx, ctx->dTgtVar, (size_t)Sp);
+	if (!rc) rc = grow(ctx, ctx->dTgtSum, 1);
+	if (!rc) rc = grow(ctx, ctx->dTgtScr, 3 * (size_t)cap);
+	if (rc) return rc;
+	const CovParams p = target_cov(ctx);
+	for (int s0 = 0; s0 < S; s0 += cap) {
+		const int mb = std::min(cap, S - s0);
+		// v(x_s) is latent: c(x_s, x_s) = the amplitude, no nugget
+		if ((rc = target_chain(ctx, p, ctx->dTgtX + (size_t)s0 * d, mb, p.amp, ctx->dTgtScr, ctx->dTgtVar + s0, ctx->dTgtR + (size_t)s0 * Rp)))
+			return rc;
+		HIPCHK(ctx, hipMemcpy2DAsync(ctx->dTgtU + (size_t)s0 * Np, (size_t)Np * sizeof(double), ctx->dV, (size_t)ldv * sizeof(double),
+		                             (size_t)Np * sizeof(double), (size_t)mb, hipMemcpyDeviceToDevice, ctx->stream));
+		HIPCHK(ctx, hipMemcpy2DAsync(ctx->dTgtQr + (size_t)s0 * Rp, (size_t)Rp * sizeof(double), ctx->dV + Np, (size_t)ldv * sizeof(double),
+		                             (size_t)Rp * sizeof(double), (size_t)mb, hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	if (prof_on(ctx, GPEMU_PROF_DESIGN_TARGET)) ctx->prof.tag.push_back("target_var");
+	{
+		ProfScope ps(ctx, GPEMU_PROF_DESIGN_TARGET, 2.0 * S, 16.0 * S);
+		HIPCHK(ctx, launch_design_target_var(ctx->stream, ctx->dTgtW, ctx->dTgtVar, S, ctx->dTgtSum));
+	}
+	ctx->tgt_serial = ctx->pred_serial;
+	ctx->tgt_mb = 0;
+	return GPEMU_OK;
+}
+
+// weight: ntargets finite values >= 0 with a positive sum, or NULL
+static bool target_weights_ok(int ntargets, const double *weight)
+{
+	if (!weight) return true;
+	double sum = 0.0;
+	for (int s = 0; s < ntargets; s++) {
+		if (!std::isfinite(weight[s]) || weight[s] < 0.0) return false;
+		sum += weight[s];
+	}
+	return sum > 0.0;
+}
+
+// both set entries behind their checks: xt in host or device memory, the results into host or device memory
+static int target_set(gpemu_ctx *ctx, int S, const double *xt, bool host, const double *weight, double *target_var, double *var_t)
+{
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d, Sp = round_up(S, 64);
+	ctx->tgt_S = 0;
+	ctx->tgt_serial = 0;
+	int rc = grow(ctx, ctx->dTgtX, (size_t)Sp * d);
+	if (!rc) rc = grow(ctx, ctx->dTgtW, (size_t)Sp);
+	if (rc) return rc;
+	std::vector<double> w((size_t)S, 1.0 / S);
+	if (weight) w.assign(weight, weight + S);
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dTgtX, xt, (size_t)S * d * sizeof(double), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(ctx->dTgtW, w.data(), (size_t)S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // w is this call's own: its upload is waited for
+	ctx->tgt_S = S;
+	if ((rc = target_build(ctx))) return rc;
+	const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+	if (target_var) HIPCHK(ctx, hipMemcpyAsync(target_var, ctx->dTgtSum, sizeof(double), out, ctx->stream));
+	if (var_t) HIPCHK(ctx, hipMemcpyAsync(var_t, ctx->dTgtVar, (size_t)S * sizeof(double), out, ctx->stream));
+	if (host) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_design_target_set_dev(gpemu_ctx *ctx, int ntargets, const double *xt_dev, const double *weight, double *target_var_dev,
+                                           double *var_t_dev)
+{
+	if (!ctx || !xt_dev || ntargets < 1 || ntargets > TARGET_MAX || !target_weights_ok(ntargets, weight)) return GPEMU_ERR_ARG;
+	return target_set(ctx, ntargets, xt_dev, false, weight, target_var_dev, var_t_dev);
+}
+
+extern "C" int gpemu_design_target_set(gpemu_ctx *ctx, int ntargets, const double *xt, const double *weight, double *target_var, double *var_t)
+{
+	if (!ctx || !xt || ntargets < 1 || ntargets > TARGET_MAX || !target_weights_ok(ntargets, weight)) return GPEMU_ERR_ARG;
+	if (ctx->d > 0)
+		for (size_t e = 0; e < (size_t)ntargets * ctx->d; e++)
+			if (!std::isfinite(xt[e])) return fail(ctx, GPEMU_ERR_ARG, "design target: a coordinate is not finite");
+	return target_set(ctx, ntargets, xt, true, weight, target_var, var_t);
+}
+
+extern "C" int gpemu_design_target_release(gpemu_ctx *ctx)
+{
+	if (!ctx) return GPEMU_ERR_ARG;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	free_targets(ctx);
+	return GPEMU_OK;
+}
+
+static int target_gain_check(gpemu_ctx *ctx, int npoints, const void *xq, const void *gain)
+{
+	if (!ctx || !xq || !gain || npoints < 1) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->tgt_S < 1) return fail(ctx, GPEMU_ERR_STATE, "gpemu_design_target_set has not been called");
+	return GPEMU_OK;
+}
+
+extern "C" int gpemu_design_target_gain_dev(gpemu_ctx *ctx, int npoints, const double *xq_dev, double *gain_dev, double *num_dev, double *var_dev)
+{
+	if (const int rc = target_gain_check(ctx, npoints, xq_dev, gain_dev)) return rc;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const int d = ctx->d, Np = ctx->Np, Rp = ctx->Rp, nreg = ctx->nreg, M = npoints, S = ctx->tgt_S;
+	const int cap = std::min(PRED_BATCH_MAX, round_up(M, 64)), pw = std::min(ctx->sched.target_panel, round_up(S, 64));
+	const long ldv = (long)Np + Rp;
+	int rc = ensure_pred_batch(ctx, cap);
+	if (!rc) rc = grow(ctx, ctx->dTgtCR, (size_t)cap * Rp);
+	if (!rc) rc = grow(ctx, ctx->dTgtPanel, (size_t)cap * pw, false, "out of device memory for a panel of the targets' product (8 M' panel bytes)");
+	if (!rc) rc = grow(ctx, ctx->dTgtPart, (size_t)(pw / 64) * cap);
+	if (!rc) rc = grow(ctx, ctx->dTgtScr, 3 * (size_t)cap);
+	if (!rc && ctx->tgt_serial != ctx->pred_serial) rc = target_build(ctx);     // another set-up since: the store from the kept coordinates
+	if (rc) return rc;
+	const CovParams p = target_cov(ctx);
+	const bool prof = prof_on(ctx, GPEMU_PROF_DESIGN_TARGET);
+	double *scr_mean = ctx->dTgtScr, *scr_var = scr_mean + cap, *scr_num = scr_var + cap;
+	for (int q0 = 0; q0 < M; q0 += cap) {
+		const int mb = std::min(cap, M - q0);
+		const double *xq = xq_dev + (size_t)q0 * d;
+		double *var = var_dev ? var_dev + q0 : scr_var, *num = num_dev ? num_dev + q0 : scr_num;
+		// var is the variance a run at x* is observed with: c(x*, x*) = kappa carries the nugget once
+		if ((rc = target_chain(ctx, p, xq, mb, ctx->kappa, scr_mean, var, ctx->dTgtCR))) return rc;
+		for (int s0 = 0; s0 < S; s0 += pw) {
+			const int ns = std::min(pw, S - s0), ntile = (ns + 63) / 64;
+			GemmArgs g{};
+			g.C = ctx->dTgtPanel; g.ldc = pw;
+			g.A = ctx->dV; g.lda = ldv;
+			g.B = ctx->dTgtU + (size_t)s0 * Np; g.ldb = Np;
+			g.m = mb; g.n = ns; g.k0 = 0; g.k1 = Np; g.alpha = 1.0; g.beta = 0;
+			HIPCHK(ctx, gemm(ctx, g));
+			if (prof) for (const char *t : {"target_sweep", "target_finish"}) ctx->prof.tag.push_back(t);
+			{
+				// per pair the squared distance (3 d), the kernel (about 20), the regression sum (2 nreg) and the square, weight and
+				// sum (5); the panel read, one partial per candidate and tile written
+				ProfScope ps(ctx, GPEMU_PROF_DESIGN_TARGET, (double)mb * ns * (3.0 * d + 2.0 * nreg + 25.0), 8.0 * (double)mb * (ns + ntile));
+				HIPCHK(ctx, launch_design_target_sweep(ctx->stream, xq, mb, ctx->dTgtX, S, s0, ns, d, p, ctx->dTgtPanel, pw, ctx->dTgtCR, Rp,
+				                                       ctx->dTgtQr, Rp, ctx->dTgtW, nreg, ctx->dTgtPart, cap));
+			}
+			{
+				ProfScope ps(ctx, GPEMU_PROF_DESIGN_TARGET, (double)mb * ntile, 8.0 * (double)mb * (ntile + 3));
+				HIPCHK(ctx, launch_design_target_finish(ctx->stream, ctx->dTgtPart, cap, ntile, mb, s0 == 0, s0 + pw >= S, var, num, gain_dev + q0));
+			}
+		}
+		ctx->tgt_mb = mb;
+	}
+	return GPEMU_OK;
+}
+
+// host buffers: candidates and results through a buffer of the entry's own, so that a pending prediction batch keeps its staging
+extern "C" int gpemu_design_target_gain(gpemu_ctx *ctx, int npoints, const double *xq, double *gain, double *num, double *var)
+{
+	if (const int rc = target_gain_check(ctx, npoints, xq, gain)) return rc;
+	const size_t M = (size_t)npoints, d = (size_t)ctx->d;
+	for (size_t e = 0; e < M * d; e++)
+		if (!std::isfinite(xq[e])) return fail(ctx, GPEMU_ERR_ARG, "design target: a coordinate is not finite");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (const int rc = grow(ctx, ctx->dTgtIO, M * (d + 3))) return rc;
+	double *dx = ctx->dTgtIO, *dg = dx + M * d, *dn = dg + M, *dv = dn + M;
+	HIPCHK(ctx, hipMemcpyAsync(dx, xq, M * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	if (const int rc = gpemu_design_target_gain_dev(ctx, npoints, dx, dg, dn, dv)) return rc;
+	HIPCHK(ctx, hipMemcpyAsync(gain, dg, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (num) HIPCHK(ctx, hipMemcpyAsync(num, dn, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (var) HIPCHK(ctx, hipMemcpyAsync(var, dv, M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	return GPEMU_OK;
+}
+
+// u (npoints x N), r and Q r (npoints x nreg each) bit for bit as the sweep reads them (parity tests): which = 0 the resident
+// store of the npoints targets, which = 1 the last block of candidates of the last gain call -- its u and Q r rows are read out of
+// the prediction batch buffer, so the call has to follow that gain call directly
+extern "C" int gpemu_test_design_target_state(gpemu_ctx *ctx, int which, int npoints, double *u_out, double *r_out, double *qr_out)
+{
+	if (!ctx || !u_out || !r_out || !qr_out || npoints < 1 || which < 0 || which > 1) return GPEMU_ERR_ARG;
+	if (!ctx->pred_ready) return fail(ctx, GPEMU_ERR_STATE, "gpemu_predict_setup has not been called");
+	if (ctx->tgt_serial != ctx->pred_serial || (which == 0 ? ctx->tgt_S : ctx->tgt_mb) != npoints)
+		return fail(ctx, GPEMU_ERR_STATE, which == 0 ? "no target set of this size" : "no gpemu_design_target_gain block of this size");
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const size_t N = (size_t)ctx->N, nreg = (size_t)ctx->nreg, Np = (size_t)ctx->Np, Rp = (size_t)ctx->Rp, ldv = Np + Rp;
+	const double *u = which == 0 ? (const double *)ctx->dTgtU : (const double *)ctx->dV;
+	const double *r = which == 0 ? (const double *)ctx->dTgtR : (const double *)ctx->dTgtCR;
+	const double *qr = which == 0 ? (const double *)ctx->dTgtQr + 1 : (const double *)ctx->dV + Np + 1;
+	const size_t ldu = which == 0 ? Np : ldv, ldq = which == 0 ? Rp : ldv;
+	HIPCHK(ctx, hipMemcpy2DAsync(u_out, N * sizeof(double), u, ldu * sizeof(double), N * sizeof(double), (size_t)npoints, hipMemcpyDeviceToHost,
+	                             ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(r_out, nreg * sizeof(double), r, Rp * sizeof(double), nreg * sizeof(double), (size_t)npoints,
+	                             hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipMemcpy2DAsync(qr_out, nreg * sizeof(double), qr, ldq * sizeof(double), nreg * sizeof(double), (size_t)npoints,
+	                             hipMemcpyDeviceToHost, ctx->stream));
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	return GPEMU_OK;
 }

@@ -127,6 +127,7 @@ struct Sched {
 	int stagger_us = 20;         // GPEMU_STAGGER_US: first-round offset between the two workgroups of a CU in the 128x128 GEMM (0 = none)
 	int panel_rows = 1;          // GPEMU_PANEL_ROWS: the rows under a 256-column group's cut in one pass (panel_rows_kernel): 0 never, 1 lock-step batches by launch size, 2 always
 	int panel_split = 1;         // GPEMU_PANEL_SPLIT: the cut: k > 0 = 64 k rows under the group (1 measured best), 0 = the end of the outer panel's diagonal square
+	int target_panel = 2048;     // GPEMU_TARGET_PANEL: target columns per panel of U_q U_t^T in gpemu_design_target_gain, a multiple of 64 (the bits do not depend on it)
 };
 
 // The one owner of device or pinned host memory in this library: move-only, released by the destructor, knows its element
@@ -377,6 +378,16 @@ struct gpemu_ctx {
 	// marks) and dBatchIO (the host entry's candidates and results).  batch_mb, batch_nb: the last call's sizes (0: none)
 	gpemu::DevBuf<double> dBatchW, dBatchLam, dBatchMu, dBatchE, dBatchSv, dBatchDots, dBatchSt, dBatchTab, dBatchIO;
 	int batch_mb = 0, batch_nb = 0;
+	// gain over a weighted target set (gpemu_design_target_*).  The resident store of tgt_S targets (0: none), S' =
+	// tgt_S rounded up to 64: dTgtX their coordinates (S' x d) and dTgtW their weights, both kept across prediction set-ups;
+	// dTgtU the u rows (S' x Np), dTgtR the r rows and dTgtQr the [0 | Q r] rows (S' x Rp each), dTgtVar v(x_s), dTgtSum the
+	// target variance, all built for the set-up tgt_serial says (pred_serial; 0: to be rebuilt from dTgtX).  Per block of
+	// candidates: dTgtCR their r rows, dTgtPanel one panel of U_q U_t^T, dTgtPart its partials, dTgtScr a mean nobody reads, then
+	// var and num where the caller keeps neither; dTgtIO the host entries' coordinates and results.  tgt_mb: the candidates of the
+	// last block (0: none), whose u and Q r rows are still in dV
+	gpemu::DevBuf<double> dTgtX, dTgtW, dTgtU, dTgtR, dTgtQr, dTgtVar, dTgtSum, dTgtCR, dTgtPanel, dTgtPart, dTgtScr, dTgtIO;
+	int tgt_S = 0, tgt_mb = 0;
+	unsigned long long tgt_serial = 0;
 	// calibration against observations (gpemu_calib_*): dCalibTab the resident table of one observation set
 	// (kernels_calib.hip has its layout; calib_nt > 0: set up), independent of the model: gpemu_set_model leaves it alone,
 	// gpemu_calib_release and the end of the context free it.  dCalibIO / dCalibIdx the host entries' device copies of mean,
@@ -617,6 +628,16 @@ hipError_t launch_design_update(hipStream_t s, int j, const double *Xq, int mb, 
                                 long dstride, double *Lam, double *Mu, long ldl, double *vS, double *numS, double *gain);
 hipError_t launch_design_argmax(hipStream_t s, const double *const *gains, const double *weight, int nctx, int M, int *picked, int slot,
                                 int *pick, double *pick_gain, double *pick_gain_ctx, double *wout);
+// gain over a weighted target set (gpemu_design_target_*).  sweep: mb candidates (Xq; Rq their r rows) against the
+// ns targets from s0 on (a multiple of 64) of the S in Xt (QRt: the targets' [0 | Q r] rows, wt their weights); P (mb x ldp) =
+// U_q U_t^T of exactly those targets, p: the covariance parameters with nug = 0; part: ceil(ns / 64) rows of pstride >= mb.
+// finish: the running num over a panel's ntile partial rows, the quotient behind the last panel.  var: sum_s wt_s vt_s into out[0]
+hipError_t launch_design_target_sweep(hipStream_t s, const double *Xq, int mb, const double *Xt, int S, int s0, int ns, int d,
+                                      const CovParams &p, const double *P, long ldp, const double *Rq, long ldr, const double *QRt, long ldq,
+                                      const double *wt, int nreg, double *part, long pstride);
+hipError_t launch_design_target_finish(hipStream_t s, const double *part, long pstride, int ntile, int mb, bool first, bool last,
+                                       const double *var, double *num, double *gain);
+hipError_t launch_design_target_var(hipStream_t s, const double *wt, const double *vt, int S, double *out);
 
 // ---- kernels_calib.hip: implausibility and calibration likelihood against observations
 // the device table of one observation set: calib_table_elems doubles, filled on the host from gpemu_calib_project's outputs

@@ -7,8 +7,11 @@
 // K, HK and Hm depend on the design, the lengths and the measure alone: they are built once and kept.  Per block of candidates
 // the unclamped k rows, then (in gpemu_api.hip) the prediction's two triangular products for a and T = a [K | HK], then the
 // cross sweep for sum_i a_i (T_i - 2 w_i) and the finish.  No atomics, no workgroup waits for another; every sum has one order.
+// At the end of the file: the gain over a weighted set of target points (gpemu_design_target_gain), which needs
+// no integral in closed form and so serves every covariance function.
 #include "gpemu_internal.hpp"
 #include "sens_device.hpp"
+#include "cov_device.hpp"
 
 #include <cmath>
 
@@ -674,6 +677,143 @@ hipError_t launch_design_finish(hipStream_t s, const double *part, long pstride,
 	else
 		hipLaunchKernelGGL(design_finish_kernel<2>, grid, dim3(256), 0, s, part, pstride, ntc, V, ldv, R, ldr, Tm, ldt, prepq, Xq, mb, Np, d, nreg,
 		                   cst, Hm, amp, kappa, gain, num, var, bkeep);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Gain over a weighted set of target points (gpemu_design_target_gain, include/gpemu.h):
+//   num(x*) = sum_s w_s c*(x_s, x*)^2,   c*(x_s, x*) = c(x_s, x*) - u_s . u_* + r_* . (Q r)_s.
+// target sweep: one workgroup per tile of 64 candidates (rows, blockIdx.y) x 64 targets (columns, tile blockIdx.x of the
+// panel, tile t0 + blockIdx.x of the set).  c is the element of the unclamped fill (cov_tile_values, mode 0, a CovParams whose
+// nugget is 0: the bare kernel value wherever the two points lie); P = U_q U_t^T (the panel the GEMM left, row pieces of 64
+// consecutive targets: whole 512-byte pieces per wave) is read where the thread holds its elements; r of the 64 candidates
+// and Q r of the 64 targets are staged in LDS as predict_cov_prior_kernel stages them.  w_s c*^2 goes into an LDS tile; then
+// thread (row = tid / 4, quarter = tid % 4) adds its 16 columns in index order and the four quarters are added in order:
+// one partial per candidate and target tile, part[tile of the panel * pstride + q].  Rows >= mb and columns >= S give 0.
+// No atomics, no workgroup waits for another.  Dynamic LDS: 2 * 64 * nreg doubles.
+// ---------------------------------------------------------------------------
+constexpr int TGT_LD = FT + 1;
+
+template <int KIND>
+__global__ __launch_bounds__(256) void design_target_sweep_kernel(const double *Xq, int mb, const double *Xt, int S, int t0, int d, CovParams p,
+                                                                  const double *P, long ldp, const double *Rq, long ldr, const double *QRt,
+                                                                  long ldq, const double *wt, int nreg, double *part, long pstride)
+{
+	extern __shared__ double tgt_reg_s[];
+	__shared__ double c_s[FT * TGT_LD];
+	double *r_s = tgt_reg_s;                    // [candidate of the tile][a]
+	double *qr_s = tgt_reg_s + FT * nreg;       // [a][target of the tile]
+	__builtin_assume(p.kind == KIND);           // (the launch picks the instantiation by p.kind; p stays in the kernel's arguments)
+	const int tid = threadIdx.x;
+	const int tr = blockIdx.y, tl = blockIdx.x, tc = t0 + tl;
+	for (int e = tid; e < FT * nreg; e += 256) {
+		const int i = e / nreg, a = e % nreg;
+		const int gr = tr * FT + i, gc = tc * FT + i;
+		r_s[i * nreg + a] = gr < mb ? Rq[(long)gr * ldr + a] : 0.0;
+		qr_s[a * FT + i] = gc < S ? QRt[(long)gc * ldq + 1 + a] : 0.0;
+	}
+	double v[16];
+	cov_tile_values(Xq, mb, Xt, S, d, p, 0, tr, tc, [&](int t, int, int, double c) { v[t] = c; });       // (its barrier also covers the staging above)
+	const int cl = tid & 63, rsub = tid >> 6;
+	double reg[16];
+#pragma unroll
+	for (int t = 0; t < 16; t++) reg[t] = 0.0;
+	for (int a = 0; a < nreg; a++) {
+		const double qr = qr_s[a * FT + cl];
+#pragma unroll
+		for (int t = 0; t < 16; t++) reg[t] = fma(r_s[(rsub + 4 * t) * nreg + a], qr, reg[t]);
+	}
+	const int col = tc * FT + cl;
+	const bool colv = col < S;
+	const double w = colv ? wt[col] : 0.0;
+	const double *pcol = P + tl * FT + cl;
+#pragma unroll
+	for (int t = 0; t < 16; t++) {
+		const int row = tr * FT + rsub + 4 * t;
+		const double pe = (colv && row < mb) ? pcol[(long)row * ldp] : 0.0;
+		const double cs = (v[t] - pe) + reg[t];
+		c_s[(rsub + 4 * t) * TGT_LD + cl] = w * (cs * cs);
+	}
+	__syncthreads();
+	const int i = tid >> 2, qd = tid & 3;
+	double s = 0.0;
+#pragma unroll
+	for (int c = 0; c < 16; c++) s += c_s[i * TGT_LD + 16 * qd + c];
+	const double s1 = __shfl_down(s, 1), s2 = __shfl_down(s, 2), s3 = __shfl_down(s, 3);
+	const int q = tr * FT + i;
+	if (qd == 0 && q < mb) part[(long)tl * pstride + q] = ((s + s1) + s2) + s3;
+}
+
+// target finish: candidate q adds the partials of a panel in ascending tile order to its running num (started at 0 by the
+// first panel), and behind the last panel forms gain = num / var (0 where var rounds to <= 0).  The sum over the targets has
+// one order whatever the panel width; the partials of a tile lie side by side over q, so a thread takes a candidate and a
+// wave reads whole row pieces.
+__global__ __launch_bounds__(256) void design_target_finish_kernel(const double *part, long pstride, int ntile, int mb, int first, int last,
+                                                                   const double *var, double *num, double *gain)
+{
+	const int q = blockIdx.x * 256 + threadIdx.x;
+	if (q >= mb) return;
+	double s = first ? 0.0 : num[q];
+	for (int t = 0; t < ntile; t++) s += part[(long)t * pstride + q];
+	num[q] = s;
+	if (last) {
+		const double v = var[q];
+		gain[q] = v > 0.0 ? s / v : 0.0;
+	}
+}
+
+// target_var = sum_s w_s v(x_s) in one fixed order: thread t of the one workgroup adds s = t, t + 256, ... in index order,
+// then the 256 sums are halved eight times through LDS
+__global__ __launch_bounds__(256) void design_target_var_kernel(const double *wt, const double *vt, int S, double *out)
+{
+	__shared__ double red[256];
+	double s = 0.0;
+	for (int i = threadIdx.x; i < S; i += 256) s += wt[i] * vt[i];
+	red[threadIdx.x] = s;
+	__syncthreads();
+	for (int h = 128; h > 0; h >>= 1) {
+		if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) out[0] = red[0];
+}
+
+hipError_t launch_design_target_sweep(hipStream_t s, const double *Xq, int mb, const double *Xt, int S, int s0, int ns, int d,
+                                      const CovParams &p, const double *P, long ldp, const double *Rq, long ldr, const double *QRt, long ldq,
+                                      const double *wt, int nreg, double *part, long pstride)
+{
+	if (mb < 1 || mb > 64 * 65535 || S < 1 || s0 < 0 || s0 % FT || ns < 1 || s0 + ns > S || ldp < ns || pstride < mb || d < 1 || d > GPEMU_MAX_PARAMS ||
+	    nreg < 1 || nreg > 63 || ldr < nreg || ldq < nreg + 1)
+		return hipErrorInvalidValue;
+	const dim3 grid((ns + FT - 1) / FT, (mb + FT - 1) / FT);
+	const size_t dyn = 2 * FT * nreg * sizeof(double);
+	if (p.kind == GPEMU_POWEREXP)
+		hipLaunchKernelGGL(design_target_sweep_kernel<GPEMU_POWEREXP>, grid, dim3(256), dyn, s, Xq, mb, Xt, S, s0 / FT, d, p, P, ldp, Rq, ldr, QRt,
+		                   ldq, wt, nreg, part, pstride);
+	else if (p.kind == GPEMU_MATERN32)
+		hipLaunchKernelGGL(design_target_sweep_kernel<GPEMU_MATERN32>, grid, dim3(256), dyn, s, Xq, mb, Xt, S, s0 / FT, d, p, P, ldp, Rq, ldr, QRt,
+		                   ldq, wt, nreg, part, pstride);
+	else if (p.kind == GPEMU_MATERN52)
+		hipLaunchKernelGGL(design_target_sweep_kernel<GPEMU_MATERN52>, grid, dim3(256), dyn, s, Xq, mb, Xt, S, s0 / FT, d, p, P, ldp, Rq, ldr, QRt,
+		                   ldq, wt, nreg, part, pstride);
+	else
+		return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+hipError_t launch_design_target_finish(hipStream_t s, const double *part, long pstride, int ntile, int mb, bool first, bool last,
+                                       const double *var, double *num, double *gain)
+{
+	if (mb < 1 || ntile < 1 || pstride < mb) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(design_target_finish_kernel, dim3((mb + 255) / 256), dim3(256), 0, s, part, pstride, ntile, mb, first ? 1 : 0, last ? 1 : 0,
+	                   var, num, gain);
+	return hipGetLastError();
+}
+
+hipError_t launch_design_target_var(hipStream_t s, const double *wt, const double *vt, int S, double *out)
+{
+	if (S < 1) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(design_target_var_kernel, dim3(1), dim3(256), 0, s, wt, vt, S, out);
 	return hipGetLastError();
 }
 

@@ -319,6 +319,32 @@ void emulator::QueryEmulatorDesignGain(const std::vector<double> &lo, const std:
 		for (size_t t = 0; t < no; t++) Gains[q][t] = g[q * no + t];
 }
 
+void emulator::QueryEmulatorTargetedDesignGain(const std::vector<std::vector<double> > &targets, const std::vector<double> &weights,
+                                               const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Gains,
+                                               std::vector<double> &TotalGains, std::vector<double> &TargetVariances)
+{
+	const size_t no = (size_t)number_outputs, np = xpoints.size(), ns = targets.size();
+	if (ns < 1 || ns > 65536 || (!weights.empty() && weights.size() != ns)) {
+		std::cerr << "Error::QueryEmulatorTargetedDesignGain needs 1 .. 65536 targets and one weight per target, or none" << std::endl;
+		gpemu_host_exit(EXIT_FAILURE);
+	}
+	Gains.assign(np, std::vector<double>(no));
+	TotalGains.assign(np, 0.0);
+	TargetVariances.assign(no, 0.0);
+	std::vector<double> tflat = flatten("QueryEmulatorTargetedDesignGain", targets, number_params);
+	std::vector<double> flat = flatten("QueryEmulatorTargetedDesignGain", xpoints, number_params), g(np * no + 1);
+	if (np == 0) {                               // the targets alone: their variance
+		std::vector<double> one(tflat.begin(), tflat.begin() + number_params), g1(no), t1(1);
+		emulate_design_target_gain_multi(the_emulator, outputPCAValues ? 1 : 0, (int)ns, tflat.data(), weights.empty() ? NULL : weights.data(), 1,
+		                                 one.data(), g1.data(), t1.data(), TargetVariances.data());
+		return;
+	}
+	emulate_design_target_gain_multi(the_emulator, outputPCAValues ? 1 : 0, (int)ns, tflat.data(), weights.empty() ? NULL : weights.data(), (int)np,
+	                                 flat.data(), g.data(), TotalGains.data(), TargetVariances.data());
+	for (size_t q = 0; q < np; q++)
+		for (size_t t = 0; t < no; t++) Gains[q][t] = g[q * no + t];
+}
+
 void emulator::QueryEmulatorDesignBatch(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
                                         int BatchSize, std::vector<int> &Picks, std::vector<double> &PickGains)
 {

@@ -83,6 +83,13 @@ public:
 	// when the design gets one more run at xpoints[q], the hyper-parameters as they are; TotalGains[q] its sum over the outputs
 	void QueryEmulatorDesignGain(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,
 	                             std::vector<std::vector<double> > &Gains, std::vector<double> &TotalGains);
+	// the same for a region given as weighted points (libemu.h: emulate_design_target_gain_multi): targets[s] the points (chain
+	// samples, the non-implausible set, quadrature nodes), weights one per target or empty for 1 / size each.  TargetVariances[t] =
+	// the weighted posterior variance of output t over the targets, Gains[q][t] how much it drops by one more run at xpoints[q],
+	// TotalGains[q] the sum over the outputs.  Every covariance function.
+	void QueryEmulatorTargetedDesignGain(const std::vector<std::vector<double> > &targets, const std::vector<double> &weights,
+	                                     const std::vector<std::vector<double> > &xpoints, std::vector<std::vector<double> > &Gains,
+	                                     std::vector<double> &TotalGains, std::vector<double> &TargetVariances);
 	// a batch of BatchSize runs chosen greedily among xpoints (libemu.h: emulate_design_batch_multi): Picks[j] the index of pick j,
 	// PickGains[j] how much the sum of IntegratedVariances drops by it, given the picks before it
 	void QueryEmulatorDesignBatch(const std::vector<double> &lo, const std::vector<double> &hi, const std::vector<std::vector<double> > &xpoints,

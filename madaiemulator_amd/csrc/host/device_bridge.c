@@ -1334,6 +1334,26 @@ void emulate_design_gain(emulator_struct *e, const double *lo, const double *hi,
 	check(en, gpemu_design_gain(en->ctx, lo, hi, npoints, points, gain, num, var), "emulate_design_gain");
 }
 
+/* the same for a weighted set of target points (gpemu_design_target_set / _gain in gpemu.h) */
+void emulate_design_target_set(emulator_struct *e, int ntargets, const double *targets, const double *weight, double *target_var,
+                               double *var_t)
+{
+	struct entry *en = entry_of(e, "emulate_design_target_set");
+	check(en, gpemu_design_target_set(en->ctx, ntargets, targets, weight, target_var, var_t), "emulate_design_target_set");
+}
+
+void emulate_design_target_release(emulator_struct *e)
+{
+	struct entry *en = entry_of(e, "emulate_design_target_release");
+	check(en, gpemu_design_target_release(en->ctx), "emulate_design_target_release");
+}
+
+void emulate_design_target_gain(emulator_struct *e, int npoints, const double *points, double *gain, double *num, double *var)
+{
+	struct entry *en = entry_of(e, "emulate_design_target_gain");
+	check(en, gpemu_design_target_gain(en->ctx, npoints, points, gain, num, var), "emulate_design_target_gain");
+}
+
 /* a greedy batch of runs (gpemu_design_batch in gpemu.h) for emulators on one design that a run observes together */
 void emulate_design_batch_components(emulator_struct **es, int n, const double *weight, const double *lo, const double *hi, int npoints,
                                      const double *points, int nbatch, int *pick_out, double *gain_out)

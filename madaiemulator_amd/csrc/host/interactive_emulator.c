@@ -37,6 +37,8 @@ struct cmdLineOpts {
 	int level, gradientFlag;
 	int best, bestGiven;
 	int batch, batchGiven;           /* design --batch=K: K greedy picks (-1: not a number) */
+	char *targetsfile;               /* design --targets=FILE: the gain over these points instead of the box */
+	int targetsColumn, targetsColumnGiven;   /* ... whose parameters start at column K of every line (-1: not a number) */
 	int walkers, steps, burn, thin, walkersGiven, burnGiven;
 	unsigned long long seed;
 	double stretch;
@@ -86,14 +88,18 @@ static const char useage[] =
 	"      output; with --gradient, behind them the d components of the log likelihood's gradient with respect to the parameters.\n"
 	"      FILE: the number of outputs, one line \"value sd [rel]\" per output, optionally \"covariance\" and the matrix)\n"
 	"or\n"
-	"  interactive_emulator design MODEL_SNAPSHOT_FILE [--box=FILE | --prior=FILE] [--best=K] [--batch=K] [--pca_output] [--quiet]  (where to put the next model\n"
+	"  interactive_emulator design MODEL_SNAPSHOT_FILE [--box=FILE | --prior=FILE] [--best=K] [--batch=K] [--targets=FILE [--targets-column=K]] [--pca_output] [--quiet]  (where to put the next model\n"
 	"      run: candidate points from stdin to the end of input; one line per candidate: index, parameters, the expected drop of the\n"
 	"      integrated posterior variance summed over the outputs if the model were run there, and that integrated variance as it\n"
 	"      is now.  --best=K prints the K candidates with the largest drop, largest first, ties in input order.  --batch=K chooses a\n"
 	"      batch of K runs greedily, each the largest drop GIVEN the picks before it, and prints them in pick order: index,\n"
 	"      parameters, that conditional drop, and the integrated variance after the pick (K <= 256, at most 16384 candidates;\n"
 	"      not with --best).  The measure as for\n"
-	"      `sensitivity`.  Power-exponential covariance only)\n"
+	"      `sensitivity`.  Power-exponential covariance only.  --targets=FILE asks for the drop of the posterior variance over the\n"
+	"      points of FILE instead -- one target per line, lines starting with # skipped, the d parameters from column K on (default 0),\n"
+	"      further columns ignored, equal weights: the output of `sample` as it is, that of `implausibility` with --targets-column=1 --;\n"
+	"      the lines then end with the expected drop of the targets' mean variance and that variance as it is now.  Any covariance\n"
+	"      function; at most 65536 targets; not with --box, --prior or --batch)\n"
 	"or\n"
 	"  interactive_emulator sample MODEL_SNAPSHOT_FILE --observations=FILE [--box=FILE | --prior=FILE] [--walkers=W] [--steps=T] [--burn=B] [--thin=K] [--seed=S] [--stretch=a] [--quiet]\n"
 	"      (posterior samples of the parameters given the observations of FILE (the format of `implausibility`), by the affine-invariant\n"
@@ -790,7 +796,9 @@ static int implausibility(struct cmdLineOpts *o)
  * outputs, if the model were run there (hyper-parameters as they are), imse that integrated variance as it is now (the same on
  * every line).  --best=K: the K candidates with the largest gain, largest first, ties in input order.  --batch=K: K greedy picks
  * (emulate_design_batch_multi) in pick order, "index param_0 .. gain imse_after": the drop by the pick given the picks before it and
- * the integrated variance once it is made. */
+ * the integrated variance once it is made.  --targets=FILE [--targets-column=K] (emulate_design_target_gain_multi): the same lines
+ * with the drop of the equally weighted posterior variance over the points of FILE, summed over the outputs, and that variance as
+ * it is now; FILE holds one target per line, lines starting with # are skipped, the d parameters start at column K (default 0). */
 static const double *design_key;
 static int design_order(const void *a, const void *b)
 {
@@ -799,8 +807,49 @@ static int design_order(const void *a, const void *b)
 	return i < j ? -1 : (i > j);
 }
 
+/* the targets of --targets=FILE: ns points of d numbers, from column `column` of every line that does not start with # */
+static double *read_targets(const char *path, int d, int column, size_t *ns)
+{
+	FILE *tf = fopen(path, "r");
+	if (!tf) { perr("design: cannot open the file of --targets"); return NULL; }
+	size_t cap = 256, n = 0, len = 0;
+	double *t = (double *)malloc(sizeof(double) * cap * (size_t)d);
+	char *line = NULL;
+	while (getline(&line, &len, tf) >= 0) {
+		char *p = line + strspn(line, " \t\r\n");
+		if (*p == '#' || !*p) continue;
+		if (n == cap) t = (double *)realloc(t, sizeof(double) * (cap *= 2) * (size_t)d);
+		int c = 0;
+		for (; c < column + d; c++) {
+			char *end;
+			const double x = strtod(p, &end);
+			if (end == p) break;
+			if (c >= column) t[n * (size_t)d + (size_t)(c - column)] = x;
+			p = end;
+		}
+		if (c < column + d) {
+			fprintf(stderr, "design: target line %zu of %s has fewer than %d columns\n", n + 1, path, column + d);
+			free(t); free(line); fclose(tf);
+			return NULL;
+		}
+		n++;
+	}
+	free(line);
+	fclose(tf);
+	if (n < 1 || n > 65536) {
+		perr("design: --targets=FILE needs 1 .. 65536 targets");
+		free(t);
+		return NULL;
+	}
+	*ns = n;
+	return t;
+}
+
 static int design(struct cmdLineOpts *o)
 {
+	if (o->targetsfile && (o->boxfile || o->priorfile || o->batchGiven)) return perr("--targets=FILE excludes --box, --prior and --batch");
+	if (o->targetsColumnGiven && !o->targetsfile) return perr("--targets-column=K needs --targets=FILE");
+	if (o->targetsColumnGiven && o->targetsColumn < 0) return perr("--targets-column=K needs a number K >= 0");
 	if (o->bestGiven && o->best < 1) return perr("--best=K needs K >= 1");
 	if (o->batchGiven && o->bestGiven) return perr("--batch=K and --best=K exclude each other");
 	if (o->batchGiven && (o->batch < 1 || o->batch > 256)) return perr("--batch=K needs a number 1 <= K <= 256");
@@ -811,7 +860,8 @@ static int design(struct cmdLineOpts *o)
 	multi_modelstruct *model = load_multi_modelstruct(fp);
 	fclose(fp);
 	const int d = model->nparams, nout = o->pcaOutputFlag ? model->nr : model->nt;
-	if (model->cov_fn_index > 1) return perr("design: the closed form exists for the power-exponential covariance only");
+	if (model->cov_fn_index > 1 && !o->targetsfile)
+		return perr("design: the closed form exists for the power-exponential covariance only (--targets=FILE takes every covariance function)");
 	size_t cap = 1024, n = 0;
 	double *v = (double *)malloc(sizeof(double) * cap), x;
 	while (fscanf(stdin, "%lf", &x) == 1) {
@@ -824,7 +874,12 @@ static int design(struct cmdLineOpts *o)
 		return perr("design: --batch=K needs at least K candidates and at most 16384");
 	double *lo = (double *)malloc(sizeof(double) * (size_t)d), *hi = (double *)malloc(sizeof(double) * (size_t)d);
 	int *kind = (int *)calloc((size_t)d, sizeof(int));                            /* GPEMU_MEASURE_UNIFORM */
-	{
+	size_t ns = 0;
+	double *targets = NULL;
+	if (o->targetsfile) {
+		targets = read_targets(o->targetsfile, d, o->targetsColumnGiven ? o->targetsColumn : 0, &ns);
+		if (!targets) return EXIT_FAILURE;
+	} else {
 		const int rc = read_measure(o, model, lo, hi, kind);
 		if (rc) return rc;
 	}
@@ -834,7 +889,8 @@ static int design(struct cmdLineOpts *o)
 	if (!o->quietFlag) {
 		fprintf(out, "# index");
 		for (int j = 0; j < d; j++) fprintf(out, " param_%d", j);
-		fprintf(out, o->batchGiven ? " conditional_imse_reduction imse_after\n" : " expected_imse_reduction imse\n");
+		fprintf(out, o->batchGiven ? " conditional_imse_reduction imse_after\n" :
+		             targets ? " expected_target_variance_reduction target_variance\n" : " expected_imse_reduction imse\n");
 	}
 	if (np && o->batchGiven) {
 		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
@@ -855,11 +911,14 @@ static int design(struct cmdLineOpts *o)
 	} else if (np) {
 		double *ve0 = (double *)malloc(sizeof(double) * 3 * (size_t)nout), *imse = ve0 + nout, *evar = imse + nout;
 		double *ef = (double *)malloc(sizeof(double) * 2 * (size_t)nout * d), *et = ef + (size_t)nout * d;
-		emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
-		double now = 0.0;
-		for (int t = 0; t < nout; t++) now += imse[t];
 		double *gain = (double *)malloc(sizeof(double) * np * (size_t)nout), *total = (double *)malloc(sizeof(double) * np);
-		emulate_design_gain_multi(emu, o->pcaOutputFlag, lo, hi, (int)np, v, gain, total);
+		if (targets) emulate_design_target_gain_multi(emu, o->pcaOutputFlag, (int)ns, targets, NULL, (int)np, v, gain, total, imse);
+		else {
+			emulate_sensitivity_uncertainty_multi(emu, o->pcaOutputFlag, lo, hi, ve0, imse, evar, ef, et);
+			emulate_design_gain_multi(emu, o->pcaOutputFlag, lo, hi, (int)np, v, gain, total);
+		}
+		double now = 0.0;                                                          /* the integrated, or the targets', variance as it is */
+		for (int t = 0; t < nout; t++) now += imse[t];
 		int *idx = (int *)malloc(sizeof(int) * np);
 		for (size_t q = 0; q < np; q++) idx[q] = (int)q;
 		size_t nprint = np;
@@ -876,7 +935,7 @@ static int design(struct cmdLineOpts *o)
 		free(ve0); free(ef); free(gain); free(total); free(idx);
 	}
 	fflush(out);
-	free(v); free(lo); free(hi); free(kind);
+	free(v); free(lo); free(hi); free(kind); free(targets);
 	free_multi_emulator(emu);
 	return 0;
 }
@@ -1012,6 +1071,8 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 		{"best", required_argument, NULL, 1018},
 		/* design: a greedy batch of K runs */
 		{"batch", required_argument, NULL, 1025},
+		/* design: the gain over the points of a file, whose parameters start at a column */
+		{"targets", required_argument, NULL, 1026},           {"targets-column", required_argument, NULL, 1027},
 		/* sample: the ensemble, the run and its random numbers */
 		{"walkers", required_argument, NULL, 1019},           {"steps", required_argument, NULL, 1020},
 		{"burn", required_argument, NULL, 1021},              {"thin", required_argument, NULL, 1022},
@@ -1069,6 +1130,14 @@ static struct cmdLineOpts *global_opt_parse(int argc, char **argv)
 			const long k = strtol(optarg, &end, 10);
 			o->batch = (*optarg && !*end && k >= 1 && k <= 256) ? (int)k : -1;
 			o->batchGiven = 1;
+			break;
+		}
+		case 1026: o->targetsfile = optarg; break;
+		case 1027: {
+			char *end;
+			const long k = strtol(optarg, &end, 10);
+			o->targetsColumn = (*optarg && !*end && k >= 0 && k <= 1 << 20) ? (int)k : -1;
+			o->targetsColumnGiven = 1;
 			break;
 		}
 		case 'h':

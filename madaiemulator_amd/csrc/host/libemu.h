@@ -354,6 +354,20 @@ void emulate_design_batch(emulator_struct *e, const double *lo, const double *hi
                           int *pick_out, double *gain_out);
 void emulate_design_batch_components(emulator_struct **es, int n, const double *weight, const double *lo, const double *hi, int npoints,
                                      const double *points, int nbatch, int *pick_out, double *gain_out);
+/* extension: where to put the next model run when what matters is a REGION, given as weighted points (gpemu_design_target_set /
+ * _gain in gpemu.h): chain samples of the posterior, the points history matching left standing, quadrature nodes.
+ * emulate_design_target_set keeps the ntargets points (ntargets x nparams, row-major; weight NULL: 1 / ntargets each, used as
+ * given otherwise) on the emulator and returns *target_var = sum_s w_s v(x_s) and var_t[s] = v(x_s), the latent posterior
+ * variance at the targets (either may be NULL); emulate_design_target_gain returns gain[q], how much *target_var drops when the
+ * design gets one more run at points[q], the hyper-parameters as they are, with its numerator num = sum_s w_s c*(x_s, x*)^2 and
+ * the variance var the run would be observed with (either may be NULL).  Every covariance function; 1 <= ntargets <= 65536.
+ * The targets stay resident on the emulator's device, 8 S' (N' + 2 * 64 + nparams + 2) bytes with S' and N' the numbers of targets
+ * and training points rounded up to 64 (4 GB at 65536 targets and 8192 points), until emulate_design_target_release, the next
+ * emulate_design_target_set or the end of the emulator; a gain call after the release is an error. */
+void emulate_design_target_release(emulator_struct *e);
+void emulate_design_target_set(emulator_struct *e, int ntargets, const double *targets, const double *weight, double *target_var,
+                               double *var_t);
+void emulate_design_target_gain(emulator_struct *e, int npoints, const double *points, double *gain, double *num, double *var);
 /* extension: second-order Sobol indices and interaction surfaces in closed form (gpemu_sens_pairs / gpemu_sens_pairs_post /
  * gpemu_sens_joint in gpemu.h).  total[j] > first[j] says that parameter j interacts; these say with which parameter.  Pairs j < k
  * are numbered p = j (2 nparams - j - 1) / 2 + (k - j - 1), npairs = nparams (nparams - 1) / 2; nparams >= 2.
@@ -555,6 +569,12 @@ void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double 
  * of the summed IMSE by pick j. */
 void emulate_design_batch_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
                                 int nbatch, int *pick_out, double *gain_out);
+/* the same for a region given as ntargets weighted points (emulate_design_target_set / _gain): the targets go to every PCA
+ * component, and both results take the squared rule, gain(y_t) = sum_c B_tc^2 gain_c and target_var(y_t) = sum_c B_tc^2
+ * target_var_c.  gain_out[q * nout + t]; total_out[q] (may be NULL) its sum over the outputs; target_var_out[t] (may be NULL).
+ * Every component's targets are released again before the next component takes its own: nothing of the call stays resident. */
+void emulate_design_target_gain_multi(multi_emulator *emu, int pca_space, int ntargets, const double *targets, const double *weight,
+                                      int npoints, const double *points, double *gain_out, double *total_out, double *target_var_out);
 /* second order per output: vpair_out, inter_out, evpair_out, einter_out are npairs values each, output-major, as
  * emulate_sensitivity_pairs / _uncertainty define them.  Observable space exactly as for emulate_sensitivity_multi /
  * _uncertainty_multi: the plug-in half keeps all cross terms between components, sum_{c,c'} B_tc B_tc' cov_pair(c, c') (every pair

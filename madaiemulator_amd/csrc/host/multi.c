@@ -970,6 +970,30 @@ void emulate_design_gain_multi(multi_emulator *emu, int pca_space, const double 
 	free(gp); free(gc);
 }
 
+/* The same over a weighted set of target points (libemu.h): the targets to every component, the components one after the other,
+ * then the squared half of the rule for the gains and for the target variance.  A component's targets are released once its gains are
+ * back. */
+void emulate_design_target_gain_multi(multi_emulator *emu, int pca_space, int ntargets, const double *targets, const double *weight,
+                                      int npoints, const double *points, double *gain_out, double *total_out, double *target_var_out)
+{
+	const size_t nr = (size_t)emu->nr, np = (size_t)(npoints > 0 ? npoints : 0), nout = pca_space ? nr : (size_t)emu->nt;
+	double *gp = doubles((np ? np : 1) * nr), *gc = doubles(np ? np : 1), *tv = doubles(nr);
+	for (size_t c = 0; c < nr; c++) {
+		emulate_design_target_set(emu->emu_struct_array[c], ntargets, targets, weight, &tv[c], NULL);
+		emulate_design_target_gain(emu->emu_struct_array[c], npoints, points, gc, NULL, NULL);
+		emulate_design_target_release(emu->emu_struct_array[c]);       /* (the store is gigabytes at the limits: not kept per component) */
+		place_component(gp, gc, np, nr, c, 1);
+	}
+	deliver(emu, pca_space, 1, 0, np, 1, gp, gain_out);
+	if (target_var_out) deliver(emu, pca_space, 1, 0, 1, 1, tv, target_var_out);
+	for (size_t q = 0; total_out && q < np; q++) {
+		double s = 0.0;
+		for (size_t t = 0; t < nout; t++) s += gain_out[q * nout + t];
+		total_out[q] = s;
+	}
+	free(gp); free(gc); free(tv);
+}
+
 /* A greedy batch of runs (libemu.h).  The weights are what total_out above sums: the squared rule applied to the unit vectors of
  * the components gives B_tc^2, and weight_c is its sum over the outputs. */
 void emulate_design_batch_multi(multi_emulator *emu, int pca_space, const double *lo, const double *hi, int npoints, const double *points,
