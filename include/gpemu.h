@@ -194,14 +194,25 @@ int gpemu_predict_setup(gpemu_ctx *ctx, const double *thetas, int nthetas, doubl
  * thetas[c * nthetas ..] with its inverse rows beside the others (one launch sequence for all, in ctxs[0]'s workspace) and
  * ctxs[c] receives the prediction state gpemu_predict_setup(ctxs[c], ...) would have given it, bit for bit.  beta_out
  * (n x nreg), info (n, 1-based failed pivot or 0) and status (n, GPEMU_OK / GPEMU_ERR_NOT_PD / GPEMU_ERR_REGRESSION per
- * component) are optional; the return value is the first failure (contexts of failed components are left without a set-up). */
+ * component) are optional; the return value is the first failure (contexts of failed components are left without a set-up).
+ * GPEMU_ERR_STATE, before any context is touched, while a host-buffer prediction batch is pending on one of the contexts
+ * (collect it first); so are the other refusals that look at the contexts (a context without a model, listed twice, or of
+ * another device, design, covariance function, order or mode): every context, those listed before the offending one too,
+ * keeps its set-up, its joint factor and everything else.  gpemu_predict_setup itself does not refuse then: the pending batch was computed on the state it was
+ * enqueued under and stays collectable with those bits. */
 int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const double *thetas, int nthetas, double *beta_out, int *info,
                               int *status);
 /* Pays what a process pays once -- the HIP runtime's start, the loading of this library's device code, its tables -- on a
  * throw-away context with a 64-point model, so that a caller can do it on a thread of its own while it is still reading its
  * input (interactive_mode: the snapshot).  Returns GPEMU_OK or the first error (GPEMU_ERR_NO_DEVICE ...). */
 int gpemu_warm_start(int device);
-/* optional: explicit C^-1 (N*N, both triangles) for emulator_struct.cinverse */
+/* optional: explicit C^-1 (N*N, both triangles) for emulator_struct.cinverse.  Reads the factorisation behind the set-up; on a
+ * context set up as a later component of gpemu_predict_setup_batch, whose factorisation ran in ctxs[0]'s workspace, the first
+ * call (of this entry, gpemu_sens_post[_dev] or gpemu_sens_pairs_post[_dev]) after the set-up factors that component again in
+ * the context's own workspace, same thetas, same bits.  Either way nothing of the set-up changes: the prediction state, a
+ * resident joint factor, a pending batch, the design block of gpemu_design_gain and the target store stay as they are.  That one
+ * factorisation on a later component does take a slot of the context's result ring, as a gpemu_loglik would:
+ * gpemu_loglik[_grad]_batch_collect_back reaches one batch less far back across it. */
 int gpemu_get_cinverse(gpemu_ctx *ctx, double *cinv_out);
 
 /* ---- a19: emulate_point, batched (emulator_struct.c:124-143) --------

@@ -1181,8 +1181,9 @@ extern "C" int gpemu_predict_setup_batch(gpemu_ctx *const *ctxs, int n, const do
 		    x->mode != lead->mode || x->hX != lead->hX)
 			return fail(lead, GPEMU_ERR_ARG, "the contexts of a batched set-up share device, design, covariance function, regression order and modes");
 		if (x->pred_pending.kind != PRED_NONE) return fail(lead, GPEMU_ERR_STATE, "a prediction batch is enqueued in one of the contexts: collect it first");
-		invalidate_prediction(x);
 	}
+	// (only now: a call refused above leaves every context as it was, the ones listed before the offending one too)
+	for (int c = 0; c < n; c++) invalidate_prediction(ctxs[c]);
 	std::vector<CovParams> ps;
 	if (const int rc = make_cov_params_batch(lead, n, thetas, nthetas, &ps)) return rc;
 	HIPCHK(lead, hipSetDevice(lead->device));
@@ -2407,11 +2408,16 @@ static int ensure_corner(gpemu_ctx *ctx)
 	if (!ctx->cinv_ready && !ctx->fact_in_T) {
 		// set up by gpemu_predict_setup_batch as a later component: its factorisation ran in the first context's workspace
 		// (round 5: reading this context's own, never allocated workspace here was a GPU memory fault).  The explicit inverse is
-		// the slow path anyway (N x N doubles to the host): factor this component alone, same thetas, same bits.
+		// the slow path anyway (N x N doubles to the host): factor this component alone, same thetas, same bits, into this
+		// context's workspace -- and nothing else.  The prediction state a whole set-up would rebuild from it is the one already
+		// here bit for bit, so it stays, and with it what belongs to the set-up: the joint factor, the transposed copy, pred_serial
+		// (the design block and the target store).  Not gpemu_predict_setup: its invalidate_prediction dropped all of those.
 		const std::vector<double> th = ctx->last_thetas;
+		CovParams p;
 		int info = 0;
-		int rc = gpemu_predict_setup(ctx, th.data(), (int)th.size(), nullptr, &info);
+		int rc = factor_with_inverse(ctx, th.data(), (int)th.size(), &p, &info);
 		if (rc) return rc;
+		ctx->fact_in_T = true;
 	}
 	if (!ctx->cinv_ready) {
 		const size_t dim = (size_t)ctx->Np + ctx->Rp;
